@@ -39,6 +39,11 @@ Beside it, under stable keys:
                 the kernel sources have changed since.
   cpu_baseline  the numpy oracle (a port of the reference) timed on the host cores of this box on a bounded sample of
                 the same windows (N = 1 only).
+
+`--dump-outputs DIR` writes what the last timed step of config 2 returned on rank 0 (windows 0..1023 at every N) as
+float64 DIR/<name>.npy: periods, powers, status, n_sweeps (all windows) and bases_sample (the bases of a fixed, seeded
+sample of DUMP_BASES_WINDOWS windows, listed in bases_sample_windows; all bases would be 335 MB).  The inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
 """
 
 import argparse
@@ -66,6 +71,7 @@ HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8 TB/s spec
 LDS_PEAK_GBS = 150000.0  # MI355X_MICROARCH.md LDS: ~150 TB/s aggregate ds_read_b64
 METRIC = "window-projections/sec (all-p sweep, N=4096)"
 DATA = "synthetic (3 sinusoids + 5 % noise, numpy default_rng(1000 + w), SURVEY 8d)"
+DUMP_BASES_WINDOWS, DUMP_SEED, DUMP_MAX_BYTES = 128, 0, 64 << 20  # --dump-outputs: 128 x 10 x 4096 fp64 bases = 42 MB
 
 
 # ------------------------------------------------------------------------------------------
@@ -232,6 +238,44 @@ def load_recorded_traffic(kernel):
     return ent.get("hbm_bytes_per_launch"), ent.get("source"), ent.get("avg_ms_rocprof")
 
 
+def build_library(ge):
+    """ge.build(): compile the library if its sources are newer, import the package.  In a tree another user built and
+    this one cannot write, a build() that takes its lock file before looking at the library (that of earlier commits)
+    cannot run: the library built there is used if it is up to date, i.e. no source in ge.DEPS is newer; a missing or
+    stale library is still an error."""
+    try:
+        ge.build()
+    except PermissionError:
+        if not os.path.exists(ge.LIB) or any(os.path.getmtime(d) > os.path.getmtime(ge.LIB) for d in ge.DEPS):
+            raise
+        print(f"bench: {os.path.dirname(ge.LIB)} is not writable, using its up-to-date library", file=sys.stderr)
+        from pyperiod_amd import _ffi
+
+        assert _ffi.load().ph_version() >= 100
+
+
+def dump_outputs(out_dir, periods, powers, bases, status, sweeps):
+    """DIR/<name>.npy, float64, of one m_best step's outputs (module docstring); -> bytes written."""
+    import numpy as np
+
+    rows = np.sort(np.random.default_rng(DUMP_SEED).choice(bases.shape[0], DUMP_BASES_WINDOWS, replace=False))
+    arrays = {
+        "periods": periods,
+        "powers": powers,
+        "status": status,
+        "n_sweeps": sweeps,
+        "bases_sample": bases[rows.tolist()],
+        "bases_sample_windows": rows,
+    }
+    arrays = {k: np.ascontiguousarray(v.cpu().numpy() if hasattr(v, "cpu") else v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, total
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return total
+
+
 def c2_workload(world):
     return (f"config 2: m_best(num={NUM_PERIODS}) all-p sweep p=2..{N_SAMPLES // 3}, {WINDOWS_PER_GPU} windows x "
             f"N={N_SAMPLES} fp64 per GPU on {world} GPU(s), windows resident in HBM")
@@ -255,9 +299,13 @@ def main():
     ap.add_argument("--pieces", default="2", help="N>1: how the scatter of each rank's block is cut: a count of equal pieces "
                     "(default 2) or comma-separated weights, e.g. 1,3 (pyperiod_amd/dist.py piece_rows)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo for rehearsals)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed config-2 step as DIR/<name>.npy (float64, bases sampled)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     pieces = int(args.pieces) if "," not in args.pieces else tuple(float(v) for v in args.pieces.split(","))
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -272,7 +320,7 @@ def main():
     # ---- host-only legs first: nothing below this block may fork/spawn after a HIP call
     import __graft_entry__ as ge
 
-    ge.build()  # hipcc runs as a child process: before the GPU is touched, before a communicator exists
+    build_library(ge)  # hipcc runs as a child process: before the GPU is touched, before a communicator exists
     cpu = None
     x4_host = x3_host = x5_host = None
     if rank == 0:
@@ -463,6 +511,8 @@ def main():
         }
         if cpu:
             line["gpu_over_cpu"] = line["value"] / cpu["value"]
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, periods, powers, bases, status, sweeps)
     # =============================== the fp64 all-norms sweep (north_star's literal kernel) ===============================
     if world == 1:
         warm_clock(lambda: eng.sweep(x, 2, N_SAMPLES // 3, 0))

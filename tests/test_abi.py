@@ -127,3 +127,35 @@ def test_host_dictionaries_match_reference(golden):
     from pyperiod_amd import RamanujanPeriods
 
     assert np.max(np.abs(RamanujanPeriods().Cq_complete(6, 20) - g["cq_complete_6_20"])) < 1e-12
+
+
+def test_built_tree_builds_read_only(lib, tmp_path):
+    """build() of an up-to-date tree writes nothing (no lock file, no library), so a tree built by another user
+    imports for this one: the copy is made read-only (binding for a non-root user) and every file of it must be the
+    same afterwards (binding for root too)."""
+    import shutil
+    import stat
+    import subprocess
+    import sys
+
+    tree = tmp_path / "tree"
+    skip = shutil.ignore_patterns("__pycache__", ".build.lock")
+    for d in ("pyperiod_amd", "include"):
+        shutil.copytree(os.path.join(ROOT, d), tree / d, ignore=skip)  # copy2: the library stays newer than its sources
+    shutil.copy2(os.path.join(ROOT, "__graft_entry__.py"), tree)
+
+    def files():
+        return {str(p.relative_to(tree)): (p.stat().st_mtime_ns, p.stat().st_size) for p in tree.rglob("*") if p.is_file()}
+
+    before = files()
+    dirs = [tree] + [p for p in tree.rglob("*") if p.is_dir()]
+    for p in dirs:
+        p.chmod(stat.S_IRUSR | stat.S_IXUSR)
+    try:
+        r = subprocess.run([sys.executable, "-c", "import __graft_entry__ as g; g.build(); print('built')"], cwd=tree,
+                           env=dict(os.environ, PYTHONDONTWRITEBYTECODE="1"), capture_output=True, text=True, timeout=300)
+    finally:
+        for p in dirs:
+            p.chmod(stat.S_IRWXU)
+    assert r.returncode == 0 and "built" in r.stdout, r.stderr[-3000:]
+    assert files() == before

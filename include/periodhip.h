@@ -58,6 +58,7 @@ extern "C" {
 #define PH_FLAG_SINGLE 4u /* return_single_period (Periods.py:216-217): only out[..., :p] written */
 #define PH_FLAG_DEVICE 8u /* array arguments are device pointers, call is asynchronous */
 #define PH_FLAG_NOSYNC 16u /* with PH_FLAG_DEVICE: never synchronise, not even to report PH_E_CAP */
+#define PH_FLAG_KEEP_WEIGHTS 32u /* ph_qo_find_periods: update_weights=False (QOPeriods.py:645-714) */
 
 /* sweep modes */
 #define PH_SWEEP_NORM 0       /* periodic_norm(project(x,p))        Periods.py:507-508 */
@@ -216,7 +217,7 @@ int ph_ramanujan_norms(ph_ctx* ctx, const void* x, int dtype, int64_t W, int N, 
 int ph_dict_project(ph_ctx* ctx, const double* x, const double* basis, int rows, int N,
                     unsigned flags, float* out);
 
-/* ---- QOPeriods.find_periods, non-orthogonal / update_weights=True branch -----------------
+/* ---- QOPeriods.find_periods, non-orthogonal branch --------------------------------------
  * (QOPeriods.py:373-596, get_subspaces :830-840, solve_quadratic :779-796) with the default
  * test function rms(reconstruction) > rms(data) * thresh.  The whole greedy loop runs on the
  * device, one workgroup per window: gamma sweep, phi-mass row bookkeeping, Gram matrix (closed-form
@@ -227,7 +228,20 @@ int ph_dict_project(ph_ctx* ctx, const double* x, const double* basis, int rows,
  * kept); counts (W, 2) = {periods the reference reports, blocks in the dictionary} (they differ
  * by one when the test function stopped the loop, QOPeriods.py:584-592); weights (W, kcap)
  * float64, rows of block b start at sum(keeps[:b]); residual (W, N) dtype of x.
- * kcap = capacity in dictionary rows per window (status PH_ST_CAP when exceeded). */
+ * kcap = capacity in dictionary rows per window (status PH_ST_CAP when exceeded).
+ * PH_FLAG_TRUNC: the period is chosen by the gamma norm of the trunc projection (Periods.py:178-184); the solve
+ * is unchanged.  A selection without a positive norm then ends the window with PH_ST_NO_PERIOD.
+ * PH_FLAG_KEEP_WEIGHTS (update_weights=False, QOPeriods.py:645-714): each new block is fitted alone to the running
+ * residual (residue means, no solve); kcap may then go up to 2^20, and every N and max_length fits (nothing of
+ * the dictionary lives in LDS).  Output layout:
+ *   periods / norms / keeps describe the blocks in the order fitted, duplicates included;
+ *   counts = {periods reported, blocks}: when the test function stops the loop, the last period's block is
+ *     fitted once more to the current residual and appended (the residual is not updated), and one period
+ *     fewer is reported;
+ *   block b holds keeps[b] rows, or periods[b] rows when keeps[b] == 0 (`matrix[:keep] if keep else matrix`);
+ *   weights is the concatenation of the blocks' rows.
+ *   A selection without a positive norm ends the window with PH_ST_NO_PERIOD.
+ * PH_FLAG_ORTH returns PH_E_UNSUPPORTED. */
 int ph_qo_find_periods(ph_ctx* ctx, const void* x, int dtype, int64_t W, int N, int num,
                        double thresh, int min_length, int max_length, int kcap, unsigned flags,
                        uint32_t* periods, double* norms, int32_t* keeps, int32_t* counts,

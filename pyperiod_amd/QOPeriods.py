@@ -7,7 +7,9 @@ even be constructed (QOPeriods.py:190) and only its non-orthogonal ``find_period
   * plain projection, default test function: the whole greedy loop (gamma sweep, phi-mass row
     bookkeeping, right-hand side by folds, matrix-free conjugate-gradient solve, reconstruction,
     residual) runs in ONE kernel launch per window batch -> ph_qo_find_periods
-  * other settings (custom test_function, update_weights=False, trunc, window, Ramanujan basis):
+  * a (W, N) batch: the default, update_weights=False and trunc variants run in one launch per batch
+    (ph_qo_find_periods, PH_FLAG_KEEP_WEIGHTS / PH_FLAG_TRUNC); the other settings run row by row
+  * other 1-D settings (custom test_function, update_weights=False, trunc, window, Ramanujan basis):
     the loop is driven from the host with the heavy pieces on the GPU -- the sweep (ph_sweep,
     QOPeriods.py:470-478), W = A x and A A^T as folds (ph_fold_sums, :781-782), A^T w
     (ph_tile_sum, :795) -- and the small dense solve on host LAPACK like the reference (:794).
@@ -56,6 +58,85 @@ def ramanujan_sum(q: int) -> np.ndarray:
     return out
 
 
+def _to_f64(a):
+    """float32 -> float64 copy of a (possibly large) residual batch, on torch's CPU threads when available."""
+    try:
+        import torch
+
+        return torch.from_numpy(np.ascontiguousarray(a)).to(torch.float64).numpy()
+    except ImportError:
+        return a.astype(np.float64)
+
+
+class _LazyBases(dict):
+    """The output_bases dict of one row of a batched find_periods.  Its "subspaces" entry -- the stacked
+    natural-basis rows of the dictionary blocks, rows x N doubles -- is built from the blocks on first read and
+    kept; every other key is plain.  The accessors that read values build it: ``d[k]``, ``get``, ``pop``,
+    ``setdefault``, ``items``, ``values``, ``copy``, ``==`` and copies by ``dict(d)`` / ``{**d}`` (iteration goes
+    through keys() and ``d[k]``).  ``items`` and ``values`` return lists, not views; ``keys``, ``in`` and ``len``
+    need nothing built."""
+
+    def __init__(self, blocks, n, basis_type, **items):
+        super().__init__(periods=items["periods"], norms=items["norms"], subspaces=None, weights=items["weights"],
+                         basis_dictionary=items["basis_dictionary"])
+        self._blocks, self._n, self._basis_type = blocks, n, basis_type
+
+    def _subspaces(self):
+        if self._blocks is not None:
+            rows = np.vstack([QOPeriods.Pp(q, self._n, k, self._basis_type) for q, k in self._blocks])
+            dict.__setitem__(self, "subspaces", rows)
+            self._blocks = None
+        return dict.__getitem__(self, "subspaces")
+
+    def __getitem__(self, key):
+        if key == "subspaces":
+            return self._subspaces()
+        return dict.__getitem__(self, key)
+
+    def __setitem__(self, key, value):
+        if key == "subspaces":
+            self._blocks = None
+        dict.__setitem__(self, key, value)
+
+    def get(self, key, default=None):
+        return self[key] if key in self else default
+
+    def __iter__(self):  # (a dict subclass with its own __iter__ is copied through keys() / __getitem__)
+        return iter(dict.keys(self))
+
+    def items(self):
+        return [(k, self[k]) for k in dict.keys(self)]
+
+    def values(self):
+        return [self[k] for k in dict.keys(self)]
+
+    def pop(self, key, *default):
+        if key == "subspaces" and key in self:
+            self._subspaces()
+        return dict.pop(self, key, *default)
+
+    def setdefault(self, key, default=None):
+        if key in self:
+            return self[key]
+        return dict.setdefault(self, key, default)
+
+    def __eq__(self, other):
+        for d in (self, other):
+            if isinstance(d, _LazyBases) and d._blocks is not None:
+                d._subspaces()
+        return dict.__eq__(self, other)
+
+    __hash__ = None
+
+    def copy(self):
+        return dict(self)
+
+    def __repr__(self):
+        built = "built" if self._blocks is None else f"{sum(k if k else q for q, k in self._blocks)} x {self._n}, built on read"
+        inner = ", ".join(f"{k!r}: {('<subspaces ' + built + '>') if k == 'subspaces' else repr(dict.__getitem__(self, k))}" for k in dict.keys(self))
+        return "{" + inner + "}"
+
+
 class QOPeriods(Periods):
     PRIMES = PRIMES  # QOPeriods.py:149-151
 
@@ -73,13 +154,17 @@ class QOPeriods(Periods):
     # ------------------------------------------------------------------ detection
     def find_periods(self, data, num=None, thresh=None, min_length=2, max_length=None, update_weights=True, **kwargs):
         """Greedy period selection with re-solved weights (QOPeriods.py:313-596).
-        Returns ``(dict(periods, norms, subspaces, weights, basis_dictionary), residual)``.
+        Returns ``(dict(periods, norms, subspaces, weights, basis_dictionary), residual)``; a ``(W, N)``
+        ndarray returns a list of W such tuples (see ``_find_periods_batch``: one launch per batch, with
+        ``subspaces`` built on first read).
 
         ``orthogonalize=True``: the v1 reference dies on this branch (``best_base`` is never
         assigned, QOPeriods.py:427-448).  Offered here as its commented-out lines intend: the
         period is chosen by the orthogonal (Muresan-Parks) powers -- ``get_best_period_orthogonal``
         on the device -- and its norm is that of the orthogonalised projection of the residual
         (QOPeriods.py:443-448); the solve is the same as in the plain branch."""
+        if isinstance(data, np.ndarray) and data.ndim == 2:
+            return self._find_periods_batch(data, num, thresh, min_length, max_length, update_weights, kwargs)
         data = _as_window(data)
         N = len(data)
         if max_length is None:
@@ -106,6 +191,93 @@ class QOPeriods(Periods):
             if done is not None:
                 return done
         return self._find_periods_host(data, N, num, thresh, min_length, max_length, update_weights, custom_test)
+
+    def _find_periods_batch(self, data, num, thresh, min_length, max_length, update_weights, kwargs):
+        """find_periods over a (W, N) batch: a list of W ``(output_bases, residual)`` tuples, each what the
+        1-D call on that row returns (``output_bases`` becomes the list of the per-row dicts).
+
+        Rows whose settings the device loops cover -- default test function, ``thresh`` set, natural basis,
+        no analysis window, plain selection, either ``trunc_to_integer_multiple`` and either
+        ``update_weights`` -- run in ONE launch of ph_qo_find_periods per batch (float32 batches in the fp32
+        kernels, residuals returned as float64).  Everything else (custom ``test_function``, ``window``,
+        Ramanujan basis, ``orthogonalize``, ``verbose``, ``thresh=None``) and every row the kernels hand back
+        with a fallback status or a dictionary beyond the device's capacity runs the 1-D call on that row;
+        all-zero rows get the reference's fixed answer.
+
+        ``"subspaces"`` of a device row is built from its ``basis_dictionary`` blocks on first read (W x rows
+        x N doubles for the whole batch would not fit the host's memory at scale); reading it gives the array
+        of the 1-D result."""
+        W, N = data.shape
+        windowed = not (self.window is None or self.window is False)
+        on_device = (
+            kwargs.get("test_function") is None and thresh is not None and not self._orthogonalize
+            and self._basis_type == "natural" and not windowed and not self._verbose
+        )
+        out = [None] * W
+        if on_device and W > 0:
+            x = data if data.dtype in (np.float32, np.float64) else data.astype(np.float64)
+            x = np.ascontiguousarray(x)
+            ml = int(np.floor(N / 3)) if max_length is None else int(max_length)
+            n = N if num is None else int(num)
+            for w, r in enumerate(self._find_periods_device_batch(default_engine(), x, n, thresh, min_length, ml, update_weights)):
+                # all-zero rows (QOPeriods.py:394-406) go to the 1-D call.  A gamma norm is at most rms(x) <=
+                # sum|x| / sqrt(N), so only rows whose first norm is <= 1e-16 need the sum of the 1-D test.
+                if r is not None:
+                    nrm = r[0]["norms"]
+                    if (nrm.size == 0 or nrm[0] <= 1e-16) and np.sum(np.abs(x[w].astype(np.float64))) <= 1e-16:
+                        r = None
+                out[w] = r
+        for w in range(W):
+            if out[w] is None:  # the 1-D call on the row, whatever it is
+                out[w] = self.find_periods(data[w], num, thresh, min_length, max_length, update_weights, **kwargs)
+        self._output_bases = [r[0] for r in out]
+        return out
+
+    def _find_periods_device_batch(self, eng, x, num, thresh, min_length, max_length, update_weights):
+        """One ph_qo_find_periods launch for the batch `x` (and one more per capacity doubling, for the rows that
+        needed it).  -> list of (output_bases, residual) or None (the row goes to the 1-D call)."""
+        W, N = x.shape
+        trunc = bool(self._trunc_to_integer_multiple)
+        bound = int(num) * int(max_length)  # a block adds at most max_length rows
+        if update_weights:
+            kcap, kmax = (min(2048, max(64, -(-bound // 64) * 64)) if bound <= 2048 else 512), 2048
+            while kcap > 64 and not eng.qo_feasible(N, x.dtype, kcap, max_length):
+                kcap //= 2
+            if not eng.qo_feasible(N, x.dtype, kcap, max_length):
+                return [None] * W
+        else:  # the fixed-weight loop keeps its weights in HBM only: room for every row it can fit
+            kcap, kmax = min(4096, max(64, -(-bound // 64) * 64)), 1 << 20
+        results = [None] * W
+        todo = np.arange(W)
+        while todo.size:
+            xs = x if todo.size == W else x[todo]
+            per, nrm, keeps, counts, wts, resid, st = eng.qo_find_periods(
+                xs, num, thresh, min_length, max_length, kcap, trunc=trunc, update_weights=update_weights
+            )
+            if resid.dtype != np.float64:
+                resid = _to_f64(resid)
+            for i, w in enumerate(todo):
+                if st[i] != _ffi.PH_ST_OK or counts[i, 1] == 0:
+                    continue
+                n_report, n_blocks = int(counts[i, 0]), int(counts[i, 1])
+                blocks = [(int(per[i, b]), int(keeps[i, b])) for b in range(n_blocks)]
+                n_rows = sum(k if k else q for q, k in blocks)
+                result = _LazyBases(  # (views into the batch's output arrays)
+                    blocks, N, self._basis_type,
+                    periods=per[i, :n_report],
+                    norms=nrm[i, :n_report],
+                    weights=wts[i, :n_rows],
+                    basis_dictionary={str(q): k for q, k in blocks},
+                )
+                results[w] = (result, resid[i])
+            grow = st == _ffi.PH_ST_CAP
+            if not grow.any():
+                break
+            nxt = kcap * (2 if update_weights else 4)
+            if nxt > kmax or (update_weights and not eng.qo_feasible(N, x.dtype, nxt, max_length)):
+                break
+            kcap, todo = nxt, todo[grow]
+        return results
 
     def _strongest_period(self, eng, res, found, min_length, max_length, update_weights):
         """(period, gamma norm) of the residual `res`; period 0 = stop (QOPeriods.py:425-478)."""

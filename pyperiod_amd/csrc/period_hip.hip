@@ -475,6 +475,13 @@ int qo_lds_layout(ph_ctx* c, size_t sz, int N, int max_length, int kcap, size_t*
   return PH_OK;
 }
 
+// LDS layout of k_qo_greedy: the residual window (or nothing: the HBM workspace holds it) and the reductions.  The
+// divisor bitset lives in the HBM workspace and the block's weights in the output row, so the LDS need does not depend
+// on max_length or kcap, and every N and max_length is feasible.
+size_t qo_greedy_fixed_bytes() {
+  return carve_bytes(kRedDoubles, 8) + carve_bytes(kMaxWaves, 8) + carve_bytes(kMaxWaves, 4);
+}
+
 // LDS of k_mbest_step1_pair: the pair window, one fp64 staging buffer, bookkeeping of two windows.
 size_t pair_lds_bytes(int N, int num, int P) {
   return 2 * carve_bytes(N + kPad, 8) + carve_bytes(kRedDoubles, 8) + carve_bytes(kMaxWaves, 8) +
@@ -1536,18 +1543,29 @@ int ph_qo_find_periods(ph_ctx* c, const void* x, int dtype, int64_t W, int N, in
   PH_TRY(check_common(c, x, dtype, W, N));
   if (!periods || !norms || !keeps || !counts || !weights || !residual || !status)
     return fail(PH_E_ARG, "output pointer is NULL");
-  if (flags & (PH_FLAG_TRUNC | PH_FLAG_ORTH))
-    return fail(PH_E_UNSUPPORTED, "ph_qo_find_periods implements the plain-projection branch only");
+  if (flags & PH_FLAG_ORTH)
+    return fail(PH_E_UNSUPPORTED, "ph_qo_find_periods: orthogonal selection is not implemented on the device");
+  const bool trunc = flags & PH_FLAG_TRUNC;
+  const bool keep_weights = flags & PH_FLAG_KEEP_WEIGHTS;
   if (num < 1) return fail(PH_E_ARG, "num=%d must be >= 1", num);
   if (max_length < 0) max_length = N / 3;  // QOPeriods.py:374-375
   if (min_length < 1 || max_length < min_length)
     return fail(PH_E_ARG, "need 1 <= min_length <= max_length (got %d, %d)", min_length, max_length);
-  if (kcap < 1 || kcap > 2048) return fail(PH_E_ARG, "kcap=%d must be in [1, 2048]", kcap);
+  if (!keep_weights && (kcap < 1 || kcap > 2048)) return fail(PH_E_ARG, "kcap=%d must be in [1, 2048]", kcap);
+  if (keep_weights && (kcap < 1 || kcap > ph::kQoGreedyMaxRows))
+    return fail(PH_E_ARG, "kcap=%d must be in [1, %d] with PH_FLAG_KEEP_WEIGHTS", kcap, ph::kQoGreedyMaxRows);
   PH_HIP(hipSetDevice(c->device));
   const size_t sz = elem_size(dtype);
   size_t lds;
-  bool lds_window, overlay;
-  PH_TRY(qo_lds_layout(c, sz, N, max_length, kcap, &lds, &lds_window, &overlay));
+  bool lds_window, overlay = false;
+  if (keep_weights) {
+    const size_t fixed = qo_greedy_fixed_bytes();
+    const size_t with_window = fixed + carve_bytes(N + kPad, sz);
+    lds_window = !c->qo_hbm_window && with_window <= (size_t)c->lds_limit;
+    lds = lds_window ? with_window : fixed;
+  } else {
+    PH_TRY(qo_lds_layout(c, sz, N, max_length, kcap, &lds, &lds_window, &overlay));
+  }
   void* gwin = nullptr;
   if (!lds_window) {
     PH_TRY(ensure(c, c->buf[B_GWIN], (size_t)W * ph::win_stride(N + kPad) * sz));
@@ -1564,18 +1582,25 @@ int ph_qo_find_periods(ph_ctx* c, const void* x, int dtype, int64_t W, int N, in
   for (int i = 2; i <= max_length; ++i)
     if (phi[i] == i)
       for (int j = i; j <= max_length; j += i) phi[j] -= phi[j] / i;
-  for (int q = 0; q <= max_length; ++q) {
-    off[q] = (int32_t)dq.size();
-    for (int d = 1; q > 0 && d <= q; ++d)
-      if (q % d == 0) dq.push_back(d);
+  // (by sieve, O(max_length log max_length): the divisors of q in ascending order, CSR by q)
+  for (int d = 1; d <= max_length; ++d)
+    for (int q = d; q <= max_length; q += d) ++off[q + 1];
+  for (int q = 0; q <= max_length; ++q) off[q + 1] += off[q];
+  dq.resize(off[max_length + 1]);
+  {
+    std::vector<int32_t> fill(off.begin(), off.end() - 1);
+    for (int d = 1; d <= max_length; ++d)
+      for (int q = d; q <= max_length; q += d) dq[fill[q]++] = d;
   }
-  off[max_length + 1] = (int32_t)dq.size();
   if (dq.empty()) dq.push_back(1);
   const int *d_phi, *d_off, *d_dq;
   PH_TRY(upload_table(c, T_AUX0, phi.data(), phi.size(), &d_phi));
   PH_TRY(upload_table(c, T_AUX1, off.data(), off.size(), &d_off));
   PH_TRY(upload_table(c, T_AUX2, dq.data(), dq.size(), &d_dq));
-  PH_TRY(ensure(c, c->buf[B_WS1], (size_t)W * 2 * kcap * sizeof(double)));  // last good weights + rhs of every window
+  if (!keep_weights)  // last good weights + rhs of every window
+    PH_TRY(ensure(c, c->buf[B_WS1], (size_t)W * 2 * kcap * sizeof(double)));
+  else  // divisor bitset of every window
+    PH_TRY(ensure(c, c->buf[B_WS1], (size_t)W * ((max_length + 32) / 32) * sizeof(uint32_t)));
   Stage st(c, flags);
   const void* dx;
   void *dper, *dnrm, *dkeep, *dcnt, *dwts, *dres, *dstat;
@@ -1588,17 +1613,29 @@ int ph_qo_find_periods(ph_ctx* c, const void* x, int dtype, int64_t W, int N, in
   PH_TRY(st.out(B_WS0, residual, (size_t)W * N * sz, &dres));
   PH_TRY(st.out(B_GEN0, status, (size_t)W * sizeof(int32_t), &dstat));
   const dim3 grid((unsigned)W);
+  const char* name = keep_weights ? "k_qo_greedy" : "k_qo_find";
   PH_TRY(dispatch(dtype, lds_window, [&](auto t, auto lw) {
     using T = decltype(t);
-    auto kernel = ph::k_qo_find<T, decltype(lw)::value>;
+    constexpr bool LW = decltype(lw)::value;
+    if (keep_weights) {
+      auto kernel = trunc ? ph::k_qo_greedy<T, LW, true> : ph::k_qo_greedy<T, LW, false>;
+      PH_TRY(allow_lds(kernel, lds));
+      ProfScope ps_(c, name);
+      hipLaunchKernelGGL(kernel, grid, dim3(c->qo_block), lds, c->stream, (const T*)dx, N, num, thresh, min_length,
+                         max_length, geom, plan, n_pass, d_phi, d_off, d_dq, kcap, (T*)gwin,
+                         (uint32_t*)c->buf[B_WS1].p, (uint32_t*)dper,
+                         (double*)dnrm, (int*)dkeep, (int*)dcnt, (double*)dwts, (T*)dres, (int*)dstat);
+      return (int)PH_OK;
+    }
+    auto kernel = trunc ? ph::k_qo_find<T, LW, true> : ph::k_qo_find<T, LW>;
     PH_TRY(allow_lds(kernel, lds));
-    ProfScope ps_(c, "k_qo_find");
+    ProfScope ps_(c, name);
     hipLaunchKernelGGL(kernel, grid, dim3(c->qo_block), lds, c->stream, (const T*)dx, N, num, thresh, min_length,
                        max_length, geom, plan, n_pass, d_phi, d_off, d_dq, kcap, overlay ? 1 : 0, (T*)gwin, (double*)c->buf[B_WS1].p,
                        (uint32_t*)dper, (double*)dnrm, (int*)dkeep, (int*)dcnt, (double*)dwts, (T*)dres, (int*)dstat);
     return (int)PH_OK;
   }));
-  PH_TRY(launch_check("k_qo_find"));
+  PH_TRY(launch_check(name));
   return st.finish();
 }
 

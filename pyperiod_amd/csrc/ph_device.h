@@ -995,6 +995,39 @@ __device__ __forceinline__ void wave_sweep_plan(const T* __restrict__ xs, int N,
   bf.flush(lane, consume);
 }
 
+// Gamma sweep of the TRUNC projections (Periods.py:178-184) without materialising them: the trunc mean of residue j
+// averages the trows complete rows (residue_mean(.., trunc=true): every residue uses exactly trows rows), and the
+// projection tiles it over all count_j samples of the residue, so ||P_p x||^2 = sum_j count_j mean_j^2.  One
+// wavefront per period (p = p_lo + i_first, + stride, ...); consume(ss, p) runs in every lane with the same values.
+// Periods below 64 fold the trows * p prefix with the row-group shuffle of wave_fold_small, longer ones walk their
+// residues in row order (column_sum).  A period with no complete row (p > N) has a NaN norm in the reference and is
+// skipped by the argmax there; here its ss is 0, which the consumers skip as well.
+template <typename T, typename F>
+__device__ __forceinline__ void wave_sweep_trunc(const T* __restrict__ xs, int N, int p_lo, int p_hi, int i_first,
+                                                 int stride, int lane, F&& consume) {
+  for (int p = p_lo + i_first; p <= p_hi; p += stride) {
+    const int rows = (N + p - 1) / p, shortn = rows * p - N, nfull = p - shortn;
+    const int trows = shortn == 0 ? rows : rows - 1;
+    double acc = 0.0;
+    if (trows > 0) {
+      const double div = (double)trows;
+      if (p < kWave) {
+        const double s = wave_fold_small(xs, trows * p, p, lane);
+        if (lane < p) {
+          const double m = s / div;
+          acc = (double)(lane < nfull ? rows : rows - 1) * m * m;
+        }
+      } else {
+        for (int j = lane; j < p; j += kWave) {
+          const double m = (double)column_sum(xs, j, p, trows) / div;
+          acc = fma((double)(j < nfull ? rows : rows - 1) * m, m, acc);
+        }
+      }
+    }
+    consume(wave_sum(acc), p);
+  }
+}
+
 // Wavefront argmax of (value, period): largest value, lowest period among equals
 // (the reference scans p upward with a strict '>', Periods.py:512).  period 0 = none.
 __device__ __forceinline__ void wave_argmax(double& v, int& p) {

@@ -2549,6 +2549,7 @@ __global__ __launch_bounds__(kBlock) void k_tile_sum(const double* __restrict__ 
 #define PH_QO_OCC __attribute__((amdgpu_waves_per_eu(8, 8)))  // two 16-wave workgroups per CU need <= 64 VGPRs
 #endif
 constexpr int kQoMaxBlocks = 64;
+constexpr int kQoGreedyMaxRows = 1 << 20;  // k_qo_greedy: dictionary rows per window (weights live in HBM only)
 constexpr int kQoPairTab = 16;  // dictionaries of up to this many blocks keep their pair constants in LDS
 
 __device__ __forceinline__ int qo_gcd(int a, int b) {
@@ -2610,7 +2611,10 @@ __device__ __forceinline__ double qo_offdiag(const double* __restrict__ vb, int 
   return (double)chi * shi + (double)(chi - 1) * slo;
 }
 
-template <typename T, bool LW>
+// TRUNC (trunc_to_integer_multiple): only the selection changes -- the gamma norm of the trunc projection
+// (wave_sweep_trunc); the solve ignores trunc like the reference's _update_weights.  The plain instantiations compile
+// to the code they had before the parameter existed (everything TRUNC touches is `if constexpr`).
+template <typename T, bool LW, bool TRUNC = false>
 __global__ __launch_bounds__(1024) PH_QO_OCC void k_qo_find(const T* __restrict__ x, int N, int num, double thresh,
                                                         int p_lo, int p_hi, const PGeom* __restrict__ geom,
                                                         const PassPlan* __restrict__ plan, int n_pass,
@@ -2698,7 +2702,7 @@ __global__ __launch_bounds__(1024) PH_QO_OCC void k_qo_find(const T* __restrict_
     double best = 0.0;
     int bestp = 0;
     double best_ss = 0.0;  // same lazy comparison as in k_mbest_step1 (gamma norm: ss / p)
-    wave_sweep_plan<T, LW>(work, N, geom, plan, wv, n_pass, nw, lane, [&](double ss, int p) {
+    auto consider = [&](double ss, int p) {
       if (!(ss > 0.0)) return;
       bool take = bestp == 0;
       if (!take) {
@@ -2714,7 +2718,11 @@ __global__ __launch_bounds__(1024) PH_QO_OCC void k_qo_find(const T* __restrict_
         best_ss = ss;
         bestp = p;
       }
-    });
+    };
+    if constexpr (TRUNC)
+      wave_sweep_trunc(work, N, p_lo, p_hi, wv, nw, lane, consider);
+    else
+      wave_sweep_plan<T, LW>(work, N, geom, plan, wv, n_pass, nw, lane, consider);
     best = bestp != 0 ? periodic_norm_from_sq(best_ss, N, bestp) : 0.0;
     if (!(best > 0.0)) bestp = 0;
     wave_argmax(best, bestp);
@@ -2726,7 +2734,10 @@ __global__ __launch_bounds__(1024) PH_QO_OCC void k_qo_find(const T* __restrict_
     red_argmax(wbest, wbestp, nw, best, bestp);
     __syncthreads();
     PH_QO_MARK(0)
-    if (bestp == 0) break;  // nothing left to explain; the reference keeps looping on zeros
+    if (bestp == 0) {  // nothing left to explain; the reference keeps looping on zeros
+      if constexpr (TRUNC) status = 1;  // (PH_ST_NO_PERIOD: not mirrored for trunc, the host loop takes the window)
+      break;
+    }
     // ---- rows this period contributes (QOPeriods.py:833-840); a repeated period or one whose
     //      divisors are all present adds none and makes the reference's matrix singular
     int keep = 0;
@@ -3010,6 +3021,186 @@ __global__ __launch_bounds__(1024) PH_QO_OCC void k_qo_find(const T* __restrict_
   for (int n = tid; n < N; n += blockDim.x) resid_out[w * (int64_t)N + n] = work[n];
   if (tid == 0) {
     counts_out[2 * w] = n_report < 0 ? 0 : n_report;
+    counts_out[2 * w + 1] = nb;
+    status_out[w] = status;
+  }
+}
+
+// ======================================================================================
+// QOPeriods.find_periods with update_weights=False (QOPeriods.py:645-714 as the host loop of
+// pyperiod_amd/QOPeriods.py runs it), the whole greedy loop on the device.  One workgroup per window.
+// Each new block is fitted ALONE to the running residual; its rows are disjoint residue classes, so
+// A A^T is diagonal and the fit is a set of residue means -- no solve, no Gram table.  Per step:
+//   gamma sweep of the residual (plain pass plan, or the trunc sweep)    -> strongest period p
+//   keep = phi mass of the divisors of p that divide no earlier period (_dont_update_weights)
+//   rows = keep, or all p rows when keep == 0 (`matrix[:keep] if keep else matrix`: a period that
+//     repeats or divides earlier ones)
+//   weights = residue means of the residual over those rows; residual -= tiled means
+//   stop test rms(block reconstruction) > rms(data) * thresh from sum_j count_j w_j^2
+// When the test fails the last period's block is fitted once more to the current residual and
+// appended (the residual is left as it was) and one period fewer is reported (QOPeriods.py:163-169).
+// A selection without a positive norm ends with PH_ST_NO_PERIOD (the host loop re-selects the last
+// period there), more rows than kcap with PH_ST_CAP: the caller re-runs such windows on the host.
+// ======================================================================================
+template <typename T, bool LW, bool TRUNC>
+__global__ __launch_bounds__(1024) void k_qo_greedy(const T* __restrict__ x, int N, int num, double thresh, int p_lo,
+                                                    int p_hi, const PGeom* __restrict__ geom,
+                                                    const PassPlan* __restrict__ plan, int n_pass,
+                                                    const int* __restrict__ phi, const int* __restrict__ div_off,
+                                                    const int* __restrict__ div_q, int kcap, T* gwin,
+                                                    uint32_t* __restrict__ seen_ws, uint32_t* __restrict__ periods_out, double* __restrict__ norms_out,
+                                                    int* __restrict__ keeps_out, int* __restrict__ counts_out,
+                                                    double* __restrict__ weights_out, T* __restrict__ resid_out,
+                                                    int* __restrict__ status_out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  Carve cv(smem);
+  T* work = window_buf<T, LW>(cv, gwin, N + kPad);  // the running residual
+  double* red = cv.take<double>(kRedDoubles);
+  double* wbest = cv.take<double>(kMaxWaves);
+  int* wbestp = cv.take<int>(kMaxWaves);
+  // Nothing else lives in LDS, so no N or max_length is too large: the divisors of the periods found so far are a
+  // bitset in the HBM workspace, the weights of the block being fitted go straight to the output row.
+
+  const int64_t w = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int lane = tid & (kWave - 1);
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int nw = blockDim.x >> 6;
+  double* wout = weights_out + w * (int64_t)kcap;
+  uint32_t* seen = seen_ws + w * (int64_t)((p_hi + 32) / 32);
+
+  load_window(x + w * (int64_t)N, work, N);
+  zero_pad(work, N);
+  for (int k = tid; k < (p_hi + 32) / 32; k += blockDim.x) seen[k] = 0u;
+  __syncthreads();
+  const double data_sq = block_sumsq(work, N, red);
+  double recon_sq = 0.0;
+  int nb = 0, row0 = 0, status = 0;
+  int lastp = 0, lastkeep = 0;
+  double lastnorm = 0.0;
+  bool stopped_by_test = false;
+  for (int it = 0; it < num; ++it) {
+    int p, keep;
+    double nrm;
+    if (it > 0 && !(sqrt(recon_sq / N) > sqrt(data_sq / N) * thresh)) {  // QOPeriods.py:391,418
+      stopped_by_test = true;  // re-fit of the last period's block (its keep is unchanged: same earlier periods)
+      p = lastp;
+      keep = lastkeep;
+      nrm = lastnorm;
+    } else {
+      // ---- strongest gamma-normalised projection of the residual, first maximum (QOPeriods.py:470-478)
+      double best_ss = 0.0;
+      int bestp = 0;
+      auto consider = [&](double ss, int q) {
+        if (!(ss > 0.0)) return;
+        bool take = bestp == 0;
+        if (!take) {
+          const double lhs = ss * (double)bestp, rhs = best_ss * (double)q;
+          if (lhs > rhs * (1.0 + 1e-14)) {
+            take = true;
+          } else if (lhs >= rhs * (1.0 - 1e-14)) {
+            const double vn = periodic_norm_from_sq(ss, N, q), vb = periodic_norm_from_sq(best_ss, N, bestp);
+            take = vn > vb || (vn == vb && q < bestp);
+          }
+        }
+        if (take) {
+          best_ss = ss;
+          bestp = q;
+        }
+      };
+      if constexpr (TRUNC)
+        wave_sweep_trunc(work, N, p_lo, p_hi, wv, nw, lane, consider);
+      else
+        wave_sweep_plan<T, LW>(work, N, geom, plan, wv, n_pass, nw, lane, consider);
+      double best = bestp != 0 ? periodic_norm_from_sq(best_ss, N, bestp) : 0.0;
+      if (!(best > 0.0)) bestp = 0;
+      wave_argmax(best, bestp);
+      if (lane == 0) {
+        wbest[wv] = best;
+        wbestp[wv] = bestp;
+      }
+      __syncthreads();
+      red_argmax(wbest, wbestp, nw, best, bestp);
+      if (bestp == 0 || bestp > N) {  // no positive norm (or residues without samples): not mirrored here
+        status = 1;
+        break;
+      }
+      // ---- rows of the new block: phi mass of its divisors that divide no earlier period (QOPeriods.py:244-260)
+      keep = 0;
+      for (int k = div_off[bestp]; k < div_off[bestp + 1]; ++k) {
+        const int r = div_q[k];
+        if (!((seen[r >> 5] >> (r & 31)) & 1u)) keep += phi[r];
+      }
+      __syncthreads();  // every thread has read `seen` and the wave winners
+      if (tid == 0)
+        for (int k = div_off[bestp]; k < div_off[bestp + 1]; ++k) seen[div_q[k] >> 5] |= 1u << (div_q[k] & 31);
+      p = bestp;
+      nrm = best;
+    }
+    const int rows = keep ? keep : p;  // `matrix[:keep] if keep else matrix` (QOPeriods.py Pp)
+    if (row0 + rows > kcap) {
+      status = 3;
+      break;
+    }
+    // ---- weights: residue means of the residual (A A^T is diagonal: the samples of each residue)
+    const int R = (N + p - 1) / p, nfull = p - (R * p - N);
+    if (R >= 4 * kWave) {  // few residues with many samples: one wavefront per residue
+      for (int j = wv; j < rows; j += nw) {
+        const int cnt = j < nfull ? R : R - 1;
+        double sj = 0.0;
+        for (int r = lane; r < cnt; r += kWave) sj += (double)work[j + (int64_t)r * p];
+        sj = wave_sum(sj);
+        if (lane == 0) wout[row0 + j] = sj / (double)cnt;
+      }
+    } else {  // one thread per residue, rows in order (the fold of ph_fold_sums)
+      for (int j = tid; j < rows; j += blockDim.x) {
+        const int cnt = j < nfull ? R : R - 1;
+        double sj;
+        if constexpr (sizeof(T) == 8) {
+          sj = column_sum(work, j, p, cnt);
+        } else {
+          sj = 0.0;
+          for (int r = 0; r < cnt; ++r) sj += (double)work[j + r * p];
+        }
+        wout[row0 + j] = sj / (double)cnt;
+      }
+    }
+    __syncthreads();
+    const double* mw = wout + row0;  // (read back through L2 by the other threads of the workgroup)
+    double rs = 0.0;
+    for (int j = tid; j < rows; j += blockDim.x) {
+      const double m = mw[j];
+      rs = fma((double)(j < nfull ? R : R - 1) * m, m, rs);
+    }
+    recon_sq = block_sum(rs, red);
+    if (tid == 0) {
+      periods_out[w * num + nb] = (uint32_t)p;
+      norms_out[w * num + nb] = nrm;
+      keeps_out[w * num + nb] = keep;
+    }
+    nb += 1;
+    row0 += rows;
+    if (stopped_by_test) break;  // the residual stays the one the test saw
+    // ---- residual -= A^T w
+    for (int n = tid; n < N; n += blockDim.x) {
+      const int j = n % p;
+      if (j < rows) work[n] = (T)((double)work[n] - mw[j]);
+    }
+    __syncthreads();
+    lastp = p;
+    lastkeep = keep;
+    lastnorm = nrm;
+  }
+  __syncthreads();
+  for (int b = nb + tid; b < num; b += blockDim.x) {
+    periods_out[w * num + b] = 0u;
+    norms_out[w * num + b] = 0.0;
+    keeps_out[w * num + b] = 0;
+  }
+  for (int r = row0 + tid; r < kcap; r += blockDim.x) wout[r] = 0.0;
+  for (int n = tid; n < N; n += blockDim.x) resid_out[w * (int64_t)N + n] = work[n];
+  if (tid == 0) {
+    counts_out[2 * w] = stopped_by_test ? nb - 2 : nb;  // (nb counts the re-fitted block too)
     counts_out[2 * w + 1] = nb;
     status_out[w] = status;
   }

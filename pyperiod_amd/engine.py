@@ -344,11 +344,14 @@ class PeriodEngine:
                    x.size, 0, out.ctypes.data)
         return out
 
-    def qo_find_periods(self, x, num, thresh, min_length=2, max_length=None, kcap=512):
-        """QOPeriods.find_periods (plain projection, update_weights=True, default test function)
-        for a batch.  -> periods (W,num) u32, norms (W,num), keeps (W,num) i32, counts (W,2) i32,
-        weights (W,kcap) f64, residual (W,N), status (W)."""
+    def qo_find_periods(self, x, num, thresh, min_length=2, max_length=None, kcap=512, trunc=False, update_weights=True):
+        """QOPeriods.find_periods (non-orthogonal selection, default test function) for a batch.
+        -> periods (W,num) u32, norms (W,num), keeps (W,num) i32, counts (W,2) i32, weights (W,kcap) f64,
+        residual (W,N), status (W).  trunc: trunc_to_integer_multiple selection; update_weights=False:
+        the fixed-weight loop (PH_FLAG_KEEP_WEIGHTS) -- rows of block b are keeps[b], or periods[b] when
+        keeps[b] == 0, and counts[w, 1] blocks include the re-fitted last one (periodhip.h)."""
         x, code, W, N, fl, mk = self._prep(x)
+        fl |= (_ffi.PH_FLAG_TRUNC if trunc else 0) | (0 if update_weights else _ffi.PH_FLAG_KEEP_WEIGHTS)
         if max_length is None:
             max_length = N // 3
         num = int(num)
@@ -364,9 +367,13 @@ class PeriodEngine:
                    mk.addr(weights), mk.addr(resid), mk.addr(status))
         return periods, norms, keeps, counts, weights, resid, status
 
-    def qo_feasible(self, n, dtype=np.float64, kcap=512, max_length=None) -> bool:
+    def qo_feasible(self, n, dtype=np.float64, kcap=512, max_length=None, update_weights=True) -> bool:
         """Whether ph_qo_find_periods can run a window of n samples with `kcap` dictionary rows
-        (bookkeeping + the work vectors of the conjugate-gradient solve must fit the workgroup's LDS)."""
+        (bookkeeping + the work vectors of the conjugate-gradient solve must fit the workgroup's LDS).
+        The fixed-weight loop (update_weights=False) keeps nothing but the window in LDS (its divisor set and weights
+        live in HBM): every n and max_length is feasible."""
+        if not update_weights:
+            return True
         ok = C.c_int(0)
         code = _NP_DTYPES[np.dtype(dtype)]
         _ffi.check(self._lib.ph_qo_feasible(self._ctx, code, int(n), int(max_length if max_length is not None else n // 3),

@@ -68,7 +68,7 @@ extern "C" {
 /* per-window status words written by the algorithm kernels */
 #define PH_ST_OK 0
 #define PH_ST_NO_PERIOD 1 /* no candidate period had a positive norm (reference raises) */
-#define PH_ST_ITER_CAP 2  /* iteration bound hit before `num` periods were found */
+#define PH_ST_ITER_CAP 2  /* iteration bound hit before `num` periods were found (qo_find_periods: of the solve) */
 #define PH_ST_CAP 3       /* more accepted periods than `cap` (small_to_large) */
 
 typedef struct ph_ctx ph_ctx;
@@ -229,6 +229,8 @@ int ph_dict_project(ph_ctx* ctx, const double* x, const double* basis, int rows,
  * by one when the test function stopped the loop, QOPeriods.py:584-592); weights (W, kcap)
  * float64, rows of block b start at sum(keeps[:b]); residual (W, N) dtype of x.
  * kcap = capacity in dictionary rows per window (status PH_ST_CAP when exceeded).
+ * A conjugate-gradient solve that does not converge within its iteration bound (an ill-conditioned dictionary that
+ * numpy.linalg.solve still solves) ends the window with PH_ST_ITER_CAP; callers re-run such windows on the host.
  * PH_FLAG_TRUNC: the period is chosen by the gamma norm of the trunc projection (Periods.py:178-184); the solve
  * is unchanged.  A selection without a positive norm then ends the window with PH_ST_NO_PERIOD.
  * PH_FLAG_KEEP_WEIGHTS (update_weights=False, QOPeriods.py:645-714): each new block is fitted alone to the running
@@ -251,6 +253,17 @@ int ph_qo_find_periods(ph_ctx* ctx, const void* x, int dtype, int64_t W, int N, 
  * rows on this device (bookkeeping and the six work vectors of the conjugate-gradient solve fit the
  * workgroup's LDS; the window joins them there or moves to the HBM workspace), else 0 -- callers fall back to a host-driven loop instead of catching PH_E_ARG. */
 int ph_qo_feasible(ph_ctx* ctx, int dtype, int N, int max_length, int kcap, int* ok);
+
+/* Where ph_qo_find_periods would put the residual window of one workgroup for these arguments, and the LDS it
+ * would ask for (*lds_bytes), without running anything: PH_QO_LDS_OVERLAY = window in LDS, the solver's work
+ * vectors overlay it; PH_QO_LDS_BEHIND = window in LDS, the work vectors (k_qo_find) or nothing (PH_FLAG_KEEP_WEIGHTS)
+ * behind it; PH_QO_HBM = window in the HBM workspace.  The answer is computed by the code the launch uses and honours
+ * PH_QO_HBM_WINDOW; max_length < 0 means N / 3.  Arguments the launch refuses return its error code. */
+#define PH_QO_LDS_OVERLAY 0
+#define PH_QO_LDS_BEHIND 1
+#define PH_QO_HBM 2
+int ph_qo_plan_info(ph_ctx* ctx, int dtype, int N, int max_length, int kcap, unsigned flags, int* lds_bytes,
+                    int* placement);
 
 /* ---- QOPeriods.get_best_period_orthogonal / eq_3 / auto_corr (QOPeriods.py:1122-1232) -----
  * powers (W, max_p) float64: the Muresan-Parks orthogonal period powers `pows` for q < max_p

@@ -478,10 +478,35 @@ def qo_solve_quadratic(x: np.ndarray, a: np.ndarray):
     return w, a.T @ w
 
 
-def qo_find_periods(data, num, thresh, min_length=2, max_length=None):
-    """QOPeriods.find_periods, non-orthogonal / update_weights=True branch
-    (QOPeriods.py:373-596 with :468-478 and :510-522) -- the only branch that runs in the v1
-    tree."""
+def qo_fixed_weight_block(res, nonzero, n: int):
+    """_dont_update_weights (QOPeriods.py:645-714): the newest period keeps its period minus the Euler-phi mass of the
+    divisors it shares with the earlier periods (:693-705); Pp's ``matrix[:keep] if keep else matrix`` (:970-974)
+    then hands a keep of 0 ALL p rows.  The block is solved against the running residual alone (:706-708).
+    -> (block rows, keep, weights, reconstruction)."""
+    last = int(nonzero[-1])
+    keep = last
+    existing = set()
+    for q in nonzero[:-1]:
+        existing |= factor_set(int(q))
+    for f in sorted(existing & factor_set(last)):
+        keep -= phi(f)
+    b = qo_natural_rows(last, n, keep)
+    w, recon = qo_solve_quadratic(res, b)
+    return b, keep, w, recon
+
+
+def qo_find_periods(data, num, thresh, min_length=2, max_length=None, trunc=False, update_weights=True, trace=None):
+    """QOPeriods.find_periods, non-orthogonal branch (QOPeriods.py:373-596 with :468-478) with the default test
+    function -- the only branch that runs in the v1 tree.
+
+    trunc: the candidates' projections use trunc_to_integer_multiple (Periods.py:178-184).
+    update_weights=True re-solves the whole dictionary against the data each iteration (:510-522, :598-643);
+    False fits only the newest period's block to the running residual (:523-538, :645-714) and keeps the
+    earlier weights.  When the test function stops the loop, the last period's block is fitted once more
+    (:560-583) -- with update_weights=False it is appended again and the residual is not updated -- and one
+    period fewer is reported (:584-592).
+    trace: a list that receives, per selection, the best and second-best gamma norm and the best period."""
+    data = np.asarray(data)
     n = len(data)
     if max_length is None:
         max_length = n // 3
@@ -503,21 +528,36 @@ def qo_find_periods(data, num, thresh, min_length=2, max_length=None):
         )
     recon = None
     nonzero = periods[:0]
+    a, dims, w = np.empty((0, n)), {}, np.array([])  # :384-386
+
+    def fixed_weights(res):  # :645-714
+        b, keep, wb, rec = qo_fixed_weight_block(res, nonzero, n)
+        dims[str(nonzero[-1])] = keep
+        return np.vstack((a, b)), dims, np.concatenate((w, wb)), rec
+
     for i in range(num):
         if i == 0 or rms(recon) > rms(data) * thresh:  # default test_function, :391,418
-            best_p, best_norm = 0, 0
+            best_p, best_norm, second = 0, 0, 0.0
             for p in range(min_length, max_length + 1):  # :470-478
-                nrm = periodic_norm(project(res, p, False, False), p)
+                nrm = periodic_norm(project(res, p, trunc, False), p)
                 if nrm > best_norm:
-                    best_p, best_norm = p, nrm
+                    best_p, best_norm, second = p, nrm, best_norm
+                elif nrm > second:
+                    second = nrm
+            if trace is not None:
+                trace.append((best_norm, second, best_p))
             periods[i], norms[i] = best_p, best_norm
             nonzero = periods[periods > 0]
             try:
-                a, dims = qo_get_subspaces(nonzero, n)
-                w, recon = qo_solve_quadratic(data, a)
+                if update_weights:
+                    a, dims = qo_get_subspaces(nonzero, n)
+                    w, recon = qo_solve_quadratic(data, a)
+                    res = data - recon
+                else:
+                    a, dims, w, recon = fixed_weights(res)
+                    res = res - recon
             except np.linalg.LinAlgError:  # :552-559
                 break
-            res = data - recon
             out = {
                 "periods": nonzero,
                 "norms": norms[: len(nonzero)],
@@ -526,8 +566,11 @@ def qo_find_periods(data, num, thresh, min_length=2, max_length=None):
                 "basis_dictionary": dims,
             }
         else:  # :560-594
-            a, dims = qo_get_subspaces(nonzero, n)
-            w, recon = qo_solve_quadratic(data, a)
+            if update_weights:
+                a, dims = qo_get_subspaces(nonzero, n)
+                w, recon = qo_solve_quadratic(data, a)
+            else:
+                a, dims, w, recon = fixed_weights(res)
             out = {
                 "periods": nonzero[:-1],
                 "norms": norms[: len(nonzero) - 1],

@@ -20,6 +20,7 @@ PH_FLAG_KEEP_WEIGHTS = 32  # ph_qo_find_periods: update_weights=False
 PH_STREAM_DEFAULT = 1  # ph_set_stream handle of the device default stream (its real handle, 0, means "own stream")
 PH_SWEEP_NORM, PH_SWEEP_NORM_GAMMA, PH_SWEEP_MAXABS = 0, 1, 2
 PH_ST_OK, PH_ST_NO_PERIOD, PH_ST_ITER_CAP, PH_ST_CAP = 0, 1, 2, 3
+PH_QO_LDS_OVERLAY, PH_QO_LDS_BEHIND, PH_QO_HBM = 0, 1, 2  # ph_qo_plan_info placements
 
 _vp, _i, _i64, _u, _d = C.c_void_p, C.c_int, C.c_int64, C.c_uint, C.c_double
 _pi32 = C.c_void_p  # int32 tables are passed as raw addresses of numpy arrays
@@ -53,6 +54,7 @@ SIGNATURES = {
     "ph_dict_project": [_vp, _vp, _vp, _i, _i, _u, _vp],
     "ph_qo_find_periods": [_vp, _vp, _i, _i64, _i, _i, _d, _i, _i, _i, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ph_qo_feasible": [_vp, _i, _i, _i, _i, C.POINTER(_i)],
+    "ph_qo_plan_info": [_vp, _i, _i, _i, _i, _u, C.POINTER(_i), C.POINTER(_i)],
     "ph_orth_powers": [_vp, _vp, _i, _i64, _i, _i, _i, _u, _vp, _vp, _vp],
     "ph_fold_sums": [_vp, _vp, _i, _i64, _i, _pi32, _pi32, _i, _u, _vp],
     "ph_tile_sum": [_vp, _vp, _i64, _i, _pi32, _pi32, _i, _i, _u, _vp],

@@ -452,8 +452,8 @@ using ph::kRedDoubles;
 // it fits; the work vectors then OVERLAY it if it is large enough (the window is dead during a solve) -- 79 KB per
 // workgroup for N = 16384 fp32 with kcap = 1024, two workgroups per CU -- and sit behind it otherwise.  Windows
 // that do not fit (long fp64 windows) move to the HBM workspace and the sweeps read them through L2.
-int qo_lds_layout(ph_ctx* c, size_t sz, int N, int max_length, int kcap, size_t* lds_out, bool* lds_window_out,
-                  bool* overlay_out) {
+// *placement_out = PH_QO_LDS_OVERLAY, PH_QO_LDS_BEHIND or PH_QO_HBM.
+int qo_lds_layout(ph_ctx* c, size_t sz, int N, int max_length, int kcap, size_t* lds_out, int* placement_out) {
   const size_t kv = (size_t)kcap + ph::kQoMaxBlocks;
   const size_t fixed = carve_bytes(kRedDoubles, 8) + carve_bytes(kMaxWaves, 8) + carve_bytes(kMaxWaves, 4) +
                        2 * carve_bytes(ph::kQoMaxBlocks, 4) + carve_bytes(ph::kQoMaxBlocks + 1, 4) +
@@ -470,16 +470,39 @@ int qo_lds_layout(ph_ctx* c, size_t sz, int N, int max_length, int kcap, size_t*
   const size_t with_window = fixed + (overlay ? win : win + solver);
   const bool lds_window = !c->qo_hbm_window && with_window <= limit;
   *lds_out = lds_window ? with_window : fixed + solver;
-  *lds_window_out = lds_window;
-  *overlay_out = lds_window && overlay;
+  *placement_out = !lds_window ? PH_QO_HBM : overlay ? PH_QO_LDS_OVERLAY : PH_QO_LDS_BEHIND;
   return PH_OK;
 }
 
 // LDS layout of k_qo_greedy: the residual window (or nothing: the HBM workspace holds it) and the reductions.  The
 // divisor bitset lives in the HBM workspace and the block's weights in the output row, so the LDS need does not depend
-// on max_length or kcap, and every N and max_length is feasible.
-size_t qo_greedy_fixed_bytes() {
-  return carve_bytes(kRedDoubles, 8) + carve_bytes(kMaxWaves, 8) + carve_bytes(kMaxWaves, 4);
+// on max_length or kcap, and every N and max_length is feasible.  A window in LDS counts as PH_QO_LDS_BEHIND (there
+// are no work vectors to overlay it).
+void qo_greedy_layout(const ph_ctx* c, size_t sz, int N, size_t* lds_out, int* placement_out) {
+  const size_t fixed = carve_bytes(kRedDoubles, 8) + carve_bytes(kMaxWaves, 8) + carve_bytes(kMaxWaves, 4);
+  const size_t with_window = fixed + carve_bytes(N + kPad, sz);
+  const bool lds_window = !c->qo_hbm_window && with_window <= (size_t)c->lds_limit;
+  *lds_out = lds_window ? with_window : fixed;
+  *placement_out = lds_window ? PH_QO_LDS_BEHIND : PH_QO_HBM;
+}
+
+// Argument checks and layout of ph_qo_find_periods, shared by the launch and ph_qo_plan_info.  max_length < 0 means
+// N / 3 (QOPeriods.py:374-375); *max_length_io receives the value used.
+int qo_plan(ph_ctx* c, int dtype, int N, int* max_length_io, int kcap, unsigned flags, size_t* lds_out,
+            int* placement_out) {
+  if (flags & PH_FLAG_ORTH)
+    return fail(PH_E_UNSUPPORTED, "ph_qo_find_periods: orthogonal selection is not implemented on the device");
+  const bool keep_weights = flags & PH_FLAG_KEEP_WEIGHTS;
+  if (*max_length_io < 0) *max_length_io = N / 3;
+  if (!keep_weights && (kcap < 1 || kcap > 2048)) return fail(PH_E_ARG, "kcap=%d must be in [1, 2048]", kcap);
+  if (keep_weights && (kcap < 1 || kcap > ph::kQoGreedyMaxRows))
+    return fail(PH_E_ARG, "kcap=%d must be in [1, %d] with PH_FLAG_KEEP_WEIGHTS", kcap, ph::kQoGreedyMaxRows);
+  const size_t sz = elem_size(dtype);
+  if (keep_weights) {
+    qo_greedy_layout(c, sz, N, lds_out, placement_out);
+    return PH_OK;
+  }
+  return qo_lds_layout(c, sz, N, *max_length_io, kcap, lds_out, placement_out);
 }
 
 // LDS of k_mbest_step1_pair: the pair window, one fp64 staging buffer, bookkeeping of two windows.
@@ -1543,29 +1566,17 @@ int ph_qo_find_periods(ph_ctx* c, const void* x, int dtype, int64_t W, int N, in
   PH_TRY(check_common(c, x, dtype, W, N));
   if (!periods || !norms || !keeps || !counts || !weights || !residual || !status)
     return fail(PH_E_ARG, "output pointer is NULL");
-  if (flags & PH_FLAG_ORTH)
-    return fail(PH_E_UNSUPPORTED, "ph_qo_find_periods: orthogonal selection is not implemented on the device");
   const bool trunc = flags & PH_FLAG_TRUNC;
   const bool keep_weights = flags & PH_FLAG_KEEP_WEIGHTS;
   if (num < 1) return fail(PH_E_ARG, "num=%d must be >= 1", num);
-  if (max_length < 0) max_length = N / 3;  // QOPeriods.py:374-375
+  size_t lds;
+  int placement;
+  PH_TRY(qo_plan(c, dtype, N, &max_length, kcap, flags, &lds, &placement));
   if (min_length < 1 || max_length < min_length)
     return fail(PH_E_ARG, "need 1 <= min_length <= max_length (got %d, %d)", min_length, max_length);
-  if (!keep_weights && (kcap < 1 || kcap > 2048)) return fail(PH_E_ARG, "kcap=%d must be in [1, 2048]", kcap);
-  if (keep_weights && (kcap < 1 || kcap > ph::kQoGreedyMaxRows))
-    return fail(PH_E_ARG, "kcap=%d must be in [1, %d] with PH_FLAG_KEEP_WEIGHTS", kcap, ph::kQoGreedyMaxRows);
   PH_HIP(hipSetDevice(c->device));
   const size_t sz = elem_size(dtype);
-  size_t lds;
-  bool lds_window, overlay = false;
-  if (keep_weights) {
-    const size_t fixed = qo_greedy_fixed_bytes();
-    const size_t with_window = fixed + carve_bytes(N + kPad, sz);
-    lds_window = !c->qo_hbm_window && with_window <= (size_t)c->lds_limit;
-    lds = lds_window ? with_window : fixed;
-  } else {
-    PH_TRY(qo_lds_layout(c, sz, N, max_length, kcap, &lds, &lds_window, &overlay));
-  }
+  const bool lds_window = placement != PH_QO_HBM, overlay = placement == PH_QO_LDS_OVERLAY;
   void* gwin = nullptr;
   if (!lds_window) {
     PH_TRY(ensure(c, c->buf[B_GWIN], (size_t)W * ph::win_stride(N + kPad) * sz));
@@ -1645,8 +1656,19 @@ int ph_qo_feasible(ph_ctx* c, int dtype, int N, int max_length, int kcap, int* o
   if (N < 1 || kcap < 1 || kcap > 2048) return PH_OK;
   if (max_length < 0) max_length = N / 3;
   size_t lds;
-  bool lds_window, overlay;
-  if (qo_lds_layout(c, elem_size(dtype), N, max_length, kcap, &lds, &lds_window, &overlay) == PH_OK) *ok = 1;
+  int placement;
+  if (qo_lds_layout(c, elem_size(dtype), N, max_length, kcap, &lds, &placement) == PH_OK) *ok = 1;
+  return PH_OK;
+}
+
+int ph_qo_plan_info(ph_ctx* c, int dtype, int N, int max_length, int kcap, unsigned flags, int* lds_bytes,
+                    int* placement) {
+  if (!c || !lds_bytes || !placement) return fail(PH_E_ARG, "NULL argument");
+  if (dtype != PH_F64 && dtype != PH_F32) return fail(PH_E_ARG, "dtype must be PH_F64 or PH_F32");
+  if (N < 1) return fail(PH_E_ARG, "N=%d must be >= 1", N);
+  size_t lds;
+  PH_TRY(qo_plan(c, dtype, N, &max_length, kcap, flags, &lds, placement));
+  *lds_bytes = (int)lds;
   return PH_OK;
 }
 

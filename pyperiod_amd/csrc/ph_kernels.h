@@ -2541,9 +2541,11 @@ __global__ __launch_bounds__(kBlock) void k_tile_sum(const double* __restrict__ 
 //   counts of the indicator rows) is never formed, its rows are regenerated inside the product (qo_offdiag)
 //   reconstruction A^T w, residual
 // The reference stops when rms(reconstruction) <= rms(data) * thresh (default test_function)
-// or when numpy.linalg.solve raises LinAlgError (here: non-positive curvature or no convergence of the
-// solve, a period that adds no new rows, or a repeated period -- the cases that make the reference's
-// matrix singular).  counts[w] = {periods reported, blocks in the dictionary}.
+// or when numpy.linalg.solve raises LinAlgError (here: non-positive curvature or a non-finite residual of
+// the solve, a period that adds no new rows, or a repeated period -- the cases that make the reference's
+// matrix singular).  A solve that has not converged after its iteration bound (an ill-conditioned but
+// regular dictionary) ends the window with PH_ST_ITER_CAP: the host loop, which solves as the reference
+// does, takes it.  counts[w] = {periods reported, blocks in the dictionary}.
 // ======================================================================================
 #ifndef PH_QO_OCC
 #define PH_QO_OCC __attribute__((amdgpu_waves_per_eu(8, 8)))  // two 16-wave workgroups per CU need <= 64 VGPRs
@@ -2960,7 +2962,13 @@ __global__ __launch_bounds__(1024) PH_QO_OCC void k_qo_find(const T* __restrict_
         }
         __syncthreads();
       }
-      if (!(rr <= tol2)) singular = true;  // no convergence (or not finite): a numerically singular dictionary
+      if (!(rr <= tol2)) {
+        // no convergence: a residual that is not finite means a singular dictionary; a finite one after itmax
+        // positive-curvature steps is an ill-conditioned but regular one, which numpy.linalg.solve still solves --
+        // PH_ST_ITER_CAP hands the window to the host loop
+        singular = true;
+        if (rr < 1.0 / 0.0 && status == 0) status = 2;
+      }
 #ifdef PH_QO_TIMERS
       cg_iters += iter;
 #endif

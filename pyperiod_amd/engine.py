@@ -380,6 +380,17 @@ class PeriodEngine:
                                             int(kcap), C.byref(ok)))
         return bool(ok.value)
 
+    def qo_plan_info(self, n, dtype=np.float64, kcap=512, max_length=None, trunc=False, update_weights=True):
+        """-> (placement, lds_bytes): where qo_find_periods would keep the residual window of n samples --
+        _ffi.PH_QO_LDS_OVERLAY, PH_QO_LDS_BEHIND or PH_QO_HBM (periodhip.h) -- and the LDS one workgroup asks for.
+        Nothing runs on the device."""
+        fl = (_ffi.PH_FLAG_TRUNC if trunc else 0) | (0 if update_weights else _ffi.PH_FLAG_KEEP_WEIGHTS)
+        lds, where = C.c_int(0), C.c_int(0)
+        code = _NP_DTYPES[np.dtype(dtype)]
+        _ffi.check(self._lib.ph_qo_plan_info(self._ctx, code, int(n), int(max_length if max_length is not None else n // 3),
+                                             int(kcap), fl, C.byref(lds), C.byref(where)))
+        return where.value, lds.value
+
     def orth_powers(self, x, max_p=None, normalize=False, want_autocorr=False, want_eq3=False):
         """Orthogonal period powers (QOPeriods.get_best_period_orthogonal(return_powers=True)).
         -> pows (W, max_p) [, autocorr (W, N)] [, eq3 (W, max_p)]."""

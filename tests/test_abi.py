@@ -44,7 +44,8 @@ def test_header_constants_match_binding():
     text = open(os.path.join(ROOT, "include", "periodhip.h")).read()
     for name in ("PH_OK", "PH_E_ARG", "PH_E_HIP", "PH_E_NOMEM", "PH_E_CAP", "PH_E_UNSUPPORTED", "PH_F64", "PH_F32",
                  "PH_FLAG_TRUNC", "PH_FLAG_ORTH", "PH_FLAG_SINGLE", "PH_FLAG_DEVICE", "PH_FLAG_NOSYNC", "PH_SWEEP_NORM",
-                 "PH_SWEEP_NORM_GAMMA", "PH_SWEEP_MAXABS", "PH_ST_OK", "PH_ST_NO_PERIOD", "PH_ST_ITER_CAP", "PH_ST_CAP"):
+                 "PH_SWEEP_NORM_GAMMA", "PH_SWEEP_MAXABS", "PH_ST_OK", "PH_ST_NO_PERIOD", "PH_ST_ITER_CAP", "PH_ST_CAP",
+                 "PH_QO_LDS_OVERLAY", "PH_QO_LDS_BEHIND", "PH_QO_HBM"):
         m = re.search(rf"#define {name} \(?(-?\d+)u?\)?", text)
         assert m, name
         assert int(m.group(1)) == getattr(_ffi, name), name
@@ -68,6 +69,7 @@ def test_helper_entry_points_reject_null_without_gpu(lib):
     n_pass, n_per, ok = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(7)
     assert lib.ph_sweep_plan_info(None, 2, 1365, ctypes.byref(n_pass), ctypes.byref(n_per)) == _ffi.PH_E_ARG
     assert lib.ph_qo_feasible(None, _ffi.PH_F64, 4096, -1, 512, ctypes.byref(ok)) == _ffi.PH_E_ARG
+    assert lib.ph_qo_plan_info(None, _ffi.PH_F64, 4096, -1, 512, 0, ctypes.byref(ok), ctypes.byref(ok)) == _ffi.PH_E_ARG
     assert lib.ph_small_to_large(None, None, 0, 1, 16, 0.1, -1, None, None, 0, _ffi.PH_FLAG_DEVICE | _ffi.PH_FLAG_NOSYNC, 4,
                                  None, None, None, None, None) == _ffi.PH_E_ARG
     assert _ffi.PH_FLAG_NOSYNC == 16

@@ -324,3 +324,39 @@ def test_oracle_project_float32_trunc_matches_reference(golden):
             for orth in (False, True):
                 got = po.project(x, p, True, orth)
                 assert got.dtype == np.float32 and np.array_equal(got, g[f"n{n}_p{p}_o{int(orth)}"]), (n, p, orth)
+
+
+# cases of tests/golden/qoperiods_edges.npz whose oracle run takes seconds on the CPU (blocks40, blocks40_t and
+# blocks70 solve dense dictionaries of 1700-1800 rows 40-70 times; make_golden_qo_edges.py checks them)
+QO_EDGE_SLOW = ("blocks40", "blocks40_t", "blocks70")
+
+
+def qo_edge_case(g, tag):
+    """-> (input, find_periods keywords, trunc, update_weights) of one case of qoperiods_edges.npz."""
+    num, thresh, lo, hi, trunc, uw = g[f"{tag}_kw"]
+    kw = dict(num=int(num), thresh=float(thresh), min_length=int(lo), max_length=None if hi < 0 else int(hi))
+    return g[f"{tag}_x"], kw, bool(trunc), bool(uw)
+
+
+def test_qoperiods_edges(golden):
+    """QOPeriods.find_periods at the edges of the device loops (update_weights=False with its keep == 0 quirk and the
+    re-fitted last block, trunc, 16/17/70-block dictionaries, windows of 24-127 samples, float32 input): the oracle's
+    trunc= and update_weights= branches against the reference."""
+    g = golden("qoperiods_edges")
+    tags = [str(t) for t in g["tags"]]
+    assert {"keep_a_p", "keep_b_t", "blocks16", "blocks17", "blocks70_k", "small24_kt", "f32_t"} <= set(tags)
+    for tag in ("keep_d301", "keep_d777"):  # cases where trunc changes the fixed-weight loop's selection
+        assert not np.array_equal(g[f"{tag}_p_periods"], g[f"{tag}_t_periods"]), tag
+    for tag in tags:
+        if tag in QO_EDGE_SLOW:
+            continue
+        x, kw, trunc, uw = qo_edge_case(g, tag)
+        f32 = x.dtype == np.float32
+        out, res = po.qo_find_periods(x.astype(np.float64), trunc=trunc, update_weights=uw, **kw)
+        assert np.array_equal(out["periods"], g[f"{tag}_periods"]), tag
+        assert [int(k) for k in out["basis_dictionary"]] == list(g[f"{tag}_dict_keys"]), tag
+        assert list(out["basis_dictionary"].values()) == list(g[f"{tag}_dict_vals"]), tag
+        assert out["subspaces"].shape[0] == int(g[f"{tag}_rows"]) == out["weights"].size, tag
+        assert rel_err(out["norms"], g[f"{tag}_norms"]) < (1e-5 if f32 else TOL), tag
+        assert rel_err(out["weights"], g[f"{tag}_weights"]) < (1e-4 if f32 else 1e-8), tag
+        assert rel_err(res, g[f"{tag}_residual"]) < (1e-4 if f32 else 1e-8), tag

@@ -161,6 +161,24 @@ def test_fixed_weight_restatement_keep_quirk():
     assert out["subspaces"].shape == (40 + 36 + 36, 900) and out["basis_dictionary"] == {"40": 40, "37": 36}
 
 
+def test_restatement_matches_edge_fixture(golden):
+    """np_find_periods against the reference's edge cases (tests/golden/qoperiods_edges.npz; the three cases with
+    dictionaries of 1700+ rows are left to the generator's oracle check)."""
+    g = golden("qoperiods_edges")
+    for tag in (str(t) for t in g["tags"]):
+        if tag in ("blocks40", "blocks40_t", "blocks70"):
+            continue
+        num, thresh, lo, hi, trunc, uw = g[f"{tag}_kw"]
+        x = g[f"{tag}_x"]
+        hi = x.size // 3 if hi < 0 else int(hi)
+        out, res = np_find_periods(x, int(num), thresh, int(lo), hi, trunc=bool(trunc), update_weights=bool(uw))
+        tol = 1e-4 if x.dtype == np.float32 else 1e-8
+        assert np.array_equal(out["periods"], g[f"{tag}_periods"]), tag
+        assert list(out["basis_dictionary"].values()) == list(g[f"{tag}_dict_vals"]), tag
+        assert out["weights"].size == int(g[f"{tag}_rows"]), tag
+        assert rel_err(out["weights"], g[f"{tag}_weights"]) < tol and rel_err(res, g[f"{tag}_residual"]) < tol, tag
+
+
 @pytest.fixture(scope="module")
 def lib():
     import __graft_entry__ as ge

@@ -77,7 +77,9 @@ typedef struct ph_ctx ph_ctx;
 int ph_version(void);
 const char* ph_last_error(void);
 int ph_device_count(int* count);
-/* Create a context on HIP device `device` with its own non-blocking stream. */
+/* Create a context on HIP device `device` with its own non-blocking stream.  PH_HBM_WINDOW=1 in the environment
+ * (read here) makes the context keep every window and every second window-sized buffer in its HBM workspaces, as
+ * if the LDS could not hold them: an independent same-precision reference for the LDS paths. */
 int ph_create(int device, ph_ctx** out);
 int ph_destroy(ph_ctx* ctx);
 /* Borrow an existing hipStream_t (e.g. torch.cuda.current_stream().cuda_stream); NULL
@@ -100,10 +102,12 @@ int ph_profile_read(ph_ctx* ctx, float* ms, int cap, int* count);
 const char* ph_profile_name(ph_ctx* ctx, int i);
 /* Multiprocessor count and per-workgroup LDS limit of the context's device. */
 int ph_device_info(ph_ctx* ctx, int* num_cu, int* lds_bytes);
-/* Largest N for which a window of `dtype` stays LDS-resident (the fast path).  Longer windows are
- * accepted by every entry point: the window then lives in (or is read straight from) HBM / L2 --
+/* Largest N for which ph_sweep keeps a window of `dtype` in LDS (the fast path): exactly the last N at which
+ * ph_plan_info(PH_OP_SWEEP) reports PH_PLAN_LDS for the window (the same N in every mode: a second buffer leaves
+ * the LDS first).  Every other entry point switches at an N of its own, which ph_plan_info reports.  Longer
+ * windows are accepted by every entry point: the window then lives in (or is read straight from) HBM / L2 --
  * project, sweep, m_best, small_to_large, best_correlation, ramanujan_norms, best_frequency,
- * qo_find_periods, fold_sums and orth_powers alike.  `flags` is ignored. */
+ * qo_find_periods, fold_sums and orth_powers alike.  `flags` is ignored.  0 under PH_HBM_WINDOW. */
 int ph_max_window(ph_ctx* ctx, int dtype, unsigned flags, int* max_n);
 
 /* Pass plan of the norm sweeps (ph_sweep norm modes, ph_m_best, ph_qo_find_periods) over the
@@ -264,6 +268,69 @@ int ph_qo_feasible(ph_ctx* ctx, int dtype, int N, int max_length, int kcap, int*
 #define PH_QO_HBM 2
 int ph_qo_plan_info(ph_ctx* ctx, int dtype, int N, int max_length, int kcap, unsigned flags, int* lds_bytes,
                     int* placement);
+
+/* ---- launch plan of an entry point ------------------------------------------------------
+ * What entry point `op` would launch for windows of N samples of `dtype` with these parameters and `flags`, without
+ * running anything.  The answer comes from the planning function the launch itself uses (it honours PH_HBM_WINDOW
+ * and the PH_*_PAIR / block overrides of the context); arguments the launch refuses return its error code.
+ * params[0 .. n_params-1], by op (a missing entry takes the default shown; -1 = the reference's default):
+ *   PH_OP_PROJECT           {max period in p_list}
+ *   PH_OP_SWEEP             {p_lo, p_hi, mode}                       p_hi default N / 3
+ *   PH_OP_M_BEST            {num, min_length, max_length, max_fac}  max_fac: most entries of one fac_off row
+ *                                                                   (default: proper divisors, 1 and p removed)
+ *   PH_OP_SMALL_TO_LARGE    {n_periods}                              default N / 2
+ *   PH_OP_BEST_CORRELATION  {max_length}                             default N / 3
+ *   PH_OP_BEST_FREQUENCY    {win_size}                               default N
+ *   PH_OP_RAMANUJAN         {q_lo, q_hi}                             default 2, N / 3
+ *   PH_OP_ORTH_POWERS       {max_p}                                  default N / 2
+ *   PH_OP_FOLD_SUMS         {}
+ * ph_tile_sum and ph_dict_project do not depend on N (LDS of sum(keep) doubles / none) and have no op.
+ * out[PH_PLAN_LEN] int32: out[PH_PLAN_KERNELS] kernels launched per call (per round for best_frequency), then one
+ * record of PH_PLAN_STRIDE words per kernel at out[PH_PLAN_K0] (m_best step 1, best_frequency spectrum) and
+ * out[PH_PLAN_K1] (m_best step 2, best_frequency update); slot i of kernel k is out[PH_PLAN_K0 + k * PH_PLAN_STRIDE + i]:
+ *   PH_PLAN_VARIANT      PH_PLAN_ONE (one window per workgroup), PH_PLAN_PAIR (two windows, float screen),
+ *                        PH_PLAN_FFT / PH_PLAN_CHIRP / PH_PLAN_DIRECT (best_frequency spectrum)
+ *   PH_PLAN_WINDOW       PH_PLAN_LDS or PH_PLAN_HBM: where the kernel reads the window (the k_bf_fft / k_bf_chirp
+ *                        spectra always read the residual from HBM into their LDS work array)
+ *   PH_PLAN_SECOND       PH_PLAN_NONE, PH_PLAN_LDS or PH_PLAN_HBM: the second window-sized buffer (materialised
+ *                        projection; ph_orth_powers: its autocorrelation work arrays)
+ *   PH_PLAN_BLOCK        threads per workgroup
+ *   PH_PLAN_LDS_BYTES    dynamic LDS per workgroup
+ *   PH_PLAN_SMALL_MEANS  m_best step 1: 1 when the means of a short winner go through LDS (split_row_means), else 0
+ *   PH_PLAN_WAVES        Ramanujan: wavefronts per workgroup (one strip pair each), else 0
+ *   PH_PLAN_PAD          Ramanujan: zeroed elements behind the LDS window (0 or 256), else 0 */
+#define PH_OP_PROJECT 0
+#define PH_OP_SWEEP 1
+#define PH_OP_M_BEST 2
+#define PH_OP_SMALL_TO_LARGE 3
+#define PH_OP_BEST_CORRELATION 4
+#define PH_OP_BEST_FREQUENCY 5
+#define PH_OP_RAMANUJAN 6
+#define PH_OP_ORTH_POWERS 7
+#define PH_OP_FOLD_SUMS 8
+#define PH_PLAN_KERNELS 0
+#define PH_PLAN_K0 1
+#define PH_PLAN_K1 9
+#define PH_PLAN_STRIDE 8
+#define PH_PLAN_LEN 17
+#define PH_PLAN_VARIANT 0
+#define PH_PLAN_WINDOW 1
+#define PH_PLAN_SECOND 2
+#define PH_PLAN_BLOCK 3
+#define PH_PLAN_LDS_BYTES 4
+#define PH_PLAN_SMALL_MEANS 5
+#define PH_PLAN_WAVES 6
+#define PH_PLAN_PAD 7
+#define PH_PLAN_ONE 0
+#define PH_PLAN_PAIR 1
+#define PH_PLAN_FFT 2
+#define PH_PLAN_CHIRP 3
+#define PH_PLAN_DIRECT 4
+#define PH_PLAN_NONE 0
+#define PH_PLAN_LDS 1
+#define PH_PLAN_HBM 2
+int ph_plan_info(ph_ctx* ctx, int op, int dtype, int N, const int32_t* params, int n_params, unsigned flags,
+                 int32_t* out);
 
 /* ---- QOPeriods.get_best_period_orthogonal / eq_3 / auto_corr (QOPeriods.py:1122-1232) -----
  * powers (W, max_p) float64: the Muresan-Parks orthogonal period powers `pows` for q < max_p

@@ -21,6 +21,14 @@ PH_STREAM_DEFAULT = 1  # ph_set_stream handle of the device default stream (its 
 PH_SWEEP_NORM, PH_SWEEP_NORM_GAMMA, PH_SWEEP_MAXABS = 0, 1, 2
 PH_ST_OK, PH_ST_NO_PERIOD, PH_ST_ITER_CAP, PH_ST_CAP = 0, 1, 2, 3
 PH_QO_LDS_OVERLAY, PH_QO_LDS_BEHIND, PH_QO_HBM = 0, 1, 2  # ph_qo_plan_info placements
+# ph_plan_info: ops, the record layout and its values (periodhip.h)
+(PH_OP_PROJECT, PH_OP_SWEEP, PH_OP_M_BEST, PH_OP_SMALL_TO_LARGE, PH_OP_BEST_CORRELATION, PH_OP_BEST_FREQUENCY,
+ PH_OP_RAMANUJAN, PH_OP_ORTH_POWERS, PH_OP_FOLD_SUMS) = range(9)
+PH_PLAN_KERNELS, PH_PLAN_K0, PH_PLAN_K1, PH_PLAN_STRIDE, PH_PLAN_LEN = 0, 1, 9, 8, 17
+(PH_PLAN_VARIANT, PH_PLAN_WINDOW, PH_PLAN_SECOND, PH_PLAN_BLOCK, PH_PLAN_LDS_BYTES, PH_PLAN_SMALL_MEANS, PH_PLAN_WAVES,
+ PH_PLAN_PAD) = range(8)
+PH_PLAN_ONE, PH_PLAN_PAIR, PH_PLAN_FFT, PH_PLAN_CHIRP, PH_PLAN_DIRECT = 0, 1, 2, 3, 4
+PH_PLAN_NONE, PH_PLAN_LDS, PH_PLAN_HBM = 0, 1, 2
 
 _vp, _i, _i64, _u, _d = C.c_void_p, C.c_int, C.c_int64, C.c_uint, C.c_double
 _pi32 = C.c_void_p  # int32 tables are passed as raw addresses of numpy arrays
@@ -55,6 +63,7 @@ SIGNATURES = {
     "ph_qo_find_periods": [_vp, _vp, _i, _i64, _i, _i, _d, _i, _i, _i, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ph_qo_feasible": [_vp, _i, _i, _i, _i, C.POINTER(_i)],
     "ph_qo_plan_info": [_vp, _i, _i, _i, _i, _u, C.POINTER(_i), C.POINTER(_i)],
+    "ph_plan_info": [_vp, _i, _i, _i, _pi32, _i, _u, _pi32],
     "ph_orth_powers": [_vp, _vp, _i, _i64, _i, _i, _i, _u, _vp, _vp, _vp],
     "ph_fold_sums": [_vp, _vp, _i, _i64, _i, _pi32, _pi32, _i, _u, _vp],
     "ph_tile_sum": [_vp, _vp, _i64, _i, _pi32, _pi32, _i, _i, _u, _vp],

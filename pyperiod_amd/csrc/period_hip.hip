@@ -88,6 +88,7 @@ struct ph_ctx {
   int qo_block = 1024;               // k_qo_find threads per workgroup (PH_QO_BLOCK overrides)
   int s2l_block = 1024;              // k_small_to_large_pair threads per workgroup (PH_S2L_BLOCK overrides, >= 512)
   bool qo_hbm_window = false;        // PH_QO_HBM_WINDOW=1: keep the residual of k_qo_find in HBM even when it fits LDS
+  bool hbm_window = false;           // PH_HBM_WINDOW=1: every window and second window-sized buffer in HBM
   // optional per-kernel HIP-event timing (ph_profile_*)
   bool prof_on = false;
   int prof_n = 0;
@@ -273,33 +274,10 @@ int check_common(ph_ctx* c, const void* x, int dtype, int64_t W, int N) {
   return PH_OK;
 }
 
-int check_lds(ph_ctx* c, size_t bytes, int N, const char* what) {
+int check_lds(const ph_ctx* c, size_t bytes, int N, const char* what) {
   if (bytes > (size_t)c->lds_limit)
     return fail(PH_E_ARG, "%s: window of N=%d needs %zu B of LDS, device limit is %d B", what, N, bytes,
                 c->lds_limit);
-  return PH_OK;
-}
-
-// Second window-sized buffer (materialised projections): in LDS when both fit, otherwise in an HBM
-// workspace of `blocks` x N elements.  `lds` comes in with the second buffer included.
-int place_second_buffer(ph_ctx* c, size_t* lds, bool needed, size_t buf_bytes, int64_t blocks, void** gbuf) {
-  *gbuf = nullptr;
-  if (!needed || *lds <= (size_t)c->lds_limit) return PH_OK;
-  *lds -= ((buf_bytes + 15) & ~size_t(15));
-  PH_TRY(ensure(c, c->buf[B_GBUF], (size_t)blocks * buf_bytes));
-  *gbuf = c->buf[B_GBUF].p;
-  return PH_OK;
-}
-
-// Window buffer: LDS when it fits (after the second buffer has been placed), otherwise an HBM
-// workspace of `blocks` slices that the kernels' <T, false> instantiations fold through L2.
-// `lds` comes in with the window buffer included.
-int place_window(ph_ctx* c, size_t* lds, size_t win_len, size_t sz, int64_t blocks, void** gwin) {
-  *gwin = nullptr;
-  if (*lds <= (size_t)c->lds_limit) return PH_OK;
-  *lds -= ph::carve_bytes(win_len, sz);
-  PH_TRY(ensure(c, c->buf[B_GWIN], (size_t)blocks * ph::win_stride(win_len) * sz));
-  *gwin = c->buf[B_GWIN].p;
   return PH_OK;
 }
 
@@ -521,6 +499,287 @@ bool pair_eligible(const ph_ctx* c, int dtype, int N, int num, int min_length, i
          pair_lds_bytes(N, num, max_length - min_length + 1) <= (size_t)c->lds_limit;
 }
 
+// ----------------------------------------------------------------------------- launch plans
+// One planning function per entry point: the variant, the placement of the window and of the second window-sized
+// buffer, the block size and the LDS of every kernel it launches, from the arguments alone (nothing is allocated or
+// launched).  The launcher and ph_plan_info both call it; the launcher only allocates the workspaces the plan names.
+struct KernelPlan {
+  int variant = PH_PLAN_ONE;
+  int window = PH_PLAN_LDS;
+  int second = PH_PLAN_NONE;
+  int block = 0;
+  size_t lds = 0;
+  int small_means = 0;
+  int waves = 0;
+  int pad = 0;
+};
+
+struct Plan {
+  int n_kernels = 1;
+  KernelPlan k[2];
+};
+
+// Second window-sized buffer (materialised projections): in LDS when both fit, otherwise in an HBM workspace.
+// `lds` comes in with the second buffer included and loses it when it moves.
+int plan_second_buffer(const ph_ctx* c, size_t* lds, bool needed, size_t buf_bytes) {
+  if (!needed) return PH_PLAN_NONE;
+  if (!c->hbm_window && *lds <= (size_t)c->lds_limit) return PH_PLAN_LDS;
+  *lds -= ((buf_bytes + 15) & ~size_t(15));
+  return PH_PLAN_HBM;
+}
+
+// Window buffer: LDS when it fits (after the second buffer has been placed), otherwise an HBM workspace that the
+// kernels' <T, false> instantiations fold through L2.  `lds` comes in with the window buffer included.
+int plan_window(const ph_ctx* c, size_t* lds, size_t win_len, size_t sz) {
+  if (!c->hbm_window && *lds <= (size_t)c->lds_limit) return PH_PLAN_LDS;
+  *lds -= carve_bytes(win_len, sz);
+  return PH_PLAN_HBM;
+}
+
+// The HBM workspace (slot, `bytes`) of a buffer the plan put there; nullptr when it stays in LDS or is not needed.
+int place(ph_ctx* c, int where, int slot, size_t bytes, void** p) {
+  *p = nullptr;
+  if (where != PH_PLAN_HBM) return PH_OK;
+  PH_TRY(ensure(c, c->buf[slot], bytes));
+  *p = c->buf[slot].p;
+  return PH_OK;
+}
+
+// k_project_batch: window + projection scratch (min(p_max, N), N with PH_FLAG_ORTH).
+int plan_project(const ph_ctx* c, int dtype, int N, int pmax, unsigned flags, Plan* pl, int* scratch_len) {
+  const size_t sz = elem_size(dtype);
+  KernelPlan& k = pl->k[0];
+  *scratch_len = (flags & PH_FLAG_ORTH) ? N : std::min(pmax, N);
+  k.lds = carve_bytes(N, sz) + carve_bytes(*scratch_len, sz);
+  k.second = plan_second_buffer(c, &k.lds, true, (size_t)*scratch_len * sz);
+  k.window = plan_window(c, &k.lds, N, sz);
+  k.block = kBlock;
+  return check_lds(c, k.lds, N, "ph_project_batch");
+}
+
+// k_sweep: the norm modes with trunc / orth materialise the projection in a second buffer.
+int plan_sweep(const ph_ctx* c, int dtype, int N, int mode, unsigned flags, Plan* pl) {
+  const size_t sz = elem_size(dtype);
+  KernelPlan& k = pl->k[0];
+  const bool general = (flags & (PH_FLAG_TRUNC | PH_FLAG_ORTH)) && mode != PH_SWEEP_MAXABS;
+  k.lds = carve_bytes(N + kPad, sz) + (general ? carve_bytes(N, sz) : 0) + carve_bytes(kRedDoubles, 8) + carve_bytes(4, 4);
+  // long windows (at most two workgroups per CU): 16 wavefronts per workgroup
+  k.block = (3 * k.lds > (size_t)c->lds_limit && c->sweep_block == ph::kBlockWide) ? 1024 : c->sweep_block;
+  k.second = plan_second_buffer(c, &k.lds, general, (size_t)N * sz);
+  k.window = plan_window(c, &k.lds, N + kPad, sz);
+  return check_lds(c, k.lds, N, "ph_sweep");
+}
+
+// m_best: k[0] = step 1 (k_mbest_step1 or the window-pair screen k_mbest_step1_pair), k[1] = step 2.  max_fac = most
+// proper divisors any candidate period has (PGeom / divisor slots of step 2).
+int plan_m_best(const ph_ctx* c, int dtype, int N, int num, int min_length, int max_length, int max_fac, unsigned flags,
+                Plan* pl) {
+  const size_t sz = elem_size(dtype);
+  const bool general = flags & (PH_FLAG_TRUNC | PH_FLAG_ORTH);
+  const int P = max_length - min_length + 1;
+  KernelPlan& s1 = pl->k[0];
+  KernelPlan& s2 = pl->k[1];
+  pl->n_kernels = 2;
+  size_t lds1 = carve_bytes(N + kPad, sz) + (general ? carve_bytes(N, sz) : 0) + carve_bytes(kRedDoubles, 8) +
+                carve_bytes(kMaxWaves, 8) + carve_bytes(kMaxWaves, 4) + carve_bytes(num, 8) +
+                carve_bytes(num, 4) + carve_bytes((P + 31) / 32, 4);
+  size_t lds2 = carve_bytes(N + kPad, sz) + carve_bytes(N, sz) + carve_bytes(kRedDoubles, 8) +
+                carve_bytes(num, 8) + carve_bytes(num, 4) + carve_bytes(max_fac, 8) + carve_bytes(max_fac, 4) +
+                carve_bytes(kMaxWaves, sizeof(ph::PGeom)) + 3 * carve_bytes(num, 4) + carve_bytes(std::max(max_fac, 64), 4);
+  // LDS for the means of a short winning period (split_row_means): only when the window stays in LDS beside it
+  const size_t lds_small = carve_bytes(ph::kPairSmallP, sz) + carve_bytes(ph::kPairSplitW, sz);
+  s1.small_means = (!general && !c->hbm_window && lds1 + lds_small <= (size_t)c->lds_limit) ? 1 : 0;
+  if (s1.small_means) lds1 += lds_small;
+  s1.second = plan_second_buffer(c, &lds1, general, (size_t)N * sz);
+  // step 2 materialises a projection only when a row is split (rare) or in the trunc/orth modes:
+  // in plain mode that buffer always lives in the HBM workspace, which lets four workgroups of
+  // eight wavefronts share a CU instead of two of four
+  if (general) {
+    s2.second = plan_second_buffer(c, &lds2, true, (size_t)N * sz);
+  } else {
+    lds2 -= carve_bytes(N, sz);
+    s2.second = PH_PLAN_HBM;
+  }
+  s1.window = plan_window(c, &lds1, N + kPad, sz);
+  s2.window = plan_window(c, &lds2, N + kPad, sz);
+  PH_TRY(check_lds(c, std::max(lds1, lds2), N, "ph_m_best"));
+  // Window-pair screen (k_mbest_step1_pair): fp64 windows, plain projection, candidate periods below N, and room for
+  // the pair window plus one fp64 staging buffer in LDS.
+  const bool pair = pair_eligible(c, dtype, N, num, min_length, max_length, flags) && s1.window == PH_PLAN_LDS &&
+                    s2.window == PH_PLAN_LDS;
+  if (pair) {
+    s1.variant = PH_PLAN_PAIR;
+    s1.lds = pair_lds_bytes(N, num, P);
+    s1.block = 1024;
+    s1.small_means = 0;  // the pair kernel keeps its own short-period means (kPairSmallP)
+  } else {
+    s1.lds = lds1;
+    // 16 wavefronts per window: two workgroups per CU at N = 4096 (-2.4 % against four of 8 waves),
+    // and long windows, which leave room for one or two workgroups per CU, still fill the SIMDs
+    // (N = 8192: -15 %, N = 16384: -23 %)
+    // (short windows, N < 3072, keep 8: four workgroups per CU there)
+    s1.block = c->step1_block ? c->step1_block : (c->sweep_block == ph::kBlockWide && N >= 3072) ? 1024 : c->sweep_block;
+  }
+  s2.lds = lds2;
+  s2.block = general ? kBlock : c->sweep_block;
+  return PH_OK;
+}
+
+// small_to_large: k_small_to_large or the persistent window-pair screen k_small_to_large_pair.
+int plan_small_to_large(const ph_ctx* c, int dtype, int N, int n_periods, unsigned flags, Plan* pl) {
+  const size_t sz = elem_size(dtype);
+  const bool general = flags & (PH_FLAG_TRUNC | PH_FLAG_ORTH);
+  KernelPlan& k = pl->k[0];
+  k.lds = carve_bytes(N + kPad, sz) + (general ? carve_bytes(N, sz) : carve_bytes(kBlockWide, sz)) +
+          carve_bytes(kRedDoubles, 8) + carve_bytes(ph::kS2LBatch, 8) + carve_bytes(4, 4);
+  k.second = plan_second_buffer(c, &k.lds, general, (size_t)N * sz);
+  k.window = plan_window(c, &k.lds, N + kPad, sz);
+  PH_TRY(check_lds(c, k.lds, N, "ph_small_to_large"));
+  // Window-pair screen (ph_s2l.h): fp64 windows, plain projection, candidate periods below N.  LDS: the pair window and
+  // one fp64 staging buffer, two 16-wave workgroups per CU; the fp64 residuals live in an HBM workspace.
+  const size_t lds_pair = ph::s2l_pair_lds_bytes(N);
+  const bool pair = c->s2l_pair && dtype == PH_F64 && !general && k.window == PH_PLAN_LDS && n_periods < N &&
+                    n_periods >= 2 && c->sweep_block >= 512 && lds_pair <= (size_t)c->lds_limit;
+  k.variant = pair ? PH_PLAN_PAIR : PH_PLAN_ONE;
+  k.block = pair ? c->s2l_block : c->sweep_block;
+  if (pair) k.lds = lds_pair;
+  return PH_OK;
+}
+
+// best_correlation: k_best_correlation or the window-pair screen k_best_correlation_pair.
+int plan_best_correlation(const ph_ctx* c, int dtype, int N, int max_length, unsigned flags, Plan* pl) {
+  const size_t sz = elem_size(dtype);
+  const bool general = flags & (PH_FLAG_TRUNC | PH_FLAG_ORTH);
+  KernelPlan& k = pl->k[0];
+  k.lds = carve_bytes(N + kPad, sz) + (general ? carve_bytes(N, sz) : 0) + carve_bytes(kRedDoubles, 8) +
+          carve_bytes(kMaxWaves, 8) + carve_bytes(kMaxWaves, 4) + carve_bytes(ph::kCandCap, 4) +
+          carve_bytes(ph::kCandCap, 8) + carve_bytes(1, sizeof(ph::CandCtl));
+  k.second = plan_second_buffer(c, &k.lds, general, (size_t)N * sz);
+  k.window = plan_window(c, &k.lds, N + kPad, sz);
+  PH_TRY(check_lds(c, k.lds, N, "ph_best_correlation"));
+  // Window-pair screen (k_best_correlation_pair): fp64 windows, plain projection, pair window + staging buffer in LDS
+  const size_t lds_pair = 2 * carve_bytes(N + kPad, 8) + carve_bytes(kRedDoubles, 8) + carve_bytes(kMaxWaves, 8) +
+                          carve_bytes(kMaxWaves, 4) + carve_bytes(2 * ph::kPairListCap, 4) + carve_bytes(8, 4) +
+                          carve_bytes(10, 8);
+  const bool pair = c->bc_pair && dtype == PH_F64 && !general && k.window == PH_PLAN_LDS && max_length <= N &&
+                    max_length - 1 >= 2 && lds_pair <= (size_t)c->lds_limit;
+  k.variant = pair ? PH_PLAN_PAIR : PH_PLAN_ONE;
+  k.block = pair ? 1024 : c->sweep_block;
+  if (pair) k.lds = lds_pair;
+  return PH_OK;
+}
+
+// best_frequency: k[0] = the spectrum (in-LDS FFT, Bluestein chirp or direct DFT), k[1] = k_bf_update.
+struct BfShape {
+  size_t lds_spec, lds_fft, lds_chirp;
+  int logL, M0, M, logM, nchunk, wlen;
+};
+
+int plan_best_frequency(const ph_ctx* c, int dtype, int N, int L, Plan* pl, BfShape* g) {
+  const size_t sz = elem_size(dtype);
+  KernelPlan& s = pl->k[0];
+  KernelPlan& u = pl->k[1];
+  pl->n_kernels = 2;
+  size_t lds = 2 * carve_bytes(N, sz) + carve_bytes(kRedDoubles, 8);  // update kernel
+  u.second = plan_second_buffer(c, &lds, true, (size_t)N * sz);
+  // windows longer than the LDS: both kernels work on the residual where it lives (HBM workspace)
+  u.window = (!c->hbm_window && lds <= (size_t)c->lds_limit) ? PH_PLAN_LDS : PH_PLAN_HBM;
+  if (u.window == PH_PLAN_HBM) lds -= carve_bytes(N, sz);
+  PH_TRY(check_lds(c, lds, N, "ph_best_frequency"));
+  u.lds = lds;
+  u.block = kBlockWide;
+  g->lds_spec = (u.window == PH_PLAN_LDS ? carve_bytes(N, sz) : 0) + carve_bytes(kMaxWaves, 8) + carve_bytes(kMaxWaves, 4);
+  PH_TRY(check_lds(c, g->lds_spec, N, "ph_best_frequency"));
+  // power-of-two win_size whose complex work array fits the LDS: in-LDS FFT, one record per window
+  g->lds_fft = 2 * carve_bytes(L, 8) + carve_bytes(kMaxWaves, 8) + carve_bytes(kMaxWaves, 4);
+  const bool use_fft = (L & (L - 1)) == 0 && L >= 4 && g->lds_fft <= (size_t)c->lds_limit && !std::getenv("PH_BF_DIRECT");
+  g->logL = 0;
+  while ((1 << g->logL) < L) ++g->logL;
+  // any other win_size: Bluestein's chirp convolution on two FFTs of size M >= min(N, L) + L / 2 + 1, if that fits
+  g->M0 = std::min(N, L);
+  g->logM = 0;
+  while ((1LL << g->logM) < (long long)g->M0 + L / 2 + 1) ++g->logM;
+  g->M = 1 << g->logM;
+  g->lds_chirp = 2 * carve_bytes(g->M, 8) + carve_bytes(kMaxWaves, 8) + carve_bytes(kMaxWaves, 4);
+  const bool use_chirp =
+      !use_fft && L >= 4 && g->logM <= 20 && g->lds_chirp <= (size_t)c->lds_limit && !std::getenv("PH_BF_DIRECT");
+  g->nchunk = (use_fft || use_chirp) ? 1 : (L / 2 + 1 + ph::kBfBlock - 1) / ph::kBfBlock;
+  g->wlen = std::max(g->M0, L / 2 + 1);  // chirp entries the kernel and the wrapped filter need
+  s.variant = use_fft ? PH_PLAN_FFT : use_chirp ? PH_PLAN_CHIRP : PH_PLAN_DIRECT;
+  s.window = (use_fft || use_chirp) ? PH_PLAN_HBM : u.window;
+  s.lds = use_fft ? g->lds_fft : use_chirp ? g->lds_chirp : g->lds_spec;
+  s.block = (use_fft || use_chirp) ? kBlockWide : ph::kBfBlock;
+  return PH_OK;
+}
+
+// k_ramanujan: per wavefront strip A (q_hi doubles, the root fold) and strip B (q_hi / 2, one child).  As many
+// wavefronts as the LDS left by the window allows, at most 16; when fewer than four fit beside an LDS-resident window
+// (the reference's default range q_hi = N / 3 on a long window) the window moves to the HBM workspace and the strips
+// get the whole LDS.
+int plan_ramanujan(const ph_ctx* c, int dtype, int N, int q_hi, Plan* pl) {
+  const size_t sz = elem_size(dtype);
+  KernelPlan& k = pl->k[0];
+  const size_t strip = carve_bytes((size_t)q_hi, 8) + carve_bytes((size_t)std::max(1, q_hi / 2), 8);
+  const size_t win_bytes = carve_bytes(N + kPad, sz);
+  auto waves_for = [&](size_t room) { return (int)std::min<size_t>(ph::kRamMaxWaves, room / strip); };
+  const size_t limit = (size_t)c->lds_limit;
+  int nw = 0, pad = kPad;
+  bool hbm = c->hbm_window;
+  if (hbm) {
+    nw = waves_for(limit);
+  } else {
+    nw = win_bytes < limit ? waves_for(limit - win_bytes) : 0;
+    // The zeroed pad behind the window serves the row-split fold of roots below 64 (q_hi < 128) only; a fold of a root
+    // >= 64 merely reads up to 255 elements past the window for lanes whose sums it discards.  Without the pad those
+    // reads land in the strips -- and at config 3 window + 16 x 6 KB of strips are exactly the 160 KB of the CU.
+    const size_t win_bare = carve_bytes(N, sz);
+    if (q_hi >= 128 && nw >= 2 && nw < ph::kRamMaxWaves && waves_for(limit - win_bare) > nw) {
+      nw = waves_for(limit - win_bare);
+      pad = 0;
+    }
+    if (nw < 4) {
+      const int nw_hbm = waves_for(limit);
+      if (nw_hbm > nw) {
+        nw = nw_hbm;
+        pad = kPad;
+        hbm = true;
+      }
+    }
+  }
+  if (nw < 1)
+    return fail(PH_E_ARG, "ph_ramanujan_norms: q_hi=%d needs %zu B of LDS per wavefront, device limit is %d B", q_hi, strip,
+                c->lds_limit);
+  k.lds = (hbm ? 0 : pad ? win_bytes : carve_bytes(N, sz)) + carve_bytes((size_t)nw * q_hi, 8) +
+          carve_bytes((size_t)nw * std::max(1, q_hi / 2), 8);
+  PH_TRY(check_lds(c, k.lds, N, "ph_ramanujan_norms"));
+  if (q_hi >= 30030 || q_hi > 0xffff) return fail(PH_E_ARG, "ph_ramanujan_norms: q_hi=%d is beyond the record format", q_hi);
+  k.window = hbm ? PH_PLAN_HBM : PH_PLAN_LDS;
+  k.waves = nw;
+  k.pad = pad;
+  k.block = nw * 64;
+  return PH_OK;
+}
+
+// k_orth_powers: window + autocorrelation + clipped eq. 3 values in LDS when they fit, otherwise the window is read
+// from HBM / L2 and the two work arrays live in an HBM workspace.
+void plan_orth_powers(const ph_ctx* c, int dtype, int N, int max_p, Plan* pl) {
+  KernelPlan& k = pl->k[0];
+  k.lds = carve_bytes(N, elem_size(dtype)) + carve_bytes(N, 8) + carve_bytes(max_p, 8);
+  const bool lds_window = !c->hbm_window && k.lds <= (size_t)c->lds_limit;
+  if (!lds_window) k.lds = 0;
+  k.window = k.second = lds_window ? PH_PLAN_LDS : PH_PLAN_HBM;
+  k.block = kBlockWide;
+}
+
+// k_fold_sums: longer windows are folded from HBM / L2.
+void plan_fold_sums(const ph_ctx* c, int dtype, int N, Plan* pl) {
+  KernelPlan& k = pl->k[0];
+  const bool lds_window = !c->hbm_window && carve_bytes(N, elem_size(dtype)) <= (size_t)c->lds_limit;
+  k.lds = lds_window ? carve_bytes(N, elem_size(dtype)) : 0;
+  k.window = lds_window ? PH_PLAN_LDS : PH_PLAN_HBM;
+  k.block = kBlock;
+}
+
 }  // namespace
 
 // =========================================================================================
@@ -601,6 +860,8 @@ int ph_create(int device, ph_ctx** out) {
     if (v >= 64 && v <= 1024 && v % 64 == 0) c->qo_block = v;
   }
   if (std::getenv("PH_QO_HBM_WINDOW")) c->qo_hbm_window = true;
+  if (const char* e = std::getenv("PH_HBM_WINDOW"))
+    if (std::atoi(e) != 0) c->hbm_window = c->qo_hbm_window = true;
   if (const char* e = std::getenv("PH_SWEEP_BLOCK")) {
     const int v = std::atoi(e);
     if (v >= 64 && v <= 512 && v % 64 == 0) c->sweep_block = v;
@@ -730,10 +991,116 @@ int ph_device_info(ph_ctx* c, int* num_cu, int* lds_bytes) {
 
 int ph_max_window(ph_ctx* c, int dtype, unsigned flags, int* max_n) {
   if (!c || !max_n) return fail(PH_E_ARG, "NULL argument");
-  const size_t sz = elem_size(dtype);
-  const size_t overhead = 8192;  // reduction scratch, bookkeeping arrays
-  (void)flags;  // a second (projection) buffer moves to an HBM workspace when LDS cannot hold two
-  *max_n = (int)(((size_t)c->lds_limit - overhead) / sz);
+  if (dtype != PH_F64 && dtype != PH_F32) return fail(PH_E_ARG, "dtype must be PH_F64 or PH_F32");
+  (void)flags;  // a second (projection) buffer moves to an HBM workspace before the window does
+  // the last N whose sweep window stays in LDS (the placement is monotone in N): sweep_lds(lo), !sweep_lds(hi)
+  auto sweep_lds = [&](int n) {
+    Plan pl;
+    return n < 1 || (plan_sweep(c, dtype, n, PH_SWEEP_NORM, 0u, &pl) == PH_OK && pl.k[0].window == PH_PLAN_LDS);
+  };
+  int lo = 0, hi = (int)((size_t)c->lds_limit / elem_size(dtype)) + 1;
+  while (hi - lo > 1) {
+    const int mid = lo + (hi - lo) / 2;
+    (sweep_lds(mid) ? lo : hi) = mid;
+  }
+  *max_n = lo;
+  return PH_OK;
+}
+
+int ph_plan_info(ph_ctx* c, int op, int dtype, int N, const int32_t* params, int n_params, unsigned flags,
+                 int32_t* out) {
+  if (!c || !out) return fail(PH_E_ARG, "NULL argument");
+  if (n_params < 0 || (n_params > 0 && !params)) return fail(PH_E_ARG, "params NULL or n_params=%d < 0", n_params);
+  if (dtype != PH_F64 && dtype != PH_F32) return fail(PH_E_ARG, "dtype must be PH_F64 or PH_F32");
+  if (N < 1) return fail(PH_E_ARG, "N=%d must be >= 1", N);
+  static_assert(PH_PLAN_K1 == PH_PLAN_K0 + PH_PLAN_STRIDE && PH_PLAN_LEN == PH_PLAN_K0 + 2 * PH_PLAN_STRIDE,
+                "periodhip.h plan record layout");
+  auto prm = [&](int i, int def) { return i < n_params ? (int)params[i] : def; };
+  Plan pl;
+  switch (op) {
+    case PH_OP_PROJECT: {
+      const int pmax = prm(0, N);
+      if (pmax < 1) return fail(PH_E_ARG, "p_list max %d must be >= 1", pmax);
+      int scratch_len;
+      PH_TRY(plan_project(c, dtype, N, pmax, flags, &pl, &scratch_len));
+      break;
+    }
+    case PH_OP_SWEEP: {
+      const int p_lo = prm(0, 1), p_hi = prm(1, N / 3), mode = prm(2, PH_SWEEP_NORM);
+      if (p_lo < 1 || p_hi < p_lo) return fail(PH_E_ARG, "need 1 <= p_lo <= p_hi (got %d, %d)", p_lo, p_hi);
+      if (mode < 0 || mode > 2) return fail(PH_E_ARG, "mode %d unknown", mode);
+      PH_TRY(plan_sweep(c, dtype, N, mode, flags, &pl));
+      break;
+    }
+    case PH_OP_M_BEST: {
+      const int num = prm(0, 5), min_length = prm(1, 2);
+      int max_length = prm(2, -1), max_fac = prm(3, -1);
+      if (num < 1 || num > 4096) return fail(PH_E_ARG, "num=%d must be in [1, 4096]", num);
+      if (max_length < 0) max_length = N / 3;  // Periods.py:485-486
+      if (min_length < 1 || max_length < min_length)
+        return fail(PH_E_ARG, "need 1 <= min_length <= max_length (got %d, %d)", min_length, max_length);
+      if (max_fac < 0) {  // proper divisors (1 and p removed) of the candidate periods, as _factors.factor_tables
+        std::vector<int32_t> nd((size_t)max_length + 1, 0);
+        for (int d = 2; d <= max_length; ++d)
+          for (int q = 2 * d; q <= max_length; q += d) ++nd[q];
+        max_fac = std::max(1, *std::max_element(nd.begin(), nd.end()));
+      }
+      PH_TRY(plan_m_best(c, dtype, N, num, min_length, max_length, max_fac, flags, &pl));
+      break;
+    }
+    case PH_OP_SMALL_TO_LARGE: {
+      int n_periods = prm(0, -1);
+      if (n_periods < 0) n_periods = N / 2;  // Periods.py:271-272
+      PH_TRY(plan_small_to_large(c, dtype, N, n_periods, flags, &pl));
+      break;
+    }
+    case PH_OP_BEST_CORRELATION: {
+      int max_length = prm(0, -1);
+      if (max_length < 0) max_length = N / 3;  // Periods.py:311-312
+      PH_TRY(plan_best_correlation(c, dtype, N, max_length, flags, &pl));
+      break;
+    }
+    case PH_OP_BEST_FREQUENCY: {
+      const int win_size = prm(0, -1);
+      const int L = win_size < 1 ? N : win_size;  // Periods.py:381-382
+      if (L < 2 || L > (1 << 24)) return fail(PH_E_ARG, "win_size=%d out of range", L);
+      BfShape g;
+      PH_TRY(plan_best_frequency(c, dtype, N, L, &pl, &g));
+      break;
+    }
+    case PH_OP_RAMANUJAN: {
+      const int q_lo = prm(0, 2), q_hi = prm(1, N / 3);
+      if (q_lo < 1 || q_hi < 1) return fail(PH_E_ARG, "need q_lo, q_hi >= 1 (got %d, %d)", q_lo, q_hi);
+      PH_TRY(plan_ramanujan(c, dtype, N, q_hi, &pl));
+      break;
+    }
+    case PH_OP_ORTH_POWERS: {
+      int max_p = prm(0, -1);
+      if (max_p < 0) max_p = N / 2;  // QOPeriods.py:1204-1207
+      if (max_p < 2) return fail(PH_E_ARG, "max_p=%d must be >= 2", max_p);
+      plan_orth_powers(c, dtype, N, max_p, &pl);
+      break;
+    }
+    case PH_OP_FOLD_SUMS:
+      plan_fold_sums(c, dtype, N, &pl);
+      break;
+    default:
+      return fail(PH_E_ARG, "op %d unknown", op);
+  }
+  std::memset(out, 0, PH_PLAN_LEN * sizeof(int32_t));
+  out[PH_PLAN_KERNELS] = pl.n_kernels;
+  for (int i = 0; i < pl.n_kernels; ++i) {
+    const KernelPlan& k = pl.k[i];
+    int32_t* r = out + PH_PLAN_K0 + i * PH_PLAN_STRIDE;
+    r[PH_PLAN_VARIANT] = k.variant;
+    r[PH_PLAN_WINDOW] = k.window;
+    r[PH_PLAN_SECOND] = k.second;
+    r[PH_PLAN_BLOCK] = k.block;
+    r[PH_PLAN_LDS_BYTES] = (int32_t)k.lds;
+    r[PH_PLAN_SMALL_MEANS] = k.small_means;
+    r[PH_PLAN_WAVES] = k.waves;
+    r[PH_PLAN_PAD] = k.pad;
+  }
   return PH_OK;
 }
 
@@ -750,14 +1117,14 @@ int ph_project_batch(ph_ctx* c, const void* x, int dtype, int64_t W, int N, cons
   }
   PH_HIP(hipSetDevice(c->device));
   const size_t sz = elem_size(dtype);
-  const int scratch_len = (flags & PH_FLAG_ORTH) ? N : std::min(pmax, N);
-  size_t lds = carve_bytes(N, sz) + carve_bytes(scratch_len, sz);
+  Plan pl;
+  int scratch_len;
+  PH_TRY(plan_project(c, dtype, N, pmax, flags, &pl, &scratch_len));
+  const size_t lds = pl.k[0].lds;
   const int chunks = pick_chunks(c, W, n_p, 1);
-  void* gbuf;
-  PH_TRY(place_second_buffer(c, &lds, true, (size_t)scratch_len * sz, W * chunks, &gbuf));
-  void* gwin;
-  PH_TRY(place_window(c, &lds, N, sz, W * chunks, &gwin));
-  PH_TRY(check_lds(c, lds, N, "ph_project_batch"));
+  void *gbuf, *gwin;
+  PH_TRY(place(c, pl.k[0].second, B_GBUF, (size_t)W * chunks * scratch_len * sz, &gbuf));
+  PH_TRY(place(c, pl.k[0].window, B_GWIN, (size_t)W * chunks * ph::win_stride(N) * sz, &gwin));
   ph::Tables tb{};
   PH_TRY(prepare_orth(c, flags, orth_off, orth_q, table_max_p, pmax, &tb));
   const int* d_plist;
@@ -792,17 +1159,16 @@ int ph_sweep(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int p_lo, in
   if (mode < 0 || mode > 2) return fail(PH_E_ARG, "mode %d unknown", mode);
   PH_HIP(hipSetDevice(c->device));
   const size_t sz = elem_size(dtype);
-  const bool general = (flags & (PH_FLAG_TRUNC | PH_FLAG_ORTH)) && mode != PH_SWEEP_MAXABS;
-  size_t lds = carve_bytes(N + kPad, sz) + (general ? carve_bytes(N, sz) : 0) + carve_bytes(kRedDoubles, 8) + carve_bytes(4, 4);
+  Plan pl;
+  PH_TRY(plan_sweep(c, dtype, N, mode, flags, &pl));
+  const bool general = pl.k[0].second != PH_PLAN_NONE;
+  const size_t lds = pl.k[0].lds;
   const int P = p_hi - p_lo + 1;
-  // long windows (at most two workgroups per CU): 16 wavefronts per workgroup
-  const int sweep_block = (3 * lds > (size_t)c->lds_limit && c->sweep_block == ph::kBlockWide) ? 1024 : c->sweep_block;
+  const int sweep_block = pl.k[0].block;
   const int chunks = pick_chunks(c, W, P, 8 * (sweep_block / 64));
-  void* gbuf;
-  PH_TRY(place_second_buffer(c, &lds, general, (size_t)N * sz, W * chunks, &gbuf));
-  void* gwin;
-  PH_TRY(place_window(c, &lds, N + kPad, sz, W * chunks, &gwin));
-  PH_TRY(check_lds(c, lds, N, "ph_sweep"));
+  void *gbuf, *gwin;
+  PH_TRY(place(c, pl.k[0].second, B_GBUF, (size_t)W * chunks * N * sz, &gbuf));
+  PH_TRY(place(c, pl.k[0].window, B_GWIN, (size_t)W * chunks * ph::win_stride(N + kPad) * sz, &gwin));
   const ph::PGeom* geom;
   PH_TRY(prepare_geom(c, N, p_hi, &geom));
   const ph::PassPlan* plan;
@@ -844,39 +1210,22 @@ int ph_m_best(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int num, in
     return fail(PH_E_ARG, "need 1 <= min_length <= max_length (got %d, %d)", min_length, max_length);
   PH_HIP(hipSetDevice(c->device));
   const size_t sz = elem_size(dtype);
-  const bool general = flags & (PH_FLAG_TRUNC | PH_FLAG_ORTH);
   const int P = max_length - min_length + 1;
-  size_t lds1 = carve_bytes(N + kPad, sz) + (general ? carve_bytes(N, sz) : 0) + carve_bytes(kRedDoubles, 8) +
-                carve_bytes(kMaxWaves, 8) + carve_bytes(kMaxWaves, 4) + carve_bytes(num, 8) +
-                carve_bytes(num, 4) + carve_bytes((P + 31) / 32, 4);
   if (!fac_off || !fac_q) return fail(PH_E_ARG, "fac_off/fac_q tables are required");
   if (table_max_p < max_length)
     return fail(PH_E_ARG, "factor tables cover p <= %d, need %d", table_max_p, max_length);
   int max_fac = 1;  // most proper divisors any candidate period has
   for (int q = 0; q <= max_length; ++q) max_fac = std::max(max_fac, fac_off[q + 1] - fac_off[q]);
-  size_t lds2 = carve_bytes(N + kPad, sz) + carve_bytes(N, sz) + carve_bytes(kRedDoubles, 8) +
-                carve_bytes(num, 8) + carve_bytes(num, 4) + carve_bytes(max_fac, 8) + carve_bytes(max_fac, 4) +
-                carve_bytes(kMaxWaves, sizeof(ph::PGeom)) + 3 * carve_bytes(num, 4) + carve_bytes(std::max(max_fac, 64), 4);
-  // LDS for the means of a short winning period (split_row_means): only when the window stays in LDS beside it
-  const size_t lds_small = carve_bytes(ph::kPairSmallP, sz) + carve_bytes(ph::kPairSplitW, sz);
-  const int small_means = (!general && lds1 + lds_small <= (size_t)c->lds_limit) ? 1 : 0;
-  if (small_means) lds1 += lds_small;
-  void *gbuf1, *gbuf2;
-  PH_TRY(place_second_buffer(c, &lds1, general, (size_t)N * sz, W, &gbuf1));
-  // step 2 materialises a projection only when a row is split (rare) or in the trunc/orth modes:
-  // in plain mode that buffer always lives in the HBM workspace, which lets four workgroups of
-  // eight wavefronts share a CU instead of two of four
-  if (general) {
-    PH_TRY(place_second_buffer(c, &lds2, true, (size_t)N * sz, W, &gbuf2));
-  } else {
-    lds2 -= carve_bytes(N, sz);
-    PH_TRY(ensure(c, c->buf[B_GBUF], (size_t)W * N * sz));
-    gbuf2 = c->buf[B_GBUF].p;
-  }
-  void *gwin1, *gwin2;  // the two kernels run back to back on one stream and may share the workspace
-  PH_TRY(place_window(c, &lds1, N + kPad, sz, W, &gwin1));
-  PH_TRY(place_window(c, &lds2, N + kPad, sz, W, &gwin2));
-  PH_TRY(check_lds(c, std::max(lds1, lds2), N, "ph_m_best"));
+  Plan pl;
+  PH_TRY(plan_m_best(c, dtype, N, num, min_length, max_length, max_fac, flags, &pl));
+  const KernelPlan &s1 = pl.k[0], &s2 = pl.k[1];
+  const bool pair = s1.variant == PH_PLAN_PAIR;
+  // the two kernels run back to back on one stream and may share the workspaces
+  void *gbuf1, *gbuf2, *gwin1, *gwin2;
+  PH_TRY(place(c, s1.second, B_GBUF, (size_t)W * N * sz, &gbuf1));
+  PH_TRY(place(c, s2.second, B_GBUF, (size_t)W * N * sz, &gbuf2));
+  PH_TRY(place(c, s1.window, B_GWIN, (size_t)W * ph::win_stride(N + kPad) * sz, &gwin1));
+  PH_TRY(place(c, s2.window, B_GWIN, (size_t)W * ph::win_stride(N + kPad) * sz, &gwin2));
   ph::Tables tb{};
   PH_TRY(prepare_orth(c, flags, orth_off, orth_q, table_max_p, max_length, &tb));
   PH_TRY(prepare_fac(c, fac_off, fac_q, table_max_p, max_length, &tb));
@@ -884,9 +1233,6 @@ int ph_m_best(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int num, in
   PH_TRY(prepare_geom(c, N, max_length, &geom));
   const ph::PassPlan* plan;
   int n_pass;
-  // Window-pair screen (k_mbest_step1_pair): fp64 windows, plain projection, candidate periods below N, and room for
-  // the pair window plus one fp64 staging buffer in LDS.
-  const bool pair = pair_eligible(c, dtype, N, num, min_length, max_length, flags) && !gwin1 && !gwin2;
   PH_TRY(prepare_plan(c, min_length, max_length, &plan, &n_pass, 4, false, pair));
   Stage st(c, flags);
   const void* dx;
@@ -908,14 +1254,13 @@ int ph_m_best(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int num, in
   const unsigned kflags = flags & (PH_FLAG_TRUNC | PH_FLAG_ORTH);
   const int max_iters = 12 * (P + num) + 64;
   const dim3 grid((unsigned)W);
-  const size_t lds_pair = pair_lds_bytes(N, num, P);
   if (pair) {
     const size_t gstride = ph::win_stride((size_t)N);
     PH_TRY(ensure(c, c->buf[B_GWIN], (size_t)W * gstride * sizeof(double)));
     auto kernel = ph::k_mbest_step1_pair;
-    PH_TRY(allow_lds(kernel, lds_pair));
+    PH_TRY(allow_lds(kernel, s1.lds));
     ProfScope ps_(c, "k_mbest_step1");
-    hipLaunchKernelGGL(kernel, dim3((unsigned)((W + 1) / 2)), dim3(1024), lds_pair, c->stream, (const double*)dx, (int)W, N,
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((W + 1) / 2)), dim3(s1.block), s1.lds, c->stream, (const double*)dx, (int)W, N,
                        num, min_length, max_length, gamma, geom, static_cast<const ph::PGeomF*>(c->geomf.p), plan, n_pass,
                        static_cast<double*>(c->buf[B_GWIN].p), max_iters, (uint32_t*)dper, (double*)dpow, (double*)drows,
                        row_stride, dnorm, (int*)dstat, (int*)dsweeps);
@@ -923,27 +1268,20 @@ int ph_m_best(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int num, in
   PH_TRY(dispatch(dtype, !gwin1, [&](auto t, auto lw) {
     using T = decltype(t);
     auto kernel = ph::k_mbest_step1<T, decltype(lw)::value>;
-    PH_TRY(allow_lds(kernel, lds1));
+    PH_TRY(allow_lds(kernel, s1.lds));
     ProfScope ps_(c, "k_mbest_step1");
-    // 16 wavefronts per window: two workgroups per CU at N = 4096 (-2.4 % against four of 8 waves),
-    // and long windows, which leave room for one or two workgroups per CU, still fill the SIMDs
-    // (N = 8192: -15 %, N = 16384: -23 %)
-    // (short windows, N < 3072, keep 8: four workgroups per CU there)
-    const int block1 = c->step1_block ? c->step1_block
-                       : (c->sweep_block == ph::kBlockWide && N >= 3072) ? 1024
-                                                                         : c->sweep_block;
-    hipLaunchKernelGGL(kernel, grid, dim3(block1), lds1, c->stream, (const T*)dx, N, num, min_length,
+    hipLaunchKernelGGL(kernel, grid, dim3(s1.block), s1.lds, c->stream, (const T*)dx, N, num, min_length,
                        max_length, gamma, kflags, tb, geom, plan, n_pass, (T*)gbuf1, (T*)gwin1, max_iters,
-                       (uint32_t*)dper, (double*)dpow, (T*)drows, row_stride, dnorm, (int*)dstat, (int*)dsweeps, small_means);
+                       (uint32_t*)dper, (double*)dpow, (T*)drows, row_stride, dnorm, (int*)dstat, (int*)dsweeps, s1.small_means);
     return (int)PH_OK;
   }));
   PH_TRY(launch_check("k_mbest_step1"));
   PH_TRY(dispatch(dtype, !gwin2, [&](auto t, auto lw) {
     using T = decltype(t);
     auto kernel = ph::k_mbest_step2<T, decltype(lw)::value>;
-    PH_TRY(allow_lds(kernel, lds2));
+    PH_TRY(allow_lds(kernel, s2.lds));
     ProfScope ps_(c, "k_mbest_step2");
-    hipLaunchKernelGGL(kernel, grid, dim3(general ? kBlock : c->sweep_block), lds2, c->stream, N, num, gamma,
+    hipLaunchKernelGGL(kernel, grid, dim3(s2.block), s2.lds, c->stream, N, num, gamma,
                        max_length, kflags, tb, geom,
                        max_fac, (T*)gbuf2, (T*)gwin2, (uint32_t*)dper, (double*)dpow, (T*)dbases, dnorm,
                        (const int*)dstat, (T*)drows, row_stride);
@@ -963,14 +1301,12 @@ int ph_small_to_large(ph_ctx* c, const void* x, int dtype, int64_t W, int N, dou
   if (n_periods < 0) n_periods = N / 2;  // Periods.py:271-272
   PH_HIP(hipSetDevice(c->device));
   const size_t sz = elem_size(dtype);
-  const bool general = flags & (PH_FLAG_TRUNC | PH_FLAG_ORTH);
-  size_t lds = carve_bytes(N + kPad, sz) + (general ? carve_bytes(N, sz) : carve_bytes(kBlockWide, sz)) + carve_bytes(kRedDoubles, 8) +
-               carve_bytes(ph::kS2LBatch, 8) + carve_bytes(4, 4);
-  void* gbuf;
-  PH_TRY(place_second_buffer(c, &lds, general, (size_t)N * sz, W, &gbuf));
-  void* gwin;
-  PH_TRY(place_window(c, &lds, N + kPad, sz, W, &gwin));
-  PH_TRY(check_lds(c, lds, N, "ph_small_to_large"));
+  Plan pl;
+  PH_TRY(plan_small_to_large(c, dtype, N, n_periods, flags, &pl));
+  const KernelPlan& k = pl.k[0];
+  void *gbuf, *gwin;
+  PH_TRY(place(c, k.second, B_GBUF, (size_t)W * N * sz, &gbuf));
+  PH_TRY(place(c, k.window, B_GWIN, (size_t)W * ph::win_stride(N + kPad) * sz, &gwin));
   const ph::PGeom* geom;
   PH_TRY(prepare_geom(c, N, std::max(n_periods, 2), &geom));
   ph::Tables tb{};
@@ -991,23 +1327,17 @@ int ph_small_to_large(ph_ctx* c, const void* x, int dtype, int64_t W, int N, dou
   PH_HIP(hipMemsetAsync(dmax, 0, 2 * sizeof(int), c->stream));  // [1]: pair counter of the persistent pair kernel
   const unsigned kflags = flags & (PH_FLAG_TRUNC | PH_FLAG_ORTH);
   const dim3 grid((unsigned)W);
-  // Window-pair screen (ph_s2l.h): fp64 windows, plain projection, candidate periods below N.  LDS: the pair window and
-  // one fp64 staging buffer, two 16-wave workgroups per CU; the fp64 residuals live in an HBM workspace.
-  const size_t lds_pair = ph::s2l_pair_lds_bytes(N);
-  const bool pair_ok = c->s2l_pair && dtype == PH_F64 && !general && !gwin && n_periods < N && n_periods >= 2 &&
-                       c->sweep_block >= 512;
-  const bool pair = pair_ok && lds_pair <= (size_t)c->lds_limit;
-  if (pair) {
+  if (k.variant == PH_PLAN_PAIR) {
     const size_t gstride = ph::win_stride((size_t)N);
     PH_TRY(ensure(c, c->buf[B_GWIN], (size_t)W * gstride * sizeof(double)));
     auto kernel = ph::k_small_to_large_pair;
-    PH_TRY(allow_lds(kernel, lds_pair));
+    PH_TRY(allow_lds(kernel, k.lds));
     ProfScope ps_(c, "k_small_to_large");
     // persistent workgroups: as many as are resident at once (LDS and the 32 wavefronts of a CU), pairs from a counter
     const int64_t npairs = (W + 1) / 2;
-    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>((size_t)c->lds_limit / lds_pair, 2048 / (size_t)c->s2l_block));
+    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>((size_t)c->lds_limit / k.lds, 2048 / (size_t)k.block));
     const unsigned grid_pairs = (unsigned)std::min<int64_t>(npairs, (int64_t)c->num_cu * per_cu);
-    hipLaunchKernelGGL(kernel, dim3(grid_pairs), dim3(c->s2l_block), lds_pair, c->stream, (const double*)dx, (int)W, N,
+    hipLaunchKernelGGL(kernel, dim3(grid_pairs), dim3(k.block), k.lds, c->stream, (const double*)dx, (int)W, N,
                        thresh, n_periods, static_cast<const ph::PGeomF*>(c->geomf.p), static_cast<const float*>(c->kapf.p),
                        static_cast<double*>(c->buf[B_GWIN].p), cap, (int*)dcnt, (int*)dper, (double*)dpow, (double*)dbases,
                        (int*)dstat, dmax, dmax + 1);
@@ -1015,9 +1345,9 @@ int ph_small_to_large(ph_ctx* c, const void* x, int dtype, int64_t W, int N, dou
   PH_TRY(dispatch(dtype, !gwin, [&](auto t, auto lw) {
     using T = decltype(t);
     auto kernel = ph::k_small_to_large<T, decltype(lw)::value>;
-    PH_TRY(allow_lds(kernel, lds));
+    PH_TRY(allow_lds(kernel, k.lds));
     ProfScope ps_(c, "k_small_to_large");
-    hipLaunchKernelGGL(kernel, grid, dim3(c->sweep_block), lds, c->stream, (const T*)dx, N, thresh, n_periods, kflags,
+    hipLaunchKernelGGL(kernel, grid, dim3(k.block), k.lds, c->stream, (const T*)dx, N, thresh, n_periods, kflags,
                        tb, geom, (T*)gbuf, (T*)gwin, cap, (int*)dcnt, (int*)dper, (double*)dpow, (T*)dbases,
                        (int*)dstat, dmax);
     return (int)PH_OK;
@@ -1046,23 +1376,15 @@ int ph_best_correlation(ph_ctx* c, const void* x, int dtype, int64_t W, int N, i
   if (max_length < 0) max_length = N / 3;  // Periods.py:311-312
   PH_HIP(hipSetDevice(c->device));
   const size_t sz = elem_size(dtype);
-  const bool general = flags & (PH_FLAG_TRUNC | PH_FLAG_ORTH);
-  size_t lds = carve_bytes(N + kPad, sz) + (general ? carve_bytes(N, sz) : 0) + carve_bytes(kRedDoubles, 8) +
-               carve_bytes(kMaxWaves, 8) + carve_bytes(kMaxWaves, 4) + carve_bytes(ph::kCandCap, 4) +
-               carve_bytes(ph::kCandCap, 8) + carve_bytes(1, sizeof(ph::CandCtl));
-  void* gbuf;
-  PH_TRY(place_second_buffer(c, &lds, general, (size_t)N * sz, W, &gbuf));
-  void* gwin;
-  PH_TRY(place_window(c, &lds, N + kPad, sz, W, &gwin));
-  PH_TRY(check_lds(c, lds, N, "ph_best_correlation"));
+  Plan pl;
+  PH_TRY(plan_best_correlation(c, dtype, N, max_length, flags, &pl));
+  const KernelPlan& k = pl.k[0];
+  const bool pair = k.variant == PH_PLAN_PAIR;
+  void *gbuf, *gwin;
+  PH_TRY(place(c, k.second, B_GBUF, (size_t)W * N * sz, &gbuf));
+  PH_TRY(place(c, k.window, B_GWIN, (size_t)W * ph::win_stride(N + kPad) * sz, &gwin));
   const ph::PassPlan* plan = nullptr;
   int n_pass = 0;
-  // Window-pair screen (k_best_correlation_pair): fp64 windows, plain projection, pair window + staging buffer in LDS
-  const size_t lds_pair = 2 * carve_bytes(N + kPad, 8) + carve_bytes(kRedDoubles, 8) + carve_bytes(kMaxWaves, 8) +
-                          carve_bytes(kMaxWaves, 4) + carve_bytes(2 * ph::kPairListCap, 4) + carve_bytes(8, 4) +
-                          carve_bytes(10, 8);
-  const bool pair = c->bc_pair && dtype == PH_F64 && !general && !gwin && max_length <= N && max_length - 1 >= 2 &&
-                    lds_pair <= (size_t)c->lds_limit;
   if (max_length - 1 >= 2) PH_TRY(prepare_plan(c, 2, max_length - 1, &plan, &n_pass, 4, true, pair));
   const ph::PGeom* geom;
   PH_TRY(prepare_geom(c, N, std::max(max_length, 2), &geom));
@@ -1082,18 +1404,18 @@ int ph_best_correlation(ph_ctx* c, const void* x, int dtype, int64_t W, int N, i
     const size_t gstride = ph::win_stride((size_t)N);
     PH_TRY(ensure(c, c->buf[B_GWIN], (size_t)W * gstride * sizeof(double)));
     auto kernel = ph::k_best_correlation_pair;
-    PH_TRY(allow_lds(kernel, lds_pair));
+    PH_TRY(allow_lds(kernel, k.lds));
     ProfScope ps_(c, "k_best_correlation");
-    hipLaunchKernelGGL(kernel, dim3((unsigned)((W + 1) / 2)), dim3(1024), lds_pair, c->stream, (const double*)dx, (int)W, N,
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((W + 1) / 2)), dim3(k.block), k.lds, c->stream, (const double*)dx, (int)W, N,
                        num, max_length, ratio, geom, static_cast<const ph::PGeomF*>(c->geomf.p), plan, n_pass,
                        static_cast<double*>(c->buf[B_GWIN].p), (uint32_t*)dper, (double*)dnrm, (double*)dbases, (int*)dstat);
   } else
   PH_TRY(dispatch(dtype, !gwin, [&](auto t, auto lw) {
     using T = decltype(t);
     auto kernel = ph::k_best_correlation<T, decltype(lw)::value>;
-    PH_TRY(allow_lds(kernel, lds));
+    PH_TRY(allow_lds(kernel, k.lds));
     ProfScope ps_(c, "k_best_correlation");
-    hipLaunchKernelGGL(kernel, grid, dim3(c->sweep_block), lds, c->stream, (const T*)dx, N, num, max_length, ratio,
+    hipLaunchKernelGGL(kernel, grid, dim3(k.block), k.lds, c->stream, (const T*)dx, N, num, max_length, ratio,
                        kflags, tb, geom, plan, n_pass, (T*)gbuf, (T*)gwin, (uint32_t*)dper, (double*)dnrm, (T*)dbases,
                        (int*)dstat);
     return (int)PH_OK;
@@ -1114,29 +1436,15 @@ int ph_best_frequency(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int
   if (W > 65535) return fail(PH_E_ARG, "ph_best_frequency: W=%lld exceeds 65535 windows per call", (long long)W);
   PH_HIP(hipSetDevice(c->device));
   const size_t sz = elem_size(dtype);
-  size_t lds = 2 * carve_bytes(N, sz) + carve_bytes(kRedDoubles, 8);  // update kernel
+  Plan pl;
+  BfShape g;
+  PH_TRY(plan_best_frequency(c, dtype, N, L, &pl, &g));
+  const bool use_fft = pl.k[0].variant == PH_PLAN_FFT, use_chirp = pl.k[0].variant == PH_PLAN_CHIRP;
+  const bool lds_window = pl.k[1].window == PH_PLAN_LDS;
+  const size_t lds = pl.k[1].lds, lds_spec = g.lds_spec, lds_fft = g.lds_fft, lds_chirp = g.lds_chirp;
+  const int logL = g.logL, M0 = g.M0, M = g.M, logM = g.logM, nchunk = g.nchunk, wlen = g.wlen;
   void* gbuf;
-  PH_TRY(place_second_buffer(c, &lds, true, (size_t)N * sz, W, &gbuf));
-  // windows longer than the LDS: both kernels work on the residual where it lives (HBM workspace)
-  const bool lds_window = lds <= (size_t)c->lds_limit;
-  if (!lds_window) lds -= carve_bytes(N, sz);
-  PH_TRY(check_lds(c, lds, N, "ph_best_frequency"));
-  const size_t lds_spec = (lds_window ? carve_bytes(N, sz) : 0) + carve_bytes(kMaxWaves, 8) + carve_bytes(kMaxWaves, 4);
-  PH_TRY(check_lds(c, lds_spec, N, "ph_best_frequency"));
-  // power-of-two win_size whose complex work array fits the LDS: in-LDS FFT, one record per window
-  const size_t lds_fft = 2 * carve_bytes(L, 8) + carve_bytes(kMaxWaves, 8) + carve_bytes(kMaxWaves, 4);
-  const bool use_fft = (L & (L - 1)) == 0 && L >= 4 && lds_fft <= (size_t)c->lds_limit && !std::getenv("PH_BF_DIRECT");
-  int logL = 0;
-  while ((1 << logL) < L) ++logL;
-  // any other win_size: Bluestein's chirp convolution on two FFTs of size M >= min(N, L) + L / 2 + 1, if that fits
-  const int M0 = std::min(N, L);
-  int logM = 0;
-  while ((1LL << logM) < (long long)M0 + L / 2 + 1) ++logM;
-  const int M = 1 << logM;
-  const size_t lds_chirp = 2 * carve_bytes(M, 8) + carve_bytes(kMaxWaves, 8) + carve_bytes(kMaxWaves, 4);
-  const bool use_chirp = !use_fft && L >= 4 && logM <= 20 && lds_chirp <= (size_t)c->lds_limit && !std::getenv("PH_BF_DIRECT");
-  const int nchunk = (use_fft || use_chirp) ? 1 : (L / 2 + 1 + ph::kBfBlock - 1) / ph::kBfBlock;
-  const int wlen = std::max(M0, L / 2 + 1);  // chirp entries the kernel and the wrapped filter need
+  PH_TRY(place(c, pl.k[1].second, B_GBUF, (size_t)W * N * sz, &gbuf));
   if (use_chirp && (c->bs_L != L || c->bs_M0 != M0)) {
     const long double pi = 3.141592653589793238462643383279L;
     std::vector<double> tab(2 * ((size_t)M + wlen + M));  // [twiddles M | chirp wlen | B M] as (re, im) pairs
@@ -1243,22 +1551,22 @@ int ph_best_frequency(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int
     for (int it = 0; it < num; ++it) {
       if (use_fft) {
         ProfScope ps_(c, "k_bf_fft");
-        hipLaunchKernelGGL((ph::k_bf_fft<T>), grid_u, dim3(kBlockWide), lds_fft, c->stream, (const T*)dres, N, L, logL,
+        hipLaunchKernelGGL((ph::k_bf_fft<T>), grid_u, dim3(pl.k[0].block), lds_fft, c->stream, (const T*)dres, N, L, logL,
                            (const double2*)c->twid.p, (const int*)dstat, dpart, dpartk);
       } else if (use_chirp) {
         const double2* twm = (const double2*)c->bs_tab.p;
         ProfScope ps_(c, "k_bf_chirp");
-        hipLaunchKernelGGL((ph::k_bf_chirp<T>), grid_u, dim3(kBlockWide), lds_chirp, c->stream, (const T*)dres, N, L, M, logM,
+        hipLaunchKernelGGL((ph::k_bf_chirp<T>), grid_u, dim3(pl.k[0].block), lds_chirp, c->stream, (const T*)dres, N, L, M, logM,
                            twm, twm + M, twm + M + wlen, (const int*)dstat, dpart, dpartk);
       } else {
         ProfScope ps_(c, "k_bf_spectrum");
-        hipLaunchKernelGGL((ph::k_bf_spectrum<T, LW>), grid_s, dim3(ph::kBfBlock), lds_spec, c->stream, (const T*)dres, N, L,
+        hipLaunchKernelGGL((ph::k_bf_spectrum<T, LW>), grid_s, dim3(pl.k[0].block), lds_spec, c->stream, (const T*)dres, N, L,
                            (const double2*)c->twid.p, (const int*)dstat, dpart, dpartk);
       }
       PH_TRY(launch_check("k_bf_spectrum"));
       {
         ProfScope ps_(c, "k_bf_update");
-        hipLaunchKernelGGL((ph::k_bf_update<T, LW>), grid_u, dim3(kBlockWide), lds, c->stream, (T*)dres, N, L, num, it,
+        hipLaunchKernelGGL((ph::k_bf_update<T, LW>), grid_u, dim3(pl.k[1].block), lds, c->stream, (T*)dres, N, L, num, it,
                            kflags, tb, (T*)gbuf, nchunk, (const double*)dpart, (const int*)dpartk, dnrm,
                            (uint32_t*)dper, (double*)dpow, (T*)dbases, (int*)dstat);
       }
@@ -1277,44 +1585,14 @@ int ph_ramanujan_norms(ph_ctx* c, const void* x, int dtype, int64_t W, int N, in
   if (q_lo < 1 || q_hi < 1) return fail(PH_E_ARG, "need q_lo, q_hi >= 1 (got %d, %d)", q_lo, q_hi);
   PH_HIP(hipSetDevice(c->device));
   const size_t sz = elem_size(dtype);
-  // Per wavefront: strip A (q_hi doubles, the root fold) and strip B (q_hi / 2, one child).  As many
-  // wavefronts as the LDS left by the window allows, at most 16; when fewer than four fit beside an
-  // LDS-resident window (the reference's default range q_hi = N / 3 on a long window) the window moves
-  // to the HBM workspace and the strips get the whole LDS.
-  const size_t strip = carve_bytes((size_t)q_hi, 8) + carve_bytes((size_t)std::max(1, q_hi / 2), 8);
-  const size_t win_bytes = carve_bytes(N + kPad, sz);
-  auto waves_for = [&](size_t room) { return (int)std::min<size_t>(ph::kRamMaxWaves, room / strip); };
-  const size_t limit = (size_t)c->lds_limit;
-  int nw = win_bytes < limit ? waves_for(limit - win_bytes) : 0;
-  int pad = kPad;
-  // The zeroed pad behind the window serves the row-split fold of roots below 64 (q_hi < 128) only; a fold of a root
-  // >= 64 merely reads up to 255 elements past the window for lanes whose sums it discards.  Without the pad those reads
-  // land in the strips -- and at config 3 window + 16 x 6 KB of strips are exactly the 160 KB of the CU.
-  const size_t win_bare = carve_bytes(N, sz);
-  if (q_hi >= 128 && nw >= 2 && nw < ph::kRamMaxWaves && waves_for(limit - win_bare) > nw) {
-    nw = waves_for(limit - win_bare);
-    pad = 0;
-  }
-  void* gwin = nullptr;
-  if (nw < 4) {
-    const int nw_hbm = waves_for(limit);
-    if (nw_hbm > nw) {
-      nw = nw_hbm;
-      pad = kPad;
-      PH_TRY(ensure(c, c->buf[B_GWIN], (size_t)W * ph::win_stride(N + kPad) * sz));
-      gwin = c->buf[B_GWIN].p;
-    }
-  }
-  if (nw < 1)
-    return fail(PH_E_ARG, "ph_ramanujan_norms: q_hi=%d needs %zu B of LDS per wavefront, device limit is %d B", q_hi, strip,
-                c->lds_limit);
-  const size_t lds = (gwin ? 0 : pad ? win_bytes : win_bare) + carve_bytes((size_t)nw * q_hi, 8) +
-                     carve_bytes((size_t)nw * std::max(1, q_hi / 2), 8);
-  PH_TRY(check_lds(c, lds, N, "ph_ramanujan_norms"));
+  Plan pl;
+  PH_TRY(plan_ramanujan(c, dtype, N, q_hi, &pl));
+  const KernelPlan& k = pl.k[0];
+  void* gwin;
+  PH_TRY(place(c, k.window, B_GWIN, (size_t)W * ph::win_stride(N + kPad) * sz, &gwin));
   // One 128-byte record per period (ph::RamJob): the factors (I - P_d) of its projector (d = q / r for each prime
   // r | q, with 1 / r and the row-split geometry of a coset count below 64), the scale (q / phi(q))^2 and the
   // geometry of its fold of the window.
-  if (q_hi >= 30030 || q_hi > 0xffff) return fail(PH_E_ARG, "ph_ramanujan_norms: q_hi=%d is beyond the record format", q_hi);
   auto small_geom = [](int d) { return d >= 1 && d < 64 ? (64 / d) | (((65536 + d - 1) / d) << 8) : 0; };
   std::vector<ph::RamJob> job((size_t)q_hi + 1);
   {
@@ -1402,10 +1680,10 @@ int ph_ramanujan_norms(ph_ctx* c, const void* x, int dtype, int64_t W, int N, in
     PH_TRY(dispatch(dtype, !gwin, [&](auto t, auto lw) {
       using T = decltype(t);
       auto kernel = ph::k_ramanujan<T, decltype(lw)::value>;
-      PH_TRY(allow_lds(kernel, lds));
+      PH_TRY(allow_lds(kernel, k.lds));
       ProfScope ps_(c, "k_ramanujan");
-      hipLaunchKernelGGL(kernel, grid, dim3(nw * 64), lds, c->stream, (const T*)dx, N, q_hi, d_roots, n_root, d_roots + n_root,
-                         (T*)gwin, pad, (double*)dout);
+      hipLaunchKernelGGL(kernel, grid, dim3(k.block), k.lds, c->stream, (const T*)dx, N, q_hi, d_roots, n_root,
+                         d_roots + n_root, (T*)gwin, k.pad, (double*)dout);
       return (int)PH_OK;
     }));
     PH_TRY(launch_check("k_ramanujan"));
@@ -1437,8 +1715,10 @@ int ph_fold_sums(ph_ctx* c, const void* x, int dtype, int64_t W, int N, const in
   if (!out) return fail(PH_E_ARG, "out is NULL");
   PH_HIP(hipSetDevice(c->device));
   const size_t sz = elem_size(dtype);
-  const bool lds_window = carve_bytes(N, sz) <= (size_t)c->lds_limit;  // longer windows are folded from HBM / L2
-  const size_t lds = lds_window ? carve_bytes(N, sz) : 0;
+  Plan pl;
+  plan_fold_sums(c, dtype, N, &pl);
+  const bool lds_window = pl.k[0].window == PH_PLAN_LDS;
+  const size_t lds = pl.k[0].lds;
   const int *d_p, *d_keep, *d_off;
   int stride;
   PH_TRY(qo_tables(c, p_list, keep, n_p, &d_p, &d_keep, &d_off, &stride));
@@ -1453,7 +1733,7 @@ int ph_fold_sums(ph_ctx* c, const void* x, int dtype, int64_t W, int N, const in
     auto kernel = ph::k_fold_sums<T, decltype(lw)::value>;
     PH_TRY(allow_lds(kernel, lds));
     ProfScope ps_(c, "k_fold_sums");
-    hipLaunchKernelGGL(kernel, grid, dim3(kBlock), lds, c->stream, (const T*)dx, N, d_p, d_keep, d_off, n_p, stride,
+    hipLaunchKernelGGL(kernel, grid, dim3(pl.k[0].block), lds, c->stream, (const T*)dx, N, d_p, d_keep, d_off, n_p, stride,
                        (double*)dout);
     return (int)PH_OK;
   }));
@@ -1681,16 +1961,12 @@ int ph_orth_powers(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int ma
   if (max_p < 2) return fail(PH_E_ARG, "max_p=%d must be >= 2", max_p);
   PH_HIP(hipSetDevice(c->device));
   const size_t sz = elem_size(dtype);
-  // window + autocorrelation + clipped eq. 3 values in LDS when they fit, otherwise the window is read
-  // from HBM / L2 and the two work arrays live in an HBM workspace
-  size_t lds = carve_bytes(N, sz) + carve_bytes(N, 8) + carve_bytes(max_p, 8);
-  const bool lds_window = lds <= (size_t)c->lds_limit;
-  double* gws = nullptr;
-  if (!lds_window) {
-    lds = 0;
-    PH_TRY(ensure(c, c->buf[B_WS1], (size_t)W * ((size_t)N + max_p) * sizeof(double)));
-    gws = static_cast<double*>(c->buf[B_WS1].p);
-  }
+  Plan pl;
+  plan_orth_powers(c, dtype, N, max_p, &pl);
+  const bool lds_window = pl.k[0].window == PH_PLAN_LDS;
+  const size_t lds = pl.k[0].lds;
+  void* gws;
+  PH_TRY(place(c, pl.k[0].second, B_WS1, (size_t)W * ((size_t)N + max_p) * sizeof(double), &gws));
   // divisors d of q with mu(q/d) != 0, for q < max_p
   std::vector<int32_t> mu(max_p, 1), off(max_p + 1, 0), dd, dm;
   {
@@ -1730,8 +2006,8 @@ int ph_orth_powers(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int ma
     auto kernel = ph::k_orth_powers<T, decltype(lw)::value>;
     PH_TRY(allow_lds(kernel, lds));
     ProfScope ps_(c, "k_orth_powers");
-    hipLaunchKernelGGL(kernel, grid, dim3(kBlockWide), lds, c->stream, (const T*)dx, N, max_p, normalize, d_off, d_d, d_mu,
-                       gws, (double*)dr, (double*)de, (double*)dp);
+    hipLaunchKernelGGL(kernel, grid, dim3(pl.k[0].block), lds, c->stream, (const T*)dx, N, max_p, normalize, d_off, d_d, d_mu,
+                       (double*)gws, (double*)dr, (double*)de, (double*)dp);
     return (int)PH_OK;
   }));
   PH_TRY(launch_check("k_orth_powers"));

@@ -16,6 +16,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import threading
+from typing import NamedTuple
 
 import numpy as np
 
@@ -58,6 +59,19 @@ class _Out:
         if _is_torch(a):
             return a.data_ptr()
         return a.ctypes.data
+
+
+class KernelPlan(NamedTuple):
+    """One kernel of an entry point's launch plan (ph_plan_info; values are the PH_PLAN_* constants of _ffi)."""
+
+    variant: int  # PH_PLAN_ONE, PH_PLAN_PAIR, PH_PLAN_FFT, PH_PLAN_CHIRP, PH_PLAN_DIRECT
+    window: int  # PH_PLAN_LDS or PH_PLAN_HBM
+    second: int  # PH_PLAN_NONE, PH_PLAN_LDS or PH_PLAN_HBM
+    block: int
+    lds_bytes: int
+    small_means: int
+    waves: int
+    pad: int
 
 
 def _i32(a):
@@ -390,6 +404,26 @@ class PeriodEngine:
         _ffi.check(self._lib.ph_qo_plan_info(self._ctx, code, int(n), int(max_length if max_length is not None else n // 3),
                                              int(kcap), fl, C.byref(lds), C.byref(where)))
         return where.value, lds.value
+
+    _PLAN_OPS = {"project": _ffi.PH_OP_PROJECT, "sweep": _ffi.PH_OP_SWEEP, "m_best": _ffi.PH_OP_M_BEST,
+                 "small_to_large": _ffi.PH_OP_SMALL_TO_LARGE, "best_correlation": _ffi.PH_OP_BEST_CORRELATION,
+                 "best_frequency": _ffi.PH_OP_BEST_FREQUENCY, "ramanujan": _ffi.PH_OP_RAMANUJAN,
+                 "orth_powers": _ffi.PH_OP_ORTH_POWERS, "fold_sums": _ffi.PH_OP_FOLD_SUMS}
+
+    def plan_info(self, op, n, params=(), dtype=np.float64, trunc=False, orth=False):
+        """-> tuple of one KernelPlan per kernel the entry point `op` ("project", "sweep", "m_best", ...) would launch
+        for windows of n samples: m_best (step 1, step 2), best_frequency (spectrum, update), one otherwise.  `params`
+        are the op's int parameters in the order periodhip.h lists for ph_plan_info.  Nothing runs on the device."""
+        prm = np.ascontiguousarray(np.asarray(params, dtype=np.int32).reshape(-1))
+        out = np.zeros(_ffi.PH_PLAN_LEN, dtype=np.int32)
+        _ffi.check(self._lib.ph_plan_info(self._ctx, self._PLAN_OPS[op], _NP_DTYPES[np.dtype(dtype)], int(n),
+                                          prm.ctypes.data if prm.size else None, int(prm.size), self._flags(trunc, orth),
+                                          out.ctypes.data))
+        recs = []
+        for k in range(int(out[_ffi.PH_PLAN_KERNELS])):
+            r = out[_ffi.PH_PLAN_K0 + k * _ffi.PH_PLAN_STRIDE:][:_ffi.PH_PLAN_STRIDE]
+            recs.append(KernelPlan(*(int(v) for v in r)))
+        return tuple(recs)
 
     def orth_powers(self, x, max_p=None, normalize=False, want_autocorr=False, want_eq3=False):
         """Orthogonal period powers (QOPeriods.get_best_period_orthogonal(return_powers=True)).

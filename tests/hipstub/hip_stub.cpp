@@ -14,15 +14,40 @@ void** __hipRegisterFatBinary(const void*) {
 }
 void __hipUnregisterFatBinary(void**) {}
 void __hipRegisterFunction(void**, const void*, char*, const char*, unsigned, void*, void*, void*, void*, int*) {}
-hipError_t __hipPushCallConfiguration(dim3, dim3, size_t, hipStream_t) { return hipSuccess; }
+// the launch configuration travels from the <<<>>> push to the kernel stub's pop, and every launch's block size and
+// dynamic LDS are recorded at the push (stub_launches) so that the driver can hold a launch to its ph_plan_info record
+static dim3 g_cfg_grid(1), g_cfg_block(1);
+static size_t g_cfg_shmem = 0;
+static int g_n_launch = 0;
+static int g_launch_block[16];
+static long long g_launch_lds[16];
+hipError_t __hipPushCallConfiguration(dim3 g, dim3 b, size_t s, hipStream_t) {
+  g_cfg_grid = g;
+  g_cfg_block = b;
+  g_cfg_shmem = s;
+  if (g_n_launch < 16) {  // every <<<>>> launch pushes its configuration once
+    g_launch_block[g_n_launch] = (int)(b.x * b.y * b.z);
+    g_launch_lds[g_n_launch] = (long long)s;
+  }
+  ++g_n_launch;
+  return hipSuccess;
+}
 hipError_t __hipPopCallConfiguration(dim3* g, dim3* b, size_t* s, hipStream_t* st) {
-  *g = dim3(1);
-  *b = dim3(1);
-  *s = 0;
+  *g = g_cfg_grid;
+  *b = g_cfg_block;
+  *s = g_cfg_shmem;
   *st = nullptr;
   return hipSuccess;
 }
 hipError_t hipLaunchKernel(const void*, dim3, dim3, void**, size_t, hipStream_t) { return hipSuccess; }
+void stub_reset_launches() { g_n_launch = 0; }
+int stub_launches(int* block, long long* lds, int cap) {
+  for (int i = 0; i < g_n_launch && i < cap && i < 16; ++i) {
+    block[i] = g_launch_block[i];
+    lds[i] = g_launch_lds[i];
+  }
+  return g_n_launch;
+}
 hipError_t hipGetDeviceCount(int* n) {
   *n = 1;
   return hipSuccess;

@@ -9,6 +9,9 @@
 
 #include "../../include/periodhip.h"
 
+extern "C" void stub_reset_launches();
+extern "C" int stub_launches(int* block, long long* lds, int cap);
+
 static int fails = 0;
 #define EXPECT(call, want)                                                              \
   do {                                                                                  \
@@ -52,6 +55,127 @@ static Csr orth_tables(int max_p) {
   t.off[max_p + 1] = (int32_t)t.q.size();
   if (t.q.empty()) t.q.push_back(1);
   return t;
+}
+
+// ph_plan_info for `op`, then the entry point itself (run): the launches the stub records must be the plan's kernels,
+// with the plan's block size and dynamic LDS.
+template <typename F>
+static void expect_plan(ph_ctx* c, int op, int dtype, int N, std::vector<int32_t> prm, unsigned fl, int line, F run) {
+  int32_t rec[PH_PLAN_LEN];
+  const int rc = ph_plan_info(c, op, dtype, N, prm.data(), (int)prm.size(), fl, rec);
+  if (rc != PH_OK) {
+    std::printf("FAIL line %d: ph_plan_info(op %d, N %d) -> %d (%s)\n", line, op, N, rc, ph_last_error());
+    ++fails;
+    return;
+  }
+  stub_reset_launches();
+  const int rr = run();
+  int block[16];
+  long long lds[16];
+  const int n = stub_launches(block, lds, 16);
+  bool ok = rr == PH_OK && n == rec[PH_PLAN_KERNELS];
+  for (int k = 0; ok && k < n; ++k) {
+    const int32_t* r = rec + PH_PLAN_K0 + k * PH_PLAN_STRIDE;
+    ok = block[k] == r[PH_PLAN_BLOCK] && lds[k] == r[PH_PLAN_LDS_BYTES];
+  }
+  if (!ok) {
+    std::printf("FAIL line %d: op %d dtype %d N %d flags %u: run -> %d, %d launches, plan %d kernels", line, op, dtype, N, fl,
+                rr, n, rec[PH_PLAN_KERNELS]);
+    for (int k = 0; k < n && k < 2; ++k)
+      std::printf(" | launch %d: block %d lds %lld, plan block %d lds %d", k, block[k], lds[k],
+                  rec[PH_PLAN_K0 + k * PH_PLAN_STRIDE + PH_PLAN_BLOCK], rec[PH_PLAN_K0 + k * PH_PLAN_STRIDE + PH_PLAN_LDS_BYTES]);
+    std::printf("\n");
+    ++fails;
+  }
+}
+
+static void plan_checks(ph_ctx* c) {
+  int32_t rec[PH_PLAN_LEN];
+  const int32_t prm[4] = {2, 300, 0, 0};
+  // bad arguments
+  EXPECT(ph_plan_info(c, 99, PH_F64, 4096, nullptr, 0, 0, rec), PH_E_ARG);
+  EXPECT(ph_plan_info(c, PH_OP_SWEEP, 7, 4096, nullptr, 0, 0, rec), PH_E_ARG);
+  EXPECT(ph_plan_info(c, PH_OP_SWEEP, PH_F64, 0, nullptr, 0, 0, rec), PH_E_ARG);
+  EXPECT(ph_plan_info(c, PH_OP_SWEEP, PH_F64, 4096, nullptr, 2, 0, rec), PH_E_ARG);
+  EXPECT(ph_plan_info(c, PH_OP_SWEEP, PH_F64, 4096, prm, -1, 0, rec), PH_E_ARG);
+  EXPECT(ph_plan_info(c, PH_OP_SWEEP, PH_F64, 4096, prm, 2, 0, nullptr), PH_E_ARG);
+  EXPECT(ph_plan_info(nullptr, PH_OP_SWEEP, PH_F64, 4096, prm, 2, 0, rec), PH_E_ARG);
+  const int32_t bad_sweep[3] = {5, 4, 0}, bad_mode[3] = {2, 40, 3}, bad_num[3] = {0, 2, 40}, bad_len[3] = {5, 9, 3};
+  EXPECT(ph_plan_info(c, PH_OP_SWEEP, PH_F64, 4096, bad_sweep, 3, 0, rec), PH_E_ARG);
+  EXPECT(ph_plan_info(c, PH_OP_SWEEP, PH_F64, 4096, bad_mode, 3, 0, rec), PH_E_ARG);
+  EXPECT(ph_plan_info(c, PH_OP_M_BEST, PH_F64, 4096, bad_num, 3, 0, rec), PH_E_ARG);
+  EXPECT(ph_plan_info(c, PH_OP_M_BEST, PH_F64, 4096, bad_len, 3, 0, rec), PH_E_ARG);
+  const int32_t ram_wide[2] = {2, 20000}, ram_format[2] = {2, 30030}, orth_small[1] = {1}, bf_bad[1] = {1};
+  EXPECT(ph_plan_info(c, PH_OP_RAMANUJAN, PH_F64, 60000, ram_wide, 2, 0, rec), PH_E_ARG);  // one wave's strips > LDS
+  EXPECT(ph_plan_info(c, PH_OP_RAMANUJAN, PH_F64, 100000, ram_format, 2, 0, rec), PH_E_ARG);
+  EXPECT(ph_plan_info(c, PH_OP_ORTH_POWERS, PH_F64, 4096, orth_small, 1, 0, rec), PH_E_ARG);
+  EXPECT(ph_plan_info(c, PH_OP_BEST_FREQUENCY, PH_F64, 1, bf_bad, 1, 0, rec), PH_E_ARG);
+  {
+    std::vector<double> x(60000, 0.5), out((size_t)20001);
+    EXPECT(ph_ramanujan_norms(c, x.data(), PH_F64, 1, 60000, 2, 20000, 0, out.data()), PH_E_ARG);
+  }
+  // both sides of the pair, step-1 block, small_means, second-buffer, window and FFT / chirp switches
+  const int max_len = 300;
+  const Csr fac = factor_tables(max_len), orth = orth_tables(2 * 8192);
+  for (int N : {1000, 3071, 3072, 5400, 6500, 9400, 9800, 10100, 19400, 20200, 21000, 40500, 41000}) {
+    std::vector<double> x((size_t)N);
+    for (int i = 0; i < N; ++i) x[i] = std::sin(0.37 * i) + 0.25 * std::sin(0.05 * i);
+    std::vector<float> xf(x.begin(), x.end());
+    for (int dtype : {PH_F64, PH_F32}) {
+      const void* px = dtype == PH_F64 ? (const void*)x.data() : (const void*)xf.data();
+      for (unsigned fl : {0u, (unsigned)PH_FLAG_TRUNC}) {
+        const int num = 3;
+        std::vector<uint32_t> per(num);
+        std::vector<double> pw(num), bases((size_t)num * N), sw(max_len + 1), proj((size_t)2 * N);
+        std::vector<int32_t> st(1), cnt(1), ip(16);
+        std::vector<int32_t> pl = {7, max_len};
+        expect_plan(c, PH_OP_PROJECT, dtype, N, {max_len}, fl, __LINE__, [&] {
+          return ph_project_batch(c, px, dtype, 1, N, pl.data(), 2, nullptr, nullptr, 0, fl, proj.data());
+        });
+        expect_plan(c, PH_OP_SWEEP, dtype, N, {2, max_len, PH_SWEEP_NORM}, fl, __LINE__, [&] {
+          return ph_sweep(c, px, dtype, 1, N, 2, max_len, PH_SWEEP_NORM, nullptr, nullptr, 0, fl, sw.data());
+        });
+        expect_plan(c, PH_OP_M_BEST, dtype, N, {num, 2, max_len}, fl, __LINE__, [&] {
+          return ph_m_best(c, px, dtype, 1, N, num, 2, max_len, 0, nullptr, nullptr, fac.off.data(), fac.q.data(), max_len, fl,
+                           per.data(), pw.data(), bases.data(), st.data(), nullptr);
+        });
+        std::vector<double> sb((size_t)16 * N), spw(16);
+        expect_plan(c, PH_OP_SMALL_TO_LARGE, dtype, N, {max_len}, fl, __LINE__, [&] {
+          return ph_small_to_large(c, px, dtype, 1, N, 0.05, max_len, nullptr, nullptr, 0, fl, 16, cnt.data(), ip.data(),
+                                   spw.data(), sb.data(), st.data());
+        });
+        expect_plan(c, PH_OP_BEST_CORRELATION, dtype, N, {max_len}, fl, __LINE__, [&] {
+          return ph_best_correlation(c, px, dtype, 1, N, num, max_len, 0.01, nullptr, nullptr, 0, fl, per.data(), pw.data(),
+                                     bases.data(), st.data());
+        });
+        for (int win : {256, 300, 4096, 5400, 5500, 8192, 16384}) {
+          std::vector<uint32_t> bp(1);
+          std::vector<double> bpw(1), bb((size_t)N);
+          expect_plan(c, PH_OP_BEST_FREQUENCY, dtype, N, {win}, fl, __LINE__, [&] {
+            return ph_best_frequency(c, px, dtype, 1, N, win, 1, orth.off.data(), orth.q.data(), 2 * 8192, fl, bp.data(),
+                                     bpw.data(), bb.data(), st.data());
+          });
+        }
+        if (fl) continue;  // the remaining ops take no flags
+        for (int qh : {64, 128, 512, N / 3}) {
+          if (12 * (size_t)qh + 32 > 160 * 1024) continue;  // one wave's strips exceed the LDS: refused above
+          std::vector<double> rn((size_t)qh + 1);
+          expect_plan(c, PH_OP_RAMANUJAN, dtype, N, {2, qh}, 0, __LINE__, [&] {
+            return ph_ramanujan_norms(c, px, dtype, 1, N, 2, qh, 0, rn.data());
+          });
+        }
+        std::vector<double> op((size_t)max_len);
+        expect_plan(c, PH_OP_ORTH_POWERS, dtype, N, {max_len}, 0, __LINE__, [&] {
+          return ph_orth_powers(c, px, dtype, 1, N, max_len, 0, 0, nullptr, nullptr, op.data());
+        });
+        std::vector<int32_t> fp = {3, 8}, fk = {3, 7};
+        std::vector<double> fs(10);
+        expect_plan(c, PH_OP_FOLD_SUMS, dtype, N, {}, 0, __LINE__, [&] {
+          return ph_fold_sums(c, px, dtype, 1, N, fp.data(), fk.data(), 2, 0, fs.data());
+        });
+      }
+    }
+  }
 }
 
 int main() {
@@ -174,6 +298,7 @@ int main() {
     EXPECT(ph_project_batch(c, nullptr, PH_F64, W, N, one.data(), 1, nullptr, nullptr, 0, 0, out.data()), PH_E_ARG);
     EXPECT(ph_sweep(c, x.data(), PH_F64, 0, N, 2, 3, 0, nullptr, nullptr, 0, 0, out.data()), PH_E_ARG);
   }
+  plan_checks(c);
   float ms[300];
   int cntp = 0;
   EXPECT(ph_profile_read(c, ms, 300, &cntp), PH_OK);

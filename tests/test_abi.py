@@ -45,7 +45,13 @@ def test_header_constants_match_binding():
     for name in ("PH_OK", "PH_E_ARG", "PH_E_HIP", "PH_E_NOMEM", "PH_E_CAP", "PH_E_UNSUPPORTED", "PH_F64", "PH_F32",
                  "PH_FLAG_TRUNC", "PH_FLAG_ORTH", "PH_FLAG_SINGLE", "PH_FLAG_DEVICE", "PH_FLAG_NOSYNC", "PH_SWEEP_NORM",
                  "PH_SWEEP_NORM_GAMMA", "PH_SWEEP_MAXABS", "PH_ST_OK", "PH_ST_NO_PERIOD", "PH_ST_ITER_CAP", "PH_ST_CAP",
-                 "PH_QO_LDS_OVERLAY", "PH_QO_LDS_BEHIND", "PH_QO_HBM"):
+                 "PH_QO_LDS_OVERLAY", "PH_QO_LDS_BEHIND", "PH_QO_HBM",
+                 "PH_OP_PROJECT", "PH_OP_SWEEP", "PH_OP_M_BEST", "PH_OP_SMALL_TO_LARGE", "PH_OP_BEST_CORRELATION",
+                 "PH_OP_BEST_FREQUENCY", "PH_OP_RAMANUJAN", "PH_OP_ORTH_POWERS", "PH_OP_FOLD_SUMS",
+                 "PH_PLAN_KERNELS", "PH_PLAN_K0", "PH_PLAN_K1", "PH_PLAN_STRIDE", "PH_PLAN_LEN", "PH_PLAN_VARIANT",
+                 "PH_PLAN_WINDOW", "PH_PLAN_SECOND", "PH_PLAN_BLOCK", "PH_PLAN_LDS_BYTES", "PH_PLAN_SMALL_MEANS",
+                 "PH_PLAN_WAVES", "PH_PLAN_PAD", "PH_PLAN_ONE", "PH_PLAN_PAIR", "PH_PLAN_FFT", "PH_PLAN_CHIRP",
+                 "PH_PLAN_DIRECT", "PH_PLAN_NONE", "PH_PLAN_LDS", "PH_PLAN_HBM"):
         m = re.search(rf"#define {name} \(?(-?\d+)u?\)?", text)
         assert m, name
         assert int(m.group(1)) == getattr(_ffi, name), name
@@ -70,6 +76,8 @@ def test_helper_entry_points_reject_null_without_gpu(lib):
     assert lib.ph_sweep_plan_info(None, 2, 1365, ctypes.byref(n_pass), ctypes.byref(n_per)) == _ffi.PH_E_ARG
     assert lib.ph_qo_feasible(None, _ffi.PH_F64, 4096, -1, 512, ctypes.byref(ok)) == _ffi.PH_E_ARG
     assert lib.ph_qo_plan_info(None, _ffi.PH_F64, 4096, -1, 512, 0, ctypes.byref(ok), ctypes.byref(ok)) == _ffi.PH_E_ARG
+    rec = (ctypes.c_int32 * _ffi.PH_PLAN_LEN)()
+    assert lib.ph_plan_info(None, _ffi.PH_OP_SWEEP, _ffi.PH_F64, 4096, None, 0, 0, ctypes.addressof(rec)) == _ffi.PH_E_ARG
     assert lib.ph_small_to_large(None, None, 0, 1, 16, 0.1, -1, None, None, 0, _ffi.PH_FLAG_DEVICE | _ffi.PH_FLAG_NOSYNC, 4,
                                  None, None, None, None, None) == _ffi.PH_E_ARG
     assert _ffi.PH_FLAG_NOSYNC == 16

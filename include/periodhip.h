@@ -284,6 +284,13 @@ int ph_qo_plan_info(ph_ctx* ctx, int dtype, int N, int max_length, int kcap, uns
  *   PH_OP_RAMANUJAN         {q_lo, q_hi}                             default 2, N / 3
  *   PH_OP_ORTH_POWERS       {max_p}                                  default N / 2
  *   PH_OP_FOLD_SUMS         {}
+ *   PH_OP_QO_FIT            {kcap, max period}                       default 512, N   (ph_qo_fit; ph_ramanujan_fit's
+ *                                                                   third kernel with max period = q_hi).  N and dtype
+ *                                                                   do not enter: the window is read from HBM / L2
+ *                                                                   (PH_PLAN_HBM) and the LDS holds the solver only.
+ *                                                                   A kcap whose vectors do not fit the LDS returns
+ *                                                                   PH_E_ARG here as at the launch, so the largest
+ *                                                                   feasible kcap is found without launching.
  * ph_tile_sum and ph_dict_project do not depend on N (LDS of sum(keep) doubles / none) and have no op.
  * out[PH_PLAN_LEN] int32: out[PH_PLAN_KERNELS] kernels launched per call (per round for best_frequency), then one
  * record of PH_PLAN_STRIDE words per kernel at out[PH_PLAN_K0] (m_best step 1, best_frequency spectrum) and
@@ -308,6 +315,7 @@ int ph_qo_plan_info(ph_ctx* ctx, int dtype, int N, int max_length, int kcap, uns
 #define PH_OP_RAMANUJAN 6
 #define PH_OP_ORTH_POWERS 7
 #define PH_OP_FOLD_SUMS 8
+#define PH_OP_QO_FIT 9
 #define PH_PLAN_KERNELS 0
 #define PH_PLAN_K0 1
 #define PH_PLAN_K1 9
@@ -331,6 +339,41 @@ int ph_qo_plan_info(ph_ctx* ctx, int dtype, int N, int max_length, int kcap, uns
 #define PH_PLAN_HBM 2
 int ph_plan_info(ph_ctx* ctx, int op, int dtype, int N, const int32_t* params, int n_params, unsigned flags,
                  int32_t* out);
+
+/* ---- fit of a GIVEN period list: QOPeriods.compute_reconstruction / get_subspaces + solve_quadratic ------------
+ * (QOPeriods.py:807-852, :779-796, :1054-1116), natural basis, no analysis window.  One workgroup per window runs the
+ * phi-mass row bookkeeping, the right-hand side by folds, the matrix-free preconditioned conjugate gradients of
+ * ph_qo_find_periods (same product, tolerances and iteration bound 4 K + 100, started from zero) and the residual.
+ * periods (W, pcap) int32 with n_periods (W) int32 entries used per window, rows per_stride >= pcap apart;
+ * per_stride == 0: one list periods[0 .. pcap) with n_periods[0] shared by all windows.  Both follow PH_FLAG_DEVICE
+ * like every array, so the host may not be able to read the lists: max_period (<= 2^20) bounds the phi / divisor
+ * tables and the divisor bitset, and a window whose list holds an entry < 1 or > max_period gets PH_ST_ITER_CAP.
+ * keeps (W, pcap) int32 (0 behind the list); weights (W, kcap) float64, rows of block b start at sum(keeps[:b]);
+ * residual (W, N) dtype of x; status (W) int32:
+ *   PH_ST_OK
+ *   PH_ST_NO_PERIOD  empty list
+ *   PH_ST_CAP        more than pcap or 64 entries, or sum(keeps) > kcap
+ *   PH_ST_ITER_CAP   a period outside 1 .. max_period; a block without rows (a repeated period, or one whose
+ *                    divisors are all present: the reference's matrix is singular) or with more rows than samples;
+ *                    sum(keeps) > N (rank deficient);
+ *                    non-positive curvature or a non-finite residual of the solve; no convergence within the bound
+ * Windows that are not PH_ST_OK have zero weights and an unspecified residual; callers re-run them on the host. */
+int ph_qo_fit(ph_ctx* ctx, const void* x, int dtype, int64_t W, int N,
+              const int32_t* periods, const int32_t* n_periods, int pcap, int per_stride, int max_period,
+              int kcap, unsigned flags,
+              int32_t* keeps, double* weights, void* residual, int32_t* status);
+
+/* ---- RamanujanPeriods.find_periods_with_weights (RamanujanPeriods.py:88-122), default test function ----------
+ * ph_ramanujan_norms, the threshold (periods = the q with norms[q] / |max(norms)| > thresh, that IEEE division and
+ * strict comparison, NaN never selected) and ph_qo_fit's kernel, enqueued on the context's stream with no host round
+ * trip between them.  norms (W, q_hi + 1) float64 as ph_ramanujan_norms writes them; periods (W, pcap) int32
+ * ascending (0 behind the list); counts (W) int32 = periods selected (may exceed pcap: PH_ST_CAP); keeps, weights,
+ * residual, status as ph_qo_fit with max_period = q_hi.  thresh must be > 0 (PH_E_ARG otherwise: index 0 would be
+ * selected and the reference dies on period 0). */
+int ph_ramanujan_fit(ph_ctx* ctx, const void* x, int dtype, int64_t W, int N, int q_lo, int q_hi, double thresh,
+                     int pcap, int kcap, unsigned flags,
+                     double* norms, int32_t* periods, int32_t* counts, int32_t* keeps,
+                     double* weights, void* residual, int32_t* status);
 
 /* ---- QOPeriods.get_best_period_orthogonal / eq_3 / auto_corr (QOPeriods.py:1122-1232) -----
  * powers (W, max_p) float64: the Muresan-Parks orthogonal period powers `pows` for q < max_p

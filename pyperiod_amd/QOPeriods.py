@@ -77,8 +77,8 @@ class _LazyBases(dict):
     need nothing built."""
 
     def __init__(self, blocks, n, basis_type, **items):
-        super().__init__(periods=items["periods"], norms=items["norms"], subspaces=None, weights=items["weights"],
-                         basis_dictionary=items["basis_dictionary"])
+        head = {k: items[k] for k in ("periods", "norms") if k in items}  # (compute_reconstruction reports no norms)
+        super().__init__(**head, subspaces=None, weights=items["weights"], basis_dictionary=items["basis_dictionary"])
         self._blocks, self._n, self._basis_type = blocks, n, basis_type
 
     def _subspaces(self):
@@ -470,8 +470,89 @@ class QOPeriods(Periods):
         A = np.vstack(blocks) if blocks else np.array([]).reshape((0, N))
         return (A, d)
 
+    def _fit_lists_device(self, eng, x, per, counts, max_period, first=None):
+        """Fit the period lists per[w, :counts[w]] (int32, at most 64 columns) to the rows of the float32 / float64 batch
+        `x` with ph_qo_fit.  `first` = (kcap, keeps, weights, residual, status) of a launch that already ran on these
+        lists (ph_ramanujan_fit).  Capacity grows by re-running only the PH_ST_CAP rows while the plan query says the
+        larger kcap fits.  -> per row None (the caller runs its 1-D call) or (blocks, weights, float64 residual)."""
+        W, N = x.shape
+        out = [None] * W
+
+        def take(todo, kcap, keeps, wts, resid, st):
+            if resid.dtype != np.float64:
+                resid = _to_f64(resid)
+            for i, w in enumerate(todo):
+                if st[i] != _ffi.PH_ST_OK:
+                    continue
+                blocks = [(int(per[w, b]), int(keeps[i, b])) for b in range(int(counts[w]))]
+                out[w] = (blocks, wts[i, : sum(k for _, k in blocks)], resid[i])
+            # a list longer than the device's 64 blocks stays PH_ST_CAP at every capacity
+            return todo[(st == _ffi.PH_ST_CAP) & (counts[todo] <= per.shape[1])]
+
+        if first is None:
+            kcap = 512
+            while kcap > 64 and not eng.qo_fit_feasible(kcap, max_period):
+                kcap //= 2
+            if not eng.qo_fit_feasible(kcap, max_period):
+                return out
+            todo = np.arange(W)
+            todo = take(todo, kcap, *eng.qo_fit(x, per, counts, kcap, max_period))
+        else:
+            kcap = first[0]
+            todo = take(np.arange(W), *first)
+        while todo.size:
+            nxt = 2 * kcap
+            if not eng.qo_fit_feasible(nxt, max_period):  # the last feasible capacity below the doubling, in steps of 64
+                lo, hi = kcap // 64, nxt // 64
+                while hi - lo > 1:
+                    mid = (lo + hi) // 2
+                    lo, hi = (mid, hi) if eng.qo_fit_feasible(64 * mid, max_period) else (lo, mid)
+                nxt = 64 * lo
+            if nxt <= kcap:
+                break
+            kcap = nxt
+            todo = take(todo, kcap, *eng.qo_fit(np.ascontiguousarray(x[todo]), np.ascontiguousarray(per[todo]),
+                                                np.ascontiguousarray(counts[todo]), kcap, max_period))
+        return out
+
+    def _compute_reconstruction_batch(self, x, periods, type, window):
+        """compute_reconstruction over a (W, N) batch: `periods` is one list for every row or a list of W lists.  A list
+        of W ``(reconstruction, output_bases)`` tuples (``None`` where the 1-D call returns ``None``), each what the 1-D
+        call on that row returns.  Natural basis without an analysis window: one ph_qo_fit launch per batch (float32
+        batches in the fp32 kernel), ``subspaces`` built on first read; rows the kernel hands back (singular or
+        ill-conditioned dictionaries, more than 64 periods or more rows than the LDS holds) and every other setting run
+        the 1-D call on the row."""
+        W, N = x.shape
+        per_row = len(periods) == W and W > 0 and all(np.ndim(p) == 1 for p in periods)
+        lists = [periods[w] if per_row else periods for w in range(W)]
+        out = [None] * W
+        done = [False] * W
+        if window is None and self._basis_type == "natural" and W > 0:
+            xs = np.ascontiguousarray(x if x.dtype in (np.float32, np.float64) else x.astype(np.float64))
+            arrs = [np.asarray(p).astype(np.int64).reshape(-1) for p in lists]
+            counts = np.array([a.size for a in arrs], dtype=np.int32)
+            per = np.zeros((W, 64), dtype=np.int32)
+            for w, a in enumerate(arrs):
+                per[w, : min(a.size, 64)] = np.clip(a[:64], -1, (1 << 20) + 1)  # (out-of-range entries stay out of range)
+            max_period = int(min(max(1, per.max()), 1 << 20))
+            x64 = xs if xs.dtype == np.float64 else _to_f64(xs)
+            for w, r in enumerate(self._fit_lists_device(default_engine(), xs, per, counts, max_period)):
+                if r is None:
+                    continue
+                blocks, wts, resid = r
+                bases = _LazyBases(blocks, N, self._basis_type, periods=lists[w], weights=wts,
+                                   basis_dictionary={str(q): k for q, k in zip(lists[w], (k for _, k in blocks))})
+                out[w], done[w] = (x64[w] - resid, bases), True
+        for w in range(W):
+            if not done[w]:  # the 1-D call on the row, whatever it is
+                out[w] = self.compute_reconstruction(x[w], lists[w], type, window)
+        return out
+
     def compute_reconstruction(self, x, periods, type: str = "lstsq", window=None):
-        """QOPeriods.py:1054-1116."""
+        """QOPeriods.py:1054-1116.  A ``(W, N)`` ndarray with one period list or a list of W lists returns a list of W
+        results (see ``_compute_reconstruction_batch``)."""
+        if isinstance(x, np.ndarray) and x.ndim == 2:
+            return self._compute_reconstruction_batch(x, periods, type, window)
         basis_matricies, basis_dictionary = self.get_subspaces(periods, len(x))
         try:
             output_weights, reconstruction = self.solve_quadratic(x, basis_matricies, window=window, type=type)

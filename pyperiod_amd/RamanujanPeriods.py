@@ -14,7 +14,7 @@ import numpy as np
 from ._factors import get_factors, phi  # noqa: F401
 from .engine import default_engine
 from .Periods import _as_window, rms  # noqa: F401
-from .QOPeriods import QOPeriods, flatten, ramanujan_sum  # noqa: F401
+from .QOPeriods import QOPeriods, _LazyBases, flatten, ramanujan_sum  # noqa: F401
 
 
 class RamanujanPeriods(QOPeriods):
@@ -45,7 +45,12 @@ class RamanujanPeriods(QOPeriods):
         periods to the window (RamanujanPeriods.py:88-122).  The v1 reference cannot run this
         method (``_k`` is missing and solve_quadratic's pair is unpacked the wrong way round,
         :109); it is implemented as written otherwise: periods = indices whose norm exceeds
-        ``thresh`` x the largest norm, or whatever ``test_function(norms)`` returns."""
+        ``thresh`` x the largest norm, or whatever ``test_function(norms)`` returns.
+
+        A ``(W, N)`` ndarray returns a list of W ``(output_bases, residual)`` tuples, each what the 1-D call on that
+        row returns, and ``_output`` becomes the list of the dicts (see ``_find_periods_with_weights_batch``)."""
+        if isinstance(x, np.ndarray) and x.ndim == 2:
+            return self._find_periods_with_weights_batch(x, min_length, max_length, thresh, kwargs.get("test_function"))
         sig = _as_window(x)
         norms = self.find_periods(sig, min_length, max_length)
         select = kwargs.get("test_function")
@@ -63,6 +68,53 @@ class RamanujanPeriods(QOPeriods):
             "basis_dictionary": dims,
         }
         return (self._output, sig - recon)
+
+    def _find_periods_with_weights_batch(self, data, min_length, max_length, thresh, select):
+        """find_periods_with_weights over a (W, N) batch.  Natural basis without an analysis window: the norms, the
+        threshold and the fit run as three kernels of ONE ph_ramanujan_fit call with no host round trip between them
+        (float32 batches in the fp32 kernels, residuals returned as float64).  With ``test_function`` the norms of the
+        batch come from one ph_ramanujan_norms call, the function is called per row on that row's norms and the lists
+        go through ph_qo_fit.  ``subspaces`` of a device row is built on first read.  Rows the fit hands back -- a
+        singular or ill-conditioned dictionary, more than 64 periods, more rows than the LDS holds -- and every other
+        setting run the 1-D call on the row."""
+        W, N = data.shape
+        windowed = not (self.window is None or self.window is False)
+        out = [None] * W
+        if self._basis_type == "natural" and not windowed and W > 0 and (select is not None or thresh > 0):
+            x = np.ascontiguousarray(data if data.dtype in (np.float32, np.float64) else data.astype(np.float64))
+            q_hi = int(max_length) if max_length else N // 3
+            eng = default_engine()
+            if select is None:
+                kcap = 512
+                while kcap > 64 and not eng.qo_fit_feasible(kcap, q_hi):
+                    kcap //= 2
+                if eng.qo_fit_feasible(kcap, q_hi):
+                    norms, per, counts, keeps, wts, resid, st = eng.ramanujan_fit(x, int(min_length), q_hi, thresh, 64, kcap)
+                    fits = self._fit_lists_device(eng, x, per, counts, q_hi, first=(kcap, keeps, wts, resid, st))
+                    lists = [per[w, : min(int(counts[w]), 64)].astype(np.int64) for w in range(W)]
+                else:
+                    fits = [None] * W
+            else:
+                norms = eng.ramanujan_norms(x, int(min_length), q_hi)
+                lists = [select(norms[w]) for w in range(W)]
+                arrs = [np.asarray(p).astype(np.int64).reshape(-1) for p in lists]
+                counts = np.array([a.size for a in arrs], dtype=np.int32)
+                per = np.zeros((W, 64), dtype=np.int32)
+                for w, a in enumerate(arrs):
+                    per[w, : min(a.size, 64)] = np.clip(a[:64], -1, q_hi + 1)  # (out-of-range entries stay out of range)
+                fits = self._fit_lists_device(eng, x, per, counts, q_hi)
+            for w, r in enumerate(fits):
+                if r is None:
+                    continue
+                blocks, weights, resid_w = r
+                out[w] = (_LazyBases(blocks, N, self._basis_type, periods=lists[w], norms=norms[w][lists[w]], weights=weights,
+                                     basis_dictionary={str(q): k for q, k in zip(lists[w], (k for _, k in blocks))}), resid_w)
+        kw = {} if select is None else {"test_function": select}
+        for w in range(W):
+            if out[w] is None:  # the 1-D call on the row, whatever it is
+                out[w] = self.find_periods_with_weights(data[w], min_length, max_length, thresh, **kw)
+        self._output = [r[0] for r in out]
+        return out
 
     @staticmethod
     def project(x, basis):

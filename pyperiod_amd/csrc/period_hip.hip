@@ -13,6 +13,7 @@
 
 #include "../../include/periodhip.h"
 #include "ph_kernels.h"
+#include "ph_fit.h"
 
 namespace {
 
@@ -53,7 +54,7 @@ struct TableSlot {
   bool valid = false;
 };
 
-enum { T_PLIST, T_ORTH_OFF, T_ORTH_Q, T_FAC_OFF, T_FAC_Q, T_AUX0, T_AUX1, T_AUX2, T_AUX3, T_COUNT };
+enum { T_PLIST, T_ORTH_OFF, T_ORTH_Q, T_FAC_OFF, T_FAC_Q, T_AUX0, T_AUX1, T_AUX2, T_AUX3, T_FIT_PHI, T_FIT_OFF, T_FIT_DQ, T_COUNT };
 enum { B_IN, B_OUT0, B_OUT1, B_OUT2, B_OUT3, B_OUT4, B_WS0, B_WS1, B_GEN0, B_GBUF, B_GWIN, B_COUNT };
 
 }  // namespace
@@ -377,14 +378,14 @@ struct Stage {
   };
   std::vector<Out> outs;
   Stage(ph_ctx* ctx, unsigned flags) : c(ctx), device(flags & PH_FLAG_DEVICE) {}
-  int in(const void* user, size_t bytes, const void** dev) {
+  int in(const void* user, size_t bytes, const void** dev, int slot = B_IN) {
     if (device) {
       *dev = user;
       return PH_OK;
     }
-    PH_TRY(ensure(c, c->buf[B_IN], bytes));
-    PH_HIP(hipMemcpyAsync(c->buf[B_IN].p, user, bytes, hipMemcpyHostToDevice, c->stream));
-    *dev = c->buf[B_IN].p;
+    PH_TRY(ensure(c, c->buf[slot], bytes));
+    PH_HIP(hipMemcpyAsync(c->buf[slot].p, user, bytes, hipMemcpyHostToDevice, c->stream));
+    *dev = c->buf[slot].p;
     return PH_OK;
   }
   int out(int slot, void* user, size_t bytes, void** dev) {
@@ -780,7 +781,46 @@ void plan_fold_sums(const ph_ctx* c, int dtype, int N, Plan* pl) {
   k.block = kBlock;
 }
 
+// Euler phi of every q <= max_p and all divisors of q in ascending order, CSR by q (QOPeriods.py:834-838), by sieve:
+// O(max_p log max_p).
+void divisor_tables(int max_p, std::vector<int32_t>* phi_out, std::vector<int32_t>* off_out, std::vector<int32_t>* dq_out) {
+  std::vector<int32_t>&phi = *phi_out, &off = *off_out, &dq = *dq_out;
+  phi.assign((size_t)max_p + 1, 0);
+  off.assign((size_t)max_p + 2, 0);
+  for (int i = 0; i <= max_p; ++i) phi[i] = i;
+  for (int i = 2; i <= max_p; ++i)
+    if (phi[i] == i)
+      for (int j = i; j <= max_p; j += i) phi[j] -= phi[j] / i;
+  for (int d = 1; d <= max_p; ++d)
+    for (int q = d; q <= max_p; q += d) ++off[q + 1];
+  for (int q = 0; q <= max_p; ++q) off[q + 1] += off[q];
+  dq.assign((size_t)off[max_p + 1], 0);
+  {
+    std::vector<int32_t> fill(off.begin(), off.end() - 1);
+    for (int d = 1; d <= max_p; ++d)
+      for (int q = d; q <= max_p; q += d) dq[fill[q]++] = d;
+  }
+  if (dq.empty()) dq.push_back(1);
+}
+
+// k_qo_fit: the LDS holds the solver's vectors only (ph::qo_fit_lds_bytes, the layout the kernel carves); the window is
+// read from HBM / L2.  The largest feasible kcap is the last one this accepts.
+int plan_qo_fit(const ph_ctx* c, int kcap, int max_period, Plan* pl) {
+  if (max_period < 1 || max_period > ph::kFitMaxPeriod)
+    return fail(PH_E_ARG, "ph_qo_fit: max_period=%d must be in [1, %d]", max_period, ph::kFitMaxPeriod);
+  if (kcap < 1 || kcap > ph::kQoGreedyMaxRows) return fail(PH_E_ARG, "ph_qo_fit: kcap=%d must be in [1, %d]", kcap, ph::kQoGreedyMaxRows);
+  KernelPlan& k = pl->k[0];
+  k.lds = ph::qo_fit_lds_bytes(kcap, max_period);
+  if (k.lds > (size_t)c->lds_limit)
+    return fail(PH_E_ARG, "ph_qo_fit: kcap=%d, max_period=%d need %zu B of LDS (limit %d B)", kcap, max_period, k.lds,
+                c->lds_limit);
+  k.window = PH_PLAN_HBM;
+  k.block = ph::qo_fit_block(kcap);
+  return PH_OK;
+}
+
 }  // namespace
+
 
 // =========================================================================================
 extern "C" {
@@ -1083,6 +1123,9 @@ int ph_plan_info(ph_ctx* c, int op, int dtype, int N, const int32_t* params, int
     }
     case PH_OP_FOLD_SUMS:
       plan_fold_sums(c, dtype, N, &pl);
+      break;
+    case PH_OP_QO_FIT:
+      PH_TRY(plan_qo_fit(c, prm(0, 512), prm(1, N), &pl));
       break;
     default:
       return fail(PH_E_ARG, "op %d unknown", op);
@@ -1578,17 +1621,21 @@ int ph_best_frequency(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int
 }
 
 // ----------------------------------------------------------------------------- Ramanujan
-int ph_ramanujan_norms(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int q_lo, int q_hi,
-                       unsigned flags, double* out) {
-  PH_TRY(check_common(c, x, dtype, W, N));
-  if (!out) return fail(PH_E_ARG, "out is NULL");
-  if (q_lo < 1 || q_hi < 1) return fail(PH_E_ARG, "need q_lo, q_hi >= 1 (got %d, %d)", q_lo, q_hi);
-  PH_HIP(hipSetDevice(c->device));
-  const size_t sz = elem_size(dtype);
+// What a launch of k_ramanujan needs besides the data: the plan, the HBM window workspace (or nullptr) and the job
+// table on the device.  ph_ramanujan_norms and ph_ramanujan_fit both prepare it here and launch through ram_enqueue.
+struct RamLaunch {
   Plan pl;
+  void* gwin = nullptr;
+  const int* d_tab = nullptr;
+  int n_root = 0;
+};
+
+static int ram_prepare(ph_ctx* c, int dtype, int64_t W, int N, int q_lo, int q_hi, RamLaunch* rl) {
+  const size_t sz = elem_size(dtype);
+  Plan& pl = rl->pl;
   PH_TRY(plan_ramanujan(c, dtype, N, q_hi, &pl));
   const KernelPlan& k = pl.k[0];
-  void* gwin;
+  void*& gwin = rl->gwin;
   PH_TRY(place(c, k.window, B_GWIN, (size_t)W * ph::win_stride(N + kPad) * sz, &gwin));
   // One 128-byte record per period (ph::RamJob): the factors (I - P_d) of its projector (d = q / r for each prime
   // r | q, with 1 / r and the row-split geometry of a coset count below 64), the scale (q / phi(q))^2 and the
@@ -1632,7 +1679,8 @@ int ph_ramanujan_norms(ph_ctx* c, const void* x, int dtype, int64_t W, int N, in
   // of its multiples there (the least loaded one; children cost a strip fold and a filter, O(Q + q)).
   // Roots are dealt to the wavefronts in order of decreasing work.
   std::vector<ph::RamJob> tab;  // root records, then the children
-  int n_root = 0;
+  int& n_root = rl->n_root;
+  n_root = 0;
   if (q_lo <= q_hi) {
     const int half = q_hi / 2;
     std::vector<std::vector<int32_t>> kids((size_t)q_hi + 1);
@@ -1666,17 +1714,20 @@ int ph_ramanujan_norms(ph_ctx* c, const void* x, int dtype, int64_t W, int N, in
     }
   }
   if (tab.empty()) tab.push_back(ph::RamJob{});
-  const int* d_tab;  // the records travel as raw int32 words through a cached table slot
-  PH_TRY(upload_table(c, T_AUX2, reinterpret_cast<const int32_t*>(tab.data()), tab.size() * (sizeof(ph::RamJob) / 4), &d_tab));
-  Stage st(c, flags);
-  const void* dx;
-  void* dout;
-  PH_TRY(st.in(x, (size_t)W * N * sz, &dx));
-  PH_TRY(st.out(B_OUT0, out, (size_t)W * (q_hi + 1) * sizeof(double), &dout));
+  // the records travel as raw int32 words through a cached table slot
+  PH_TRY(upload_table(c, T_AUX2, reinterpret_cast<const int32_t*>(tab.data()), tab.size() * (sizeof(ph::RamJob) / 4), &rl->d_tab));
+  return PH_OK;
+}
+
+// zero the norms, then one k_ramanujan launch on the context's stream
+static int ram_enqueue(ph_ctx* c, const RamLaunch& rl, int dtype, int64_t W, int N, int q_hi, const void* dx, void* dout) {
+  const KernelPlan& k = rl.pl.k[0];
+  void* gwin = rl.gwin;
+  const int n_root = rl.n_root;
   PH_HIP(hipMemsetAsync(dout, 0, (size_t)W * (q_hi + 1) * sizeof(double), c->stream));
   const dim3 grid((unsigned)W);
   if (n_root > 0) {
-    const ph::RamJob* d_roots = reinterpret_cast<const ph::RamJob*>(d_tab);
+    const ph::RamJob* d_roots = reinterpret_cast<const ph::RamJob*>(rl.d_tab);
     PH_TRY(dispatch(dtype, !gwin, [&](auto t, auto lw) {
       using T = decltype(t);
       auto kernel = ph::k_ramanujan<T, decltype(lw)::value>;
@@ -1688,6 +1739,24 @@ int ph_ramanujan_norms(ph_ctx* c, const void* x, int dtype, int64_t W, int N, in
     }));
     PH_TRY(launch_check("k_ramanujan"));
   }
+  return PH_OK;
+}
+
+int ph_ramanujan_norms(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int q_lo, int q_hi,
+                       unsigned flags, double* out) {
+  PH_TRY(check_common(c, x, dtype, W, N));
+  if (!out) return fail(PH_E_ARG, "out is NULL");
+  if (q_lo < 1 || q_hi < 1) return fail(PH_E_ARG, "need q_lo, q_hi >= 1 (got %d, %d)", q_lo, q_hi);
+  PH_HIP(hipSetDevice(c->device));
+  const size_t sz = elem_size(dtype);
+  RamLaunch rl;
+  PH_TRY(ram_prepare(c, dtype, W, N, q_lo, q_hi, &rl));
+  Stage st(c, flags);
+  const void* dx;
+  void* dout;
+  PH_TRY(st.in(x, (size_t)W * N * sz, &dx));
+  PH_TRY(st.out(B_OUT0, out, (size_t)W * (q_hi + 1) * sizeof(double), &dout));
+  PH_TRY(ram_enqueue(c, rl, dtype, W, N, q_hi, dx, dout));
   return st.finish();
 }
 
@@ -1868,22 +1937,8 @@ int ph_qo_find_periods(ph_ctx* c, const void* x, int dtype, int64_t W, int N, in
   int n_pass;
   PH_TRY(prepare_plan(c, min_length, max_length, &plan, &n_pass));
   // Euler phi and all divisors of every candidate period (QOPeriods.py:834-838)
-  std::vector<int32_t> phi(max_length + 1), off(max_length + 2, 0), dq;
-  for (int i = 0; i <= max_length; ++i) phi[i] = i;
-  for (int i = 2; i <= max_length; ++i)
-    if (phi[i] == i)
-      for (int j = i; j <= max_length; j += i) phi[j] -= phi[j] / i;
-  // (by sieve, O(max_length log max_length): the divisors of q in ascending order, CSR by q)
-  for (int d = 1; d <= max_length; ++d)
-    for (int q = d; q <= max_length; q += d) ++off[q + 1];
-  for (int q = 0; q <= max_length; ++q) off[q + 1] += off[q];
-  dq.resize(off[max_length + 1]);
-  {
-    std::vector<int32_t> fill(off.begin(), off.end() - 1);
-    for (int d = 1; d <= max_length; ++d)
-      for (int q = d; q <= max_length; q += d) dq[fill[q]++] = d;
-  }
-  if (dq.empty()) dq.push_back(1);
+  std::vector<int32_t> phi, off, dq;
+  divisor_tables(max_length, &phi, &off, &dq);
   const int *d_phi, *d_off, *d_dq;
   PH_TRY(upload_table(c, T_AUX0, phi.data(), phi.size(), &d_phi));
   PH_TRY(upload_table(c, T_AUX1, off.data(), off.size(), &d_off));
@@ -1950,6 +2005,110 @@ int ph_qo_plan_info(ph_ctx* c, int dtype, int N, int max_length, int kcap, unsig
   PH_TRY(qo_plan(c, dtype, N, &max_length, kcap, flags, &lds, placement));
   *lds_bytes = (int)lds;
   return PH_OK;
+}
+
+// ----------------------------------------------------------------------------- fit of a given period list
+// Checks shared by ph_qo_fit and ph_ramanujan_fit, the plan, and the phi / divisor tables of 1 .. max_period on the
+// device (slots of their own: the Ramanujan job table stays where it is while both kernels are queued).
+struct FitLaunch {
+  Plan pl;
+  const int *d_phi = nullptr, *d_off = nullptr, *d_dq = nullptr;
+};
+
+static int fit_prepare(ph_ctx* c, int pcap, int max_period, int kcap, FitLaunch* fl) {
+  if (pcap < 1 || pcap > (1 << 20)) return fail(PH_E_ARG, "pcap=%d must be in [1, 2^20]", pcap);
+  PH_TRY(plan_qo_fit(c, kcap, max_period, &fl->pl));
+  std::vector<int32_t> phi, off, dq;
+  divisor_tables(max_period, &phi, &off, &dq);
+  PH_TRY(upload_table(c, T_FIT_PHI, phi.data(), phi.size(), &fl->d_phi));
+  PH_TRY(upload_table(c, T_FIT_OFF, off.data(), off.size(), &fl->d_off));
+  PH_TRY(upload_table(c, T_FIT_DQ, dq.data(), dq.size(), &fl->d_dq));
+  return PH_OK;
+}
+
+static int fit_enqueue(ph_ctx* c, const FitLaunch& fl, int dtype, int64_t W, int N, const void* dx, const int* dper,
+                       const int* dnper, int pcap, int per_stride, int max_period, int kcap, void* dkeep, void* dwts,
+                       void* dres, void* dstat) {
+  const KernelPlan& k = fl.pl.k[0];
+  const dim3 grid((unsigned)W);
+  ProfScope ps_(c, "k_qo_fit");
+  if (dtype == PH_F64) {
+    PH_TRY(allow_lds(ph::k_qo_fit<double>, k.lds));
+    hipLaunchKernelGGL(ph::k_qo_fit<double>, grid, dim3(k.block), k.lds, c->stream, (const double*)dx, N, dper, dnper, pcap,
+                       per_stride, max_period, fl.d_phi, fl.d_off, fl.d_dq, kcap, (int*)dkeep, (double*)dwts, (double*)dres,
+                       (int*)dstat);
+  } else {
+    PH_TRY(allow_lds(ph::k_qo_fit<float>, k.lds));
+    hipLaunchKernelGGL(ph::k_qo_fit<float>, grid, dim3(k.block), k.lds, c->stream, (const float*)dx, N, dper, dnper, pcap,
+                       per_stride, max_period, fl.d_phi, fl.d_off, fl.d_dq, kcap, (int*)dkeep, (double*)dwts, (float*)dres,
+                       (int*)dstat);
+  }
+  return launch_check("k_qo_fit");
+}
+
+int ph_qo_fit(ph_ctx* c, const void* x, int dtype, int64_t W, int N, const int32_t* periods, const int32_t* n_periods,
+              int pcap, int per_stride, int max_period, int kcap, unsigned flags, int32_t* keeps, double* weights,
+              void* residual, int32_t* status) {
+  PH_TRY(check_common(c, x, dtype, W, N));
+  if (!periods || !n_periods) return fail(PH_E_ARG, "periods / n_periods is NULL");
+  if (!keeps || !weights || !residual || !status) return fail(PH_E_ARG, "output pointer is NULL");
+  if (per_stride != 0 && per_stride < pcap) return fail(PH_E_ARG, "per_stride=%d must be 0 (one shared list) or >= pcap=%d", per_stride, pcap);
+  PH_HIP(hipSetDevice(c->device));
+  FitLaunch fl;
+  PH_TRY(fit_prepare(c, pcap, max_period, kcap, &fl));
+  const size_t sz = elem_size(dtype);
+  const size_t lists = per_stride ? (size_t)W : 1;
+  Stage st(c, flags);
+  const void *dx, *dper, *dnper;
+  void *dkeep, *dwts, *dres, *dstat;
+  PH_TRY(st.in(x, (size_t)W * N * sz, &dx));
+  PH_TRY(st.in(periods, ((lists - 1) * (size_t)per_stride + pcap) * sizeof(int32_t), &dper, B_GBUF));
+  PH_TRY(st.in(n_periods, lists * sizeof(int32_t), &dnper, B_WS1));
+  PH_TRY(st.out(B_OUT3, keeps, (size_t)W * pcap * sizeof(int32_t), &dkeep));
+  PH_TRY(st.out(B_OUT4, weights, (size_t)W * kcap * sizeof(double), &dwts));
+  PH_TRY(st.out(B_WS0, residual, (size_t)W * N * sz, &dres));
+  PH_TRY(st.out(B_GEN0, status, (size_t)W * sizeof(int32_t), &dstat));
+  PH_TRY(fit_enqueue(c, fl, dtype, W, N, dx, (const int*)dper, (const int*)dnper, pcap, per_stride, max_period, kcap, dkeep,
+                     dwts, dres, dstat));
+  return st.finish();
+}
+
+int ph_ramanujan_fit(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int q_lo, int q_hi, double thresh, int pcap,
+                     int kcap, unsigned flags, double* norms, int32_t* periods, int32_t* counts, int32_t* keeps,
+                     double* weights, void* residual, int32_t* status) {
+  if (!(thresh > 0.0)) return fail(PH_E_ARG, "thresh=%g must be > 0 (index 0 would be selected)", thresh);
+  PH_TRY(check_common(c, x, dtype, W, N));
+  if (!norms || !periods || !counts || !keeps || !weights || !residual || !status)
+    return fail(PH_E_ARG, "output pointer is NULL");
+  if (q_lo < 1 || q_hi < 1) return fail(PH_E_ARG, "need q_lo, q_hi >= 1 (got %d, %d)", q_lo, q_hi);
+  PH_HIP(hipSetDevice(c->device));
+  FitLaunch fl;
+  PH_TRY(fit_prepare(c, pcap, q_hi, kcap, &fl));
+  RamLaunch rl;
+  PH_TRY(ram_prepare(c, dtype, W, N, q_lo, q_hi, &rl));
+  const size_t sz = elem_size(dtype);
+  Stage st(c, flags);
+  const void* dx;
+  void *dnrm, *dper, *dcnt, *dkeep, *dwts, *dres, *dstat;
+  PH_TRY(st.in(x, (size_t)W * N * sz, &dx));
+  PH_TRY(st.out(B_OUT0, norms, (size_t)W * (q_hi + 1) * sizeof(double), &dnrm));
+  PH_TRY(st.out(B_OUT1, periods, (size_t)W * pcap * sizeof(int32_t), &dper));
+  PH_TRY(st.out(B_OUT2, counts, (size_t)W * sizeof(int32_t), &dcnt));
+  PH_TRY(st.out(B_OUT3, keeps, (size_t)W * pcap * sizeof(int32_t), &dkeep));
+  PH_TRY(st.out(B_OUT4, weights, (size_t)W * kcap * sizeof(double), &dwts));
+  PH_TRY(st.out(B_WS0, residual, (size_t)W * N * sz, &dres));
+  PH_TRY(st.out(B_GEN0, status, (size_t)W * sizeof(int32_t), &dstat));
+  // three launches on the context's stream, no host round trip between them
+  PH_TRY(ram_enqueue(c, rl, dtype, W, N, q_hi, dx, dnrm));
+  {
+    ProfScope ps_(c, "k_ram_select");
+    hipLaunchKernelGGL(ph::k_ram_select, dim3((unsigned)W), dim3(ph::kWave), 0, c->stream, (const double*)dnrm, q_hi, thresh,
+                       pcap, (int*)dper, (int*)dcnt);
+  }
+  PH_TRY(launch_check("k_ram_select"));
+  PH_TRY(fit_enqueue(c, fl, dtype, W, N, dx, (const int*)dper, (const int*)dcnt, pcap, pcap, q_hi, kcap, dkeep, dwts, dres,
+                     dstat));
+  return st.finish();
 }
 
 // ----------------------------------------------------------------------------- orthogonal period powers

@@ -1,0 +1,405 @@
+// Fit of a GIVEN period list (QOPeriods.compute_reconstruction, RamanujanPeriods.find_periods_with_weights) on the
+// device: k_qo_fit runs get_subspaces' row bookkeeping, the right-hand side by folds and the matrix-free conjugate
+// gradients of k_qo_find for a list it is handed instead of one it selects greedily; k_ram_select turns Ramanujan norms
+// into that list.  Included by period_hip.hip behind ph_kernels.h.  Reference citations are file:line into
+// /root/reference/pyPeriod/.
+#pragma once
+
+#include "ph_kernels.h"
+
+namespace ph {
+
+constexpr int kFitMaxPeriod = 1 << 20;  // qo_offdiag's index arithmetic holds for periods below 2^20
+constexpr int kFitCtl = 4;              // control words: status, blocks, rows
+
+// Dynamic LDS of k_qo_fit, the one statement of its layout (the kernel carves in this order; the host plans with it).
+// Bookkeeping, then the solver's seven vectors + the sample counts, one slot per dictionary row and one per block.  The
+// divisor bitset over 1 .. max_period is only alive during the row bookkeeping and overlays the vectors, so the size
+// depends on kcap alone unless the bitset is the larger of the two.  The window never enters LDS.
+__host__ __device__ inline size_t qo_fit_fixed_bytes() {
+  return carve_bytes(kRedDoubles, 8) + carve_bytes(6 * kMaxWaves, 8) + 4 * carve_bytes(kQoMaxBlocks + 1, 4) +
+         2 * carve_bytes(kQoMaxBlocks, 4) + carve_bytes(2 * kQoPairTab * kQoPairTab, 4) + carve_bytes(kFitCtl, 4);
+}
+__host__ __device__ inline size_t qo_fit_vector_bytes(int kcap) {
+  const size_t kv = (size_t)kcap + kQoMaxBlocks;
+  return 7 * carve_bytes(kv, 8) + carve_bytes(kv, 4);
+}
+__host__ __device__ inline size_t qo_fit_lds_bytes(int kcap, int max_period) {
+  const size_t vec = qo_fit_vector_bytes(kcap), seen = carve_bytes((size_t)(max_period + 32) / 32, 4);
+  return qo_fit_fixed_bytes() + (vec > seen ? vec : seen);
+}
+// Threads per workgroup: small dictionaries take small workgroups, so that several share a CU.
+__host__ __device__ inline int qo_fit_block(int kcap) { return kcap > 512 ? 1024 : kcap > 128 ? 512 : 256; }
+
+// sum over the 16 lanes of a DPP row (every lane of the row gets it)
+__device__ __forceinline__ double row16_sum(double v) {
+  v += dpp_f64<kDppRor8>(v);
+  v += dpp_f64<kDppHalfMirror>(v);
+  v += dpp_f64<kDppXor2>(v);
+  v += dpp_f64<kDppXor1>(v);
+  return v;
+}
+
+// ======================================================================================
+// QOPeriods.compute_reconstruction / get_subspaces + solve_quadratic for a given period list (QOPeriods.py:807-852,
+// :779-796, :1054-1116), natural basis, no analysis window.  One workgroup per window; all solver arithmetic in fp64.
+//   rows of block b = Euler-phi mass the divisors of p_b add to the running divisor set (get_subspaces :830-840)
+//   right-hand side A x by folds of the window, read from HBM / L2 (the window is read twice: here and for the residual)
+//   A A^T w = A x by the Jacobi-preconditioned single-reduction conjugate gradients of k_qo_find, started from zero:
+//     same matrix-free product (qo_offdiag, lanes-per-row split, DPP combine), tolerances and iteration bound.
+//     The solver is a copy of k_qo_find's, not shared code: k_qo_find's code object stays what it was.
+//   weights in row order, residual x - A^T w
+// status: 0 ok; 1 empty list; 3 more entries than pcap or kQoMaxBlocks, or more rows than kcap; 2 a period outside
+// 1 .. max_period, a block without rows (repeated period / all divisors present: the reference's Pp(.., keep=0) hands
+// back all p rows and its matrix is singular) or with more rows than samples (zero diagonal), a dictionary with more
+// rows than samples altogether (rank deficient: conjugate gradients would still converge on it), non-positive curvature, a
+// non-finite residual of the solve, or no convergence within 4 K + 100 iterations.  Windows that are not ok get zero
+// weights; their residual is not written.  Every loop is bounded; nothing waits on anything outside the workgroup.
+// ======================================================================================
+template <typename T>
+__global__ __launch_bounds__(1024) void k_qo_fit(const T* __restrict__ x, int N, const int* __restrict__ periods,
+                                                 const int* __restrict__ n_periods, int pcap, int per_stride,
+                                                 int max_period, const int* __restrict__ phi,
+                                                 const int* __restrict__ div_off, const int* __restrict__ div_q, int kcap,
+                                                 int* __restrict__ keeps_out, double* __restrict__ weights_out,
+                                                 T* __restrict__ resid_out, int* __restrict__ status_out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  Carve cv(smem);
+  double* red = cv.take<double>(kRedDoubles);
+  double* red3 = cv.take<double>(6 * kMaxWaves);  // wave partials of the solver's fused reduction (two parities)
+  int* bper = cv.take<int>(kQoMaxBlocks + 1);     // period of dictionary block b
+  int* bkeep = cv.take<int>(kQoMaxBlocks + 1);    // rows kept for it
+  int* boff = cv.take<int>(kQoMaxBlocks + 1);     // first row of block b
+  int* ioff = cv.take<int>(kQoMaxBlocks + 1);     // first work item of block b
+  int* blg = cv.take<int>(kQoMaxBlocks);          // log2 of the lanes that share a row of block b in the product
+  int* bsteps = cv.take<int>(kQoMaxBlocks);       // steps one row of block b walks in the product
+  int* ptab = cv.take<int>(2 * kQoPairTab * kQoPairTab);  // (a, b): {p_b / gcd(p_a, p_b), p_a mod p_b}
+  int* ctl = cv.take<int>(kFitCtl);
+  // the divisor bitset (bookkeeping only) and the solver's vectors share what follows
+  uint32_t* seen = reinterpret_cast<uint32_t*>(cv.base + cv.off);
+  const int kv = kcap + kQoMaxBlocks;
+  double* xv = cv.take<double>(kv);   // weights, solver layout: block b's k_b entries at boff[b] + b, then one zero
+  double* rv = cv.take<double>(kv);   // residual of the normal equations (starts as A x, QOPeriods.py:782)
+  double* pv = cv.take<double>(kv);   // search direction
+  double* qv = cv.take<double>(kv);   // A A^T pv
+  double* zv = cv.take<double>(kv);   // preconditioned residual
+  double* wv_ = cv.take<double>(kv);  // A A^T zv
+  double* dv = cv.take<double>(kv);   // 1 / diagonal = 1 / samples of the row's residue (Jacobi preconditioner)
+  int* trm = cv.take<int>(kv);        // samples of the row's residue
+
+  const int64_t w = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int lane = tid & (kWave - 1);
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int nw = blockDim.x >> 6;
+  const T* data = x + w * (int64_t)N;
+  const int* list = periods + (per_stride ? w * (int64_t)per_stride : 0);
+  const int n_list = n_periods[per_stride ? w : 0];
+  int* keeps_row = keeps_out + w * (int64_t)pcap;
+  double* wout = weights_out + w * (int64_t)kcap;
+
+  for (int k = tid; k < pcap; k += blockDim.x) keeps_row[k] = 0;
+  for (int r = tid; r < kcap; r += blockDim.x) wout[r] = 0.0;
+  int status = 0;
+  if (n_list <= 0) status = 1;
+  if (n_list > pcap || n_list > kQoMaxBlocks) status = 3;
+  if (status != 0) {  // (uniform over the workgroup)
+    if (tid == 0) status_out[w] = status;
+    return;
+  }
+  for (int k = tid; k < (max_period + 32) / 32; k += blockDim.x) seen[k] = 0u;
+  __syncthreads();
+  // ---- rows each period contributes (QOPeriods.py:830-840): one wavefront, the lanes over the divisors
+  if (wv == 0) {
+    int st = 0, rows = 0;
+    for (int b = 0; b < n_list; ++b) {
+      const int p = list[b];
+      if (p < 1 || p > max_period) {  // (uniform)
+        st = 2;
+        break;
+      }
+      const int d0 = div_off[p], d1 = div_off[p + 1];
+      double mass = 0.0;
+      for (int k = d0 + lane; k < d1; k += kWave) {
+        const int r = div_q[k];
+        if (!((seen[r >> 5] >> (r & 31)) & 1u)) mass += (double)phi[r];
+      }
+      const int keep = (int)wave_sum(mass);  // (exact: the mass of all divisors of p is p)
+      ram_wave_sync();
+      for (int k = d0 + lane; k < d1; k += kWave) {
+        const int r = div_q[k];
+        atomicOr(&seen[r >> 5], 1u << (r & 31));
+      }
+      ram_wave_sync();
+      if (lane == 0) {
+        bper[b] = p;
+        bkeep[b] = keep;
+        boff[b] = rows;
+        keeps_row[b] = keep;
+      }
+      if (keep == 0 || keep > N) st = 2;
+      rows += keep;  // (<= 64 * 2^20: no overflow)
+    }
+    if (st == 0 && rows > N) st = 2;  // more rows than samples: rank(A A^T) <= N, singular whatever the blocks are
+    if (st == 0 && rows > kcap) st = 3;
+    if (lane == 0) {
+      boff[n_list] = rows;
+      ctl[0] = st;
+      ctl[1] = rows;
+    }
+  }
+  __syncthreads();
+  status = ctl[0];
+  if (status != 0) {
+    if (tid == 0) status_out[w] = status;
+    return;
+  }
+  const int nblk = n_list;
+  const int K = ctl[1];
+  const int KS = K + nblk;  // slots
+  __syncthreads();          // the bitset is dead: the vectors take its place
+  // pair constants of every block against every block (the diagonal is unused)
+  if (nblk <= kQoPairTab) {
+    for (int e = tid; e < nblk * nblk; e += blockDim.x) {
+      const int a = e / nblk, b = e - a * nblk;
+      const int pa = bper[a], pb = bper[b];
+      ptab[2 * (a * kQoPairTab + b)] = pb / qo_gcd(pa, pb);
+      ptab[2 * (a * kQoPairTab + b) + 1] = pa % pb;
+    }
+  }
+  // per slot: samples of the row's residue, the preconditioner, zeros
+  for (int sl = tid; sl < KS; sl += blockDim.x) {
+    int a = 0;
+    while (a + 1 < nblk && boff[a + 1] + a + 1 <= sl) ++a;
+    const int i = sl - boff[a] - a;
+    const bool pad = i >= bkeep[a];  // the zero behind block a
+    const int terms = pad ? 1 : (N - 1 - i) / bper[a] + 1;
+    trm[sl] = terms;
+    dv[sl] = pad ? 0.0 : 1.0 / (double)terms;
+    xv[sl] = 0.0;
+    rv[sl] = 0.0;
+    zv[sl] = 0.0;  // (the product never writes the pad slots)
+    wv_[sl] = 0.0;
+    qv[sl] = 0.0;
+    pv[sl] = 0.0;
+  }
+  __syncthreads();
+  // ---- right-hand side A x (QOPeriods.py:782): folds of the window.  One wavefront per residue; blocks whose residues
+  //      have at most 16 samples take four residues per wavefront, one per DPP row.
+  for (int a = 0; a < nblk; ++a) {
+    const int p = bper[a], keep = bkeep[a], s0 = boff[a] + a;
+    if ((N - 1) / p + 1 > 16) {
+      for (int j = wv; j < keep; j += nw) {
+        const int terms = (N - 1 - j) / p + 1;
+        double sj = 0.0;
+        for (int r = lane; r < terms; r += kWave) sj += (double)data[j + (int64_t)r * p];
+        sj = wave_sum(sj);
+        if (lane == 0) rv[s0 + j] = sj;
+      }
+    } else {
+      const int sub = lane >> 4, l = lane & 15;
+      for (int j0 = 4 * wv; j0 < keep; j0 += 4 * nw) {
+        const int j = j0 + sub;
+        const int64_t n = j + (int64_t)l * p;
+        double sj = (j < keep && n < N) ? (double)data[n] : 0.0;
+        sj = row16_sum(sj);
+        if (l == 0 && j < keep) rv[s0 + j] = sj;
+      }
+    }
+  }
+  // Work split of the product, as in k_qo_find: a row of block a costs sum_b min(cycle_ab, samples) steps; block a gets
+  // L_a = 1, 2, ..., 16 lanes per row, the lanes of a row are neighbours and combine with DPP.
+  for (int a = tid; a < nblk; a += blockDim.x) {
+    const int pa = bper[a], terms = (N - 1) / pa + 1;
+    int st = 0;
+    for (int b = 0; b < nblk; ++b) {
+      if (b == a) continue;
+      const int cyc = bper[b] / qo_gcd(pa, bper[b]);
+      st += cyc < terms ? cyc : terms;
+    }
+    bsteps[a] = st;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int items = 0;
+    for (int a = 0; a < nblk; ++a) {
+      blg[a] = bper[a] < 64 ? 4 : 0;
+      items += ((bkeep[a] << blg[a]) + 15) & ~15;
+    }
+    for (int round = 0; round < 4 * kQoMaxBlocks; ++round) {  // (every round adds one to some blg[a] <= 4)
+      int worst = -1, wst = 24;
+      for (int a = 0; a < nblk; ++a)
+        if (blg[a] < 4 && (bsteps[a] >> blg[a]) > wst) {
+          wst = bsteps[a] >> blg[a];
+          worst = a;
+        }
+      if (worst < 0) break;
+      const int grown = items - (((bkeep[worst] << blg[worst]) + 15) & ~15) + (((bkeep[worst] << (blg[worst] + 1)) + 15) & ~15);
+      if (grown > (int)blockDim.x) break;
+      items = grown;
+      blg[worst] += 1;
+    }
+    int off = 0;
+    for (int a = 0; a < nblk; ++a) {
+      ioff[a] = off;
+      off += ((bkeep[a] << blg[a]) + 15) & ~15;  // groups never straddle a 16-lane DPP row
+    }
+    ioff[nblk] = off;
+  }
+  __syncthreads();
+  // ---- A A^T w = A x (see k_qo_find for the derivation of the product and of the single-reduction recurrence)
+  double dg = 0.0, dd = 0.0, dr = 0.0;
+  auto gram_apply = [&](const double* __restrict__ vv, double* __restrict__ out) {
+    const int nitems = ioff[nblk];
+    for (int v = tid; v < nitems; v += blockDim.x) {
+      int a = 0;
+      while (a + 1 < nblk && ioff[a + 1] <= v) ++a;
+      const int lg = blg[a], L = 1 << lg;
+      const int e = v - ioff[a];
+      const int i = e >> lg, gl = e & (L - 1);
+      const int ka = bkeep[a];
+      double acc = 0.0;
+      int terms = 1;
+      const int sl = boff[a] + a + (i < ka ? i : 0);
+      if (i < ka) {  // (the padding items of the last row group only take part in the DPP steps)
+        const int pa = bper[a];
+        terms = trm[sl];
+        for (int b = 0; b < nblk; ++b) {
+          if (b == a) continue;
+          const int pb = bper[b];
+          int cycle, step;
+          if (nblk <= kQoPairTab) {
+            cycle = ptab[2 * (a * kQoPairTab + b)];
+            step = ptab[2 * (a * kQoPairTab + b) + 1];
+          } else {
+            cycle = pb / qo_gcd(pa, pb);
+            step = pa % pb;
+          }
+          acc += qo_offdiag(vv + boff[b] + b, bkeep[b], pb, cycle, step, i, terms, gl, L);
+        }
+      }
+      if (lg >= 4) acc += dpp_f64<kDppRor8>(acc);
+      if (lg >= 3) acc += dpp_f64<kDppHalfMirror>(acc);
+      if (lg >= 2) acc += dpp_f64<kDppXor2>(acc);
+      if (lg >= 1) acc += dpp_f64<kDppXor1>(acc);
+      if (gl == 0 && i < ka) {
+        const double z = vv[sl], wrow = fma((double)terms, z, acc);
+        out[sl] = wrow;
+        const double t = rv[sl];
+        dg = fma(t, z, dg);
+        dd = fma(wrow, z, dd);
+        dr = fma(t, t, dr);
+      }
+    }
+  };
+  bool failed = false;
+  int iter = 0;
+  {
+    double bb = 0.0;
+    for (int r = tid; r < KS; r += blockDim.x) {  // start from zero: the residual is the right-hand side
+      const double t = rv[r];
+      zv[r] = t * dv[r];
+      bb = fma(t, t, bb);
+    }
+    bb = block_sum(bb, red);  // (its barriers also publish zv)
+    const double tol = sizeof(T) == 4 ? 1e-9 : 1e-13;
+    const double tol2 = tol * tol * bb;
+    const int itmax = 4 * K + 100;
+    double gamma_old = 0.0, alpha = 0.0, rr = 1.0 / 0.0;
+    for (;; ++iter) {
+      dg = dd = dr = 0.0;
+      gram_apply(zv, wv_);
+      double* part = red3 + (iter & 1) * 3 * kMaxWaves;
+      const double sg = wave_sum(dg), sd = wave_sum(dd), sr = wave_sum(dr);
+      if (lane == 0) {
+        part[wv] = sg;
+        part[kMaxWaves + wv] = sd;
+        part[2 * kMaxWaves + wv] = sr;
+      }
+      __syncthreads();
+      const double g = uniform_f64(red_combine(part, nw)), d = uniform_f64(red_combine(part + kMaxWaves, nw));
+      rr = uniform_f64(red_combine(part + 2 * kMaxWaves, nw));
+      if (rr <= tol2 || iter >= itmax) break;
+      const double beta = iter == 0 ? 0.0 : g / gamma_old;
+      const double denom = iter == 0 ? d : d - beta * g / alpha;
+      if (!(denom > 0.0) || !(g > 0.0)) {  // not positive definite: numpy.linalg.solve would raise or return garbage
+        failed = true;
+        break;
+      }
+      alpha = g / denom;
+      gamma_old = g;
+      for (int r = tid; r < KS; r += blockDim.x) {
+        const double pn = fma(beta, iter == 0 ? 0.0 : pv[r], zv[r]);
+        const double qn = fma(beta, iter == 0 ? 0.0 : qv[r], wv_[r]);
+        pv[r] = pn;
+        qv[r] = qn;
+        xv[r] = fma(alpha, pn, xv[r]);
+        const double t = fma(-alpha, qn, rv[r]);
+        rv[r] = t;
+        zv[r] = t * dv[r];
+      }
+      __syncthreads();
+    }
+    if (!(rr <= tol2)) failed = true;  // not finite, or the bound was hit: the host path solves as the reference does
+  }
+#ifdef PH_FIT_TIMERS
+  if (w < 64 && tid == 0) printf("qo_fit window %d: blocks %d rows %d cg iterations %d %s\n", (int)w, nblk, K, iter, failed ? "FAILED" : "ok");
+#endif
+  __syncthreads();
+  if (failed) {
+    if (tid == 0) status_out[w] = 2;
+    return;
+  }
+  for (int r = tid; r < K; r += blockDim.x) {
+    int a = 0;
+    while (a + 1 < nblk && boff[a + 1] <= r) ++a;
+    wout[r] = xv[r + a];
+  }
+  // ---- reconstruction A^T w (QOPeriods.py:795) in row order, residual in the dtype of x
+  for (int n = tid; n < N; n += blockDim.x) {
+    double rec = 0.0;
+    for (int b = 0; b < nblk; ++b) {
+      const int i = n % bper[b];
+      if (i < bkeep[b]) rec += xv[boff[b] + b + i];
+    }
+    resid_out[w * (int64_t)N + n] = (T)((double)data[n] - rec);
+  }
+  if (tid == 0) status_out[w] = 0;
+}
+
+// ======================================================================================
+// The threshold of RamanujanPeriods.find_periods_with_weights (RamanujanPeriods.py:95-99): one wavefront per window.
+// m = |max_q norms[w, q]| over the whole row as numpy.max sees it (a NaN anywhere makes it NaN), then the ascending
+// list of the q with norms[w, q] / m > thresh -- that IEEE double division and strict comparison, so NaN is never
+// selected.  counts[w] = how many there are (also beyond pcap), periods[w, :] the first pcap of them.
+// ======================================================================================
+__global__ __launch_bounds__(kWave) void k_ram_select(const double* __restrict__ norms, int q_hi, double thresh, int pcap,
+                                                     int* __restrict__ periods, int* __restrict__ counts) {
+  const int64_t w = blockIdx.x;
+  const int lane = threadIdx.x;
+  const double* row = norms + w * (int64_t)(q_hi + 1);
+  double m = -INFINITY;
+  int bad = 0;
+  for (int q = lane; q <= q_hi; q += kWave) {
+    const double v = row[q];
+    bad |= v != v;
+    m = fmax(m, v);
+  }
+  m = wave_max(m);
+  if (__ballot(bad) != 0ull) m = NAN;
+  m = fabs(m);
+  int* prow = periods + w * (int64_t)pcap;
+  int count = 0;
+  for (int q0 = 0; q0 <= q_hi; q0 += kWave) {
+    const int q = q0 + lane;
+    const bool sel = q <= q_hi && row[q <= q_hi ? q : 0] / m > thresh;
+    const unsigned long long mask = __ballot(sel);
+    const int pos = count + __popcll(mask & ((1ull << lane) - 1ull));
+    if (sel && pos < pcap) prow[pos] = q;
+    count += __popcll(mask);
+  }
+  for (int k = count + lane; k < pcap; k += kWave) prow[k] = 0;
+  if (lane == 0) counts[w] = count;
+}
+
+}  // namespace ph

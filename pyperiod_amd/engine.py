@@ -408,7 +408,7 @@ class PeriodEngine:
     _PLAN_OPS = {"project": _ffi.PH_OP_PROJECT, "sweep": _ffi.PH_OP_SWEEP, "m_best": _ffi.PH_OP_M_BEST,
                  "small_to_large": _ffi.PH_OP_SMALL_TO_LARGE, "best_correlation": _ffi.PH_OP_BEST_CORRELATION,
                  "best_frequency": _ffi.PH_OP_BEST_FREQUENCY, "ramanujan": _ffi.PH_OP_RAMANUJAN,
-                 "orth_powers": _ffi.PH_OP_ORTH_POWERS, "fold_sums": _ffi.PH_OP_FOLD_SUMS}
+                 "orth_powers": _ffi.PH_OP_ORTH_POWERS, "fold_sums": _ffi.PH_OP_FOLD_SUMS, "qo_fit": _ffi.PH_OP_QO_FIT}
 
     def plan_info(self, op, n, params=(), dtype=np.float64, trunc=False, orth=False):
         """-> tuple of one KernelPlan per kernel the entry point `op` ("project", "sweep", "m_best", ...) would launch
@@ -424,6 +424,79 @@ class PeriodEngine:
             r = out[_ffi.PH_PLAN_K0 + k * _ffi.PH_PLAN_STRIDE:][:_ffi.PH_PLAN_STRIDE]
             recs.append(KernelPlan(*(int(v) for v in r)))
         return tuple(recs)
+
+    def qo_fit_feasible(self, kcap, max_period) -> bool:
+        """Whether ph_qo_fit / ph_ramanujan_fit can run dictionaries of `kcap` rows with periods up to `max_period`:
+        the answer of the plan query (the launch's own planning function), nothing runs and nothing is raised."""
+        prm = np.array([int(kcap), int(max_period)], dtype=np.int32)
+        out = np.zeros(_ffi.PH_PLAN_LEN, dtype=np.int32)
+        rc = self._lib.ph_plan_info(self._ctx, _ffi.PH_OP_QO_FIT, _ffi.PH_F64, max(1, int(max_period)), prm.ctypes.data, 2, 0,
+                                    out.ctypes.data)
+        if rc not in (_ffi.PH_OK, _ffi.PH_E_ARG):
+            _ffi.check(rc)
+        return rc == _ffi.PH_OK
+
+    def qo_fit(self, x, periods, n_periods=None, kcap=512, max_period=None):
+        """Fit given period lists to a batch (QOPeriods.compute_reconstruction / get_subspaces + solve_quadratic,
+        natural basis, no window): -> keeps (W, pcap) i32, weights (W, kcap) f64, residual (W, N), status (W).
+        `periods`: one 1-D list shared by all windows, or a (W, pcap) int32 array with `n_periods` (W) entries used per
+        row (default: all pcap).  With torch input both are int32 tensors on x's device (n_periods required for 2-D
+        lists) and `max_period` should be given (default N); for numpy it defaults to the largest entry."""
+        x, code, W, N, fl, mk = self._prep(x)
+        if mk.torch:
+            per = periods.contiguous()
+            if per.dtype != mk._t.int32 or per.device != x.device:
+                raise TypeError("periods must be an int32 tensor on the device of x")
+            if n_periods is None:
+                n_periods = mk._t.full((W if per.dim() == 2 else 1,), per.shape[-1], dtype=mk._t.int32, device=x.device)
+            npr = n_periods.contiguous()
+            if npr.dtype != mk._t.int32 or npr.device != x.device:
+                raise TypeError("n_periods must be an int32 tensor on the device of x")
+            ndim, shape = per.dim(), tuple(per.shape)
+            if max_period is None:
+                max_period = N
+        else:
+            per = np.ascontiguousarray(periods, dtype=np.int32)
+            if per.shape[-1] == 0:  # an empty list still needs one readable entry
+                per = np.zeros(per.shape[:-1] + (1,), dtype=np.int32)
+                n_periods = np.zeros(W if per.ndim == 2 else 1, dtype=np.int32)
+            if n_periods is None:
+                n_periods = np.full(W if per.ndim == 2 else 1, per.shape[-1], dtype=np.int32)
+            npr = np.ascontiguousarray(np.atleast_1d(n_periods), dtype=np.int32)
+            ndim, shape = per.ndim, per.shape
+            if max_period is None:
+                max_period = max(1, int(per.max()))
+        if ndim not in (1, 2) or (ndim == 2 and shape[0] != W) or npr.shape[0] != (W if ndim == 2 else 1):
+            raise ValueError("periods must be one list or (W, pcap), n_periods (W,) or (1,)")
+        pcap = int(shape[-1])
+        keeps = mk.empty((W, pcap), np.int32)
+        weights = mk.empty((W, int(kcap)), np.float64)
+        resid = mk.empty((W, N), self._np_dtype(code))
+        status = mk.empty((W,), np.int32)
+        self._call(mk, W, self._lib.ph_qo_fit, mk.addr(x), code, W, N, mk.addr(per), mk.addr(npr), pcap,
+                   pcap if ndim == 2 else 0, int(max_period), int(kcap), fl, mk.addr(keeps), mk.addr(weights),
+                   mk.addr(resid), mk.addr(status))
+        return keeps, weights, resid, status
+
+    def ramanujan_fit(self, x, q_lo=2, q_hi=None, thresh=0.2, pcap=64, kcap=512):
+        """RamanujanPeriods.find_periods_with_weights (default test function) for a batch, three kernels on one stream:
+        -> norms (W, q_hi+1) f64, periods (W, pcap) i32 ascending, counts (W) i32 (may exceed pcap: PH_ST_CAP),
+        keeps (W, pcap) i32, weights (W, kcap) f64, residual (W, N), status (W)."""
+        x, code, W, N, fl, mk = self._prep(x)
+        if not q_hi:
+            q_hi = N // 3
+        q_hi, pcap, kcap = int(q_hi), int(pcap), int(kcap)
+        norms = mk.empty((W, q_hi + 1), np.float64)
+        periods = mk.empty((W, pcap), np.int32)
+        counts = mk.empty((W,), np.int32)
+        keeps = mk.empty((W, pcap), np.int32)
+        weights = mk.empty((W, kcap), np.float64)
+        resid = mk.empty((W, N), self._np_dtype(code))
+        status = mk.empty((W,), np.int32)
+        self._call(mk, W, self._lib.ph_ramanujan_fit, mk.addr(x), code, W, N, int(q_lo), q_hi, float(thresh), pcap, kcap, fl,
+                   mk.addr(norms), mk.addr(periods), mk.addr(counts), mk.addr(keeps), mk.addr(weights), mk.addr(resid),
+                   mk.addr(status))
+        return norms, periods, counts, keeps, weights, resid, status
 
     def orth_powers(self, x, max_p=None, normalize=False, want_autocorr=False, want_eq3=False):
         """Orthogonal period powers (QOPeriods.get_best_period_orthogonal(return_powers=True)).

@@ -127,7 +127,11 @@ int ph_m_best_info(ph_ctx* ctx, int dtype, int N, int num, int min_length, int m
 /* Measurement helper: the pass plan that step-1 kernel walks per sweep over [min_length, max_length] (max_length < 0:
  * N / 3, Periods.py:486): n_pass passes over the window for n_periods candidate periods.  The window-pair kernel
  * takes the periods up to 64 in chains (one row-split pass at L yields L, L/2, L/4, ...), so its plan is shorter
- * than ph_sweep_plan_info's. */
+ * than ph_sweep_plan_info's.  Reported is the plan plain m_best (gamma = 0) runs: there the window-pair kernel
+ * screens only the periods in (max_length / 2, max_length] -- a period with a multiple in range cannot beat that
+ * multiple, and is evaluated in fp64 only when a multiple survives the screen -- so n_pass counts the passes over
+ * that range while n_periods stays max_length - min_length + 1.  m_best_gamma (gamma = 1) runs the full plan over
+ * [min_length, max_length], and so does every context created with PH_PAIR_COVER=0 in the environment. */
 int ph_m_best_plan_info(ph_ctx* ctx, int dtype, int N, int num, int min_length, int max_length, unsigned flags,
                         int* n_pass, int* n_periods);
 
@@ -159,7 +163,9 @@ int ph_sweep(ph_ctx* ctx, const void* x, int dtype, int64_t W, int N, int p_lo, 
  * step 2 (factor refinement) both run on the device.  fac_off/fac_q: ordered proper
  * divisors (1 and p removed) of every p <= max_length, i.e. the iteration order of
  * get_factors(p, remove_1_and_n=True) at Periods.py:548-549.  Pass max_length < 0 for the
- * reference default floor(N/3). */
+ * reference default floor(N/3).  With gamma = 0 step 1 of fp64 windows reads the same table to find the divisors
+ * of the periods that survive its screen (ph_m_best_plan_info), so it must list EVERY proper divisor; with
+ * gamma = 1 (m_best_gamma) the screen runs the full plan over every period and step 1 does not read it. */
 int ph_m_best(ph_ctx* ctx, const void* x, int dtype, int64_t W, int N, int num,
               int min_length, int max_length, int gamma,
               const int32_t* orth_off, const int32_t* orth_q,

@@ -77,6 +77,7 @@ struct ph_ctx {
   bool s2l_pair = true;    // PH_S2L_PAIR=0: always the one-window kernel for small_to_large
   bool bc_pair = true;     // PH_BC_PAIR=0: always the one-window kernel for best_correlation
   bool pair_chain = true;  // PH_PAIR_CHAIN=0: the window-pair kernels take the periods below 64 one pass each
+  bool pair_cover = true;  // PH_PAIR_COVER=0: plain m_best screens every period instead of the top half (pair_screen_lo)
   DevBuf twid;  // cos/sin(2 pi k / L), k < L, of the last best_frequency win_size
   int twid_len = -1;
   DevBuf bs_tab;  // Bluestein tables of the last (win_size, min(N, win_size)): M twiddles, chirp, FFT of the wrapped chirp
@@ -500,6 +501,14 @@ bool pair_eligible(const ph_ctx* c, int dtype, int N, int num, int min_length, i
          pair_lds_bytes(N, num, max_length - min_length + 1) <= (size_t)c->lds_limit;
 }
 
+// First period the window-pair screen of m_best evaluates.  Plain m_best (gamma == 0): a period with a multiple in range
+// cannot beat that multiple (cover rule, ph_pair.h), so the screen starts behind max_length / 2 and the kernel looks at
+// a smaller period only when one of its multiples survives.  m_best_gamma compares E_q / q, which the rule does not
+// order: it screens every period, and so does PH_PAIR_COVER=0.  A result equal to min_length means "no cover logic".
+int pair_screen_lo(const ph_ctx* c, int min_length, int max_length, int gamma) {
+  return (c->pair_cover && !gamma) ? std::max(min_length, max_length / 2 + 1) : min_length;
+}
+
 // ----------------------------------------------------------------------------- launch plans
 // One planning function per entry point: the variant, the placement of the window and of the second window-sized
 // buffer, the block size and the LDS of every kernel it launches, from the arguments alone (nothing is allocated or
@@ -887,6 +896,7 @@ int ph_create(int device, ph_ctx** out) {
   if (const char* e = std::getenv("PH_S2L_PAIR")) c->s2l_pair = std::atoi(e) != 0;
   if (const char* e = std::getenv("PH_BC_PAIR")) c->bc_pair = std::atoi(e) != 0;
   if (const char* e = std::getenv("PH_PAIR_CHAIN")) c->pair_chain = std::atoi(e) != 0;
+  if (const char* e = std::getenv("PH_PAIR_COVER")) c->pair_cover = std::atoi(e) != 0;
   if (const char* e = std::getenv("PH_STEP1_BLOCK")) {
     const int v = std::atoi(e);
     if (v >= 64 && v <= 1024 && v % 64 == 0) c->step1_block = v;
@@ -976,7 +986,9 @@ int ph_m_best_plan_info(ph_ctx* c, int dtype, int N, int num, int min_length, in
   if (min_length < 1 || max_length < min_length)
     return fail(PH_E_ARG, "need 1 <= min_length <= max_length (got %d, %d)", min_length, max_length);
   const bool pair = pair_eligible(c, dtype, N, num, min_length, max_length, flags);
-  *n_pass = (int)build_plan(min_length, max_length, c->plan_max_m, false, pair && c->pair_chain).size();
+  // the passes plain m_best runs: the pair kernel screens [pair_screen_lo, max_length] only (m_best_gamma: every period)
+  const int p_scr = pair ? pair_screen_lo(c, min_length, max_length, 0) : min_length;
+  *n_pass = (int)build_plan(p_scr, max_length, c->plan_max_m, false, pair && c->pair_chain).size();
   *n_periods = max_length - min_length + 1;
   return PH_OK;
 }
@@ -1276,7 +1288,9 @@ int ph_m_best(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int num, in
   PH_TRY(prepare_geom(c, N, max_length, &geom));
   const ph::PassPlan* plan;
   int n_pass;
-  PH_TRY(prepare_plan(c, min_length, max_length, &plan, &n_pass, 4, false, pair));
+  // (the cached plan is keyed by its first period: the top-half plan of m_best and the full plan of m_best_gamma differ there)
+  const int p_scr = pair ? pair_screen_lo(c, min_length, max_length, gamma) : min_length;
+  PH_TRY(prepare_plan(c, p_scr, max_length, &plan, &n_pass, 4, false, pair));
   Stage st(c, flags);
   const void* dx;
   void *dper, *dpow, *dbases, *dstat;
@@ -1304,7 +1318,8 @@ int ph_m_best(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int num, in
     PH_TRY(allow_lds(kernel, s1.lds));
     ProfScope ps_(c, "k_mbest_step1");
     hipLaunchKernelGGL(kernel, dim3((unsigned)((W + 1) / 2)), dim3(s1.block), s1.lds, c->stream, (const double*)dx, (int)W, N,
-                       num, min_length, max_length, gamma, geom, static_cast<const ph::PGeomF*>(c->geomf.p), plan, n_pass,
+                       num, min_length, max_length, p_scr, gamma, tb.fac_off, tb.fac_q, geom,
+                       static_cast<const ph::PGeomF*>(c->geomf.p), plan, n_pass,
                        static_cast<double*>(c->buf[B_GWIN].p), max_iters, (uint32_t*)dper, (double*)dpow, (double*)drows,
                        row_stride, dnorm, (int*)dstat, (int*)dsweeps);
   } else

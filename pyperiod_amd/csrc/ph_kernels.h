@@ -396,6 +396,12 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
 //        workspace and writes its float image into pw.
 //   A window that is not finite / all zero, or whose survivor list overflows, takes every period through the
 //   exact evaluation instead (same decisions as k_mbest_step1, slower).
+//   Cover rule (plain m_best, p_scr > p_lo): the plan holds only the periods [p_scr, p_hi], p_scr = p_hi / 2 + 1, each
+//   of which bounds its divisors (E_d <= E_m for d | m, ph_pair.h).  Step 2 scans those, and every period m whose
+//   upper bound (+ pair_cover_slack) reaches L -- skipped or not -- puts itself (unless skipped) and its unskipped
+//   proper divisors >= p_lo (fac_off / fac_q, and 1) on the list; step 3 first thins the list with one fp64 value
+//   per candidate, a wavefront each, to those within 1e-9 of the largest.  p_scr == p_lo: no cover logic, every
+//   period is screened (m_best_gamma, whose E_q / q the rule does not order, and PH_PAIR_COVER=0).
 // ======================================================================================
 #ifndef PH_PAIR_QUEUE
 #define PH_PAIR_QUEUE 1
@@ -430,8 +436,8 @@ __device__ __forceinline__ double pair_exact_part(const double* __restrict__ xs,
 }
 
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_WAVES, 8))) void k_mbest_step1_pair(
-    const double* __restrict__ x, int W, int N, int num, int p_lo, int p_hi, int gamma,
-    const PGeom* __restrict__ geom, const PGeomF* __restrict__ geomf, const PassPlan* __restrict__ plan, int n_pass,
+    const double* __restrict__ x, int W, int N, int num, int p_lo, int p_hi, int p_scr, int gamma,
+    const int* __restrict__ fac_off, const int* __restrict__ fac_q, const PGeom* __restrict__ geom, const PGeomF* __restrict__ geomf, const PassPlan* __restrict__ plan, int n_pass,
     double* __restrict__ gres, int max_iters, uint32_t* __restrict__ periods_out, double* __restrict__ norms_out,
     double* __restrict__ rows_out, int row_stride, double* __restrict__ dnorm_out, int* __restrict__ status_out,
     int* __restrict__ sweeps_out) {
@@ -492,6 +498,9 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
     }
   }
 #ifdef PH_PAIR_TIMERS
+#ifndef PH_PAIR_TIMERS_WGS
+#define PH_PAIR_TIMERS_WGS 6  // workgroups that print their timers
+#endif
   long long ts[5] = {0, 0, 0, 0, 0};
   long long ts0 = wall_clock64();
   int nsurv_tot = 0, nall = 0;
@@ -531,13 +540,22 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
     const int tid = (wv << 6) + pair_lane();
     const int lane = tid & (kWave - 1);
     if (tid == 0) ctl[14] = nw;  // the pass queue of the next screen (barriers in between)
-    // ---- 2. survivors of both windows: two passes over the values (a thread sees the same <= 2 entries twice)
+    // ---- 2. survivors of both windows: two passes over the screened values (a thread sees the same <= 2 entries twice)
     {
       const bool scr0 = act0 && !__builtin_amdgcn_readfirstlane(ctl[12]), scr1 = act1 && !__builtin_amdgcn_readfirstlane(ctl[13]);
       if (scr0 || scr1) {
         const double unit0 = uniform_f64(dst2[0]), unit1 = uniform_f64(dst2[1]);
+        // cover rule: the screened periods bound their divisors below p_scr.  `seen` (a bit per such divisor and
+        // window, so that a divisor of two covering periods is listed once) lies in front of the first screened
+        // value: 2 SD words <= 8 (p_scr - p_lo) bytes.
+        const int i0 = p_scr - p_lo;
+        const bool cover = i0 > 0;
+        const int SD = (i0 + 31) >> 5;
+        uint32_t* seen = reinterpret_cast<uint32_t*>(stg);
+        for (int k = tid; k < 2 * SD; k += blockDim.x) seen[k] = 0u;
+        const double slack = cover ? pair_cover_slack(N) : 0.0;
         double lo0 = -1.0 / 0.0, lo1 = -1.0 / 0.0;
-        for (int idx = tid; idx < P; idx += blockDim.x) {
+        for (int idx = i0 + tid; idx < P; idx += blockDim.x) {
           const int q = p_lo + idx;
           const f2 v = vals[idx];
           const double rad = pair_radius(pair_rows_upper(fn, q), q);
@@ -560,12 +578,16 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
         __syncthreads();
         lo0 = uniform_f64(red_combine<true>(red, nw));
         lo1 = uniform_f64(red_combine<true>(red + kMaxWaves, nw));
+        // every screened period skipped: nothing bounds the winner from below, every period goes through the exact phase
+        const bool none0 = cover && scr0 && !(lo0 > -1.0 / 0.0), none1 = cover && scr1 && !(lo1 > -1.0 / 0.0);
+        if (tid == 0 && none0) ctl[0] = kPairListCap + 1;
+        if (tid == 0 && none1) ctl[1] = kPairListCap + 1;
         // periods that tie with the winner in the ROUNDED norm survive too
         const double thr0 = lo0 - fabs(lo0) * 1e-9, thr1 = lo1 - fabs(lo1) * 1e-9;
-        for (int idx = tid; idx < P; idx += blockDim.x) {
+        for (int idx = i0 + tid; idx < P; idx += blockDim.x) {
           const int q = p_lo + idx;
           const f2 v = vals[idx];
-          const double rad = pair_radius(pair_rows_upper(fn, q), q);
+          const double rad = pair_radius(pair_rows_upper(fn, q), q) + slack;
           const uint32_t bit = 1u << (idx & 31);
           double a = (double)v.x + rad * unit0, b = (double)v.y + rad * unit1;
           if (gamma) {
@@ -573,13 +595,30 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
             a *= rq;
             b *= rq;
           }
-          if (scr0 && !(skip[idx >> 5] & bit) && a >= thr0) {
+          const bool hit0 = scr0 && !none0 && a >= thr0, hit1 = scr1 && !none1 && b >= thr1;
+          if (hit0 && !(skip[idx >> 5] & bit)) {
             const int k = atomicAdd(&ctl[0], 1);
             if (k < kPairListCap) list[k] = q;
           }
-          if (scr1 && !(skip[SK + (idx >> 5)] & bit) && b >= thr1) {
+          if (hit1 && !(skip[SK + (idx >> 5)] & bit)) {
             const int k = atomicAdd(&ctl[1], 1);
             if (k < kPairListCap) list[kPairListCap + k] = q;
+          }
+          if (cover && (hit0 || hit1)) {
+            // q covers (skipped or not): its proper divisors in [p_lo, p_scr) may hold the maximum
+            const int f1 = fac_off[q + 1];
+            for (int f = fac_off[q] - (p_lo == 1 ? 1 : 0); f < f1; ++f) {
+              const int d = f < fac_off[q] ? 1 : fac_q[f];  // the table leaves out 1
+              if (d < p_lo || d >= p_scr) continue;
+              const int di = d - p_lo;
+              const uint32_t dbit = 1u << (di & 31);
+              for (int w = 0; w < 2; ++w) {
+                if (!(w ? hit1 : hit0) || (skip[w * SK + (di >> 5)] & dbit)) continue;
+                if (atomicOr(&seen[w * SD + (di >> 5)], dbit) & dbit) continue;
+                const int k = atomicAdd(&ctl[w], 1);
+                if (k < kPairListCap) list[w * kPairListCap + k] = d;
+              }
+            }
           }
         }
       }
@@ -594,7 +633,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
           iters = __builtin_amdgcn_readfirstlane(ctl[8 + w]);
       const int nlisted = __builtin_amdgcn_readfirstlane(ctl[w]);
       const bool exact_all = __builtin_amdgcn_readfirstlane(ctl[12 + w]) != 0 || nlisted > kPairListCap;
-      const int ncand = exact_all ? P : nlisted;
+      int ncand = exact_all ? P : nlisted;
       double* nrm = norms + w * num;
       uint32_t* per = periods + w * num;
       uint32_t* sk = skip + w * SK;
@@ -612,6 +651,36 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
         nsurv_tot += ncand;
         nall += exact_all ? 1 : 0;
 #endif
+        if (p_scr > p_lo && !exact_all && ncand > 1) {
+          // cover rule: the list holds the surviving screened periods AND their divisors, which no screen value has
+          // thinned out.  A wavefront per candidate evaluates them in fp64; only those within 1e-9 (relative) of the
+          // largest value -- the winner and whatever may tie with it in the rounded norm -- stay for the decision
+          // below.  (msm is idle until a winner is projected; kPairListCap <= kPairSmallP.)
+          for (int k = wv; k < ncand; k += nw) {
+            const int p = lst[k];
+            const PGeom g = geom[p];
+            const double part = p < 64 ? wave_partial_small(stg, N, p, g, lane) : pair_exact_part(stg, p, g, lane, kWave);
+            const double ss = wave_sum(part);
+            if (lane == 0) msm[k] = ss;
+          }
+          __syncthreads();
+          if (wv == 0) {
+            const int k0 = lane, k1 = kWave + lane;
+            const double v0 = k0 < ncand ? msm[k0] : -1.0, v1 = k1 < ncand ? msm[k1] : -1.0;
+            const int q0 = lst[k0], q1 = k1 < kPairListCap ? lst[k1] : 0;
+            const double top = wave_max(fmax(v0, v1));
+            const bool keep0 = k0 < ncand && v0 >= top - fabs(top) * 1e-9, keep1 = k1 < ncand && v1 >= top - fabs(top) * 1e-9;
+            const unsigned long long m0 = __ballot(keep0), m1 = __ballot(keep1);
+            const unsigned long long below = (1ull << lane) - 1ull;
+            const int n0 = __popcll(m0);
+            int* out = list + w * kPairListCap;
+            if (keep0) out[__popcll(m0 & below)] = q0;
+            if (keep1) out[n0 + __popcll(m1 & below)] = q1;
+            if (lane == 0) ctl[w] = n0 + __popcll(m1);
+          }
+          __syncthreads();
+          ncand = __builtin_amdgcn_readfirstlane(ctl[w]);
+        }
         double best_ss = 0.0;
         int bestp = 0;
         // same comparison as k_mbest_step1: rounded norms only when two candidates nearly tie
@@ -793,7 +862,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
   }
 #endif
 #ifdef PH_PAIR_TIMERS
-  if (blockIdx.x < 6 && tid == 0)
+  if (blockIdx.x < PH_PAIR_TIMERS_WGS && tid == 0)
     printf("pair timers (100 MHz ticks) screen %lld scan %lld load %lld exact %lld update %lld  candidates %d exact_all %d sweeps %d %d\n",
            ts[0], ts[1], ts[2], ts[3], ts[4], nsurv_tot, nall, ctl[8], ctl[9]);
 #endif

@@ -12,6 +12,11 @@
 // The float values only SCREEN the candidates of an m_best iteration (Periods.py:501-515): a rigorous radius
 // (pair_radius) bounds |screen - exact|, and the periods whose upper bound reaches the best lower bound are
 // re-evaluated in fp64 by the kernel (k_mbest_step1_pair in ph_kernels.h), which decides on those values.
+//
+// Plain m_best screens only the periods in (p_hi / 2, p_hi]: the projection onto the d-periodic vectors is never
+// longer than the one onto the m-periodic vectors when d | m, so a period with a multiple in range needs a look (in
+// fp64) only when that multiple survives -- the cover rule, derived at pair_cover_slack below.  At p = 2 ... 1365,
+// N = 4096 that is 683 few-row single passes (R = 4, 5, 6) per sweep instead of 800 mixed ones.
 #pragma once
 
 #include "ph_device.h"
@@ -555,6 +560,19 @@ __device__ __forceinline__ void pair_sweep_plan(const f2* __restrict__ xs, int N
 // Underflow: the windows are scaled to RMS ~ 1, so denormal roundings (<= 2^-149 each) are far below the radius.
 __device__ __forceinline__ double pair_radius(int rows, int q) {
   return 1.5 * (2.0 * (double)rows + (double)(q >> 6) + 32.0) * 5.9604644775390625e-08;
+}
+
+// Cover rule of k_mbest_step1_pair (plain m_best): V_d, the d-periodic vectors of length N, lie in V_m when d | m, so
+// the exact values obey E_d <= E_m, and every d <= floor(p_hi / 2) has a multiple in (floor(p_hi / 2), p_hi].  Only
+// those "top" periods are screened; a divisor is evaluated (in fp64) only when a multiple m may still hold the maximum:
+//   E^_d <= E_d + e_d ssq <= E_m + e_d ssq <= screen(m) + (pair_radius(m) + e_d) ssq,
+// E^_d being the fp64 value the exact phase computes for d and e_d <= (2 R_d + d/64 + 16) 2^-53 its rounding error (the
+// fp64 analogue of the first-order term above: u = 2^-53, no input rounding).  R_d <= N and d <= N give
+// e_d <= (2 N + N/64 + 16) 2^-53 < (2 N + 32) 2^-52, the factor 2 covering the second-order terms.  The slack is
+// ABSOLUTE, in units of ssq: after a period has been removed E_d and E_m are both rounding noise of order 1e-33 ssq in
+// either order, which no bound relative to E_m would cover.  Never less than 2^-40.
+__device__ __forceinline__ double pair_cover_slack(int N) {
+  return fmax(9.094947017729282e-13, (2.0 * (double)N + 32.0) * 2.220446049250313e-16);
 }
 
 }  // namespace ph

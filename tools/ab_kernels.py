@@ -6,7 +6,7 @@ inside one gpurun call).  Build a variant next to the in-tree library, e.g.
     gpurun -- 'for i in 1 2; do python tools/ab_kernels.py; PYPERIOD_AMD_LIB=$PWD/_var/lib_x.so python tools/ab_kernels.py; done'
 
 (`_var/` is git-ignored but travels with the gpurun snapshot).  Prints the HIP-event kernel times (library profiler) of
-the four sweep-family kernels at their BASELINE shapes."""
+the sweep-family kernels at their BASELINE shapes."""
 import os
 import sys
 
@@ -36,6 +36,7 @@ def run(name, fn, kern, reps):
 
 run("k_mbest_step1", lambda: eng.m_best(x[:1024], 10), "k_mbest_step1", 8)
 run("k_mbest_step2", lambda: eng.m_best(x[:1024], 10), "k_mbest_step2", 8)
+run("k_mbest_step1(gamma)", lambda: eng.m_best(x[:1024], 10, gamma=True), "k_mbest_step1", 8)
 run("k_small_to_large(8192)", lambda: eng.small_to_large(x, 0.05, None, False, False, cap=64, want_bases=False), "k_small_to_large", 3)
 run("k_sweep", lambda: eng.sweep(x[:1024], 2, 1365, 0), "k_sweep", 5)
 run("k_best_correlation", lambda: eng.best_correlation(x[:1024], 3, None), "k_best_correlation", 3)

@@ -131,9 +131,21 @@ int ph_m_best_info(ph_ctx* ctx, int dtype, int N, int num, int min_length, int m
  * screens only the periods in (max_length / 2, max_length] -- a period with a multiple in range cannot beat that
  * multiple, and is evaluated in fp64 only when a multiple survives the screen -- so n_pass counts the passes over
  * that range while n_periods stays max_length - min_length + 1.  m_best_gamma (gamma = 1) runs the full plan over
- * [min_length, max_length], and so does every context created with PH_PAIR_COVER=0 in the environment. */
+ * [min_length, max_length], and so does every context created with PH_PAIR_COVER=0 in the environment.
+ * n_pass = periods the screen folds, each counted as one read of the window: the window-pair kernel folds some of
+ * them two to a pass (ph_m_best_screen_info), so n_pass * N * 8 is the LDS traffic of the equivalent plan of single
+ * passes, not the bytes the kernel reads. */
 int ph_m_best_plan_info(ph_ctx* ctx, int dtype, int N, int num, int min_length, int max_length, unsigned flags,
                         int* n_pass, int* n_periods);
+
+/* Measurement helper: the plan as the step-1 kernel walks it (gamma = 0: m_best, 1: m_best_gamma).  n_entries = plan
+ * entries per sweep; n_screened = periods they fold; lds_elements = LDS elements (of lds_bytes_per_sample bytes,
+ * ph_m_best_info) one sweep reads per workgroup, 64 per wavefront load.  The window-pair kernel folds a period
+ * p >= 64 with at most 6 rows together with p + 64 from one set of loads when both have the same row count, so it has
+ * fewer entries than periods and reads less than n_screened windows; a context created with PH_PAIR_DUO=0 in the
+ * environment plans one pass per period. */
+int ph_m_best_screen_info(ph_ctx* ctx, int dtype, int N, int num, int min_length, int max_length, unsigned flags,
+                          int gamma, int* n_entries, int* n_screened, long long* lds_elements);
 
 /* ---- Periods.periodic_norm over a batch (Periods.py:221-241) ---------------------------
  * out[w] = ||x[w]||_2 / sqrt(N), additionally / sqrt(p) when p > 0.  Any N. */

@@ -78,12 +78,13 @@ struct ph_ctx {
   bool bc_pair = true;     // PH_BC_PAIR=0: always the one-window kernel for best_correlation
   bool pair_chain = true;  // PH_PAIR_CHAIN=0: the window-pair kernels take the periods below 64 one pass each
   bool pair_cover = true;  // PH_PAIR_COVER=0: plain m_best screens every period instead of the top half (pair_screen_lo)
+  bool pair_duo = true;    // PH_PAIR_DUO=0: the window-pair m_best screen folds every period in a pass of its own
   DevBuf twid;  // cos/sin(2 pi k / L), k < L, of the last best_frequency win_size
   int twid_len = -1;
   DevBuf bs_tab;  // Bluestein tables of the last (win_size, min(N, win_size)): M twiddles, chirp, FFT of the wrapped chirp
   int bs_L = -1, bs_M0 = -1;
   DevBuf plan;  // pass plan of the norm sweeps, cached for the last (p_lo, p_hi)
-  int plan_lo = -1, plan_hi = -1, plan_n = 0, plan_m = -1;
+  int plan_lo = -1, plan_hi = -1, plan_n = 0, plan_m = -1, plan_duo_n = 0;
   int plan_max_m = 4;  // largest row-class count a pass may use (PH_PLAN_MAX_M overrides: 1, 2 or 4)
   int sweep_block = ph::kBlockWide;  // threads per workgroup of the sweep kernels (PH_SWEEP_BLOCK overrides)
   int step1_block = 0;               // k_mbest_step1 only: 0 = automatic (PH_STEP1_BLOCK overrides, <= 1024)
@@ -145,7 +146,11 @@ size_t elem_size(int dtype) { return dtype == PH_F64 ? 8 : 4; }
 // Periods below 64 use the row-split path one at a time (m = 0).
 // `chains` (window-pair kernels): the periods up to 64 are taken in chains L, L/2, L/4, ... -- one row-split pass at
 // L yields them all (m = 8 + number of periods, see pair_chain_small in ph_pair.h) -- instead of one pass each.
-std::vector<ph::PassPlan> build_plan(int p_lo, int p_hi, int max_m, bool mixed = true, bool chains = false) {
+// `duo_n` (k_mbest_step1_pair only; the window length, 0 = off): a single pass at p with R = 3 ... 6 rows and more than R
+// chunk columns (p > 64 R) also takes p + 64 when that period has the same row count and no pass of its own yet (m = 3,
+// pair_pass_duo in ph_pair.h) -- greedy in ascending order, so the pairing stays inside one row class; what finds no
+// partner stays m = 1.
+std::vector<ph::PassPlan> build_plan(int p_lo, int p_hi, int max_m, bool mixed = true, bool chains = false, int duo_n = 0) {
   std::vector<ph::PassPlan> host;
   std::vector<char> covered((size_t)p_hi + 1, 0);
   if (chains) {
@@ -170,6 +175,13 @@ std::vector<ph::PassPlan> build_plan(int p_lo, int p_hi, int max_m, bool mixed =
     int m = (4LL * p <= p_hi) ? 4 : (2LL * p <= p_hi) ? 2 : 1;
     m = std::min(m, max_m);
     for (int d = 1; d <= m; d *= 2) covered[(size_t)d * p] = 1;
+    if (duo_n > 0 && m == 1 && p >= 64 && p + 64 <= p_hi && !covered[p + 64]) {
+      const int rows = (duo_n + p - 1) / p;
+      if (rows >= 3 && rows <= 6 && (p + 63) / 64 > rows && (duo_n + p + 63) / (p + 64) == rows) {
+        covered[p + 64] = 1;
+        m = 3;
+      }
+    }
     host.push_back(ph::PassPlan{p, m});
   }
   // Interleave the pass types evenly (entry i of a type with n entries gets the key (i + 0.5) / n):
@@ -204,17 +216,18 @@ std::vector<ph::PassPlan> build_plan(int p_lo, int p_hi, int max_m, bool mixed =
 // passes first and the cheap few-row singles last -- what a workgroup that walks the WHOLE plan between two
 // barriers wants (k_mbest_step1: shorter tail before the argmax barrier, -3 %).
 int prepare_plan(ph_ctx* c, int p_lo, int p_hi, const ph::PassPlan** out, int* n_pass, int max_m = 4, bool mixed = true,
-                 bool chains = false) {
+                 bool chains = false, int duo_n = 0) {
   max_m = std::min(max_m, c->plan_max_m);
   chains = chains && c->pair_chain;
+  if (!c->pair_duo) duo_n = 0;
   if (!mixed) max_m += 8;  // cache key
   if (chains) max_m += 16;
-  if (c->plan.p && c->plan_lo == p_lo && c->plan_hi == p_hi && c->plan_m == max_m) {
+  if (c->plan.p && c->plan_lo == p_lo && c->plan_hi == p_hi && c->plan_m == max_m && c->plan_duo_n == duo_n) {
     *out = static_cast<const ph::PassPlan*>(c->plan.p);
     *n_pass = c->plan_n;
     return PH_OK;
   }
-  const std::vector<ph::PassPlan> host = build_plan(p_lo, p_hi, max_m & 7, mixed, chains);
+  const std::vector<ph::PassPlan> host = build_plan(p_lo, p_hi, max_m & 7, mixed, chains, duo_n);
   PH_HIP(hipStreamSynchronize(c->stream));
   PH_TRY(ensure(c, c->plan, std::max<size_t>(1, host.size()) * sizeof(ph::PassPlan)));
   if (!host.empty())
@@ -224,6 +237,7 @@ int prepare_plan(ph_ctx* c, int p_lo, int p_hi, const ph::PassPlan** out, int* n
   c->plan_lo = p_lo;
   c->plan_hi = p_hi;
   c->plan_m = max_m;
+  c->plan_duo_n = duo_n;
   c->plan_n = (int)host.size();
   *out = static_cast<const ph::PassPlan*>(c->plan.p);
   *n_pass = c->plan_n;
@@ -897,6 +911,7 @@ int ph_create(int device, ph_ctx** out) {
   if (const char* e = std::getenv("PH_BC_PAIR")) c->bc_pair = std::atoi(e) != 0;
   if (const char* e = std::getenv("PH_PAIR_CHAIN")) c->pair_chain = std::atoi(e) != 0;
   if (const char* e = std::getenv("PH_PAIR_COVER")) c->pair_cover = std::atoi(e) != 0;
+  if (const char* e = std::getenv("PH_PAIR_DUO")) c->pair_duo = std::atoi(e) != 0;
   if (const char* e = std::getenv("PH_STEP1_BLOCK")) {
     const int v = std::atoi(e);
     if (v >= 64 && v <= 1024 && v % 64 == 0) c->step1_block = v;
@@ -990,6 +1005,51 @@ int ph_m_best_plan_info(ph_ctx* c, int dtype, int N, int num, int min_length, in
   const int p_scr = pair ? pair_screen_lo(c, min_length, max_length, 0) : min_length;
   *n_pass = (int)build_plan(p_scr, max_length, c->plan_max_m, false, pair && c->pair_chain).size();
   *n_periods = max_length - min_length + 1;
+  return PH_OK;
+}
+
+namespace {
+
+// LDS elements (64 per wavefront load) one entry of a window-pair plan reads: the loads of pair_pass_single /
+// pair_pass_multi (every chunk of the part up to the cut with all rows, the chunks behind it with one row fewer),
+// of pair_pass_duo (its load rule, column by column) and of the row-split passes below 64.
+long long plan_entry_elements(const ph::PassPlan& e, int N) {
+  const int p = e.p;
+  if (e.m == 0 || e.m >= 8) {
+    const int L = (64 / p) * p;
+    return 64LL * ((N + L - 1) / L);
+  }
+  const int rows = (N + p - 1) / p, cut = N - (rows - 1) * p;
+  if (e.m != 3) {
+    const int acols = std::min(p, (cut + 63) & ~63), rest = p - acols;
+    return 64LL * ((long long)((cut + 63) / 64) * rows + (long long)((rest + 63) / 64) * (rows - 1));
+  }
+  const int ncb = (p + 63) / 64;
+  long long loads = 0;
+  for (int col = 0; col < ncb + rows; ++col)
+    for (int r = 0; r < rows; ++r)
+      if (r >= col - ncb && 64 * col + r * p < N) loads += 1;
+  return 64 * loads;
+}
+
+}  // namespace
+
+int ph_m_best_screen_info(ph_ctx* c, int dtype, int N, int num, int min_length, int max_length, unsigned flags, int gamma,
+                          int* n_entries, int* n_screened, long long* lds_elements) {
+  if (!c || !n_entries || !n_screened || !lds_elements) return fail(PH_E_ARG, "NULL argument");
+  if (dtype != PH_F64 && dtype != PH_F32) return fail(PH_E_ARG, "dtype must be PH_F64 or PH_F32");
+  if (max_length < 0) max_length = N / 3;
+  if (min_length < 1 || max_length < min_length)
+    return fail(PH_E_ARG, "need 1 <= min_length <= max_length (got %d, %d)", min_length, max_length);
+  // (the one-window kernel folds every period of [min_length, max_length] in its own precision: same accounting)
+  const bool pair = pair_eligible(c, dtype, N, num, min_length, max_length, flags);
+  const int p_scr = pair ? pair_screen_lo(c, min_length, max_length, gamma) : min_length;
+  const std::vector<ph::PassPlan> plan =
+      build_plan(p_scr, max_length, c->plan_max_m, false, pair && c->pair_chain, pair && c->pair_duo ? N : 0);
+  *n_entries = (int)plan.size();
+  *n_screened = max_length - p_scr + 1;
+  *lds_elements = 0;
+  for (const ph::PassPlan& e : plan) *lds_elements += plan_entry_elements(e, N);
   return PH_OK;
 }
 
@@ -1290,7 +1350,7 @@ int ph_m_best(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int num, in
   int n_pass;
   // (the cached plan is keyed by its first period: the top-half plan of m_best and the full plan of m_best_gamma differ there)
   const int p_scr = pair ? pair_screen_lo(c, min_length, max_length, gamma) : min_length;
-  PH_TRY(prepare_plan(c, p_scr, max_length, &plan, &n_pass, 4, false, pair));
+  PH_TRY(prepare_plan(c, p_scr, max_length, &plan, &n_pass, 4, false, pair, pair ? N : 0));
   Stage st(c, flags);
   const void* dx;
   void *dper, *dpow, *dbases, *dstat;

@@ -635,6 +635,7 @@ struct PassPlan {
   int p;  // base period
   int m;  // 1, 2 or 4: the pass yields p, 2p (m >= 2) and 4p (m == 4); 0: p < 64, row-split path;
           // 8 + n (window-pair kernels only): p <= 64, row-split path yielding p, p/2, ..., p / 2^(n-1)
+          // 3 (k_mbest_step1_pair only): p and p + 64 from one set of LDS reads (pair_pass_duo in ph_pair.h)
 };
 
 // ---------------------------------------------------------------- segmented passes

@@ -527,7 +527,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
     if (wv == 0 && pair_lane() == 0) ctl[0] = ctl[1] = 0;  // (read as `ncand` before the last barrier of the previous round)
     // ---- 1. screen of both windows (Periods.py:501-515 in float); values into the idle staging buffer
     f2* vals = reinterpret_cast<f2*>(stg);
-    pair_sweep_plan(
+    pair_sweep_plan<false, true>(
         pw, N, geomf, plan, wv, n_pass, nw, [&](float z, int q) { pair_store1(vals, z, q, p_lo); },
         [&](float z, int q_a, int q_b) { pair_store2(vals, z, q_a, q_b, p_lo); },
         PH_PAIR_QUEUE ? &ctl[14] : nullptr);

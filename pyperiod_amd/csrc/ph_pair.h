@@ -300,9 +300,6 @@ __device__ __forceinline__ f2 pair_pass_single(const f2* __restrict__ xs, int p,
   return f2_fma(sa, f2_make(g.w_full, g.w_full), sb * g.w_short);
 }
 
-// ---------------------------------------------------------------- multi-class pass, straight-line segments
-// Period p, 2p (and 4p) from the class sums of one fold: the weights of a part are compile-time indexed and chosen on
-// the scalar unit, the tail of a part is picked by two compares, and no flag survives a branch.
 // (x < y) ? a : b of wave-uniform values on the scalar unit (the compiler's version of a float select under a scalar
 // condition is two v_mov and a v_cndmask)
 __device__ __forceinline__ float scalar_select_lt(int x, int y, float a, float b) {
@@ -311,6 +308,203 @@ __device__ __forceinline__ float scalar_select_lt(int x, int y, float a, float b
   return r;
 }
 
+// ---------------------------------------------------------------- shared-load pass: q and q + 64 from one set of reads
+// A wavefront that folds period q holds a[r][c] = x[64 c + lane + r q] (row r, chunk column c).  Because
+// (64 c + lane) + r (q + 64) = 64 (c + r) + lane + r q,
+//   S_q   [64 c + lane] = sum_r a[r][c]        S_{q+64}[64 c + lane] = sum_r a[r][c + r]:
+// the fold of q + 64 takes the same registers in the same lanes, one column further per row -- no cross-lane traffic,
+// no second set of loads, packed adds.  The host pairs q with q + 64 only when ceil(N / q) = ceil(N / (q + 64)) = R,
+// 3 <= R <= 6, and q has at least R + 1 chunk columns (build_plan, PassPlan m = 3), which keeps the bookkeeping regular:
+//   weights  both periods take 1 / R below their cut and 1 / (R - 1) behind it;
+//   cut      nfull(q + 64) = nfull(q) - 64 (R - 1): chunk c of q + 64 is complete when column c + R - 1 arrives, so
+//            both periods cross their cut in the SAME column at the same lane -- the columns in front of it feed the
+//            1 / R sums of both, the columns behind it the 1 / (R - 1) sums of both;
+//   loads    row r, column c is read only while 64 c + r q < N, and only up to column ceil(q / 64) + r, the last one
+//            q + 64 needs of it.  Every sample either period owns is read, what lies behind the window is a zero of the
+//            pad, and no read goes past index N + 62.
+// The wavefront streams over the columns and carries the R - 1 unfinished sums of q + 64 in `pend` (pend[k]: rows
+// 0 ... k of chunk c - k), rotated by unrolling.  Everything is straight-line code in the manner of pair_rows_group (U
+// columns of loads, one lgkmcnt(0), then the adds): R rows per column in front of the cut, R - 1 behind it; the column
+// that holds the cut and the last column of q classify per lane (LANES); in the first R - 1 columns, where no chunk of
+// q + 64 is complete yet, the unfinished sum is multiplied by a wave-uniform 0 (PRO); the R - 1 columns behind the last
+// one of q bring the rows that q + 64 still lacks (pair_duo_tail).  Adds and squares per period are those of two
+// single passes; the reads are ~0.63 x (45 281 -> 28 669 wavefront loads per sweep at N = 4096, p = 683 ... 1365).
+// (the window address of the lane is recomputed in front of every loop, as pair_lane() is: kept live across the pass it
+// is spilled around the groups)
+__device__ __forceinline__ pair_ptr pair_at(const f2* __restrict__ xs) { return (pair_ptr)xs + pair_lane(); }
+
+template <int R, int NR, int U, bool PRO, bool LANES>
+__device__ __forceinline__ void pair_duo_group(pair_ptr ptr, int q, int c, int cut, f2 (&pend)[R - 1], f2& sa, f2& pa, f2& sb,
+                                               f2& pb) {
+  static_assert(NR == R || NR == R - 1, "all rows (in front of the cut), or all but the last (behind it)");
+  static_assert(!LANES || U == 1, "a column that is cut comes alone");
+  f2 v[NR][U];
+#pragma unroll
+  for (int r = 0; r < NR; ++r)
+#pragma unroll
+    for (int u = 0; u < U; ++u) v[r][u] = ptr[r * q + 64 * u];
+  __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    f2 t = v[0][u];
+#pragma unroll
+    for (int r = 1; r < NR; ++r) t += v[r][u];
+    f2 d = pend[R - 2];  // chunk c + u - (R - 1) of q + 64
+    if (NR == R) d += v[NR - 1][u];
+    if (PRO || LANES) d *= scalar_select_lt(c + u, R - 1, 0.0f, 1.0f);
+    if (LANES) {
+      const int j = 64 * c + pair_lane();  // residue of q; that of q + 64 is j - 64 (R - 1) and lies below q
+      if (NR == R) {
+        const bool full = j < cut;
+        sa = f2_fma(full ? t : f2_zero(), t, sa);
+        sb = f2_fma((!full && j < q) ? t : f2_zero(), t, sb);
+        pa = f2_fma(full ? d : f2_zero(), d, pa);
+        pb = f2_fma(full ? f2_zero() : d, d, pb);
+      } else {
+        sb = f2_fma(j < q ? t : f2_zero(), t, sb);
+        pb = f2_fma(d, d, pb);
+      }
+    } else if (NR == R) {
+      sa = f2_fma(t, t, sa);
+      pa = f2_fma(d, d, pa);
+    } else {
+      sb = f2_fma(t, t, sb);
+      pb = f2_fma(d, d, pb);
+    }
+#pragma unroll
+    for (int k = R - 2; k >= 1; --k) pend[k] = pend[k - 1] + v[k][u];
+    pend[0] = v[0][u];
+  }
+}
+
+// one load of the tail that may lie behind the window: skipped as a whole (wave-uniform), its register keeps the zero
+template <int OFF>
+__device__ __forceinline__ void pair_duo_load_if(f2& val, unsigned addr, int index, int N) {
+  asm volatile(
+      "s_cmp_lt_i32 %2, %3\n\t"
+      "s_cbranch_scc0 .Lduo_skip_%=\n\t"
+      "ds_read_b64 %0, %1 offset:%4\n"
+      ".Lduo_skip_%=:"
+      : "+v"(val)
+      : "v"(addr), "s"(index + OFF / 8), "s"(N), "n"(OFF)
+      : "scc");
+}
+
+// The columns ncb + t, t = T0 ... T1 - 1 of 0 ... R - 2, behind the last column of q (ncb = ceil(q / 64)): q + 64 needs
+// the rows t ... R - 2 of them.  Rows up to R - 3 lie inside the window (q > 64 R), row R - 2 only while
+// 64 (ncb + t) + (R - 2) q < N.  Every chunk of q + 64 that completes here lies behind its cut; the last one, chunk ncb,
+// is cut at q + 64 (after column R - 2).  Six rows take the columns in two batches (15 loads would cost the registers).
+template <int R, int T0, int T1>
+__device__ __forceinline__ void pair_duo_tail(const f2* __restrict__ xs, int N, int q, int ncb, f2 (&pend)[R - 1], f2& pb) {
+  const pair_ptr at = pair_at(xs) + 64 * ncb;
+  f2 v[R - 1][R - 1];  // [row][t]
+#pragma unroll
+  for (int t = T0; t < T1; ++t) v[R - 2][t] = f2_zero();
+#pragma unroll
+  for (int t = T0; t < T1; ++t)
+#pragma unroll
+    for (int r = t; r < R - 2; ++r) v[r][t] = at[r * q + 64 * t];
+  {
+    const int first = 64 * ncb + (R - 2) * q;  // index of row R - 2 in column ncb, lane 0
+    const unsigned addr = (unsigned)(unsigned long)(at + (R - 2) * q);
+    if (T0 <= 0 && 0 < T1) pair_duo_load_if<0>(v[R - 2][0], addr, first, N);
+    if (T0 <= 1 && 1 < T1) pair_duo_load_if<512>(v[R - 2][1], addr, first, N);
+    if (T0 <= 2 && 2 < T1) pair_duo_load_if<1024>(v[R - 2][2 % (R - 1)], addr, first, N);
+    if (T0 <= 3 && 3 < T1) pair_duo_load_if<1536>(v[R - 2][3 % (R - 1)], addr, first, N);
+    if (T0 <= 4 && 4 < T1) pair_duo_load_if<2048>(v[R - 2][4 % (R - 1)], addr, first, N);
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+  for (int t = T0; t < T1; ++t) asm volatile("" : "+v"(v[R - 2][t]));  // every use of these comes behind the wait
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int t = T0; t < T1; ++t) {
+    pb = f2_fma(pend[R - 2], pend[R - 2], pb);  // chunk ncb + t - (R - 1)
+#pragma unroll
+    for (int k = R - 2; k >= 1; --k) pend[k] = k >= t ? pend[k - 1] + v[k][t] : pend[k - 1];
+    if (t == 0) pend[0] = v[0][0];
+  }
+  if (T1 == R - 1) {
+    const f2 d = (64 * (ncb - 1) + pair_lane() < q) ? pend[R - 2] : f2_zero();  // chunk ncb: residues q ... q + 63
+    pb = f2_fma(d, d, pb);
+  }
+}
+
+template <int R>
+__device__ __forceinline__ void pair_duo_rows(const f2* __restrict__ xs, int N, int q, const PGeomF g, f2& base, f2& partner) {
+  // loads in flight: 12 / 16 / 10 / 12 in front of the cut (R = 3 ... 6), 8 / 12 / 12 / 10 behind it
+  constexpr int UA = R <= 4 ? 4 : 2, UB = R <= 4 ? 4 : R == 5 ? 3 : 2;
+  const int cut = g.nfull, ncb = (q + 63) >> 6, last = ncb - 1;  // the last column of q is cut at q
+  f2 pend[R - 1];
+#pragma unroll
+  for (int k = 0; k < R - 1; ++k) pend[k] = f2_zero();
+  f2 sa = f2_zero(), pa = f2_zero(), sb, pb;
+  int c = 0;
+  {
+    const int whole = min(cut >> 6, last);
+    const pair_ptr at = pair_at(xs);
+    for (; c + UA <= whole; c += UA) {
+      if (c < R - 1) pair_duo_group<R, R, UA, true, false>(at + 64 * c, q, c, cut, pend, sa, pa, sb, pb);
+      else pair_duo_group<R, R, UA, false, false>(at + 64 * c, q, c, cut, pend, sa, pa, sb, pb);
+    }
+    for (; c < whole; ++c) {
+      asm volatile("" ::: "memory");
+      pair_duo_group<R, R, 1, true, false>(at + 64 * c, q, c, cut, pend, sa, pa, sb, pb);
+    }
+  }
+  sb = pb = f2_zero();  // (not live in front of the cut)
+  if (c < last && 64 * c < cut) {  // the column that holds the cut
+    asm volatile("" ::: "memory");
+    pair_duo_group<R, R, 1, true, true>(pair_at(xs) + 64 * c, q, c, cut, pend, sa, pa, sb, pb);
+    c += 1;
+  }
+  {
+    const pair_ptr at = pair_at(xs);
+    for (; c + UB <= last; c += UB) {
+      if (c < R - 1) pair_duo_group<R, R - 1, UB, true, false>(at + 64 * c, q, c, cut, pend, sa, pa, sb, pb);
+      else pair_duo_group<R, R - 1, UB, false, false>(at + 64 * c, q, c, cut, pend, sa, pa, sb, pb);
+    }
+    for (; c < last; ++c) {
+      asm volatile("" ::: "memory");
+      pair_duo_group<R, R - 1, 1, true, false>(at + 64 * c, q, c, cut, pend, sa, pa, sb, pb);
+    }
+  }
+  asm volatile("" ::: "memory");
+  if (64 * last < cut) pair_duo_group<R, R, 1, true, true>(pair_at(xs) + 64 * last, q, last, cut, pend, sa, pa, sb, pb);
+  else pair_duo_group<R, R - 1, 1, true, true>(pair_at(xs) + 64 * last, q, last, cut, pend, sa, pa, sb, pb);
+  const f2 wf = f2_make(g.w_full, g.w_full);
+  base = f2_fma(sa, wf, sb * g.w_short);  // (complete: two registers fewer across the tail)
+  if (R == 6) {
+    pair_duo_tail<R, 0, 2>(xs, N, q, ncb, pend, pb);
+    pair_duo_tail<R, 2, R - 1>(xs, N, q, ncb, pend, pb);
+  } else {
+    pair_duo_tail<R, 0, R - 1>(xs, N, q, ncb, pend, pb);
+  }
+  partner = f2_fma(pa, wf, pb * g.w_short);
+}
+
+// Per-lane partials of both windows for the periods q (`base`) and q + 64 (`partner`); g = geometry of q, and the host
+// guarantees that q + 64 has the same row count R, 3 <= R <= 6, and that q > 64 R.
+__device__ __forceinline__ void pair_pass_duo(const f2* __restrict__ xs, int N, int q, const PGeomF g, f2& base, f2& partner) {
+  base = partner = f2_zero();
+  switch (g.rows) {
+#define PH_DUO_CASE(R)                                \
+  case R:                                             \
+    pair_duo_rows<R>(xs, N, q, g, base, partner);     \
+    break;
+    PH_DUO_CASE(3)
+    PH_DUO_CASE(4)
+    PH_DUO_CASE(5)
+    PH_DUO_CASE(6)
+#undef PH_DUO_CASE
+    default: break;
+  }
+}
+
+// ---------------------------------------------------------------- multi-class pass, straight-line segments
+// Period p, 2p (and 4p) from the class sums of one fold: the weights of a part are compile-time indexed and chosen on
+// the scalar unit, the tail of a part is picked by two compares, and no flag survives a branch.
 template <int M, bool MX = false>
 __device__ __forceinline__ void pair_pass_multi(const f2* __restrict__ xs, int p, const PGeomF* __restrict__ geom,
                                                 f2 (&total)[3]) {
@@ -517,7 +711,8 @@ __device__ __forceinline__ void pair_chain_small(const f2* __restrict__ xs, int 
 // (pair_reduce2: rows of 16 lanes = q_a window a, q_a window b, q_b window a, q_b window b); pair_store1 / pair_store2
 // put them into an array.  Every period is reduced on its own: nothing is live across the folds (the online 8-period
 // butterfly of the fp64 sweeps kept pending partials that were spilled in every pass: 3.03 -> 2.82 ms in round 3).
-template <bool MX = false, typename F, typename F2>
+// DUO: the plan may hold shared-load entries (m = 3, pair_pass_duo); the other kernels never get such a plan.
+template <bool MX = false, bool DUO = false, typename F, typename F2>
 __device__ __forceinline__ void pair_sweep_plan(const f2* __restrict__ xs, int N, const PGeomF* __restrict__ geom,
                                                 const PassPlan* __restrict__ plan, int i_first, int i_end, int stride,
                                                 F&& consume, F2&& consume2, int* __restrict__ queue = nullptr) {
@@ -534,6 +729,10 @@ __device__ __forceinline__ void pair_sweep_plan(const f2* __restrict__ xs, int N
       consume(red(pair_partial_small<MX>(xs, N, p, geom[p])), p);
     } else if (m == 1) {
       consume(red(pair_pass_single<MX>(xs, p, geom[p])), p);
+    } else if (DUO && m == 3) {  // p and p + 64 from one set of reads (k_mbest_step1_pair only)
+      f2 va, vb;
+      pair_pass_duo(xs, N, p, geom[p], va, vb);
+      consume2(pair_reduce2<MX>(va, vb), p, p + 64);
     } else if (m == 2) {
       f2 part[3];
       pair_pass_multi<2, MX>(xs, p, geom, part);

@@ -254,6 +254,18 @@ class PeriodEngine:
                                                  self._flags(trunc, orth), C.byref(n_pass), C.byref(n_per)))
         return n_pass.value, n_per.value
 
+    def m_best_screen_info(self, n, num=5, max_length=None, min_length=2, gamma=False, dtype=np.float64, trunc=False,
+                           orth=False):
+        """(plan entries, periods they fold, LDS elements read) per sweep and workgroup of the step-1 kernel m_best
+        (gamma: m_best_gamma) would run.  The window-pair kernel folds p and p + 64 from one set of loads where it can,
+        so it has fewer entries than periods (PH_PAIR_DUO=0: one pass per period)."""
+        n_ent, n_scr, elems = C.c_int(0), C.c_int(0), C.c_longlong(0)
+        _ffi.check(self._lib.ph_m_best_screen_info(self._ctx, _NP_DTYPES[np.dtype(dtype)], int(n), int(num), int(min_length),
+                                                   int(n // 3 if max_length is None else max_length),
+                                                   self._flags(trunc, orth), int(bool(gamma)), C.byref(n_ent),
+                                                   C.byref(n_scr), C.byref(elems)))
+        return n_ent.value, n_scr.value, elems.value
+
     def m_best(self, x, num=5, max_length=None, min_length=2, gamma=False, trunc=False, orth=False, want_sweeps=False):
         """-> periods (W,num) uint32, powers (W,num) f64, bases (W,num,N), status (W) int32
         [, n_sweeps (W) int32 when want_sweeps]."""

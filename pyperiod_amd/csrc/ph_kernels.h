@@ -1784,10 +1784,27 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
 //     X[k] = sum_n x[n] (cos - i sin)(2 pi k n / L) with the phase index k n mod L kept
 //     incrementally and the twiddles read from a float64 table (L2-resident); every workgroup
 //     leaves its best (|X|^2, k), first maximum.  A single window still fills the chip.
+//   The bins are ranked on |2^-e X[k]|^2 with e = floor(log2 max |x|) over the samples the transform reads
+//   (bf_scale_exp): |X|^2 itself is inf in every bin for a window scaled by 2^520 and 0 in every bin near 2^-560,
+//   where numpy's np.abs (hypot) still ranks.  The factor is a power of two, so a window whose |X|^2 stays in range
+//   ranks exactly as before.
 //   k_bf_update: one workgroup per window: argmax over the chunks, p = rint(2 L / k), project
 //     (all flag combinations), store, subtract, residual back to the HBM workspace.
 // ======================================================================================
 constexpr int kBfBlock = 256;
+
+// floor(log2 max_n |x[n]|) from every thread's share `m` of the maximum (0 for an all-zero window or one without a
+// finite maximum; fmax skips NaN samples, which poison every bin anyway).  `red` holds >= kMaxWaves doubles; ends with
+// a barrier.
+__device__ __forceinline__ int bf_scale_exp(double m, double* red) {
+  m = block_max(m, red);
+  return (m > 0.0 && m <= 1.7976931348623157e308) ? ilogb(m) : 0;
+}
+// re^2 + im^2 of 2^-e (re + i im)
+__device__ __forceinline__ double bf_mag2(double re, double im, int e) {
+  const double r = ldexp(re, -e), i = ldexp(im, -e);
+  return r * r + i * i;
+}
 
 template <typename T, bool LW>
 __global__ __launch_bounds__(kBfBlock) void k_bf_spectrum(const T* __restrict__ res, int N, int L,
@@ -1811,6 +1828,9 @@ __global__ __launch_bounds__(kBfBlock) void k_bf_spectrum(const T* __restrict__ 
     __syncthreads();
     xs = stage;
   }
+  double xmax = 0.0;
+  for (int n = tid; n < M; n += blockDim.x) xmax = fmax(xmax, fabs((double)xs[n]));
+  const int e = bf_scale_exp(xmax, wbest);
   double best = -1.0;
   int bestk = 0;  // bin + 1; 0 = none
   const int k = chunk * (int)blockDim.x + tid;
@@ -1825,7 +1845,7 @@ __global__ __launch_bounds__(kBfBlock) void k_bf_spectrum(const T* __restrict__ 
       idx += k;
       if (idx >= L) idx -= L;
     }
-    const double m2 = re * re + im * im;
+    const double m2 = bf_mag2(re, im, e);
     if (m2 > best) {  // false for NaN
       best = m2;
       bestk = k + 1;
@@ -1874,8 +1894,8 @@ __device__ __forceinline__ void lds_fft_stages(double* __restrict__ re, double* 
   }
 }
 
-// First maximum of re[k]^2 + im[k]^2 over k <= kmax -> the (|X|^2, bin + 1) record of window w, slot 0.
-__device__ __forceinline__ void bf_store_peak(const double* __restrict__ re, const double* __restrict__ im, int kmax,
+// First maximum of |2^-e (re[k] + i im[k])|^2 over k <= kmax -> the (|X|^2, bin + 1) record of window w, slot 0.
+__device__ __forceinline__ void bf_store_peak(const double* __restrict__ re, const double* __restrict__ im, int kmax, int e,
                                               double* wbest, int* wbestp, int64_t w, double* __restrict__ part_m2,
                                               int* __restrict__ part_k) {
   const int tid = threadIdx.x, lane = tid & (kWave - 1);
@@ -1883,7 +1903,7 @@ __device__ __forceinline__ void bf_store_peak(const double* __restrict__ re, con
   double best = -1.0;
   int bestk = 0;  // bin + 1; 0 = none
   for (int k = tid; k <= kmax; k += blockDim.x) {
-    const double m2 = re[k] * re[k] + im[k] * im[k];
+    const double m2 = bf_mag2(re[k], im[k], e);
     if (m2 > best) {  // false for NaN; ascending k per thread keeps the first maximum
       best = m2;
       bestk = k + 1;
@@ -1926,14 +1946,17 @@ __global__ __launch_bounds__(kBlockWide) void k_bf_fft(const T* __restrict__ res
   if (status[w] != 0) return;  // the reference has raised for this window already
   const int M0 = N < L ? N : L;  // rfft(data, L) truncates or zero-pads to L samples
   const T* xs = res + w * (int64_t)N;
+  double xmax = 0.0;
   for (int n = threadIdx.x; n < L; n += blockDim.x) {
     const int r = (int)(__brev((unsigned)n) >> (32 - logL));
-    re[r] = n < M0 ? (double)xs[n] : 0.0;
+    const double xv = n < M0 ? (double)xs[n] : 0.0;
+    xmax = fmax(xmax, fabs(xv));
+    re[r] = xv;
     im[r] = 0.0;
   }
-  __syncthreads();
+  const int e = bf_scale_exp(xmax, wbest);  // (its barrier completes re, im)
   lds_fft_stages(re, im, L, logL, tw);
-  bf_store_peak(re, im, L >> 1, wbest, wbestp, w, part_m2, part_k);
+  bf_store_peak(re, im, L >> 1, e, wbest, wbestp, w, part_m2, part_k);
 }
 
 // Any other win_size whose chirp convolution fits the LDS: Bluestein.  With w[n] = exp(-i pi n^2 / L),
@@ -1958,11 +1981,13 @@ __global__ __launch_bounds__(kBlockWide) void k_bf_chirp(const T* __restrict__ r
   if (status[w] != 0) return;
   const int M0 = N < L ? N : L;
   const T* xs = res + w * (int64_t)N;
+  double xmax = 0.0;
   for (int n = threadIdx.x; n < M; n += blockDim.x) {
     const int r = (int)(__brev((unsigned)n) >> (32 - logM));
     double ar = 0.0, ai = 0.0;
     if (n < M0) {
       const double xv = (double)xs[n];
+      xmax = fmax(xmax, fabs(xv));
       const double2 cs = chirp[n];  // (cos, sin)(pi n^2 / L); w[n] = cos - i sin
       ar = xv * cs.x;
       ai = -xv * cs.y;
@@ -1970,7 +1995,7 @@ __global__ __launch_bounds__(kBlockWide) void k_bf_chirp(const T* __restrict__ r
     re[r] = ar;
     im[r] = ai;
   }
-  __syncthreads();
+  const int e = bf_scale_exp(xmax, wbest);  // (its barrier completes re, im)
   lds_fft_stages(re, im, M, logM, twm);
   // pointwise product with B, conjugated for the inverse transform (ifft(z) = conj(fft(conj(z))) / M), and
   // moved to bit-reversed order: element n and its mirror are handled by the thread that owns min(n, brev(n))
@@ -1995,7 +2020,7 @@ __global__ __launch_bounds__(kBlockWide) void k_bf_chirp(const T* __restrict__ r
   lds_fft_stages(re, im, M, logM, twm);
   // c[k] = conj(result[k]) / M: the magnitudes only differ by the common factor 1 / M (kept out: the record is
   // only compared with the other bins of the same window)
-  bf_store_peak(re, im, L >> 1, wbest, wbestp, w, part_m2, part_k);
+  bf_store_peak(re, im, L >> 1, e, wbest, wbestp, w, part_m2, part_k);
 }
 
 template <typename T, bool LW>

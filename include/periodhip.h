@@ -309,6 +309,14 @@ int ph_qo_plan_info(ph_ctx* ctx, int dtype, int N, int max_length, int kcap, uns
  *                                                                   A kcap whose vectors do not fit the LDS returns
  *                                                                   PH_E_ARG here as at the launch, so the largest
  *                                                                   feasible kcap is found without launching.
+ *   PH_OP_QO_FIT_WIN        {kcap, max period}                       default 512, N   (ph_qo_fit_win).  N enters:
+ *                                                                   PH_PLAN_SECOND says where the staging vector u
+ *                                                                   of N doubles lives -- PH_PLAN_LDS behind the
+ *                                                                   solver's vectors while both fit the workgroup's
+ *                                                                   limit, else PH_PLAN_HBM (always under
+ *                                                                   PH_HBM_WINDOW=1); x and the analysis window are
+ *                                                                   read from HBM / L2 (PH_PLAN_WINDOW =
+ *                                                                   PH_PLAN_HBM).  kcap as PH_OP_QO_FIT.
  * ph_tile_sum and ph_dict_project do not depend on N (LDS of sum(keep) doubles / none) and have no op.
  * out[PH_PLAN_LEN] int32: out[PH_PLAN_KERNELS] kernels launched per call (per round for best_frequency), then one
  * record of PH_PLAN_STRIDE words per kernel at out[PH_PLAN_K0] (m_best step 1, best_frequency spectrum) and
@@ -334,6 +342,7 @@ int ph_qo_plan_info(ph_ctx* ctx, int dtype, int N, int max_length, int kcap, uns
 #define PH_OP_ORTH_POWERS 7
 #define PH_OP_FOLD_SUMS 8
 #define PH_OP_QO_FIT 9
+#define PH_OP_QO_FIT_WIN 10
 #define PH_PLAN_KERNELS 0
 #define PH_PLAN_K0 1
 #define PH_PLAN_K1 9
@@ -380,6 +389,21 @@ int ph_qo_fit(ph_ctx* ctx, const void* x, int dtype, int64_t W, int N,
               const int32_t* periods, const int32_t* n_periods, int pcap, int per_stride, int max_period,
               int kcap, unsigned flags,
               int32_t* keeps, double* weights, void* residual, int32_t* status);
+
+/* ---- the same fit under an analysis window: solve_quadratic(x, A, window=win) (QOPeriods.py:779-796) ------------
+ * (A diag(win)) A^T w = (A diag(win)) x; the reconstruction A^T w and the residual x - A^T w are unwindowed.
+ * window (N) float64, one for the whole batch, follows PH_FLAG_DEVICE like every array; NULL returns PH_E_ARG
+ * (ph_qo_fit is the fit without a window).  Every other argument, the outputs and the status codes are ph_qo_fit's,
+ * with the same conjugate gradients (tolerances, bound 4 K + 100, started from zero) around a product that goes through
+ * a staging vector of N doubles per workgroup: u = win . (A^T v), then the folds A u.  ph_plan_info(PH_OP_QO_FIT_WIN)
+ * says whether u is in LDS or in an HBM workspace of the context.  The Jacobi diagonal is the fold of the window; a row
+ * whose diagonal is not > 0 (window zero or negative over a whole residue class: the reference's matrix is singular
+ * or indefinite) gives PH_ST_ITER_CAP, as does non-positive curvature met by the solve under a window with negative
+ * samples.  Windows that are not PH_ST_OK have zero weights and an unspecified residual. */
+int ph_qo_fit_win(ph_ctx* ctx, const void* x, int dtype, int64_t W, int N, const double* window,
+                  const int32_t* periods, const int32_t* n_periods, int pcap, int per_stride, int max_period,
+                  int kcap, unsigned flags,
+                  int32_t* keeps, double* weights, void* residual, int32_t* status);
 
 /* ---- RamanujanPeriods.find_periods_with_weights (RamanujanPeriods.py:88-122), default test function ----------
  * ph_ramanujan_norms, the threshold (periods = the q with norms[q] / |max(norms)| > thresh, that IEEE division and

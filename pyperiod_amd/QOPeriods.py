@@ -68,6 +68,18 @@ def _to_f64(a):
         return a.astype(np.float64)
 
 
+def _device_window(window, n):
+    """The analysis window as the float64 array ph_qo_fit_win takes, or None when it is not a finite 1-D array of n
+    samples (None and False, the reference's "no window", among them)."""
+    if window is None or window is False:
+        return None
+    try:
+        win = np.ascontiguousarray(window, dtype=np.float64)
+    except (TypeError, ValueError):
+        return None
+    return win if win.shape == (n,) and np.all(np.isfinite(win)) else None
+
+
 class _LazyBases(dict):
     """The output_bases dict of one row of a batched find_periods.  Its "subspaces" entry -- the stacked
     natural-basis rows of the dictionary blocks, rows x N doubles -- is built from the blocks on first read and
@@ -199,7 +211,10 @@ class QOPeriods(Periods):
         Rows whose settings the device loops cover -- default test function, ``thresh`` set, natural basis,
         no analysis window, plain selection, either ``trunc_to_integer_multiple`` and either
         ``update_weights`` -- run in ONE launch of ph_qo_find_periods per batch (float32 batches in the fp32
-        kernels, residuals returned as float64).  Everything else (custom ``test_function``, ``window``,
+        kernels, residuals returned as float64).  Under an analysis window (``self.window`` a finite 1-D array
+        of N samples) the same settings with ``update_weights=True`` run a batched greedy loop stepped from the host
+        (``_find_periods_window_batch``: one ph_sweep and one ph_qo_fit_win launch per round);
+        ``update_weights=False`` with a window stays on the 1-D path.  Everything else (custom ``test_function``,
         Ramanujan basis, ``orthogonalize``, ``verbose``, ``thresh=None``) and every row the kernels hand back
         with a fallback status or a dictionary beyond the device's capacity runs the 1-D call on that row;
         all-zero rows get the reference's fixed answer.
@@ -209,11 +224,18 @@ class QOPeriods(Periods):
         of the 1-D result."""
         W, N = data.shape
         windowed = not (self.window is None or self.window is False)
-        on_device = (
+        on_device_settings = (
             kwargs.get("test_function") is None and thresh is not None and not self._orthogonalize
-            and self._basis_type == "natural" and not windowed and not self._verbose
+            and self._basis_type == "natural" and not self._verbose
         )
+        on_device = on_device_settings and not windowed
         out = [None] * W
+        win = _device_window(self.window, N) if windowed else None
+        if win is not None and update_weights and on_device_settings and W > 0:
+            ml = int(np.floor(N / 3)) if max_length is None else int(max_length)
+            n = N if num is None else int(num)
+            x = np.ascontiguousarray(data, dtype=np.float64)
+            out = self._find_periods_window_batch(default_engine(), x, win, n, thresh, int(min_length), ml)
         if on_device and W > 0:
             x = data if data.dtype in (np.float32, np.float64) else data.astype(np.float64)
             x = np.ascontiguousarray(x)
@@ -278,6 +300,69 @@ class QOPeriods(Periods):
                 break
             kcap, todo = nxt, todo[grow]
         return results
+
+    def _find_periods_window_batch(self, eng, x, win, num, thresh, min_length, max_length):
+        """The greedy loop under the analysis window `win` for the float64 batch `x`, stepped from the host: per round
+        one ph_sweep launch (gamma norms of the residuals of the rows still active, the selection rule of
+        ``_strongest_period``) and one ph_qo_fit_win launch (those rows, each with its list so far), instead of one
+        dense dictionary, two uploads of it and a host solve per row and round.  A row stops when
+        ``rms(reconstruction) > rms(data) * thresh`` fails -- its result is the last fit with one period fewer
+        reported (QOPeriods.py:560-594) -- when no gamma norm is positive, or after `num` rounds.
+        -> per row (output_bases, residual), or None: the row is rerun whole by the 1-D call (all-zero rows, a fit that
+        came back not PH_ST_OK -- a block without rows, an indefinite matrix, more than 64 periods, a dictionary beyond
+        the largest feasible capacity)."""
+        W, N = x.shape
+        trunc = bool(self._trunc_to_integer_multiple)
+        out = [None] * W
+        if max_length < min_length or min_length < 1:
+            return out
+        per = np.zeros((W, 64), dtype=np.int32)
+        counts = np.zeros(W, dtype=np.int32)
+        gnorm = np.zeros((W, 64))
+        fits = [None] * W  # (blocks, weights, residual) of the row's last fit
+        res = x.copy()
+        rms_data = np.sqrt(np.sum(x * x, axis=1) / N)
+        active = np.flatnonzero(np.sum(np.abs(x), axis=1) > 1e-16)  # (QOPeriods.py:394-406: the 1-D call's fixed answer)
+
+        def finish(w, n_report):
+            blocks, wts, resid = fits[w]
+            out[w] = (_LazyBases(blocks, N, self._basis_type, periods=per[w, :n_report].astype(np.uint32),
+                                 norms=gnorm[w, :n_report].copy(), weights=wts,
+                                 basis_dictionary={str(q): k for q, k in blocks}), resid)
+
+        for i in range(num):
+            if i > 0:  # the test function on the reconstruction of the last fit
+                rec = x[active] - res[active]
+                go = np.sqrt(np.sum(rec * rec, axis=1) / N) > rms_data[active] * thresh
+                for w in active[~go]:
+                    finish(w, int(counts[w]) - 1)
+                active = active[go]
+            if active.size == 0:
+                break
+            vals = eng.sweep(np.ascontiguousarray(res[active]), min_length, max_length, _ffi.PH_SWEEP_NORM_GAMMA, trunc, False)
+            order = np.where(np.isnan(vals), -np.inf, vals)
+            k = np.argmax(order, axis=1)
+            found = order[np.arange(active.size), k] > 0
+            for w in active[~found]:  # no period left: every later round repeats this one
+                if fits[w] is not None:
+                    finish(w, int(counts[w]))
+            found &= counts[active] < 64  # (a 65th period: the 1-D call)
+            active, k, vals = active[found], k[found], vals[found]
+            if active.size == 0:
+                break
+            per[active, counts[active]] = min_length + k
+            gnorm[active, counts[active]] = vals[np.arange(active.size), k]
+            counts[active] += 1
+            fit = self._fit_lists_device(eng, np.ascontiguousarray(x[active]), np.ascontiguousarray(per[active]),
+                                         np.ascontiguousarray(counts[active]), max_length, window=win)
+            for w, r in zip(active, fit):
+                if r is not None:
+                    fits[w] = r
+                    res[w] = r[2]
+            active = active[np.array([r is not None for r in fit], dtype=bool)]
+        for w in active:
+            finish(w, int(counts[w]))
+        return out
 
     def _strongest_period(self, eng, res, found, min_length, max_length, update_weights):
         """(period, gamma norm) of the residual `res`; period 0 = stop (QOPeriods.py:425-478)."""
@@ -470,13 +555,17 @@ class QOPeriods(Periods):
         A = np.vstack(blocks) if blocks else np.array([]).reshape((0, N))
         return (A, d)
 
-    def _fit_lists_device(self, eng, x, per, counts, max_period, first=None):
+    def _fit_lists_device(self, eng, x, per, counts, max_period, first=None, window=None):
         """Fit the period lists per[w, :counts[w]] (int32, at most 64 columns) to the rows of the float32 / float64 batch
-        `x` with ph_qo_fit.  `first` = (kcap, keeps, weights, residual, status) of a launch that already ran on these
-        lists (ph_ramanujan_fit).  Capacity grows by re-running only the PH_ST_CAP rows while the plan query says the
-        larger kcap fits.  -> per row None (the caller runs its 1-D call) or (blocks, weights, float64 residual)."""
+        `x` with ph_qo_fit, or under the float64 analysis window `window` (N) with ph_qo_fit_win.  `first` = (kcap,
+        keeps, weights, residual, status) of a launch that already ran on these lists (ph_ramanujan_fit).  Capacity grows
+        by re-running only the PH_ST_CAP rows while the plan query says the larger kcap fits.  -> per row None (the
+        caller runs its 1-D call) or (blocks, weights, float64 residual)."""
         W, N = x.shape
         out = [None] * W
+
+        def feasible(kcap):
+            return eng.qo_fit_feasible(kcap, max_period, N, window is not None)
 
         def take(todo, kcap, keeps, wts, resid, st):
             if resid.dtype != np.float64:
@@ -491,43 +580,45 @@ class QOPeriods(Periods):
 
         if first is None:
             kcap = 512
-            while kcap > 64 and not eng.qo_fit_feasible(kcap, max_period):
+            while kcap > 64 and not feasible(kcap):
                 kcap //= 2
-            if not eng.qo_fit_feasible(kcap, max_period):
+            if not feasible(kcap):
                 return out
             todo = np.arange(W)
-            todo = take(todo, kcap, *eng.qo_fit(x, per, counts, kcap, max_period))
+            todo = take(todo, kcap, *eng.qo_fit(x, per, counts, kcap, max_period, window))
         else:
             kcap = first[0]
             todo = take(np.arange(W), *first)
         while todo.size:
             nxt = 2 * kcap
-            if not eng.qo_fit_feasible(nxt, max_period):  # the last feasible capacity below the doubling, in steps of 64
+            if not feasible(nxt):  # the last feasible capacity below the doubling, in steps of 64
                 lo, hi = kcap // 64, nxt // 64
                 while hi - lo > 1:
                     mid = (lo + hi) // 2
-                    lo, hi = (mid, hi) if eng.qo_fit_feasible(64 * mid, max_period) else (lo, mid)
+                    lo, hi = (mid, hi) if feasible(64 * mid) else (lo, mid)
                 nxt = 64 * lo
             if nxt <= kcap:
                 break
             kcap = nxt
             todo = take(todo, kcap, *eng.qo_fit(np.ascontiguousarray(x[todo]), np.ascontiguousarray(per[todo]),
-                                                np.ascontiguousarray(counts[todo]), kcap, max_period))
+                                                np.ascontiguousarray(counts[todo]), kcap, max_period, window))
         return out
 
     def _compute_reconstruction_batch(self, x, periods, type, window):
         """compute_reconstruction over a (W, N) batch: `periods` is one list for every row or a list of W lists.  A list
         of W ``(reconstruction, output_bases)`` tuples (``None`` where the 1-D call returns ``None``), each what the 1-D
-        call on that row returns.  Natural basis without an analysis window: one ph_qo_fit launch per batch (float32
-        batches in the fp32 kernel), ``subspaces`` built on first read; rows the kernel hands back (singular or
-        ill-conditioned dictionaries, more than 64 periods or more rows than the LDS holds) and every other setting run
-        the 1-D call on the row."""
+        call on that row returns.  Natural basis: one launch per batch -- ph_qo_fit without an analysis window
+        (``window=None``), ph_qo_fit_win under one (a finite 1-D array of N samples) -- float32 batches in the fp32
+        kernel, ``subspaces`` built on first read; rows the kernel hands back (singular, indefinite or ill-conditioned
+        dictionaries, more than 64 periods or more rows than the LDS holds) and every other setting (``window=False``
+        among them) run the 1-D call on the row.  ``type`` only reaches the 1-D calls."""
         W, N = x.shape
         per_row = len(periods) == W and W > 0 and all(np.ndim(p) == 1 for p in periods)
         lists = [periods[w] if per_row else periods for w in range(W)]
         out = [None] * W
         done = [False] * W
-        if window is None and self._basis_type == "natural" and W > 0:
+        win = _device_window(window, N)
+        if (window is None or win is not None) and self._basis_type == "natural" and W > 0:
             xs = np.ascontiguousarray(x if x.dtype in (np.float32, np.float64) else x.astype(np.float64))
             arrs = [np.asarray(p).astype(np.int64).reshape(-1) for p in lists]
             counts = np.array([a.size for a in arrs], dtype=np.int32)
@@ -536,7 +627,7 @@ class QOPeriods(Periods):
                 per[w, : min(a.size, 64)] = np.clip(a[:64], -1, (1 << 20) + 1)  # (out-of-range entries stay out of range)
             max_period = int(min(max(1, per.max()), 1 << 20))
             x64 = xs if xs.dtype == np.float64 else _to_f64(xs)
-            for w, r in enumerate(self._fit_lists_device(default_engine(), xs, per, counts, max_period)):
+            for w, r in enumerate(self._fit_lists_device(default_engine(), xs, per, counts, max_period, window=win)):
                 if r is None:
                     continue
                 blocks, wts, resid = r

@@ -842,6 +842,20 @@ int plan_qo_fit(const ph_ctx* c, int kcap, int max_period, Plan* pl) {
   return PH_OK;
 }
 
+// k_qo_fit_win: k_qo_fit's LDS plus the staging vector u of N doubles (ph::qo_fit_win_lds_bytes, the layout the kernel
+// carves).  u stays in LDS behind the solver while both fit the workgroup's limit and PH_HBM_WINDOW is not set; otherwise
+// it takes N doubles per workgroup of an HBM workspace (`second`).  The analysis window is shared by the grid and is
+// always read from HBM / L2, as x is (`window`).
+int plan_qo_fit_win(const ph_ctx* c, int N, int kcap, int max_period, Plan* pl) {
+  PH_TRY(plan_qo_fit(c, kcap, max_period, pl));
+  KernelPlan& k = pl->k[0];
+  const bool u_lds = !c->hbm_window && ph::qo_fit_win_lds_bytes(N, kcap, max_period, true) <= (size_t)c->lds_limit;
+  k.lds = ph::qo_fit_win_lds_bytes(N, kcap, max_period, u_lds);
+  k.second = u_lds ? PH_PLAN_LDS : PH_PLAN_HBM;
+  k.block = ph::qo_fit_win_block(kcap, N);
+  return PH_OK;
+}
+
 }  // namespace
 
 
@@ -1198,6 +1212,9 @@ int ph_plan_info(ph_ctx* c, int op, int dtype, int N, const int32_t* params, int
       break;
     case PH_OP_QO_FIT:
       PH_TRY(plan_qo_fit(c, prm(0, 512), prm(1, N), &pl));
+      break;
+    case PH_OP_QO_FIT_WIN:
+      PH_TRY(plan_qo_fit_win(c, N, prm(0, 512), prm(1, N), &pl));
       break;
     default:
       return fail(PH_E_ARG, "op %d unknown", op);
@@ -2090,9 +2107,12 @@ struct FitLaunch {
   const int *d_phi = nullptr, *d_off = nullptr, *d_dq = nullptr;
 };
 
-static int fit_prepare(ph_ctx* c, int pcap, int max_period, int kcap, FitLaunch* fl) {
+static int fit_prepare(ph_ctx* c, int N, bool windowed, int pcap, int max_period, int kcap, FitLaunch* fl) {
   if (pcap < 1 || pcap > (1 << 20)) return fail(PH_E_ARG, "pcap=%d must be in [1, 2^20]", pcap);
-  PH_TRY(plan_qo_fit(c, kcap, max_period, &fl->pl));
+  if (windowed)
+    PH_TRY(plan_qo_fit_win(c, N, kcap, max_period, &fl->pl));
+  else
+    PH_TRY(plan_qo_fit(c, kcap, max_period, &fl->pl));
   std::vector<int32_t> phi, off, dq;
   divisor_tables(max_period, &phi, &off, &dq);
   PH_TRY(upload_table(c, T_FIT_PHI, phi.data(), phi.size(), &fl->d_phi));
@@ -2121,31 +2141,73 @@ static int fit_enqueue(ph_ctx* c, const FitLaunch& fl, int dtype, int64_t W, int
   return launch_check("k_qo_fit");
 }
 
-int ph_qo_fit(ph_ctx* c, const void* x, int dtype, int64_t W, int N, const int32_t* periods, const int32_t* n_periods,
-              int pcap, int per_stride, int max_period, int kcap, unsigned flags, int32_t* keeps, double* weights,
-              void* residual, int32_t* status) {
+// k_qo_fit_win: `dwin` the analysis window on the device, `dws` the HBM workspace of u (nullptr when the plan keeps u in LDS)
+static int fit_win_enqueue(ph_ctx* c, const FitLaunch& fl, int dtype, int64_t W, int N, const void* dx, const double* dwin,
+                           const int* dper, const int* dnper, int pcap, int per_stride, int max_period, int kcap,
+                           double* dws, void* dkeep, void* dwts, void* dres, void* dstat) {
+  const KernelPlan& k = fl.pl.k[0];
+  const dim3 grid((unsigned)W);
+  PH_TRY(dispatch(dtype, k.second == PH_PLAN_LDS, [&](auto t, auto ul) {
+    using T = decltype(t);
+    auto kernel = ph::k_qo_fit_win<T, decltype(ul)::value>;
+    PH_TRY(allow_lds(kernel, k.lds));
+    ProfScope ps_(c, "k_qo_fit_win");
+    hipLaunchKernelGGL(kernel, grid, dim3(k.block), k.lds, c->stream, (const T*)dx, N, dwin, dper, dnper, pcap, per_stride,
+                       max_period, fl.d_phi, fl.d_off, fl.d_dq, kcap, dws, (int*)dkeep, (double*)dwts, (T*)dres, (int*)dstat);
+    return (int)PH_OK;
+  }));
+  return launch_check("k_qo_fit_win");
+}
+
+// ph_qo_fit (window == nullptr) and ph_qo_fit_win: one set of argument checks, tables and staging
+static int qo_fit_run(ph_ctx* c, const void* x, int dtype, int64_t W, int N, const double* window, const int32_t* periods,
+                      const int32_t* n_periods, int pcap, int per_stride, int max_period, int kcap, unsigned flags,
+                      int32_t* keeps, double* weights, void* residual, int32_t* status) {
   PH_TRY(check_common(c, x, dtype, W, N));
   if (!periods || !n_periods) return fail(PH_E_ARG, "periods / n_periods is NULL");
   if (!keeps || !weights || !residual || !status) return fail(PH_E_ARG, "output pointer is NULL");
   if (per_stride != 0 && per_stride < pcap) return fail(PH_E_ARG, "per_stride=%d must be 0 (one shared list) or >= pcap=%d", per_stride, pcap);
   PH_HIP(hipSetDevice(c->device));
   FitLaunch fl;
-  PH_TRY(fit_prepare(c, pcap, max_period, kcap, &fl));
+  PH_TRY(fit_prepare(c, N, window != nullptr, pcap, max_period, kcap, &fl));
   const size_t sz = elem_size(dtype);
   const size_t lists = per_stride ? (size_t)W : 1;
   Stage st(c, flags);
-  const void *dx, *dper, *dnper;
-  void *dkeep, *dwts, *dres, *dstat;
+  const void *dx, *dper, *dnper, *dwin = nullptr;
+  void *dkeep, *dwts, *dres, *dstat, *dws = nullptr;
   PH_TRY(st.in(x, (size_t)W * N * sz, &dx));
   PH_TRY(st.in(periods, ((lists - 1) * (size_t)per_stride + pcap) * sizeof(int32_t), &dper, B_GBUF));
   PH_TRY(st.in(n_periods, lists * sizeof(int32_t), &dnper, B_WS1));
+  if (window) {
+    PH_TRY(st.in(window, (size_t)N * sizeof(double), &dwin, B_GWIN));
+    PH_TRY(place(c, fl.pl.k[0].second, B_OUT0, (size_t)W * N * sizeof(double), &dws));
+  }
   PH_TRY(st.out(B_OUT3, keeps, (size_t)W * pcap * sizeof(int32_t), &dkeep));
   PH_TRY(st.out(B_OUT4, weights, (size_t)W * kcap * sizeof(double), &dwts));
   PH_TRY(st.out(B_WS0, residual, (size_t)W * N * sz, &dres));
   PH_TRY(st.out(B_GEN0, status, (size_t)W * sizeof(int32_t), &dstat));
-  PH_TRY(fit_enqueue(c, fl, dtype, W, N, dx, (const int*)dper, (const int*)dnper, pcap, per_stride, max_period, kcap, dkeep,
-                     dwts, dres, dstat));
+  if (window)
+    PH_TRY(fit_win_enqueue(c, fl, dtype, W, N, dx, (const double*)dwin, (const int*)dper, (const int*)dnper, pcap, per_stride,
+                           max_period, kcap, (double*)dws, dkeep, dwts, dres, dstat));
+  else
+    PH_TRY(fit_enqueue(c, fl, dtype, W, N, dx, (const int*)dper, (const int*)dnper, pcap, per_stride, max_period, kcap, dkeep,
+                       dwts, dres, dstat));
   return st.finish();
+}
+
+int ph_qo_fit(ph_ctx* c, const void* x, int dtype, int64_t W, int N, const int32_t* periods, const int32_t* n_periods,
+              int pcap, int per_stride, int max_period, int kcap, unsigned flags, int32_t* keeps, double* weights,
+              void* residual, int32_t* status) {
+  return qo_fit_run(c, x, dtype, W, N, nullptr, periods, n_periods, pcap, per_stride, max_period, kcap, flags, keeps, weights,
+                    residual, status);
+}
+
+int ph_qo_fit_win(ph_ctx* c, const void* x, int dtype, int64_t W, int N, const double* window, const int32_t* periods,
+                  const int32_t* n_periods, int pcap, int per_stride, int max_period, int kcap, unsigned flags,
+                  int32_t* keeps, double* weights, void* residual, int32_t* status) {
+  if (!window) return fail(PH_E_ARG, "ph_qo_fit_win: window is NULL (ph_qo_fit fits without a window)");
+  return qo_fit_run(c, x, dtype, W, N, window, periods, n_periods, pcap, per_stride, max_period, kcap, flags, keeps, weights,
+                    residual, status);
 }
 
 int ph_ramanujan_fit(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int q_lo, int q_hi, double thresh, int pcap,
@@ -2158,7 +2220,7 @@ int ph_ramanujan_fit(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int 
   if (q_lo < 1 || q_hi < 1) return fail(PH_E_ARG, "need q_lo, q_hi >= 1 (got %d, %d)", q_lo, q_hi);
   PH_HIP(hipSetDevice(c->device));
   FitLaunch fl;
-  PH_TRY(fit_prepare(c, pcap, q_hi, kcap, &fl));
+  PH_TRY(fit_prepare(c, N, false, pcap, q_hi, kcap, &fl));
   RamLaunch rl;
   PH_TRY(ram_prepare(c, dtype, W, N, q_lo, q_hi, &rl));
   const size_t sz = elem_size(dtype);

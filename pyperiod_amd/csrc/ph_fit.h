@@ -1,7 +1,8 @@
 // Fit of a GIVEN period list (QOPeriods.compute_reconstruction, RamanujanPeriods.find_periods_with_weights) on the
 // device: k_qo_fit runs get_subspaces' row bookkeeping, the right-hand side by folds and the matrix-free conjugate
-// gradients of k_qo_find for a list it is handed instead of one it selects greedily; k_ram_select turns Ramanujan norms
-// into that list.  Included by period_hip.hip behind ph_kernels.h.  Reference citations are file:line into
+// gradients of k_qo_find for a list it is handed instead of one it selects greedily; k_qo_fit_win is the same fit under an
+// analysis window (its product goes through a staged sample-length vector); k_ram_select turns Ramanujan norms into that
+// list.  Included by period_hip.hip behind ph_kernels.h.  Reference citations are file:line into
 // /root/reference/pyPeriod/.
 #pragma once
 
@@ -356,6 +357,305 @@ __global__ __launch_bounds__(1024) void k_qo_fit(const T* __restrict__ x, int N,
     wout[r] = xv[r + a];
   }
   // ---- reconstruction A^T w (QOPeriods.py:795) in row order, residual in the dtype of x
+  for (int n = tid; n < N; n += blockDim.x) {
+    double rec = 0.0;
+    for (int b = 0; b < nblk; ++b) {
+      const int i = n % bper[b];
+      if (i < bkeep[b]) rec += xv[boff[b] + b + i];
+    }
+    resid_out[w * (int64_t)N + n] = (T)((double)data[n] - rec);
+  }
+  if (tid == 0) status_out[w] = 0;
+}
+
+// ======================================================================================
+// k_qo_fit_win: k_qo_fit under an analysis window (solve_quadratic(x, A, window=win), QOPeriods.py:779-796):
+//   (A diag(win)) A^T w = (A diag(win)) x, reconstruction A^T w and residual x - A^T w unwindowed.
+// Dynamic LDS, the one statement of its layout: k_qo_fit's (qo_fit_lds_bytes: bookkeeping, the solver's vectors with the
+// divisor bitset overlaying them), then the staging vector u of N doubles when it lives in LDS.  The host places u in
+// LDS when that still fits the workgroup's limit and otherwise in an HBM workspace of N doubles per workgroup; win is
+// shared by the whole grid and is always read from HBM / L2.
+// ======================================================================================
+__host__ __device__ inline size_t qo_fit_win_u_offset(int kcap, int max_period) { return qo_fit_lds_bytes(kcap, max_period); }
+__host__ __device__ inline size_t qo_fit_win_lds_bytes(int N, int kcap, int max_period, bool u_in_lds) {
+  return qo_fit_win_u_offset(kcap, max_period) + (u_in_lds ? carve_bytes((size_t)N, 8) : 0);
+}
+// Threads per workgroup: the staging pass is one element of u per thread and step, so long windows take wide workgroups.
+__host__ __device__ inline int qo_fit_win_block(int kcap, int N) {
+  const int solver = qo_fit_block(kcap), stage = N > 4096 ? 1024 : N > 1024 ? 512 : 256;
+  return solver > stage ? solver : stage;
+}
+
+// A diag(win) A^T has no closed-form sample counts, so the product goes through u (sample length), matrix-free:
+//   stage:  u[n] = win[n] * sum_b v[b, n mod p_b] over the blocks with n mod p_b < keep_b   (win . A^T v)
+//   fold:   out[a, i] = sum_r u[i + r p_a]                                                  (A u)
+// Both passes put the lanes of a wavefront on consecutive n.  The stage takes four elements of u per thread, a workgroup
+// width apart, so that a thread divides once per block and steps the residue from there.  The fold is row r of the
+// fold with the lanes over the residues: a block of period >= 64 is cut into 64-residue work items, one fold row per
+// step; a block of period p < 64 is one work item that folds 64 / P rows per step (P = p rounded up to a power of two,
+// lane = row * P + residue, all p residues folded and keep stored), the rows' lanes then combine by butterfly.  The
+// active lanes of either 32-lane half read distinct, adjacent doubles: no LDS bank is hit twice.  The right-hand side
+// A (win . x) and the Jacobi diagonal sum_r win[i + r p_a] are the same fold of u = win . x and u = win.
+// Status as k_qo_fit; a row whose diagonal is not > 0 ends the window with status 2 (the reference's matrix is then
+// singular or indefinite).  ULDS: u is the LDS behind the solver, else ws + blockIdx.x * N.  Every loop is bounded;
+// nothing waits on anything outside the workgroup.
+template <typename T, bool ULDS>
+__global__ __launch_bounds__(1024) void k_qo_fit_win(const T* __restrict__ x, int N, const double* __restrict__ win,
+                                                     const int* __restrict__ periods, const int* __restrict__ n_periods,
+                                                     int pcap, int per_stride, int max_period,
+                                                     const int* __restrict__ phi, const int* __restrict__ div_off,
+                                                     const int* __restrict__ div_q, int kcap, double* __restrict__ ws,
+                                                     int* __restrict__ keeps_out, double* __restrict__ weights_out,
+                                                     T* __restrict__ resid_out, int* __restrict__ status_out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  Carve cv(smem);
+  double* red = cv.take<double>(kRedDoubles);
+  double* red3 = cv.take<double>(6 * kMaxWaves);  // wave partials of the solver's fused reduction (two parities)
+  int* bper = cv.take<int>(kQoMaxBlocks + 1);     // period of dictionary block b
+  int* bkeep = cv.take<int>(kQoMaxBlocks + 1);    // rows kept for it
+  int* boff = cv.take<int>(kQoMaxBlocks + 1);     // first row of block b
+  int* ioff = cv.take<int>(kQoMaxBlocks + 1);     // first fold work item of block b
+  cv.take<int>(kQoMaxBlocks);                     // (k_qo_fit's lane split and pair table: not used here)
+  cv.take<int>(kQoMaxBlocks);
+  cv.take<int>(2 * kQoPairTab * kQoPairTab);
+  int* ctl = cv.take<int>(kFitCtl);
+  // the divisor bitset (bookkeeping only) and the solver's vectors share what follows
+  uint32_t* seen = reinterpret_cast<uint32_t*>(cv.base + cv.off);
+  const int kv = kcap + kQoMaxBlocks;
+  double* xv = cv.take<double>(kv);   // weights, solver layout: block b's k_b entries at boff[b] + b, then one zero
+  double* rv = cv.take<double>(kv);   // residual of the normal equations (starts as A (win . x))
+  double* pv = cv.take<double>(kv);   // search direction
+  double* qv = cv.take<double>(kv);   // A diag(win) A^T pv
+  double* zv = cv.take<double>(kv);   // preconditioned residual
+  double* wv_ = cv.take<double>(kv);  // A diag(win) A^T zv
+  double* dv = cv.take<double>(kv);   // 1 / diagonal = 1 / fold of the window (Jacobi preconditioner)
+
+  const int64_t w = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int lane = tid & (kWave - 1);
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int nw = blockDim.x >> 6;
+  const T* data = x + w * (int64_t)N;
+  const int* list = periods + (per_stride ? w * (int64_t)per_stride : 0);
+  const int n_list = n_periods[per_stride ? w : 0];
+  int* keeps_row = keeps_out + w * (int64_t)pcap;
+  double* wout = weights_out + w * (int64_t)kcap;
+  double* u;
+  if constexpr (ULDS) {
+    u = reinterpret_cast<double*>(smem + qo_fit_win_u_offset(kcap, max_period));
+  } else {
+    u = ws + w * (int64_t)N;
+  }
+
+  for (int k = tid; k < pcap; k += blockDim.x) keeps_row[k] = 0;
+  for (int r = tid; r < kcap; r += blockDim.x) wout[r] = 0.0;
+  int status = 0;
+  if (n_list <= 0) status = 1;
+  if (n_list > pcap || n_list > kQoMaxBlocks) status = 3;
+  if (status != 0) {  // (uniform over the workgroup)
+    if (tid == 0) status_out[w] = status;
+    return;
+  }
+  for (int k = tid; k < (max_period + 32) / 32; k += blockDim.x) seen[k] = 0u;
+  __syncthreads();
+  // ---- rows each period contributes (QOPeriods.py:830-840): one wavefront, the lanes over the divisors
+  if (wv == 0) {
+    int st = 0, rows = 0, items = 0;
+    for (int b = 0; b < n_list; ++b) {
+      const int p = list[b];
+      if (p < 1 || p > max_period) {  // (uniform)
+        st = 2;
+        break;
+      }
+      const int d0 = div_off[p], d1 = div_off[p + 1];
+      double mass = 0.0;
+      for (int k = d0 + lane; k < d1; k += kWave) {
+        const int r = div_q[k];
+        if (!((seen[r >> 5] >> (r & 31)) & 1u)) mass += (double)phi[r];
+      }
+      const int keep = (int)wave_sum(mass);  // (exact: the mass of all divisors of p is p)
+      ram_wave_sync();
+      for (int k = d0 + lane; k < d1; k += kWave) {
+        const int r = div_q[k];
+        atomicOr(&seen[r >> 5], 1u << (r & 31));
+      }
+      ram_wave_sync();
+      if (lane == 0) {
+        bper[b] = p;
+        bkeep[b] = keep;
+        boff[b] = rows;
+        ioff[b] = items;
+        keeps_row[b] = keep;
+      }
+      if (keep == 0 || keep > N) st = 2;
+      rows += keep;  // (<= 64 * 2^20: no overflow)
+      items += p < kWave ? 1 : (keep + kWave - 1) / kWave;
+    }
+    if (st == 0 && rows > N) st = 2;  // more rows than samples: rank(A diag(win) A^T) <= N, singular
+    if (st == 0 && rows > kcap) st = 3;
+    if (lane == 0) {
+      boff[n_list] = rows;
+      ioff[n_list] = items;
+      ctl[0] = st;
+      ctl[1] = rows;
+      ctl[3] = 0;
+    }
+  }
+  __syncthreads();
+  status = ctl[0];
+  if (status != 0) {
+    if (tid == 0) status_out[w] = status;
+    return;
+  }
+  const int nblk = n_list;
+  const int K = ctl[1];
+  const int KS = K + nblk;  // slots
+  __syncthreads();          // the bitset is dead: the vectors take its place
+  for (int sl = tid; sl < KS; sl += blockDim.x) {
+    xv[sl] = 0.0;
+    rv[sl] = 0.0;
+    zv[sl] = 0.0;  // (the fold never writes the pad slots)
+    wv_[sl] = 0.0;
+    qv[sl] = 0.0;
+    pv[sl] = 0.0;
+    dv[sl] = 0.0;
+  }
+  // A u: consume(slot, sum_r u[i + r p_a]) for every row; the caller's barrier has published u
+  auto fold_u = [&](auto&& consume) {
+    const int nitems = ioff[nblk];
+    for (int it = wv; it < nitems; it += nw) {
+      int a = 0;
+      while (a + 1 < nblk && ioff[a + 1] <= it) ++a;
+      const int p = bper[a], keep = bkeep[a], s0 = boff[a] + a;
+      int lg = 6;  // log2 of the lanes one fold row takes
+      if (p < kWave) {
+        lg = 0;
+        while ((1 << lg) < p) ++lg;
+      }
+      const int i = p < kWave ? (lane & ((1 << lg) - 1)) : (it - ioff[a]) * kWave + lane;
+      const int64_t stride = (int64_t)p << (6 - lg);
+      double acc = 0.0;
+      if (i < (p < kWave ? p : keep))
+        for (int64_t n = i + (int64_t)(lane >> lg) * p; n < N; n += stride) acc += u[n];
+      for (int off = 1 << lg; off < kWave; off <<= 1) acc += __shfl_xor(acc, off, kWave);  // (uniform trip count)
+      if ((lane >> lg) == 0 && i < keep) consume(s0 + i, acc);
+    }
+  };
+  // ---- Jacobi diagonal: the fold of the window itself
+  for (int n = tid; n < N; n += blockDim.x) u[n] = win[n];
+  __syncthreads();
+  fold_u([&](int sl, double s) {
+    if (s > 0.0)
+      dv[sl] = 1.0 / s;
+    else
+      ctl[3] = 1;  // (every writer stores the same value)
+  });
+  __syncthreads();
+  if (ctl[3] != 0) {
+    if (tid == 0) status_out[w] = 2;
+    return;
+  }
+  // ---- right-hand side A (win . x) (QOPeriods.py:781-782)
+  for (int n = tid; n < N; n += blockDim.x) u[n] = win[n] * (double)data[n];
+  __syncthreads();
+  fold_u([&](int sl, double s) { rv[sl] = s; });
+  __syncthreads();
+  // ---- A diag(win) A^T w = A (win . x): k_qo_fit's single-reduction recurrence around the staged product
+  double dg = 0.0, dd = 0.0, dr = 0.0;
+  auto gram_apply = [&](const double* __restrict__ vv, double* __restrict__ out) {
+    for (int base = 0; base < N; base += 4 * (int)blockDim.x) {
+      double acc[4] = {0.0, 0.0, 0.0, 0.0};
+      for (int b = 0; b < nblk; ++b) {
+        const int p = bper[b], keep = bkeep[b], step = (int)blockDim.x % p;
+        const double* vb = vv + boff[b] + b;
+        int r = (base + tid) % p;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          if (r < keep) acc[c] += vb[r];
+          r += step;
+          r -= r >= p ? p : 0;
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const int n = base + tid + c * (int)blockDim.x;
+        if (n < N) u[n] = win[n] * acc[c];
+      }
+    }
+    __syncthreads();
+    fold_u([&](int sl, double wrow) {
+      const double z = vv[sl];
+      out[sl] = wrow;
+      const double t = rv[sl];
+      dg = fma(t, z, dg);
+      dd = fma(wrow, z, dd);
+      dr = fma(t, t, dr);
+    });
+  };
+  bool failed = false;
+  int iter = 0;
+  {
+    double bb = 0.0;
+    for (int r = tid; r < KS; r += blockDim.x) {  // start from zero: the residual is the right-hand side
+      const double t = rv[r];
+      zv[r] = t * dv[r];
+      bb = fma(t, t, bb);
+    }
+    bb = block_sum(bb, red);  // (its barriers also publish zv)
+    const double tol = sizeof(T) == 4 ? 1e-9 : 1e-13;
+    const double tol2 = tol * tol * bb;
+    const int itmax = 4 * K + 100;
+    double gamma_old = 0.0, alpha = 0.0, rr = 1.0 / 0.0;
+    for (;; ++iter) {
+      dg = dd = dr = 0.0;
+      gram_apply(zv, wv_);
+      double* part = red3 + (iter & 1) * 3 * kMaxWaves;
+      const double sg = wave_sum(dg), sd = wave_sum(dd), sr = wave_sum(dr);
+      if (lane == 0) {
+        part[wv] = sg;
+        part[kMaxWaves + wv] = sd;
+        part[2 * kMaxWaves + wv] = sr;
+      }
+      __syncthreads();
+      const double g = uniform_f64(red_combine(part, nw)), d = uniform_f64(red_combine(part + kMaxWaves, nw));
+      rr = uniform_f64(red_combine(part + 2 * kMaxWaves, nw));
+      if (rr <= tol2 || iter >= itmax) break;
+      const double beta = iter == 0 ? 0.0 : g / gamma_old;
+      const double denom = iter == 0 ? d : d - beta * g / alpha;
+      if (!(denom > 0.0) || !(g > 0.0)) {  // not positive definite: conjugate gradients do not apply, the host solves
+        failed = true;
+        break;
+      }
+      alpha = g / denom;
+      gamma_old = g;
+      for (int r = tid; r < KS; r += blockDim.x) {
+        const double pn = fma(beta, iter == 0 ? 0.0 : pv[r], zv[r]);
+        const double qn = fma(beta, iter == 0 ? 0.0 : qv[r], wv_[r]);
+        pv[r] = pn;
+        qv[r] = qn;
+        xv[r] = fma(alpha, pn, xv[r]);
+        const double t = fma(-alpha, qn, rv[r]);
+        rv[r] = t;
+        zv[r] = t * dv[r];
+      }
+      __syncthreads();
+    }
+    if (!(rr <= tol2)) failed = true;  // not finite, or the bound was hit: the host path solves as the reference does
+  }
+#ifdef PH_FIT_TIMERS
+  if (w < 64 && tid == 0) printf("qo_fit_win window %d: blocks %d rows %d cg iterations %d %s\n", (int)w, nblk, K, iter, failed ? "FAILED" : "ok");
+#endif
+  __syncthreads();
+  if (failed) {
+    if (tid == 0) status_out[w] = 2;
+    return;
+  }
+  for (int r = tid; r < K; r += blockDim.x) {
+    int a = 0;
+    while (a + 1 < nblk && boff[a + 1] <= r) ++a;
+    wout[r] = xv[r + a];
+  }
+  // ---- reconstruction A^T w (QOPeriods.py:795), unwindowed, in row order; residual in the dtype of x
   for (int n = tid; n < N; n += blockDim.x) {
     double rec = 0.0;
     for (int b = 0; b < nblk; ++b) {

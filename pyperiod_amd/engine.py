@@ -420,7 +420,8 @@ class PeriodEngine:
     _PLAN_OPS = {"project": _ffi.PH_OP_PROJECT, "sweep": _ffi.PH_OP_SWEEP, "m_best": _ffi.PH_OP_M_BEST,
                  "small_to_large": _ffi.PH_OP_SMALL_TO_LARGE, "best_correlation": _ffi.PH_OP_BEST_CORRELATION,
                  "best_frequency": _ffi.PH_OP_BEST_FREQUENCY, "ramanujan": _ffi.PH_OP_RAMANUJAN,
-                 "orth_powers": _ffi.PH_OP_ORTH_POWERS, "fold_sums": _ffi.PH_OP_FOLD_SUMS, "qo_fit": _ffi.PH_OP_QO_FIT}
+                 "orth_powers": _ffi.PH_OP_ORTH_POWERS, "fold_sums": _ffi.PH_OP_FOLD_SUMS, "qo_fit": _ffi.PH_OP_QO_FIT,
+                 "qo_fit_win": _ffi.PH_OP_QO_FIT_WIN}
 
     def plan_info(self, op, n, params=(), dtype=np.float64, trunc=False, orth=False):
         """-> tuple of one KernelPlan per kernel the entry point `op` ("project", "sweep", "m_best", ...) would launch
@@ -437,20 +438,24 @@ class PeriodEngine:
             recs.append(KernelPlan(*(int(v) for v in r)))
         return tuple(recs)
 
-    def qo_fit_feasible(self, kcap, max_period) -> bool:
-        """Whether ph_qo_fit / ph_ramanujan_fit can run dictionaries of `kcap` rows with periods up to `max_period`:
-        the answer of the plan query (the launch's own planning function), nothing runs and nothing is raised."""
+    def qo_fit_feasible(self, kcap, max_period, n=None, window=False) -> bool:
+        """Whether ph_qo_fit / ph_ramanujan_fit -- with ``window=True`` ph_qo_fit_win on windows of `n` samples -- can run
+        dictionaries of `kcap` rows with periods up to `max_period`: the answer of the plan query (the launch's own
+        planning function), nothing runs and nothing is raised."""
         prm = np.array([int(kcap), int(max_period)], dtype=np.int32)
         out = np.zeros(_ffi.PH_PLAN_LEN, dtype=np.int32)
-        rc = self._lib.ph_plan_info(self._ctx, _ffi.PH_OP_QO_FIT, _ffi.PH_F64, max(1, int(max_period)), prm.ctypes.data, 2, 0,
-                                    out.ctypes.data)
+        op = _ffi.PH_OP_QO_FIT_WIN if window else _ffi.PH_OP_QO_FIT
+        rc = self._lib.ph_plan_info(self._ctx, op, _ffi.PH_F64, max(1, int(max_period if n is None else n)), prm.ctypes.data,
+                                    2, 0, out.ctypes.data)
         if rc not in (_ffi.PH_OK, _ffi.PH_E_ARG):
             _ffi.check(rc)
         return rc == _ffi.PH_OK
 
-    def qo_fit(self, x, periods, n_periods=None, kcap=512, max_period=None):
+    def qo_fit(self, x, periods, n_periods=None, kcap=512, max_period=None, window=None):
         """Fit given period lists to a batch (QOPeriods.compute_reconstruction / get_subspaces + solve_quadratic,
-        natural basis, no window): -> keeps (W, pcap) i32, weights (W, kcap) f64, residual (W, N), status (W).
+        natural basis): -> keeps (W, pcap) i32, weights (W, kcap) f64, residual (W, N), status (W).
+        `window`: None (ph_qo_fit) or one float64 analysis window of N samples for the whole batch (ph_qo_fit_win,
+        solve_quadratic's ``window=``); with torch input a float64 tensor on x's device.
         `periods`: one 1-D list shared by all windows, or a (W, pcap) int32 array with `n_periods` (W) entries used per
         row (default: all pcap).  With torch input both are int32 tensors on x's device (n_periods required for 2-D
         lists) and `max_period` should be given (default N); for numpy it defaults to the largest entry."""
@@ -485,7 +490,20 @@ class PeriodEngine:
         weights = mk.empty((W, int(kcap)), np.float64)
         resid = mk.empty((W, N), self._np_dtype(code))
         status = mk.empty((W,), np.int32)
-        self._call(mk, W, self._lib.ph_qo_fit, mk.addr(x), code, W, N, mk.addr(per), mk.addr(npr), pcap,
+        if window is None:
+            self._call(mk, W, self._lib.ph_qo_fit, mk.addr(x), code, W, N, mk.addr(per), mk.addr(npr), pcap,
+                       pcap if ndim == 2 else 0, int(max_period), int(kcap), fl, mk.addr(keeps), mk.addr(weights),
+                       mk.addr(resid), mk.addr(status))
+            return keeps, weights, resid, status
+        if mk.torch:
+            win = window.contiguous()
+            if win.dtype != mk._t.float64 or win.device != x.device:
+                raise TypeError("window must be a float64 tensor on the device of x")
+        else:
+            win = np.ascontiguousarray(window, dtype=np.float64)
+        if tuple(win.shape) != (N,):
+            raise ValueError(f"window must hold N={N} samples")
+        self._call(mk, W, self._lib.ph_qo_fit_win, mk.addr(x), code, W, N, mk.addr(win), mk.addr(per), mk.addr(npr), pcap,
                    pcap if ndim == 2 else 0, int(max_period), int(kcap), fl, mk.addr(keeps), mk.addr(weights),
                    mk.addr(resid), mk.addr(status))
         return keeps, weights, resid, status

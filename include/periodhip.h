@@ -317,6 +317,12 @@ int ph_qo_plan_info(ph_ctx* ctx, int dtype, int N, int max_length, int kcap, uns
  *                                                                   PH_HBM_WINDOW=1); x and the analysis window are
  *                                                                   read from HBM / L2 (PH_PLAN_WINDOW =
  *                                                                   PH_PLAN_HBM).  kcap as PH_OP_QO_FIT.
+ *   PH_OP_QO_ORTH_SELECT    {max_p}                                  default N / 3   (ph_qo_orth_select: PH_PLAN_WINDOW
+ *                                                                   and PH_PLAN_SECOND move together -- window, the N
+ *                                                                   doubles shared by the autocorrelation and the
+ *                                                                   projection, and max_p doubles in LDS, or the
+ *                                                                   window read from HBM / L2 and the work arrays in
+ *                                                                   an HBM workspace)
  * ph_tile_sum and ph_dict_project do not depend on N (LDS of sum(keep) doubles / none) and have no op.
  * out[PH_PLAN_LEN] int32: out[PH_PLAN_KERNELS] kernels launched per call (per round for best_frequency), then one
  * record of PH_PLAN_STRIDE words per kernel at out[PH_PLAN_K0] (m_best step 1, best_frequency spectrum) and
@@ -343,6 +349,7 @@ int ph_qo_plan_info(ph_ctx* ctx, int dtype, int N, int max_length, int kcap, uns
 #define PH_OP_FOLD_SUMS 8
 #define PH_OP_QO_FIT 9
 #define PH_OP_QO_FIT_WIN 10
+#define PH_OP_QO_ORTH_SELECT 11
 #define PH_PLAN_KERNELS 0
 #define PH_PLAN_K0 1
 #define PH_PLAN_K1 9
@@ -423,6 +430,24 @@ int ph_ramanujan_fit(ph_ctx* ctx, const void* x, int dtype, int64_t W, int N, in
  * lag k, eq3 (W, max_p) = eq_3(x, q) -- both optional (NULL).  max_p < 0 = floor(N/2). */
 int ph_orth_powers(ph_ctx* ctx, const void* x, int dtype, int64_t W, int N, int max_p,
                    int normalize, unsigned flags, double* autocorr, double* eq3, double* powers);
+
+/* ---- selection step of QOPeriods.find_periods under orthogonal (Muresan-Parks) selection (QOPeriods.py:435-448) ----
+ * For every window of a batch of residuals, in one launch (one workgroup per window):
+ *   powers = get_best_period_orthogonal(x[w], max_p, normalize=True, return_powers=True)   (QOPeriods.py:1175-1232)
+ *            -- the bits ph_orth_powers(normalize = 1) gives for the same window placement;
+ *   period[w] = first maximum of powers over q in [0, max_p); 0 (all powers zero) becomes 1  (:1227-1232)
+ *   norm[w]   = periodic_norm(project(x[w], period, trunc, orthogonalize=True), period)
+ *               (Periods.py:142-219, the sub-periods p / f of :208-214 in the order of orth_off / orth_q; :221-241).
+ * All arithmetic is in float64 for either dtype: a PH_F32 call gives the bits of the PH_F64 call on the upcast windows.
+ * period (W) int32, norm (W) float64, powers (W, max_p) float64 or NULL, status (W) int32: PH_ST_OK, or
+ * PH_ST_NO_PERIOD when a power or the norm is not finite -- overflow, or a NaN sample, which the clip of eq. 3 turns into
+ * zero powers and the projection into a NaN norm -- (period 0, norm 0; callers re-run such windows on the host).
+ * flags: PH_FLAG_TRUNC (the projection's truncated mean, Periods.py:178-184) and PH_FLAG_DEVICE; the orth tables
+ * are always needed (host pointers) and must cover p <= max_p - 1.  max_p < 2 or table_max_p < max_p - 1: PH_E_ARG.
+ * ph_plan_info(PH_OP_QO_ORTH_SELECT) says where the window and the work arrays live. */
+int ph_qo_orth_select(ph_ctx* ctx, const void* x, int dtype, int64_t W, int N, int max_p,
+                      const int32_t* orth_off, const int32_t* orth_q, int table_max_p, unsigned flags,
+                      int32_t* period, double* norm, double* powers /* (W, max_p) or NULL */, int32_t* status);
 
 /* ---- QOPeriods building blocks (QOPeriods.py:779-795) -----------------------------------
  * ph_fold_sums: W = A x for natural-basis rows -- out[w, off_k + j] = sum_{n = j (mod p_k)}

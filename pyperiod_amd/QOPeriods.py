@@ -8,7 +8,9 @@ even be constructed (QOPeriods.py:190) and only its non-orthogonal ``find_period
     bookkeeping, right-hand side by folds, matrix-free conjugate-gradient solve, reconstruction,
     residual) runs in ONE kernel launch per window batch -> ph_qo_find_periods
   * a (W, N) batch: the default, update_weights=False and trunc variants run in one launch per batch
-    (ph_qo_find_periods, PH_FLAG_KEEP_WEIGHTS / PH_FLAG_TRUNC); the other settings run row by row
+    (ph_qo_find_periods, PH_FLAG_KEEP_WEIGHTS / PH_FLAG_TRUNC); under an analysis window and under orthogonal
+    (Muresan-Parks) selection the greedy loop is stepped from the host for the whole batch, two launches per round
+    (ph_sweep + ph_qo_fit_win; ph_qo_orth_select + ph_qo_fit); the other settings run row by row
   * other 1-D settings (custom test_function, update_weights=False, trunc, window, Ramanujan basis):
     the loop is driven from the host with the heavy pieces on the GPU -- the sweep (ph_sweep,
     QOPeriods.py:470-478), W = A x and A A^T as folds (ph_fold_sums, :781-782), A^T w
@@ -214,8 +216,11 @@ class QOPeriods(Periods):
         kernels, residuals returned as float64).  Under an analysis window (``self.window`` a finite 1-D array
         of N samples) the same settings with ``update_weights=True`` run a batched greedy loop stepped from the host
         (``_find_periods_window_batch``: one ph_sweep and one ph_qo_fit_win launch per round);
-        ``update_weights=False`` with a window stays on the 1-D path.  Everything else (custom ``test_function``,
-        Ramanujan basis, ``orthogonalize``, ``verbose``, ``thresh=None``) and every row the kernels hand back
+        ``update_weights=False`` with a window stays on the 1-D path.  ``orthogonalize=True`` with
+        ``update_weights=True`` and no window runs the same kind of host-stepped loop (``_find_periods_orth_batch``:
+        one ph_qo_orth_select and one ph_qo_fit launch per round); ``update_weights=False`` or a window under
+        orthogonal selection stay on the 1-D path.  Everything else (custom ``test_function``,
+        Ramanujan basis, ``verbose``, ``thresh=None``) and every row the kernels hand back
         with a fallback status or a dictionary beyond the device's capacity runs the 1-D call on that row;
         all-zero rows get the reference's fixed answer.
 
@@ -224,13 +229,16 @@ class QOPeriods(Periods):
         of the 1-D result."""
         W, N = data.shape
         windowed = not (self.window is None or self.window is False)
-        on_device_settings = (
-            kwargs.get("test_function") is None and thresh is not None and not self._orthogonalize
-            and self._basis_type == "natural" and not self._verbose
-        )
+        common = kwargs.get("test_function") is None and thresh is not None and self._basis_type == "natural" and not self._verbose
+        on_device_settings = common and not self._orthogonalize
         on_device = on_device_settings and not windowed
         out = [None] * W
         win = _device_window(self.window, N) if windowed else None
+        if common and self._orthogonalize and update_weights and not windowed and W > 0:
+            ml = int(np.floor(N / 3)) if max_length is None else int(max_length)
+            n = N if num is None else int(num)
+            x = np.ascontiguousarray(data, dtype=np.float64)  # (the 1-D call works on the float64 copy of a row)
+            out = self._find_periods_orth_batch(default_engine(), x, n, thresh, ml)
         if win is not None and update_weights and on_device_settings and W > 0:
             ml = int(np.floor(N / 3)) if max_length is None else int(max_length)
             n = N if num is None else int(num)
@@ -355,6 +363,65 @@ class QOPeriods(Periods):
             counts[active] += 1
             fit = self._fit_lists_device(eng, np.ascontiguousarray(x[active]), np.ascontiguousarray(per[active]),
                                          np.ascontiguousarray(counts[active]), max_length, window=win)
+            for w, r in zip(active, fit):
+                if r is not None:
+                    fits[w] = r
+                    res[w] = r[2]
+            active = active[np.array([r is not None for r in fit], dtype=bool)]
+        for w in active:
+            finish(w, int(counts[w]))
+        return out
+
+    def _find_periods_orth_batch(self, eng, x, num, thresh, max_length):
+        """The greedy loop under orthogonal (Muresan-Parks) selection with re-solved weights for the float64
+        batch `x`, stepped from the host: per round one ph_qo_orth_select launch on the residuals of the rows still active
+        (the period by the normalised orthogonal powers over q < max_length and the norm of the orthogonalised
+        projection: ``_strongest_period`` for every row at once; ``min_length`` does not enter, as in the 1-D call) and
+        one ph_qo_fit launch on those rows with their lists so far, instead of three launches, a dense dictionary, its
+        upload and a host solve per row and round.  A row stops when ``rms(reconstruction) > rms(data) * thresh``
+        fails -- its result is the last fit with one period fewer reported (QOPeriods.py:560-594) -- or after `num`
+        rounds.  -> per row (output_bases, residual), or None: the row is rerun whole by the 1-D call (all-zero rows,
+        a select or fit that came back not PH_ST_OK -- a non-finite power, a block without rows such as a period picked
+        twice, a dictionary beyond the largest feasible capacity -- and a 65th period)."""
+        W, N = x.shape
+        out = [None] * W
+        if max_length < 2 or num < 1:  # (ph_qo_orth_select needs max_p >= 2)
+            return out
+        trunc = bool(self._trunc_to_integer_multiple)
+        per = np.zeros((W, 64), dtype=np.int32)
+        counts = np.zeros(W, dtype=np.int32)
+        gnorm = np.zeros((W, 64))
+        fits = [None] * W  # (blocks, weights, residual) of the row's last fit
+        res = x.copy()
+        rms_data = np.sqrt(np.sum(x * x, axis=1) / N)
+        active = np.flatnonzero(np.sum(np.abs(x), axis=1) > 1e-16)  # (QOPeriods.py:394-406: the 1-D call's fixed answer)
+
+        def finish(w, n_report):
+            blocks, wts, resid = fits[w]
+            out[w] = (_LazyBases(blocks, N, self._basis_type, periods=per[w, :n_report].astype(np.uint32),
+                                 norms=gnorm[w, :n_report].copy(), weights=wts,
+                                 basis_dictionary={str(q): k for q, k in blocks}), resid)
+
+        for i in range(num):
+            if i > 0:  # the test function on the reconstruction of the last fit
+                rec = x[active] - res[active]
+                go = np.sqrt(np.sum(rec * rec, axis=1) / N) > rms_data[active] * thresh
+                for w in active[~go]:
+                    finish(w, int(counts[w]) - 1)
+                active = active[go]
+            active = active[counts[active] < 64]  # (a 65th period: the 1-D call)
+            if active.size == 0:
+                break
+            p, g, st = eng.qo_orth_select(np.ascontiguousarray(res[active]), max_length, trunc)
+            ok = st == _ffi.PH_ST_OK
+            active, p, g = active[ok], p[ok], g[ok]
+            if active.size == 0:
+                break
+            per[active, counts[active]] = p
+            gnorm[active, counts[active]] = g
+            counts[active] += 1
+            fit = self._fit_lists_device(eng, np.ascontiguousarray(x[active]), np.ascontiguousarray(per[active]),
+                                         np.ascontiguousarray(counts[active]), max_length)
             for w, r in zip(active, fit):
                 if r is not None:
                     fits[w] = r

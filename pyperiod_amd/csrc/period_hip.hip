@@ -92,6 +92,9 @@ struct ph_ctx {
   int s2l_block = 1024;              // k_small_to_large_pair threads per workgroup (PH_S2L_BLOCK overrides, >= 512)
   bool qo_hbm_window = false;        // PH_QO_HBM_WINDOW=1: keep the residual of k_qo_find in HBM even when it fits LDS
   bool hbm_window = false;           // PH_HBM_WINDOW=1: every window and second window-sized buffer in HBM
+  // Moebius tables of the orthogonal powers for the last max_p (prepare_mobius)
+  int mob_max_p = -1;
+  std::vector<int32_t> mob_off, mob_d, mob_mu;
   // optional per-kernel HIP-event timing (ph_profile_*)
   bool prof_on = false;
   int prof_n = 0;
@@ -795,6 +798,56 @@ void plan_orth_powers(const ph_ctx* c, int dtype, int N, int max_p, Plan* pl) {
   k.block = kBlockWide;
 }
 
+// k_qo_orth_select: k_orth_powers' placement rule on its own layout (the same three arrays + the reduction slots; the
+// projection reuses the autocorrelation's N doubles, so nothing is added for it).
+int plan_qo_orth_select(const ph_ctx* c, int dtype, int N, int max_p, Plan* pl) {
+  if (max_p < 2) return fail(PH_E_ARG, "ph_qo_orth_select: max_p=%d must be >= 2", max_p);
+  KernelPlan& k = pl->k[0];
+  const size_t sz = elem_size(dtype);
+  const bool lds_window = !c->hbm_window && ph::qo_orth_select_lds_bytes(N, sz, max_p, true) <= (size_t)c->lds_limit;
+  k.lds = ph::qo_orth_select_lds_bytes(N, sz, max_p, lds_window);
+  k.window = k.second = lds_window ? PH_PLAN_LDS : PH_PLAN_HBM;
+  k.block = kBlockWide;
+  return PH_OK;
+}
+
+// Divisors d of q with mu(q / d) != 0 in ascending order, CSR by q < max_p, and mu(q / d): the Moebius sum of the
+// orthogonal powers (QOPeriods.py:1210-1217).  Kept for the last max_p; upload_table skips the copy of unchanged content.
+int prepare_mobius(ph_ctx* c, int max_p, const int** d_off, const int** d_d, const int** d_mu) {
+  if (c->mob_max_p != max_p) {
+    std::vector<int32_t> mu(max_p, 1), &off = c->mob_off, &dd = c->mob_d, &dm = c->mob_mu;
+    c->mob_max_p = -1;
+    std::vector<char> comp(max_p, 0);
+    for (int i = 2; i < max_p; ++i) {
+      if (comp[i]) continue;
+      for (int j = i; j < max_p; j += i) {
+        comp[j] = j > i;
+        mu[j] = -mu[j];
+      }
+      for (int64_t j = (int64_t)i * i; j < max_p; j += (int64_t)i * i) mu[j] = 0;
+    }
+    off.assign((size_t)max_p + 1, 0);
+    for (int d = 1; d < max_p; ++d)
+      for (int q = d; q < max_p; q += d)
+        if (mu[q / d] != 0) ++off[q + 1];
+    for (int q = 0; q < max_p; ++q) off[q + 1] += off[q];
+    dd.assign((size_t)off[max_p], 0);
+    dm.assign((size_t)off[max_p], 0);
+    std::vector<int32_t> fill(off.begin(), off.end() - 1);
+    for (int d = 1; d < max_p; ++d)
+      for (int q = d; q < max_p; q += d)
+        if (mu[q / d] != 0) {
+          dd[fill[q]] = d;
+          dm[fill[q]++] = mu[q / d];
+        }
+    c->mob_max_p = max_p;
+  }
+  PH_TRY(upload_table(c, T_AUX0, c->mob_off.data(), c->mob_off.size(), d_off));
+  PH_TRY(upload_table(c, T_AUX1, c->mob_d.data(), c->mob_d.size(), d_d));
+  PH_TRY(upload_table(c, T_AUX2, c->mob_mu.data(), c->mob_mu.size(), d_mu));
+  return PH_OK;
+}
+
 // k_fold_sums: longer windows are folded from HBM / L2.
 void plan_fold_sums(const ph_ctx* c, int dtype, int N, Plan* pl) {
   KernelPlan& k = pl->k[0];
@@ -1216,6 +1269,12 @@ int ph_plan_info(ph_ctx* c, int op, int dtype, int N, const int32_t* params, int
     case PH_OP_QO_FIT_WIN:
       PH_TRY(plan_qo_fit_win(c, N, prm(0, 512), prm(1, N), &pl));
       break;
+    case PH_OP_QO_ORTH_SELECT: {
+      int max_p = prm(0, -1);
+      if (max_p < 0) max_p = N / 3;  // find_periods' max_length default (QOPeriods.py:374-375)
+      PH_TRY(plan_qo_orth_select(c, dtype, N, max_p, &pl));
+      break;
+    }
     default:
       return fail(PH_E_ARG, "op %d unknown", op);
   }
@@ -2263,32 +2322,8 @@ int ph_orth_powers(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int ma
   const size_t lds = pl.k[0].lds;
   void* gws;
   PH_TRY(place(c, pl.k[0].second, B_WS1, (size_t)W * ((size_t)N + max_p) * sizeof(double), &gws));
-  // divisors d of q with mu(q/d) != 0, for q < max_p
-  std::vector<int32_t> mu(max_p, 1), off(max_p + 1, 0), dd, dm;
-  {
-    std::vector<char> comp(max_p, 0);
-    for (int i = 2; i < max_p; ++i) {
-      if (comp[i]) continue;
-      for (int j = i; j < max_p; j += i) {
-        comp[j] = j > i;
-        mu[j] = -mu[j];
-      }
-      for (int64_t j = (int64_t)i * i; j < max_p; j += (int64_t)i * i) mu[j] = 0;
-    }
-    for (int q = 0; q < max_p; ++q) {
-      off[q] = (int32_t)dd.size();
-      for (int d = 1; q > 0 && d <= q; ++d)
-        if (q % d == 0 && mu[q / d] != 0) {
-          dd.push_back(d);
-          dm.push_back(mu[q / d]);
-        }
-    }
-    off[max_p] = (int32_t)dd.size();
-  }
   const int *d_off, *d_d, *d_mu;
-  PH_TRY(upload_table(c, T_AUX0, off.data(), off.size(), &d_off));
-  PH_TRY(upload_table(c, T_AUX1, dd.data(), dd.size(), &d_d));
-  PH_TRY(upload_table(c, T_AUX2, dm.data(), dm.size(), &d_mu));
+  PH_TRY(prepare_mobius(c, max_p, &d_off, &d_d, &d_mu));
   Stage st(c, flags);
   const void* dx;
   void *dr, *de, *dp;
@@ -2307,6 +2342,49 @@ int ph_orth_powers(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int ma
     return (int)PH_OK;
   }));
   PH_TRY(launch_check("k_orth_powers"));
+  return st.finish();
+}
+
+// ----------------------------------------------------------------------------- orthogonal selection step
+int ph_qo_orth_select(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int max_p, const int32_t* orth_off,
+                      const int32_t* orth_q, int table_max_p, unsigned flags, int32_t* period, double* norm,
+                      double* powers, int32_t* status) {
+  PH_TRY(check_common(c, x, dtype, W, N));
+  if (!period || !norm || !status) return fail(PH_E_ARG, "period/norm/status is NULL");
+  Plan pl;
+  PH_TRY(plan_qo_orth_select(c, dtype, N, max_p, &pl));
+  if (table_max_p < max_p - 1)
+    return fail(PH_E_ARG, "ph_qo_orth_select: orth tables cover p <= %d, need %d", table_max_p, max_p - 1);
+  PH_HIP(hipSetDevice(c->device));
+  const size_t sz = elem_size(dtype);
+  const bool lds_window = pl.k[0].window == PH_PLAN_LDS;
+  const size_t lds = pl.k[0].lds;
+  void* gws;
+  PH_TRY(place(c, pl.k[0].second, B_WS1, (size_t)W * ((size_t)N + max_p) * sizeof(double), &gws));
+  ph::Tables tb{};
+  PH_TRY(prepare_orth(c, PH_FLAG_ORTH, orth_off, orth_q, table_max_p, max_p - 1, &tb));
+  const int *d_off, *d_d, *d_mu;
+  PH_TRY(prepare_mobius(c, max_p, &d_off, &d_d, &d_mu));
+  Stage st(c, flags);
+  const void* dx;
+  void *dper, *dnrm, *dpow, *dstat;
+  PH_TRY(st.in(x, (size_t)W * N * sz, &dx));
+  PH_TRY(st.out(B_OUT0, period, (size_t)W * sizeof(int32_t), &dper));
+  PH_TRY(st.out(B_OUT1, norm, (size_t)W * sizeof(double), &dnrm));
+  PH_TRY(st.out(B_OUT2, powers, (size_t)W * max_p * sizeof(double), &dpow));
+  PH_TRY(st.out(B_OUT3, status, (size_t)W * sizeof(int32_t), &dstat));
+  const unsigned kflags = flags & PH_FLAG_TRUNC;
+  const dim3 grid((unsigned)W);
+  PH_TRY(dispatch(dtype, lds_window, [&](auto t, auto lw) {
+    using T = decltype(t);
+    auto kernel = ph::k_qo_orth_select<T, decltype(lw)::value>;
+    PH_TRY(allow_lds(kernel, lds));
+    ProfScope ps_(c, "k_qo_orth_select");
+    hipLaunchKernelGGL(kernel, grid, dim3(pl.k[0].block), lds, c->stream, (const T*)dx, N, max_p, kflags, tb, d_off, d_d,
+                       d_mu, (double*)gws, (int*)dper, (double*)dnrm, (double*)dpow, (int*)dstat);
+    return (int)PH_OK;
+  }));
+  PH_TRY(launch_check("k_qo_orth_select"));
   return st.finish();
 }
 

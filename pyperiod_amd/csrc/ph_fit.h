@@ -702,4 +702,141 @@ __global__ __launch_bounds__(kWave) void k_ram_select(const double* __restrict__
   if (lane == 0) counts[w] = count;
 }
 
+// ======================================================================================
+// The selection step of QOPeriods.find_periods under orthogonal (Muresan-Parks) selection for a batch of residuals
+// (QOPeriods.py:435-448): one workgroup per window does what get_best_period_orthogonal(res, max_p, normalize=True)
+// (:1175-1232), Periods.project(res, p, trunc, orthogonalize=True) (Periods.py:142-219) and periodic_norm(base, p)
+// (:221-241) do in three calls.
+//   powers   orth_powers_row, the body of k_orth_powers: the same bits as ph_orth_powers(normalize = 1) in the same
+//            placement, so the argmax is the 1-D path's on every input
+//   winner   first maximum over q < max_p; 0 (all powers zero) becomes 1 (:1227-1232); a non-finite power -- or, below,
+//            a non-finite norm: a NaN sample clips to zero powers -- ends the window with status 1 (PH_ST_NO_PERIOD),
+//            period 0 and norm 0
+//   norm     fold -> mean (truncated mean under kTrunc) -> tile into the N doubles that held the autocorrelation (dead
+//            once the powers are final), then base -= project(base, p / f) for the sub-periods of the orth tables in
+//            their order, then ||base|| / sqrt(N) / sqrt(p)
+// All arithmetic is in double whatever T is; the window is only read.  LW: window, work arrays and reductions in LDS
+// (qo_orth_select_lds_bytes: k_orth_powers' layout + the reduction slots); otherwise the window is read from HBM / L2
+// and the work arrays are N + max_p doubles per workgroup of the workspace `gws`.
+// ======================================================================================
+__host__ __device__ inline size_t qo_orth_select_lds_bytes(int N, size_t elem, int max_p, bool lds_window) {
+  const size_t red = carve_bytes(kRedDoubles, 8) + carve_bytes(kMaxWaves, 8) + carve_bytes(kMaxWaves, 4);
+  return (lds_window ? carve_bytes(N, elem) + carve_bytes(N, 8) + carve_bytes(max_p, 8) : 0) + red;
+}
+
+// Row-order sum of residue j over n rows of a window of T, in double: column_sum's order for either element type.
+template <typename T>
+__device__ __forceinline__ double column_sum_f64(const T* __restrict__ xs, int j, int p, int n) {
+  if (n <= 0) return 0.0;
+  const T* ptr = xs + j;
+  double s = (double)ptr[0];
+  ptr += p;
+  int r = 1;
+  for (; r + 8 <= n; r += 8) {
+    double v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = (double)ptr[u * p];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) s += v[u];
+    ptr += 8 * p;
+  }
+  for (; r < n; ++r) {
+    s += (double)ptr[0];
+    ptr += p;
+  }
+  return s;
+}
+
+// dst[n] = mean[n mod p] in double from a window of T (fold_mean_tile with residue_mean's two means).  No barrier.
+template <typename T>
+__device__ __forceinline__ void fold_mean_tile_f64(const T* __restrict__ src, double* __restrict__ dst, int N, int p,
+                                                   bool trunc) {
+  const Fold f(N, p);
+  for (int j = threadIdx.x; j < p; j += blockDim.x) {
+    const int cnt = f.count(j);
+    const int n = trunc ? (f.trows < cnt ? f.trows : cnt) : cnt;
+    const double m = column_sum_f64(src, j, p, n) / (double)(trunc ? f.trows : cnt);
+    for (int r = 0; r < cnt; ++r) dst[r * p + j] = m;
+  }
+}
+
+template <typename T, bool LW>
+__global__ __launch_bounds__(kBlockWide) void k_qo_orth_select(const T* __restrict__ x, int N, int max_p, unsigned flags,
+                                                               Tables tb, const int* __restrict__ mob_off,
+                                                               const int* __restrict__ mob_d,
+                                                               const int* __restrict__ mob_mu, double* __restrict__ gws,
+                                                               int* __restrict__ period_out, double* __restrict__ norm_out,
+                                                               double* __restrict__ pows_out, int* __restrict__ status_out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int64_t w = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int nw = (blockDim.x + kWave - 1) / kWave;
+  Carve cv(smem);
+  const T* xs = x + w * (int64_t)N;
+  double *r, *m;
+  if constexpr (LW) {
+    T* stage = cv.take<T>(N);
+    r = cv.take<double>(N);
+    m = cv.take<double>(max_p);
+    load_window(xs, stage, N);
+    __syncthreads();
+    xs = stage;
+  } else {
+    r = gws + w * ((int64_t)N + max_p);
+    m = r + N;
+  }
+  double* red = cv.take<double>(kRedDoubles);
+  double* wbest = cv.take<double>(kMaxWaves);
+  int* wbestp = cv.take<int>(kMaxWaves);
+
+  // ---- powers; each thread keeps the first maximum of its own q (ascending), keyed q + 1 (0 = none)
+  double bv = -1.0;
+  int bkey = 0, bad = 0;
+  double* prow = pows_out ? pows_out + w * (int64_t)max_p : nullptr;
+  orth_powers_row(xs, r, m, N, max_p, 1, mob_off, mob_d, mob_mu, nullptr, nullptr, [&](int q, double v) {
+    if (prow) prow[q] = v;
+    bad |= !(fabs(v) <= 1.7976931348623157e308);  // NaN or infinite
+    if (v > bv) {
+      bv = v;
+      bkey = q + 1;
+    }
+  });
+  wave_argmax(bv, bkey);
+  if ((tid & (kWave - 1)) == 0) {
+    wbest[tid >> 6] = bv;
+    wbestp[tid >> 6] = bkey;
+  }
+  const double nbad = block_sum((double)bad, red);  // (its barriers also publish the wave winners and retire `m`)
+  if (nbad != 0.0) {
+    if (tid == 0) {
+      period_out[w] = 0;
+      norm_out[w] = 0.0;
+      status_out[w] = 1;
+    }
+    return;
+  }
+  double best;
+  int key;
+  red_argmax(wbest, wbestp, nw, best, key);  // takes positive values only: all powers zero -> key 0
+  const int p = key > 1 ? key - 1 : 1;       // (QOPeriods.py:1227-1232)
+
+  // ---- base = project(row, p, trunc, orthogonalize=True) in the autocorrelation's N doubles, then its norm
+  const bool trunc = flags & kTrunc;
+  fold_mean_tile_f64(xs, r, N, p, trunc);
+  __threadfence_block();
+  __syncthreads();
+  for (int k = tb.orth_off[p]; k < tb.orth_off[p + 1]; ++k) {
+    subtract_projection_inplace(r, N, tb.orth_q[k], trunc);
+    __threadfence_block();
+    __syncthreads();
+  }
+  const double ss = block_sumsq(r, N, red);
+  const bool finite = ss <= 1.7976931348623157e308;  // (a NaN sample clips to a zero power -- fmax -- and shows here)
+  if (tid == 0) {
+    period_out[w] = finite ? p : 0;
+    norm_out[w] = finite ? periodic_norm_from_sq(ss, N, p) : 0.0;
+    status_out[w] = finite ? 0 : 1;
+  }
+}
+
 }  // namespace ph

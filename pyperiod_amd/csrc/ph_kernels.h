@@ -3318,6 +3318,53 @@ __global__ __launch_bounds__(1024) void k_qo_greedy(const T* __restrict__ x, int
 //           = sum_{d | q} mu(q/d) max(e3[d], 0)   (Moebius inversion of the same recursion),
 //   negatives clipped to 0 afterwards, optionally divided by q (:1218-1223).
 // ======================================================================================
+// The powers of ONE window for the calling workgroup: `xs` is the window (LDS or HBM / L2), `r` (N doubles) and `m`
+// (max_p doubles) are its work arrays.  r_out / e3_out are this window's output rows or nullptr; emit(q, pows[q]) is
+// called once per q < max_p by the thread that owns q (q = tid, tid + blockDim.x, ...: ascending per thread).  Shared
+// by k_orth_powers and k_qo_orth_select (ph_fit.h): same loops, same summation order, same bits.  No barrier at the
+// end: `r` is dead on return (its last read lies before the second barrier), `m` is read until the caller's next one.
+template <typename T, typename Emit>
+__device__ __forceinline__ void orth_powers_row(const T* xs, double* r, double* m, int N, int max_p, int normalize,
+                                                const int* __restrict__ mob_off, const int* __restrict__ mob_d,
+                                                const int* __restrict__ mob_mu, double* __restrict__ r_out,
+                                                double* __restrict__ e3_out, Emit&& emit) {
+  const int tid = threadIdx.x;
+  // autocorrelation: lags k and N-1-k are paired on one thread (N-k plus k+1 products = N+1)
+  for (int k = tid; k < (N + 1) / 2; k += blockDim.x) {
+    const int k2 = N - 1 - k;
+    double a = 0.0, b = 0.0;
+    for (int n = 0; n + k < N; ++n) a += (double)xs[n] * (double)xs[n + k];
+    if (k2 != k)
+      for (int n = 0; n + k2 < N; ++n) b += (double)xs[n] * (double)xs[n + k2];
+    r[k] = a;
+    if (k2 != k) r[k2] = b;
+  }
+  __threadfence_block();
+  __syncthreads();
+  if (r_out)
+    for (int k = tid; k < N; k += blockDim.x) r_out[k] = r[k];
+  for (int q = tid; q < max_p; q += blockDim.x) {
+    double v = 0.0;
+    if (q >= 1) {
+      const int M = N / q;
+      double second = 0.0;
+      for (int l = 1; l < M; ++l) second += r[l * q];
+      v = ((double)q / (double)N) * (r[0] + 2.0 * second);
+    }
+    if (e3_out) e3_out[q] = v;
+    m[q] = fmax(v, 0.0);
+  }
+  __threadfence_block();
+  __syncthreads();
+  for (int q = tid; q < max_p; q += blockDim.x) {
+    double v = 0.0;
+    for (int k = mob_off[q]; k < mob_off[q + 1]; ++k) v += (double)mob_mu[k] * m[mob_d[k]];
+    v = v < 0.0 ? 0.0 : v;
+    if (normalize && q >= 1) v = v / (double)q;
+    emit(q, q >= 1 ? v : 0.0);
+  }
+}
+
 template <typename T, bool LW>
 __global__ __launch_bounds__(kBlockWide) void k_orth_powers(const T* __restrict__ x, int N, int max_p, int normalize,
                                                             const int* __restrict__ mob_off,
@@ -3328,7 +3375,6 @@ __global__ __launch_bounds__(kBlockWide) void k_orth_powers(const T* __restrict_
                                                             double* __restrict__ pows_out) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int64_t w = blockIdx.x;
-  const int tid = threadIdx.x;
   // LW: window, autocorrelation and clipped eq. 3 values live in LDS.  Otherwise (long windows) the
   // window is read straight from HBM / L2 and the two work arrays sit in the HBM workspace `gws`.
   const T* xs = x + w * (int64_t)N;
@@ -3345,40 +3391,9 @@ __global__ __launch_bounds__(kBlockWide) void k_orth_powers(const T* __restrict_
     r = gws + w * ((int64_t)N + max_p);
     m = r + N;
   }
-  // autocorrelation: lags k and N-1-k are paired on one thread (N-k plus k+1 products = N+1)
-  for (int k = tid; k < (N + 1) / 2; k += blockDim.x) {
-    const int k2 = N - 1 - k;
-    double a = 0.0, b = 0.0;
-    for (int n = 0; n + k < N; ++n) a += (double)xs[n] * (double)xs[n + k];
-    if (k2 != k)
-      for (int n = 0; n + k2 < N; ++n) b += (double)xs[n] * (double)xs[n + k2];
-    r[k] = a;
-    if (k2 != k) r[k2] = b;
-  }
-  __threadfence_block();
-  __syncthreads();
-  if (r_out)
-    for (int k = tid; k < N; k += blockDim.x) r_out[w * (int64_t)N + k] = r[k];
-  for (int q = tid; q < max_p; q += blockDim.x) {
-    double v = 0.0;
-    if (q >= 1) {
-      const int M = N / q;
-      double second = 0.0;
-      for (int l = 1; l < M; ++l) second += r[l * q];
-      v = ((double)q / (double)N) * (r[0] + 2.0 * second);
-    }
-    if (e3_out) e3_out[w * (int64_t)max_p + q] = v;
-    m[q] = fmax(v, 0.0);
-  }
-  __threadfence_block();
-  __syncthreads();
-  for (int q = tid; q < max_p; q += blockDim.x) {
-    double v = 0.0;
-    for (int k = mob_off[q]; k < mob_off[q + 1]; ++k) v += (double)mob_mu[k] * m[mob_d[k]];
-    v = v < 0.0 ? 0.0 : v;
-    if (normalize && q >= 1) v = v / (double)q;
-    pows_out[w * (int64_t)max_p + q] = q >= 1 ? v : 0.0;
-  }
+  double* prow = pows_out + w * (int64_t)max_p;
+  orth_powers_row(xs, r, m, N, max_p, normalize, mob_off, mob_d, mob_mu, r_out ? r_out + w * (int64_t)N : nullptr,
+                  e3_out ? e3_out + w * (int64_t)max_p : nullptr, [&](int q, double v) { prow[q] = v; });
 }
 
 // ======================================================================================

@@ -421,7 +421,7 @@ class PeriodEngine:
                  "small_to_large": _ffi.PH_OP_SMALL_TO_LARGE, "best_correlation": _ffi.PH_OP_BEST_CORRELATION,
                  "best_frequency": _ffi.PH_OP_BEST_FREQUENCY, "ramanujan": _ffi.PH_OP_RAMANUJAN,
                  "orth_powers": _ffi.PH_OP_ORTH_POWERS, "fold_sums": _ffi.PH_OP_FOLD_SUMS, "qo_fit": _ffi.PH_OP_QO_FIT,
-                 "qo_fit_win": _ffi.PH_OP_QO_FIT_WIN}
+                 "qo_fit_win": _ffi.PH_OP_QO_FIT_WIN, "qo_orth_select": _ffi.PH_OP_QO_ORTH_SELECT}
 
     def plan_info(self, op, n, params=(), dtype=np.float64, trunc=False, orth=False):
         """-> tuple of one KernelPlan per kernel the entry point `op` ("project", "sweep", "m_best", ...) would launch
@@ -546,6 +546,22 @@ class PeriodEngine:
         if want_eq3:
             out += (e3,)
         return out if len(out) > 1 else pows
+
+    def qo_orth_select(self, x, max_p, trunc=False, want_powers=False):
+        """The selection step of QOPeriods.find_periods under orthogonal selection for a batch of residuals, one launch:
+        -> period (W) i32 = argmax of the normalised orthogonal powers over q < max_p (0 -> 1), norm (W) f64 =
+        periodic_norm(project(x[w], period, trunc, orthogonalize=True), period), status (W) i32 (PH_ST_NO_PERIOD: a
+        power or the norm is not finite) [, powers (W, max_p) f64 when want_powers]."""
+        x, code, W, N, fl, mk = self._prep(x)
+        max_p = int(max_p)
+        keep = self._orth(True, max(max_p - 1, 1))
+        period = mk.empty((W,), np.int32)
+        norm = mk.empty((W,), np.float64)
+        status = mk.empty((W,), np.int32)
+        pows = mk.empty((W, max(max_p, 0)), np.float64) if want_powers else None
+        self._call(mk, W, self._lib.ph_qo_orth_select, mk.addr(x), code, W, N, max_p, keep[2], keep[3], keep[4],
+                   fl | (_ffi.PH_FLAG_TRUNC if trunc else 0), mk.addr(period), mk.addr(norm), mk.addr(pows), mk.addr(status))
+        return (period, norm, status, pows) if want_powers else (period, norm, status)
 
     def fold_sums(self, x, p_list, keep):
         """W = A x for natural-basis rows (QOPeriods.py:782): (W, sum(keep)) float64."""

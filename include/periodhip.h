@@ -271,6 +271,24 @@ int ph_qo_find_periods(ph_ctx* ctx, const void* x, int dtype, int64_t W, int N, 
                        uint32_t* periods, double* norms, int32_t* keeps, int32_t* counts,
                        double* weights, void* residual, int32_t* status);
 
+/* ---- QOPeriods.find_periods with update_weights=False under an analysis window ----------
+ * ph_qo_find_periods with PH_FLAG_KEEP_WEIGHTS, each block fitted under `window` (N float64 samples, one window for
+ * the whole batch; a device pointer with PH_FLAG_DEVICE like every array; NULL returns PH_E_ARG): the weights of a
+ * block are solve_quadratic(residual, block, window=window) (QOPeriods.py:779-796 as _dont_update_weights calls it,
+ * :707-709), i.e. w_j = sum(window[n] residual[n]) / sum(window[n]) over n = j (mod period) -- the windowed Gram matrix
+ * of one natural-basis block is diagonal.  Selection, the stop test and the residual update are not windowed.  One
+ * launch per batch (k_qo_greedy_win).
+ * Outputs, counts, the keeps[b] == 0 rule and kcap in [1, 2^20]: the PH_FLAG_KEEP_WEIGHTS section above.
+ * flags: PH_FLAG_TRUNC selects the trunc sweep; PH_FLAG_KEEP_WEIGHTS is accepted and implied; PH_FLAG_ORTH returns
+ * PH_E_UNSUPPORTED.
+ * status: PH_ST_OK, PH_ST_NO_PERIOD, PH_ST_CAP as above; PH_ST_ITER_CAP when a fitted residue class has a window sum
+ * of exactly zero (the reference's matrix is singular and its loop ends on LinAlgError) or a sum that is not finite.
+ * Callers re-run windows that are not PH_ST_OK on the host. */
+int ph_qo_greedy_win(ph_ctx* ctx, const void* x, int dtype, int64_t W, int N, const double* window, int num,
+                     double thresh, int min_length, int max_length, int kcap, unsigned flags, uint32_t* periods,
+                     double* norms, int32_t* keeps, int32_t* counts, double* weights, void* residual,
+                     int32_t* status);
+
 /* *ok = 1 when ph_qo_find_periods can run windows of N samples of `dtype` with `kcap` dictionary
  * rows on this device (bookkeeping and the six work vectors of the conjugate-gradient solve fit the
  * workgroup's LDS; the window joins them there or moves to the HBM workspace), else 0 -- callers fall back to a host-driven loop instead of catching PH_E_ARG. */
@@ -280,7 +298,8 @@ int ph_qo_feasible(ph_ctx* ctx, int dtype, int N, int max_length, int kcap, int*
  * would ask for (*lds_bytes), without running anything: PH_QO_LDS_OVERLAY = window in LDS, the solver's work
  * vectors overlay it; PH_QO_LDS_BEHIND = window in LDS, the work vectors (k_qo_find) or nothing (PH_FLAG_KEEP_WEIGHTS)
  * behind it; PH_QO_HBM = window in the HBM workspace.  The answer is computed by the code the launch uses and honours
- * PH_QO_HBM_WINDOW; max_length < 0 means N / 3.  Arguments the launch refuses return its error code. */
+ * PH_QO_HBM_WINDOW; max_length < 0 means N / 3.  Arguments the launch refuses return its error code.
+ * With PH_FLAG_KEEP_WEIGHTS this is also the plan of ph_qo_greedy_win (its analysis window takes no LDS). */
 #define PH_QO_LDS_OVERLAY 0
 #define PH_QO_LDS_BEHIND 1
 #define PH_QO_HBM 2

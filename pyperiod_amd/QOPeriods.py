@@ -8,9 +8,10 @@ even be constructed (QOPeriods.py:190) and only its non-orthogonal ``find_period
     bookkeeping, right-hand side by folds, matrix-free conjugate-gradient solve, reconstruction,
     residual) runs in ONE kernel launch per window batch -> ph_qo_find_periods
   * a (W, N) batch: the default, update_weights=False and trunc variants run in one launch per batch
-    (ph_qo_find_periods, PH_FLAG_KEEP_WEIGHTS / PH_FLAG_TRUNC); under an analysis window and under orthogonal
-    (Muresan-Parks) selection the greedy loop is stepped from the host for the whole batch, two launches per round
-    (ph_sweep + ph_qo_fit_win; ph_qo_orth_select + ph_qo_fit); the other settings run row by row
+    (ph_qo_find_periods, PH_FLAG_KEEP_WEIGHTS / PH_FLAG_TRUNC), update_weights=False under an analysis window too
+    (ph_qo_greedy_win); with re-solved weights under an analysis window and under orthogonal (Muresan-Parks) selection
+    -- with or without a window -- the greedy loop is stepped from the host for the whole batch, two launches per round
+    (ph_sweep + ph_qo_fit_win; ph_qo_orth_select + ph_qo_fit or ph_qo_fit_win); the other settings run row by row
   * other 1-D settings (custom test_function, update_weights=False, trunc, window, Ramanujan basis):
     the loop is driven from the host with the heavy pieces on the GPU -- the sweep (ph_sweep,
     QOPeriods.py:470-478), W = A x and A A^T as folds (ph_fold_sums, :781-782), A^T w
@@ -169,8 +170,8 @@ class QOPeriods(Periods):
     def find_periods(self, data, num=None, thresh=None, min_length=2, max_length=None, update_weights=True, **kwargs):
         """Greedy period selection with re-solved weights (QOPeriods.py:313-596).
         Returns ``(dict(periods, norms, subspaces, weights, basis_dictionary), residual)``; a ``(W, N)``
-        ndarray returns a list of W such tuples (see ``_find_periods_batch``: one launch per batch, with
-        ``subspaces`` built on first read).
+        ndarray returns a list of W such tuples (see ``_find_periods_batch``: one launch per batch -- also for
+        ``update_weights=False`` under ``self.window`` -- or two per round, with ``subspaces`` built on first read).
 
         ``orthogonalize=True``: the v1 reference dies on this branch (``best_base`` is never
         assigned, QOPeriods.py:427-448).  Offered here as its commented-out lines intend: the
@@ -215,11 +216,12 @@ class QOPeriods(Periods):
         ``update_weights`` -- run in ONE launch of ph_qo_find_periods per batch (float32 batches in the fp32
         kernels, residuals returned as float64).  Under an analysis window (``self.window`` a finite 1-D array
         of N samples) the same settings with ``update_weights=True`` run a batched greedy loop stepped from the host
-        (``_find_periods_window_batch``: one ph_sweep and one ph_qo_fit_win launch per round);
-        ``update_weights=False`` with a window stays on the 1-D path.  ``orthogonalize=True`` with
-        ``update_weights=True`` and no window runs the same kind of host-stepped loop (``_find_periods_orth_batch``:
-        one ph_qo_orth_select and one ph_qo_fit launch per round); ``update_weights=False`` or a window under
-        orthogonal selection stay on the 1-D path.  Everything else (custom ``test_function``,
+        (``_find_periods_window_batch``: one ph_sweep and one ph_qo_fit_win launch per round), and with
+        ``update_weights=False`` the whole fixed-weight loop in ONE launch of ph_qo_greedy_win per batch (each block
+        fitted under the window).  ``orthogonalize=True`` with ``update_weights=True`` runs the same kind of
+        host-stepped loop (``_find_periods_orth_batch``: one ph_qo_orth_select and one ph_qo_fit launch per round,
+        ph_qo_fit_win under such a window); ``update_weights=False`` under orthogonal selection stays on the 1-D path,
+        and so does every setting under a window that is not a finite 1-D array of N samples.  Everything else (custom ``test_function``,
         Ramanujan basis, ``verbose``, ``thresh=None``) and every row the kernels hand back
         with a fallback status or a dictionary beyond the device's capacity runs the 1-D call on that row;
         all-zero rows get the reference's fixed answer.
@@ -234,22 +236,23 @@ class QOPeriods(Periods):
         on_device = on_device_settings and not windowed
         out = [None] * W
         win = _device_window(self.window, N) if windowed else None
-        if common and self._orthogonalize and update_weights and not windowed and W > 0:
+        if common and self._orthogonalize and update_weights and (not windowed or win is not None) and W > 0:
             ml = int(np.floor(N / 3)) if max_length is None else int(max_length)
             n = N if num is None else int(num)
             x = np.ascontiguousarray(data, dtype=np.float64)  # (the 1-D call works on the float64 copy of a row)
-            out = self._find_periods_orth_batch(default_engine(), x, n, thresh, ml)
+            out = self._find_periods_orth_batch(default_engine(), x, n, thresh, ml, window=win)
         if win is not None and update_weights and on_device_settings and W > 0:
             ml = int(np.floor(N / 3)) if max_length is None else int(max_length)
             n = N if num is None else int(num)
             x = np.ascontiguousarray(data, dtype=np.float64)
             out = self._find_periods_window_batch(default_engine(), x, win, n, thresh, int(min_length), ml)
-        if on_device and W > 0:
+        if (on_device or (win is not None and on_device_settings and not update_weights)) and W > 0:
             x = data if data.dtype in (np.float32, np.float64) else data.astype(np.float64)
             x = np.ascontiguousarray(x)
             ml = int(np.floor(N / 3)) if max_length is None else int(max_length)
             n = N if num is None else int(num)
-            for w, r in enumerate(self._find_periods_device_batch(default_engine(), x, n, thresh, min_length, ml, update_weights)):
+            for w, r in enumerate(self._find_periods_device_batch(default_engine(), x, n, thresh, min_length, ml, update_weights,
+                                                                  window=win)):
                 # all-zero rows (QOPeriods.py:394-406) go to the 1-D call.  A gamma norm is at most rms(x) <=
                 # sum|x| / sqrt(N), so only rows whose first norm is <= 1e-16 need the sum of the 1-D test.
                 if r is not None:
@@ -263,9 +266,10 @@ class QOPeriods(Periods):
         self._output_bases = [r[0] for r in out]
         return out
 
-    def _find_periods_device_batch(self, eng, x, num, thresh, min_length, max_length, update_weights):
+    def _find_periods_device_batch(self, eng, x, num, thresh, min_length, max_length, update_weights, window=None):
         """One ph_qo_find_periods launch for the batch `x` (and one more per capacity doubling, for the rows that
-        needed it).  -> list of (output_bases, residual) or None (the row goes to the 1-D call)."""
+        needed it); with the float64 analysis window `window` (N, ``update_weights=False`` only) the launch is
+        ph_qo_greedy_win.  -> list of (output_bases, residual) or None (the row goes to the 1-D call)."""
         W, N = x.shape
         trunc = bool(self._trunc_to_integer_multiple)
         bound = int(num) * int(max_length)  # a block adds at most max_length rows
@@ -282,7 +286,7 @@ class QOPeriods(Periods):
         while todo.size:
             xs = x if todo.size == W else x[todo]
             per, nrm, keeps, counts, wts, resid, st = eng.qo_find_periods(
-                xs, num, thresh, min_length, max_length, kcap, trunc=trunc, update_weights=update_weights
+                xs, num, thresh, min_length, max_length, kcap, trunc=trunc, update_weights=update_weights, window=window
             )
             if resid.dtype != np.float64:
                 resid = _to_f64(resid)
@@ -372,13 +376,14 @@ class QOPeriods(Periods):
             finish(w, int(counts[w]))
         return out
 
-    def _find_periods_orth_batch(self, eng, x, num, thresh, max_length):
+    def _find_periods_orth_batch(self, eng, x, num, thresh, max_length, window=None):
         """The greedy loop under orthogonal (Muresan-Parks) selection with re-solved weights for the float64
         batch `x`, stepped from the host: per round one ph_qo_orth_select launch on the residuals of the rows still active
         (the period by the normalised orthogonal powers over q < max_length and the norm of the orthogonalised
         projection: ``_strongest_period`` for every row at once; ``min_length`` does not enter, as in the 1-D call) and
-        one ph_qo_fit launch on those rows with their lists so far, instead of three launches, a dense dictionary, its
-        upload and a host solve per row and round.  A row stops when ``rms(reconstruction) > rms(data) * thresh``
+        one ph_qo_fit launch on those rows with their lists so far -- ph_qo_fit_win under the float64 analysis window
+        `window` (N), which only the fit sees -- instead of three launches, a dense dictionary, its upload and a host
+        solve per row and round.  A row stops when ``rms(reconstruction) > rms(data) * thresh``
         fails -- its result is the last fit with one period fewer reported (QOPeriods.py:560-594) -- or after `num`
         rounds.  -> per row (output_bases, residual), or None: the row is rerun whole by the 1-D call (all-zero rows,
         a select or fit that came back not PH_ST_OK -- a non-finite power, a block without rows such as a period picked
@@ -421,7 +426,7 @@ class QOPeriods(Periods):
             gnorm[active, counts[active]] = g
             counts[active] += 1
             fit = self._fit_lists_device(eng, np.ascontiguousarray(x[active]), np.ascontiguousarray(per[active]),
-                                         np.ascontiguousarray(counts[active]), max_length)
+                                         np.ascontiguousarray(counts[active]), max_length, window=window)
             for w, r in zip(active, fit):
                 if r is not None:
                     fits[w] = r

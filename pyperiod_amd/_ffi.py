@@ -62,6 +62,7 @@ SIGNATURES = {
     "ph_ramanujan_norms": [_vp, _vp, _i, _i64, _i, _i, _i, _u, _vp],
     "ph_dict_project": [_vp, _vp, _vp, _i, _i, _u, _vp],
     "ph_qo_find_periods": [_vp, _vp, _i, _i64, _i, _i, _d, _i, _i, _i, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ph_qo_greedy_win": [_vp, _vp, _i, _i64, _i, _vp, _i, _d, _i, _i, _i, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ph_qo_fit": [_vp, _vp, _i, _i64, _i, _pi32, _pi32, _i, _i, _i, _i, _u, _vp, _vp, _vp, _vp],
     "ph_qo_fit_win": [_vp, _vp, _i, _i64, _i, _vp, _pi32, _pi32, _i, _i, _i, _i, _u, _vp, _vp, _vp, _vp],
     "ph_ramanujan_fit": [_vp, _vp, _i, _i64, _i, _i, _i, _d, _i, _i, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp],

@@ -2059,7 +2059,9 @@ int ph_dict_project(ph_ctx* c, const double* x, const double* basis, int rows, i
 }
 
 // ----------------------------------------------------------------------------- QOPeriods.find_periods
-int ph_qo_find_periods(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int num, double thresh,
+// ph_qo_find_periods (window == nullptr) and ph_qo_greedy_win (the fixed-weight loop under `window`): one set of
+// argument checks, tables and staging
+static int qo_find_run(ph_ctx* c, const void* x, int dtype, int64_t W, int N, const double* window, int num, double thresh,
                        int min_length, int max_length, int kcap, unsigned flags, uint32_t* periods,
                        double* norms, int32_t* keeps, int32_t* counts, double* weights, void* residual,
                        int32_t* status) {
@@ -2101,7 +2103,9 @@ int ph_qo_find_periods(ph_ctx* c, const void* x, int dtype, int64_t W, int N, in
   Stage st(c, flags);
   const void* dx;
   void *dper, *dnrm, *dkeep, *dcnt, *dwts, *dres, *dstat;
+  const void* dwin = nullptr;
   PH_TRY(st.in(x, (size_t)W * N * sz, &dx));
+  if (window) PH_TRY(st.in(window, (size_t)N * sizeof(double), &dwin, B_GBUF));
   PH_TRY(st.out(B_OUT0, periods, (size_t)W * num * sizeof(uint32_t), &dper));
   PH_TRY(st.out(B_OUT1, norms, (size_t)W * num * sizeof(double), &dnrm));
   PH_TRY(st.out(B_OUT2, keeps, (size_t)W * num * sizeof(int32_t), &dkeep));
@@ -2110,18 +2114,19 @@ int ph_qo_find_periods(ph_ctx* c, const void* x, int dtype, int64_t W, int N, in
   PH_TRY(st.out(B_WS0, residual, (size_t)W * N * sz, &dres));
   PH_TRY(st.out(B_GEN0, status, (size_t)W * sizeof(int32_t), &dstat));
   const dim3 grid((unsigned)W);
-  const char* name = keep_weights ? "k_qo_greedy" : "k_qo_find";
+  const char* name = window ? "k_qo_greedy_win" : keep_weights ? "k_qo_greedy" : "k_qo_find";
   PH_TRY(dispatch(dtype, lds_window, [&](auto t, auto lw) {
     using T = decltype(t);
     constexpr bool LW = decltype(lw)::value;
     if (keep_weights) {
-      auto kernel = trunc ? ph::k_qo_greedy<T, LW, true> : ph::k_qo_greedy<T, LW, false>;
+      auto kernel = window ? (trunc ? ph::k_qo_greedy<T, LW, true, true> : ph::k_qo_greedy<T, LW, false, true>)
+                           : (trunc ? ph::k_qo_greedy<T, LW, true> : ph::k_qo_greedy<T, LW, false>);
       PH_TRY(allow_lds(kernel, lds));
       ProfScope ps_(c, name);
       hipLaunchKernelGGL(kernel, grid, dim3(c->qo_block), lds, c->stream, (const T*)dx, N, num, thresh, min_length,
                          max_length, geom, plan, n_pass, d_phi, d_off, d_dq, kcap, (T*)gwin,
                          (uint32_t*)c->buf[B_WS1].p, (uint32_t*)dper,
-                         (double*)dnrm, (int*)dkeep, (int*)dcnt, (double*)dwts, (T*)dres, (int*)dstat);
+                         (double*)dnrm, (int*)dkeep, (int*)dcnt, (double*)dwts, (T*)dres, (int*)dstat, (const double*)dwin);
       return (int)PH_OK;
     }
     auto kernel = trunc ? ph::k_qo_find<T, LW, true> : ph::k_qo_find<T, LW>;
@@ -2134,6 +2139,23 @@ int ph_qo_find_periods(ph_ctx* c, const void* x, int dtype, int64_t W, int N, in
   }));
   PH_TRY(launch_check(name));
   return st.finish();
+}
+
+int ph_qo_find_periods(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int num, double thresh,
+                       int min_length, int max_length, int kcap, unsigned flags, uint32_t* periods,
+                       double* norms, int32_t* keeps, int32_t* counts, double* weights, void* residual,
+                       int32_t* status) {
+  return qo_find_run(c, x, dtype, W, N, nullptr, num, thresh, min_length, max_length, kcap, flags, periods, norms, keeps,
+                     counts, weights, residual, status);
+}
+
+int ph_qo_greedy_win(ph_ctx* c, const void* x, int dtype, int64_t W, int N, const double* window, int num, double thresh,
+                     int min_length, int max_length, int kcap, unsigned flags, uint32_t* periods, double* norms,
+                     int32_t* keeps, int32_t* counts, double* weights, void* residual, int32_t* status) {
+  PH_TRY(check_common(c, x, dtype, W, N));
+  if (!window) return fail(PH_E_ARG, "ph_qo_greedy_win: window is NULL (ph_qo_find_periods fits without a window)");
+  return qo_find_run(c, x, dtype, W, N, window, num, thresh, min_length, max_length, kcap, flags | PH_FLAG_KEEP_WEIGHTS,
+                     periods, norms, keeps, counts, weights, residual, status);
 }
 
 int ph_qo_feasible(ph_ctx* c, int dtype, int N, int max_length, int kcap, int* ok) {

@@ -3143,8 +3143,52 @@ __global__ __launch_bounds__(1024) PH_QO_OCC void k_qo_find(const T* __restrict_
 // appended (the residual is left as it was) and one period fewer is reported (QOPeriods.py:163-169).
 // A selection without a positive norm ends with PH_ST_NO_PERIOD (the host loop re-selects the last
 // period there), more rows than kcap with PH_ST_CAP: the caller re-runs such windows on the host.
+//
+// WIN: the fit under one analysis window `win` of N doubles (solve_quadratic(res, A, window=win), QOPeriods.py:779-796,
+// as _dont_update_weights calls it).  A diag(win) A^T of one natural-basis block is diag(den), so
+//   w_j = num_j / den_j,  num_j = sum win[n] res[n],  den_j = sum win[n]  over n = j (mod p),
+// both sums in double from one traversal of the class in the order of the unwindowed fit.  The reconstruction A^T w
+// is not windowed: the stop test and the residual update are those of WIN = false.  A class with den_j == 0 (the
+// reference's matrix is singular there) or a sum that is not finite ends the window with PH_ST_ITER_CAP.  The window
+// is read through L2 (once per round; the sweep reads the residual hundreds of times) and takes no LDS.
 // ======================================================================================
-template <typename T, bool LW, bool TRUNC>
+// num / den of residue j over `n` rows, row order, eight loads of each array ahead of their adds (column_sum's shape).
+template <typename T>
+__device__ __forceinline__ void window_class_sums(const T* __restrict__ xs, const double* __restrict__ win, int j, int p,
+                                                  int n, double& num, double& den) {
+  double sn = 0.0, sd = 0.0;
+  int64_t i = j;
+  int r = 0;
+  for (; r + 8 <= n; r += 8) {
+    double v[8], g[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      g[u] = win[i + (int64_t)u * p];
+      v[u] = (double)xs[i + (int64_t)u * p];
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      sn += g[u] * v[u];
+      sd += g[u];
+    }
+    i += 8 * (int64_t)p;
+  }
+  for (; r < n; ++r) {
+    const double g = win[i];
+    sn += g * (double)xs[i];
+    sd += g;
+    i += p;
+  }
+  num = sn;
+  den = sd;
+}
+
+// A windowed class that cannot be fitted: den == 0, or a sum that is NaN or infinite.
+__device__ __forceinline__ bool window_class_bad(double num, double den) {
+  return den == 0.0 || !(fabs(den) <= 1.7976931348623157e308) || !(fabs(num) <= 1.7976931348623157e308);
+}
+
+template <typename T, bool LW, bool TRUNC, bool WIN = false>
 __global__ __launch_bounds__(1024) void k_qo_greedy(const T* __restrict__ x, int N, int num, double thresh, int p_lo,
                                                     int p_hi, const PGeom* __restrict__ geom,
                                                     const PassPlan* __restrict__ plan, int n_pass,
@@ -3153,7 +3197,7 @@ __global__ __launch_bounds__(1024) void k_qo_greedy(const T* __restrict__ x, int
                                                     uint32_t* __restrict__ seen_ws, uint32_t* __restrict__ periods_out, double* __restrict__ norms_out,
                                                     int* __restrict__ keeps_out, int* __restrict__ counts_out,
                                                     double* __restrict__ weights_out, T* __restrict__ resid_out,
-                                                    int* __restrict__ status_out) {
+                                                    int* __restrict__ status_out, const double* __restrict__ win) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   Carve cv(smem);
   T* work = window_buf<T, LW>(cv, gwin, N + kPad);  // the running residual
@@ -3246,7 +3290,37 @@ __global__ __launch_bounds__(1024) void k_qo_greedy(const T* __restrict__ x, int
     }
     // ---- weights: residue means of the residual (A A^T is diagonal: the samples of each residue)
     const int R = (N + p - 1) / p, nfull = p - (R * p - N);
-    if (R >= 4 * kWave) {  // few residues with many samples: one wavefront per residue
+    if constexpr (WIN) {  // windowed residue means num_j / den_j, same two traversals
+      int bad = 0;
+      if (R >= 4 * kWave) {
+        for (int j = wv; j < rows; j += nw) {
+          const int cnt = j < nfull ? R : R - 1;
+          double sn = 0.0, sd = 0.0;
+          for (int r = lane; r < cnt; r += kWave) {
+            const int64_t n = j + (int64_t)r * p;
+            const double g = win[n];
+            sn += g * (double)work[n];
+            sd += g;
+          }
+          sn = wave_sum(sn);
+          sd = wave_sum(sd);
+          bad |= window_class_bad(sn, sd);
+          if (lane == 0) wout[row0 + j] = sn / sd;
+        }
+      } else {
+        for (int j = tid; j < rows; j += blockDim.x) {
+          double sn, sd;
+          window_class_sums(work, win, j, p, j < nfull ? R : R - 1, sn, sd);
+          bad |= window_class_bad(sn, sd);
+          wout[row0 + j] = sn / sd;
+        }
+      }
+      // uniform over the workgroup: every thread leaves together (the rows written above are zeroed at the end)
+      if (block_sum((double)bad, red) != 0.0) {
+        status = 2;
+        break;
+      }
+    } else if (R >= 4 * kWave) {  // few residues with many samples: one wavefront per residue
       for (int j = wv; j < rows; j += nw) {
         const int cnt = j < nfull ? R : R - 1;
         double sj = 0.0;

@@ -370,13 +370,32 @@ class PeriodEngine:
                    x.size, 0, out.ctypes.data)
         return out
 
-    def qo_find_periods(self, x, num, thresh, min_length=2, max_length=None, kcap=512, trunc=False, update_weights=True):
+    def _window(self, mk, x, window, N):
+        """One float64 analysis window of N samples for a batch: a numpy array, or with torch input a tensor on x's device."""
+        if mk.torch:
+            win = window.contiguous()
+            if win.dtype != mk._t.float64 or win.device != x.device:
+                raise TypeError("window must be a float64 tensor on the device of x")
+        else:
+            win = np.ascontiguousarray(window, dtype=np.float64)
+        if tuple(win.shape) != (N,):
+            raise ValueError(f"window must hold N={N} samples")
+        return win
+
+    def qo_find_periods(self, x, num, thresh, min_length=2, max_length=None, kcap=512, trunc=False, update_weights=True,
+                        window=None):
         """QOPeriods.find_periods (non-orthogonal selection, default test function) for a batch.
         -> periods (W,num) u32, norms (W,num), keeps (W,num) i32, counts (W,2) i32, weights (W,kcap) f64,
         residual (W,N), status (W).  trunc: trunc_to_integer_multiple selection; update_weights=False:
         the fixed-weight loop (PH_FLAG_KEEP_WEIGHTS) -- rows of block b are keeps[b], or periods[b] when
-        keeps[b] == 0, and counts[w, 1] blocks include the re-fitted last one (periodhip.h)."""
+        keeps[b] == 0, and counts[w, 1] blocks include the re-fitted last one (periodhip.h).
+        `window`: None, or with update_weights=False one float64 analysis window of N samples for the whole batch
+        (ph_qo_greedy_win; with torch input a float64 tensor on x's device).  With update_weights=True a window raises
+        ValueError: that loop is stepped from the host (sweep + qo_fit(window=...))."""
         x, code, W, N, fl, mk = self._prep(x)
+        if window is not None and update_weights:
+            raise ValueError("window needs update_weights=False here: the re-solved loop under a window is host-stepped")
+        win = None if window is None else self._window(mk, x, window, N)
         fl |= (_ffi.PH_FLAG_TRUNC if trunc else 0) | (0 if update_weights else _ffi.PH_FLAG_KEEP_WEIGHTS)
         if max_length is None:
             max_length = N // 3
@@ -388,6 +407,11 @@ class PeriodEngine:
         weights = mk.empty((W, int(kcap)), np.float64)
         resid = mk.empty((W, N), self._np_dtype(code))
         status = mk.empty((W,), np.int32)
+        if win is not None:
+            self._call(mk, W, self._lib.ph_qo_greedy_win, mk.addr(x), code, W, N, mk.addr(win), num, float(thresh),
+                       int(min_length), int(max_length), int(kcap), fl, mk.addr(periods), mk.addr(norms), mk.addr(keeps),
+                       mk.addr(counts), mk.addr(weights), mk.addr(resid), mk.addr(status))
+            return periods, norms, keeps, counts, weights, resid, status
         self._call(mk, W, self._lib.ph_qo_find_periods, mk.addr(x), code, W, N, num, float(thresh), int(min_length),
                    int(max_length), int(kcap), fl, mk.addr(periods), mk.addr(norms), mk.addr(keeps), mk.addr(counts),
                    mk.addr(weights), mk.addr(resid), mk.addr(status))
@@ -495,14 +519,7 @@ class PeriodEngine:
                        pcap if ndim == 2 else 0, int(max_period), int(kcap), fl, mk.addr(keeps), mk.addr(weights),
                        mk.addr(resid), mk.addr(status))
             return keeps, weights, resid, status
-        if mk.torch:
-            win = window.contiguous()
-            if win.dtype != mk._t.float64 or win.device != x.device:
-                raise TypeError("window must be a float64 tensor on the device of x")
-        else:
-            win = np.ascontiguousarray(window, dtype=np.float64)
-        if tuple(win.shape) != (N,):
-            raise ValueError(f"window must hold N={N} samples")
+        win = self._window(mk, x, window, N)
         self._call(mk, W, self._lib.ph_qo_fit_win, mk.addr(x), code, W, N, mk.addr(win), mk.addr(per), mk.addr(npr), pcap,
                    pcap if ndim == 2 else 0, int(max_period), int(kcap), fl, mk.addr(keeps), mk.addr(weights),
                    mk.addr(resid), mk.addr(status))

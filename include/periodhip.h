@@ -342,6 +342,14 @@ int ph_qo_plan_info(ph_ctx* ctx, int dtype, int N, int max_length, int kcap, uns
  *                                                                   projection, and max_p doubles in LDS, or the
  *                                                                   window read from HBM / L2 and the work arrays in
  *                                                                   an HBM workspace)
+ *   PH_OP_QO_GET_PERIODS    {ccap, max period}                       default N, N   (ph_qo_get_periods; N and dtype do not
+ *                                                                   enter otherwise).  PH_PLAN_WINDOW (the concatenated
+ *                                                                   input) and PH_PLAN_SECOND (the accumulators) move
+ *                                                                   together: both, two vectors of
+ *                                                                   min(max period, ccap / 2) doubles and as many
+ *                                                                   int32 in LDS while that fits the workgroup's
+ *                                                                   limit, else in an HBM workspace (always under
+ *                                                                   PH_HBM_WINDOW=1)
  * ph_tile_sum and ph_dict_project do not depend on N (LDS of sum(keep) doubles / none) and have no op.
  * out[PH_PLAN_LEN] int32: out[PH_PLAN_KERNELS] kernels launched per call (per round for best_frequency), then one
  * record of PH_PLAN_STRIDE words per kernel at out[PH_PLAN_K0] (m_best step 1, best_frequency spectrum) and
@@ -369,6 +377,7 @@ int ph_qo_plan_info(ph_ctx* ctx, int dtype, int N, int max_length, int kcap, uns
 #define PH_OP_QO_FIT 9
 #define PH_OP_QO_FIT_WIN 10
 #define PH_OP_QO_ORTH_SELECT 11
+#define PH_OP_QO_GET_PERIODS 12
 #define PH_PLAN_KERNELS 0
 #define PH_PLAN_K0 1
 #define PH_PLAN_K1 9
@@ -467,6 +476,39 @@ int ph_orth_powers(ph_ctx* ctx, const void* x, int dtype, int64_t W, int N, int 
 int ph_qo_orth_select(ph_ctx* ctx, const void* x, int dtype, int64_t W, int N, int max_p,
                       const int32_t* orth_off, const int32_t* orth_q, int table_max_p, unsigned flags,
                       int32_t* period, double* norm, double* powers /* (W, max_p) or NULL */, int32_t* status);
+
+/* ---- QOPeriods.get_periods (QOPeriods.py:719-741; concatenate_periods :854-887, stack_pairwise_gcd_subspaces :889-938,
+ * reduce_rows :86-94) for a batch of fitted dictionaries, one launch (k_qo_extract, one workgroup per window), float64.
+ * Window w has counts[w] dictionary blocks: periods[w, a] and rows[w, a] (row stride pcap) in dictionary order, and the
+ * weights row weights[w, :] (stride kcap) is the concatenation of the blocks' weights -- block a starts at
+ * sum(rows[w, :a]).  These are the (periods, keeps, counts[:, 1], weights) ph_qo_find_periods and ph_qo_fit write (with
+ * PH_FLAG_KEEP_WEIGHTS a keeps entry of 0 stands for `period` rows and must be replaced first).  All five arrays
+ * follow PH_FLAG_DEVICE, the int32 lists included, as ph_qo_fit's do.
+ * The result is  actual = c - P c:  c the concatenated segments (segment a = rows[a] weights, then zeros up to
+ * periods[a]) and P the orthogonal projector onto the span of the pairwise gcd rows -- for every pair a < b and shift
+ * i < g = gcd(p_a, p_b): -1 on segment a at j = i (mod g), +1 on segment b at j = i (mod g).  It is evaluated in closed
+ * form by fold-means and Moebius sums, no matrix is built.  out (W, ccap) float64: segment a of window w
+ * starts at sum(periods[w, :a]); the row is zero behind sum(periods[w, :]).
+ * Deliberate deviations from the (repaired) reference -- v1 cannot run the method at all, it passes `self._k` into the
+ * positional `type` of solve_quadratic and dies with TypeError; with that call repaired:
+ *   - every decomp_type ('row reduction', 'lu', 'qr', least squares) is a factorisation of the same projector, and this
+ *     entry point returns the projector's result for all of them.  The reference raises LinAlgError for 'row reduction'
+ *     on a rank-1 matrix (one period, or two coprime periods: reduce_rows hands back a 1-D row) and for 'lu' with three
+ *     or more periods (singular U); those accidents of the factorisation are NOT mirrored.
+ *   - `self._k` is ignored (the reference's regularisation line is commented out).
+ * Mirrored: one period alone gives c - mean(c) (the reference's matrix is ones((1, p))); an empty dictionary is
+ * PH_ST_NO_PERIOD (the reference ends in ValueError).
+ * max_period (<= 2^20) bounds the Moebius tables; ccap in [1, 2^24], kcap in [1, 2^24], pcap in [1, 2^20].  NULL pointers
+ * and range errors return PH_E_ARG before any HIP call.  status (W) int32:
+ *   PH_ST_OK
+ *   PH_ST_NO_PERIOD  counts[w] <= 0
+ *   PH_ST_CAP        counts[w] > pcap, sum(periods) > ccap or sum(rows) > kcap
+ *   PH_ST_ITER_CAP   a period < 1 or > max_period; rows < 0 or rows > period; a period listed twice
+ * Rows that are not PH_ST_OK are zero.  ph_plan_info(PH_OP_QO_GET_PERIODS) says where the work arrays live; both
+ * placements give the same bits (one fixed summation order). */
+int ph_qo_get_periods(ph_ctx* ctx, const int32_t* periods, const int32_t* rows, const int32_t* counts,
+                      int64_t W, int pcap, const double* weights, int kcap, int max_period,
+                      int ccap, unsigned flags, double* out, int32_t* status);
 
 /* ---- QOPeriods building blocks (QOPeriods.py:779-795) -----------------------------------
  * ph_fold_sums: W = A x for natural-basis rows -- out[w, off_k + j] = sum_{n = j (mod p_k)}

@@ -34,6 +34,27 @@ def flatten(t: list) -> list:
     return [item for sublist in t for item in sublist]
 
 
+def reduce_rows(A):
+    """The rows of `A` that are not in the span of the rows above them, in order: a maximal independent subset
+    (QOPeriods.py:86-94, which takes one SVD per row).  Here every row is tested against an orthonormal basis of the
+    rows kept so far (two Gram-Schmidt passes, one matrix-vector product each).  Always 2-D -- the reference hands a
+    rank-1 input back as its 1-D first row, which is what breaks its own ``get_periods``."""
+    A = np.atleast_2d(np.asarray(A, dtype=np.float64))
+    basis = np.zeros((0, A.shape[1]))
+    kept = []
+    tol = max(A.shape) * np.finfo(np.float64).eps
+    for i, row in enumerate(A):
+        scale = np.linalg.norm(row)
+        r = row - basis.T @ (basis @ row)
+        r = r - basis.T @ (basis @ r)
+        n = np.linalg.norm(r)
+        if (n > tol * scale and scale > 0.0) or i == 0:
+            kept.append(i)
+            if n > 0.0:
+                basis = np.vstack((basis, r / n))
+    return A[kept]
+
+
 def normalize(x, level: int = 1):
     """Scale so that max |x| == level (QOPeriods.py:119-145)."""
     x = np.asarray(x)
@@ -730,9 +751,96 @@ class QOPeriods(Periods):
         return (reconstruction, output_bases)
 
     def get_periods(self, weights, dictionary, decomp_type="row reduction"):
-        """QOPeriods.py:719-741 -- raises TypeError in the v1 reference (positional `_k` lands
-        in `type`); out of the hot-path scope (SURVEY.md section 2, #13)."""
-        raise NotImplementedError("QOPeriods.get_periods is outside the accelerated path (broken in reference v1)")
+        """One waveform per period from the weights of a fit (QOPeriods.py:719-741): the dictionary's segments with
+        what two or more periods share redistributed among them, ``c - P c`` with ``P`` the orthogonal projector onto
+        the rows of ``stack_pairwise_gcd_subspaces``.  Returns a tuple of float64 arrays, one of ``int(q)`` samples per
+        key ``q`` of `dictionary` in its order; tiling and adding them reproduces the reconstruction.  The 1-D call is
+        a batch of one through k_qo_extract (ph_qo_get_periods, closed form); there is no CPU path.
+
+        Batch form: `weights` a list / tuple of W arrays and `dictionary` a list / tuple of W dicts -- e.g.
+        ``[b["weights"] for b in qo.output_bases], [b["basis_dictionary"] for b in qo.output_bases]`` after a batched
+        ``find_periods`` -- returns a list of W tuples from one launch.  A row that would raise in the 1-D call makes
+        the batch raise the same exception with the row named.
+
+        Deviations from the reference, which cannot run this method in v1 (``self._k`` lands in the positional ``type``
+        of solve_quadratic: TypeError) and, with that call repaired, raises ``LinAlgError`` for the default
+        ``decomp_type="row reduction"`` on one period or two coprime periods (``reduce_rows`` returns a 1-D row) and for
+        ``"lu"`` with three or more periods (singular ``U``): every `decomp_type` is a factorisation of the same
+        projector, and all of them return the projector's result here; ``self._k`` is ignored as the reference ignores
+        it.  Mirrored: one period alone returns ``c - mean(c)`` and an empty dictionary raises ValueError."""
+        batch = isinstance(dictionary, (list, tuple))
+        dicts = list(dictionary) if batch else [dictionary]
+        wlist = list(weights) if batch else [weights]
+        if len(wlist) != len(dicts):
+            raise ValueError(f"get_periods: {len(wlist)} weight arrays for {len(dicts)} dictionaries")
+        W = len(dicts)
+        if W == 0:
+            return []
+
+        def named(w, exc):
+            return type(exc)(f"get_periods: row {w}: {exc}") if batch else exc
+
+        keys, rows, blocks = [], [], []
+        for w, (wt, d) in enumerate(zip(wlist, dicts)):
+            if len(d) == 0:
+                raise named(w, ValueError("empty dictionary (the reference's matmul has nothing to multiply)"))
+            wt = np.asarray(wt, dtype=np.float64).reshape(-1)
+            per = [int(q) for q in d.keys()]
+            kp, bl, read = [], [], 0
+            for q, r in zip(per, d.values()):
+                # concatenate_periods' own slice semantics: an entry with more rows than its period keeps what the
+                # slice assignment keeps (the all-zero answer {"1": N} with one weight among them)
+                try:
+                    seg = self.concatenate_periods(wt[read:], {str(q): r})
+                except ValueError as exc:
+                    raise named(w, exc) from None
+                k = int(r) if 0 <= int(r) <= q else q
+                read += int(r)
+                kp.append(k)
+                bl.append(seg[:k])
+            keys.append(per)
+            rows.append(kp)
+            blocks.append(np.concatenate(bl) if bl else np.zeros(0))
+        pcap = max(len(k) for k in keys)
+        kcap = max(1, max(b.size for b in blocks))
+        per = np.zeros((W, pcap), dtype=np.int32)
+        rws = np.zeros((W, pcap), dtype=np.int32)
+        wts = np.zeros((W, kcap), dtype=np.float64)
+        counts = np.array([len(k) for k in keys], dtype=np.int32)
+        for w in range(W):
+            per[w, : counts[w]] = np.clip(keys[w], -1, (1 << 20) + 1)  # (out-of-range entries stay out of range)
+            rws[w, : counts[w]] = rows[w]
+            wts[w, : blocks[w].size] = blocks[w]
+        out, status = default_engine().qo_get_periods(per, rws, counts, wts)
+        result = []
+        for w in range(W):
+            if status[w] != _ffi.PH_ST_OK:
+                why = "a repeated period, or a period outside 1 .. 2^20" if status[w] == _ffi.PH_ST_ITER_CAP else f"status {int(status[w])}"
+                raise named(w, ValueError(f"dictionary {dicts[w]!r} cannot be extracted ({why})"))
+            edges = np.concatenate(([0], np.cumsum(keys[w])))
+            result.append(tuple(out[w, a:b].copy() for a, b in zip(edges[:-1], edges[1:])))
+        return result if batch else result[0]
+
+    @staticmethod
+    def stack_pairwise_gcd_subspaces(periods):
+        """The rows whose span get_periods projects out (QOPeriods.py:889-938): for every pair a < b of `periods` and
+        every shift i < g = gcd(p_a, p_b) one row over the concatenated segments with -1 on segment a and +1 on
+        segment b at the indices = i (mod g), zeros elsewhere.  One period gives ones((1, p)), none ones((1, 1)).
+        A host table like ``Pp`` (the device path never builds it)."""
+        per = np.asarray(periods, dtype=np.int64).reshape(-1)
+        if per.size == 0:
+            return np.ones((1, 1))
+        if per.size == 1:
+            return np.ones((1, int(per[0])))
+        ia, ib = np.triu_indices(per.size, 1)  # the pairs in itertools.combinations order
+        g = np.gcd(per[ia], per[ib])
+        pair = np.repeat(np.arange(ia.size), g)  # pair of every row
+        shift = np.arange(g.sum()) - np.repeat(np.cumsum(g) - g, g)  # its shift
+        seg = np.repeat(np.arange(per.size), per)  # segment of every column
+        idx = np.arange(per.sum()) - np.repeat(np.cumsum(per) - per, per)  # index inside it
+        hit = idx[None, :] % g[pair][:, None] == shift[:, None]
+        sign = (seg[None, :] == ib[pair][:, None]).astype(np.float64) - (seg[None, :] == ia[pair][:, None])
+        return np.where(hit, sign, sign * 0.0)
 
     @staticmethod
     def concatenate_periods(weights, dictionary):

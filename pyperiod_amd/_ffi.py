@@ -23,7 +23,8 @@ PH_ST_OK, PH_ST_NO_PERIOD, PH_ST_ITER_CAP, PH_ST_CAP = 0, 1, 2, 3
 PH_QO_LDS_OVERLAY, PH_QO_LDS_BEHIND, PH_QO_HBM = 0, 1, 2  # ph_qo_plan_info placements
 # ph_plan_info: ops, the record layout and its values (periodhip.h)
 (PH_OP_PROJECT, PH_OP_SWEEP, PH_OP_M_BEST, PH_OP_SMALL_TO_LARGE, PH_OP_BEST_CORRELATION, PH_OP_BEST_FREQUENCY,
- PH_OP_RAMANUJAN, PH_OP_ORTH_POWERS, PH_OP_FOLD_SUMS, PH_OP_QO_FIT, PH_OP_QO_FIT_WIN, PH_OP_QO_ORTH_SELECT) = range(12)
+ PH_OP_RAMANUJAN, PH_OP_ORTH_POWERS, PH_OP_FOLD_SUMS, PH_OP_QO_FIT, PH_OP_QO_FIT_WIN, PH_OP_QO_ORTH_SELECT,
+ PH_OP_QO_GET_PERIODS) = range(13)
 PH_PLAN_KERNELS, PH_PLAN_K0, PH_PLAN_K1, PH_PLAN_STRIDE, PH_PLAN_LEN = 0, 1, 9, 8, 17
 (PH_PLAN_VARIANT, PH_PLAN_WINDOW, PH_PLAN_SECOND, PH_PLAN_BLOCK, PH_PLAN_LDS_BYTES, PH_PLAN_SMALL_MEANS, PH_PLAN_WAVES,
  PH_PLAN_PAD) = range(8)
@@ -71,6 +72,7 @@ SIGNATURES = {
     "ph_plan_info": [_vp, _i, _i, _i, _pi32, _i, _u, _pi32],
     "ph_orth_powers": [_vp, _vp, _i, _i64, _i, _i, _i, _u, _vp, _vp, _vp],
     "ph_qo_orth_select": [_vp, _vp, _i, _i64, _i, _i, _pi32, _pi32, _i, _u, _vp, _vp, _vp, _vp],
+    "ph_qo_get_periods": [_vp, _pi32, _pi32, _pi32, _i64, _i, _vp, _i, _i, _i, _u, _vp, _vp],
     "ph_fold_sums": [_vp, _vp, _i, _i64, _i, _pi32, _pi32, _i, _u, _vp],
     "ph_tile_sum": [_vp, _vp, _i64, _i, _pi32, _pi32, _i, _i, _u, _vp],
 }

@@ -909,6 +909,22 @@ int plan_qo_fit_win(const ph_ctx* c, int N, int kcap, int max_period, Plan* pl) 
   return PH_OK;
 }
 
+// k_qo_extract: the concatenated input, the accumulators, the two d-length vectors and the list of shared d
+// (ph::qo_extract_work_bytes, the layout the kernel carves) live in LDS behind the control words while they fit the
+// workgroup's limit and PH_HBM_WINDOW is not set; otherwise in one slice per workgroup of an HBM workspace.  Both move
+// together (`window` = the input, `second` = the accumulators).
+int plan_qo_extract(const ph_ctx* c, int ccap, int max_period, Plan* pl) {
+  if (max_period < 1 || max_period > ph::kFitMaxPeriod)
+    return fail(PH_E_ARG, "ph_qo_get_periods: max_period=%d must be in [1, %d]", max_period, ph::kFitMaxPeriod);
+  if (ccap < 1 || ccap > (1 << 24)) return fail(PH_E_ARG, "ph_qo_get_periods: ccap=%d must be in [1, 2^24]", ccap);
+  KernelPlan& k = pl->k[0];
+  const bool in_lds = !c->hbm_window && ph::qo_extract_lds_bytes(ccap, max_period, true) <= (size_t)c->lds_limit;
+  k.lds = ph::qo_extract_lds_bytes(ccap, max_period, in_lds);
+  k.window = k.second = in_lds ? PH_PLAN_LDS : PH_PLAN_HBM;
+  k.block = kBlock;
+  return PH_OK;
+}
+
 }  // namespace
 
 
@@ -1275,6 +1291,9 @@ int ph_plan_info(ph_ctx* c, int op, int dtype, int N, const int32_t* params, int
       PH_TRY(plan_qo_orth_select(c, dtype, N, max_p, &pl));
       break;
     }
+    case PH_OP_QO_GET_PERIODS:
+      PH_TRY(plan_qo_extract(c, prm(0, N), prm(1, N), &pl));
+      break;
     default:
       return fail(PH_E_ARG, "op %d unknown", op);
   }
@@ -2407,6 +2426,49 @@ int ph_qo_orth_select(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int
     return (int)PH_OK;
   }));
   PH_TRY(launch_check("k_qo_orth_select"));
+  return st.finish();
+}
+
+// ----------------------------------------------------------------------------- QOPeriods.get_periods
+int ph_qo_get_periods(ph_ctx* c, const int32_t* periods, const int32_t* rows, const int32_t* counts, int64_t W, int pcap,
+                      const double* weights, int kcap, int max_period, int ccap, unsigned flags, double* out,
+                      int32_t* status) {
+  if (!c) return fail(PH_E_ARG, "ctx is NULL");
+  if (!periods || !rows || !counts || !weights) return fail(PH_E_ARG, "periods / rows / counts / weights is NULL");
+  if (!out || !status) return fail(PH_E_ARG, "output pointer is NULL");
+  if (W < 1 || W > 0x7fffffffLL / 64) return fail(PH_E_ARG, "W=%lld out of range", (long long)W);
+  if (pcap < 1 || pcap > (1 << 20)) return fail(PH_E_ARG, "pcap=%d must be in [1, 2^20]", pcap);
+  if (kcap < 1 || kcap > (1 << 24)) return fail(PH_E_ARG, "kcap=%d must be in [1, 2^24]", kcap);
+  Plan pl;
+  PH_TRY(plan_qo_extract(c, ccap, max_period, &pl));
+  PH_HIP(hipSetDevice(c->device));
+  const KernelPlan& k = pl.k[0];
+  const int *d_off, *d_d, *d_mu;
+  PH_TRY(prepare_mobius(c, max_period + 1, &d_off, &d_d, &d_mu));  // (the tables cover q < their bound)
+  void *gws, *gidx;
+  PH_TRY(place(c, k.second, B_WS0, (size_t)W * ph::qo_extract_work_bytes(ccap, max_period), &gws));
+  PH_TRY(place(c, PH_PLAN_HBM, B_OUT1, (size_t)W * 2 * ((size_t)pcap + 1) * sizeof(int32_t), &gidx));
+  Stage st(c, flags);
+  const void *dper, *drow, *dcnt, *dwts;
+  void *dout, *dstat;
+  PH_TRY(st.in(periods, (size_t)W * pcap * sizeof(int32_t), &dper, B_GBUF));
+  PH_TRY(st.in(rows, (size_t)W * pcap * sizeof(int32_t), &drow, B_WS1));
+  PH_TRY(st.in(counts, (size_t)W * sizeof(int32_t), &dcnt, B_GWIN));
+  PH_TRY(st.in(weights, (size_t)W * kcap * sizeof(double), &dwts, B_IN));
+  PH_TRY(st.out(B_OUT0, out, (size_t)W * ccap * sizeof(double), &dout));
+  PH_TRY(st.out(B_GEN0, status, (size_t)W * sizeof(int32_t), &dstat));
+  const dim3 grid((unsigned)W);
+  auto launch = [&](auto wl) {
+    auto kernel = ph::k_qo_extract<decltype(wl)::value>;
+    PH_TRY(allow_lds(kernel, k.lds));
+    ProfScope ps_(c, "k_qo_extract");
+    hipLaunchKernelGGL(kernel, grid, dim3(k.block), k.lds, c->stream, (const int*)dper, (const int*)drow, (const int*)dcnt, pcap,
+                       (const double*)dwts, kcap, max_period, ccap, d_off, d_d, d_mu, (int*)gidx, (double*)gws, (double*)dout,
+                       (int*)dstat);
+    return (int)PH_OK;
+  };
+  PH_TRY(k.second == PH_PLAN_LDS ? launch(std::true_type{}) : launch(std::false_type{}));
+  PH_TRY(launch_check("k_qo_extract"));
   return st.finish();
 }
 

@@ -839,4 +839,237 @@ __global__ __launch_bounds__(kBlockWide) void k_qo_orth_select(const T* __restri
   }
 }
 
+// ======================================================================================
+// QOPeriods.get_periods (QOPeriods.py:719-741 with concatenate_periods :854-887 and stack_pairwise_gcd_subspaces
+// :889-938) for a batch of fitted dictionaries: one workgroup per window, float64 throughout.
+//   c       the concatenated segments: segment a holds rows_a weights and p_a - rows_a zeros
+//   actual  c - P c, P the orthogonal projector onto the span of the pairwise gcd rows -- what every decomp_type of the
+//           reference computes through a different factorisation.  Closed form, nothing is factorised: with M_e(x) the
+//           fold-mean of a segment to period e and u_a^d = sum_{e | d} mu(d / e) tile_d(M_e(c_a)) (the part of c_a that is
+//           d-periodic and not periodic with a proper divisor of d), for every d that divides at least two periods
+//             v = sum_{a : d | p_a} u_a^d / sum_{a : d | p_a} (d / p_a),   actual_a += tile((d / p_a) v - u_a^d).
+//           One period alone: the reference's matrix is ones((1, p)), actual = c - mean(c).
+// Order of every sum, the same in both placements (equal bits): d ascending; a in list order; e ascending over the
+// divisors with mu(d / e) != 0 (the tables of prepare_mobius); a fold of `rows` rows is split over L = 2^k lanes (L depends
+// on e, rows and the workgroup width only), lane l adds rows l, l + L, ... in order and the lanes combine by butterfly.
+// Working storage, the one statement of its layout (the kernel carves in this order; the host plans with it): c and
+// actual, ccap doubles each; u and the running sum, dcap doubles each; the list of shared d, dcap int32 --
+// dcap = min(max_period, ccap / 2) bounds the second largest period, hence every shared d and their number.  WL: in LDS
+// behind the control words; otherwise one slice per workgroup of the HBM workspace `gws`.  The segment and weight
+// offsets (2 (pcap + 1) int32 per window) always live in the HBM workspace `gidx`, so the placement depends on ccap
+// and max_period alone.
+// status: 0 ok; 1 K <= 0; 3 K > pcap, sum(p) > ccap or sum(rows) > kcap; 2 a period outside 1 .. max_period, rows
+// outside 0 .. period, or a period listed twice (2 before 3).  Rows that are not ok are zero.  Every loop is bounded;
+// nothing waits on anything outside the workgroup.
+// ======================================================================================
+constexpr int kExtCtl = 4;  // control words: status, shared d's, second largest period (then: a repeated period), sum of the periods
+__host__ __device__ inline int qo_extract_dcap(int ccap, int max_period) {
+  const int d = ccap / 2 < max_period ? ccap / 2 : max_period;
+  return d < 1 ? 1 : d;
+}
+__host__ __device__ inline size_t qo_extract_fixed_bytes() { return carve_bytes(kExtCtl, 4); }
+__host__ __device__ inline size_t qo_extract_work_bytes(int ccap, int max_period) {
+  const size_t d = (size_t)qo_extract_dcap(ccap, max_period);
+  return 2 * carve_bytes((size_t)ccap, 8) + 2 * carve_bytes(d, 8) + carve_bytes(d, 4);
+}
+__host__ __device__ inline size_t qo_extract_lds_bytes(int ccap, int max_period, bool work_in_lds) {
+  return qo_extract_fixed_bytes() + (work_in_lds ? qo_extract_work_bytes(ccap, max_period) : 0);
+}
+
+template <bool WL>
+__global__ __launch_bounds__(kBlock) void k_qo_extract(const int* __restrict__ periods, const int* __restrict__ rows,
+                                                       const int* __restrict__ counts, int pcap,
+                                                       const double* __restrict__ weights, int kcap, int max_period, int ccap,
+                                                       const int* __restrict__ mob_off, const int* __restrict__ mob_d,
+                                                       const int* __restrict__ mob_mu, int* __restrict__ gidx,
+                                                       double* __restrict__ gws, double* __restrict__ out,
+                                                       int* __restrict__ status_out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int64_t w = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int lane = tid & (kWave - 1);
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int nthr = blockDim.x;
+  Carve cv(smem);
+  int* ctl = cv.take<int>(kExtCtl);
+  const int dcap = qo_extract_dcap(ccap, max_period);
+  Carve wk(WL ? smem + qo_extract_fixed_bytes()
+              : reinterpret_cast<unsigned char*>(gws) + w * (int64_t)qo_extract_work_bytes(ccap, max_period));
+  double* cin = wk.take<double>(ccap);  // the concatenated input segments
+  double* acc = wk.take<double>(ccap);  // the output accumulators
+  double* uv = wk.take<double>(dcap);   // u_a^d of the current (d, a)
+  double* sv = wk.take<double>(dcap);   // sum_a u_a^d, then v
+  int* dl = wk.take<int>(dcap);         // the d shared by at least two periods, ascending
+  int* soff = gidx + w * 2 * ((int64_t)pcap + 1);  // first element of segment a
+  int* woff = soff + pcap + 1;                     // first weight of block a
+  const int* per = periods + w * (int64_t)pcap;
+  const int* rws = rows + w * (int64_t)pcap;
+  const double* wrow = weights + w * (int64_t)kcap;
+  double* orow = out + w * (int64_t)ccap;
+  auto sync = [] {
+    __threadfence_block();
+    __syncthreads();
+  };
+  auto leave = [&](int st) {  // (uniform over the workgroup)
+    for (int n = tid; n < ccap; n += nthr) orow[n] = 0.0;
+    if (tid == 0) status_out[w] = st;
+  };
+
+  const int K = counts[w];
+  if (K <= 0 || K > pcap) {
+    leave(K <= 0 ? 1 : 3);
+    return;
+  }
+  // ---- the lists: ranges, capacities, offsets, the second largest period
+  if (tid == 0) {
+    int64_t sp = 0, sr = 0;
+    int bad = 0, cap = 0, m1 = 0, m2 = 0;
+    for (int a = 0; a < K; ++a) {
+      const int p = per[a], r = rws[a];
+      if (p < 1 || p > max_period || r < 0 || r > p) {
+        bad = 1;
+        continue;
+      }
+      if (!cap) {
+        soff[a] = (int)sp;
+        woff[a] = (int)sr;
+      }
+      sp += p;  // (<= 2^20 entries of <= 2^20: no overflow)
+      sr += r;
+      if (sp > ccap || sr > kcap) cap = 1;
+      if (p > m1) {
+        m2 = m1;
+        m1 = p;
+      } else if (p > m2) {
+        m2 = p;
+      }
+    }
+    ctl[0] = bad ? 2 : cap ? 3 : 0;
+    ctl[1] = 0;
+    ctl[2] = m2;
+    ctl[3] = cap ? 0 : (int)sp;
+  }
+  sync();
+  if (ctl[0] != 0) {
+    leave(ctl[0]);
+    return;
+  }
+  const int total = ctl[3];
+  // ---- the d that divide at least two periods (all <= the second largest period), repeated periods: one wavefront
+  if (K >= 2 && wv == 0) {
+    const int dmax = ctl[2];
+    int cnt = 0, dup = 0;
+    for (int d0 = 1; d0 <= dmax; d0 += kWave) {
+      const int d = d0 + lane;
+      int nd = 0, ne = 0;
+      if (d <= dmax)
+        for (int a = 0; a < K; ++a) {
+          const int p = per[a];
+          nd += p % d == 0;
+          ne += p == d;
+        }
+      dup |= ne >= 2;
+      const bool sel = nd >= 2;
+      const unsigned long long mask = __ballot(sel);
+      if (sel) dl[cnt + __popcll(mask & ((1ull << lane) - 1ull))] = d;  // (fewer than dmax <= dcap entries)
+      cnt += __popcll(mask);
+    }
+    const bool any_dup = __ballot(dup) != 0ull;
+    if (lane == 0) {
+      ctl[1] = cnt;
+      ctl[2] = any_dup ? 1 : 0;  // (only this wavefront read the second largest period there)
+    }
+  }
+  sync();
+  if (K >= 2 && ctl[2] != 0) {
+    leave(2);
+    return;
+  }
+  // ---- concatenate (QOPeriods.py:879-887)
+  for (int a = 0; a < K; ++a) {
+    const int p = per[a], r = rws[a], so = soff[a], wo = woff[a];
+    for (int j = tid; j < p; j += nthr) {
+      const double v = j < r ? wrow[wo + j] : 0.0;
+      cin[so + j] = v;
+      acc[so + j] = v;
+    }
+  }
+  sync();
+  // fold-means of a segment of p doubles to period e: consume(i, mean of ca[i::e]) from one thread per residue
+  auto fold_means = [&](const double* __restrict__ ca, int p, int e, auto&& consume) {
+    const int nrows = p / e;
+    int lg = 0;
+    while (lg < 6 && (2 << lg) * e <= nthr && (2 << lg) <= nrows) ++lg;
+    const int L = 1 << lg, l = tid & (L - 1), per_pass = nthr >> lg;
+    for (int base = 0; base < e; base += per_pass) {  // (uniform trip count)
+      const int i = base + (tid >> lg);
+      double s = 0.0;
+      if (i < e) {
+        const double* ptr = ca + i + (int64_t)l * e;
+        const int64_t stride = (int64_t)e << lg;
+        for (int r = l; r < nrows; r += L) {
+          s += *ptr;
+          ptr += stride;
+        }
+      }
+      for (int off = 1; off < L; off <<= 1) s += __shfl_xor(s, off, kWave);
+      if (i < e && l == 0) consume(i, s / (double)nrows);
+    }
+  };
+  // dst[n] += scale * src[n mod d] for n < p
+  auto tile_add = [&](double* __restrict__ dst, const double* __restrict__ src, int p, int d, double scale) {
+    int r = tid % d;
+    const int step = nthr % d;
+    for (int n = tid; n < p; n += nthr) {
+      dst[n] = fma(scale, src[r], dst[n]);
+      r += step;
+      r -= r >= d ? d : 0;
+    }
+  };
+  if (K == 1) {  // ones((1, p)): actual = c - mean(c)
+    fold_means(cin, per[0], 1, [&](int, double m) { uv[0] = m; });
+    sync();
+    tile_add(acc, uv, per[0], 1, -1.0);
+  }
+  const int nshared = K >= 2 ? ctl[1] : 0;
+  for (int s = 0; s < nshared; ++s) {
+    const int d = dl[s];
+    const int k0 = mob_off[d], k1 = mob_off[d + 1];
+    double den = 0.0;
+    for (int a = 0; a < K; ++a) {
+      const int p = per[a];
+      if (p % d == 0) den += (double)d / (double)p;
+    }
+    for (int j = tid; j < d; j += nthr) sv[j] = 0.0;
+    for (int a = 0; a < K; ++a) {
+      const int p = per[a];
+      if (p % d != 0) continue;  // (uniform)
+      for (int j = tid; j < d; j += nthr) uv[j] = 0.0;
+      sync();
+      for (int k = k0; k < k1; ++k) {
+        const int e = mob_d[k];
+        const double mu = (double)mob_mu[k];
+        fold_means(cin + soff[a], p, e, [&](int i, double m) {
+          const double val = mu * m;
+          for (int n = i; n < d; n += e) uv[n] += val;
+        });
+        sync();
+      }
+      for (int j = tid; j < d; j += nthr) sv[j] += uv[j];
+      tile_add(acc + soff[a], uv, p, d, -1.0);
+      sync();
+    }
+    for (int j = tid; j < d; j += nthr) sv[j] = sv[j] / den;
+    sync();
+    for (int a = 0; a < K; ++a) {
+      const int p = per[a];
+      if (p % d == 0) tile_add(acc + soff[a], sv, p, d, (double)d / (double)p);
+    }
+    sync();
+  }
+  sync();
+  for (int n = tid; n < ccap; n += nthr) orow[n] = n < total ? acc[n] : 0.0;
+  if (tid == 0) status_out[w] = 0;
+}
+
 }  // namespace ph

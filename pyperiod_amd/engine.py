@@ -445,7 +445,8 @@ class PeriodEngine:
                  "small_to_large": _ffi.PH_OP_SMALL_TO_LARGE, "best_correlation": _ffi.PH_OP_BEST_CORRELATION,
                  "best_frequency": _ffi.PH_OP_BEST_FREQUENCY, "ramanujan": _ffi.PH_OP_RAMANUJAN,
                  "orth_powers": _ffi.PH_OP_ORTH_POWERS, "fold_sums": _ffi.PH_OP_FOLD_SUMS, "qo_fit": _ffi.PH_OP_QO_FIT,
-                 "qo_fit_win": _ffi.PH_OP_QO_FIT_WIN, "qo_orth_select": _ffi.PH_OP_QO_ORTH_SELECT}
+                 "qo_fit_win": _ffi.PH_OP_QO_FIT_WIN, "qo_orth_select": _ffi.PH_OP_QO_ORTH_SELECT,
+                 "qo_get_periods": _ffi.PH_OP_QO_GET_PERIODS}
 
     def plan_info(self, op, n, params=(), dtype=np.float64, trunc=False, orth=False):
         """-> tuple of one KernelPlan per kernel the entry point `op` ("project", "sweep", "m_best", ...) would launch
@@ -579,6 +580,53 @@ class PeriodEngine:
         self._call(mk, W, self._lib.ph_qo_orth_select, mk.addr(x), code, W, N, max_p, keep[2], keep[3], keep[4],
                    fl | (_ffi.PH_FLAG_TRUNC if trunc else 0), mk.addr(period), mk.addr(norm), mk.addr(pows), mk.addr(status))
         return (period, norm, status, pows) if want_powers else (period, norm, status)
+
+    def qo_get_periods(self, periods, rows, counts, weights, max_period=None, ccap=None):
+        """QOPeriods.get_periods for a batch of fitted dictionaries, one launch (ph_qo_get_periods):
+        -> out (W, ccap) f64 -- segment a of row w (periods[w, a] doubles) starts at sum(periods[w, :a]), zeros behind
+        the last -- and status (W) i32.
+        `periods`, `rows` (W, pcap) int32: the blocks of every dictionary in order, `counts` (W) how many of them are
+        used; `weights` (W, kcap) float64, block a of row w at sum(rows[w, :a]).  numpy arrays, or torch tensors on the
+        engine's device (on torch's current stream; outputs are then tensors): the periods, keeps, counts[:, 1] and
+        weights of qo_find_periods / qo_fit can be passed on as they are (with update_weights=False a keeps entry of 0
+        means `period` rows and has to be replaced first).  `ccap` defaults to the largest sum of periods of the batch
+        and `max_period` to the largest period (numpy) or ccap (torch); computing ccap from device tensors reads one
+        word back, so pass it to stay asynchronous."""
+        if _is_torch(weights):
+            wts, code, W, kcap, fl, mk = self._prep(weights)
+            t = mk._t
+            per, rws, cnt = periods.contiguous(), rows.contiguous(), counts.contiguous()
+            for a in (per, rws, cnt):
+                if a.dtype != t.int32 or a.device != wts.device:
+                    raise TypeError("periods, rows and counts must be int32 tensors on the device of weights")
+            shapes = tuple(per.shape), tuple(rws.shape), tuple(cnt.shape)
+            if ccap is None:
+                used = t.arange(per.shape[1], device=per.device)[None, :] < cnt[:, None]
+                ccap = max(1, int((per.clamp(min=0).to(t.int64) * used).sum(dim=1).max().item())) if W else 1
+            if max_period is None:
+                max_period = min(int(ccap), 1 << 20)
+        else:
+            wts, code, W, kcap, fl, mk = self._prep(np.asarray(weights, dtype=np.float64))
+            per = np.ascontiguousarray(periods, dtype=np.int32)
+            rws = np.ascontiguousarray(rows, dtype=np.int32)
+            cnt = np.ascontiguousarray(counts, dtype=np.int32)
+            shapes = per.shape, rws.shape, cnt.shape
+            if per.ndim == 2 and per.shape == rws.shape and cnt.shape == (W,):
+                used = np.arange(per.shape[1])[None, :] < cnt[:, None]
+                if ccap is None:
+                    ccap = max(1, int((np.clip(per, 0, None).astype(np.int64) * used).sum(axis=1).max())) if W else 1
+                if max_period is None:
+                    max_period = int(min(max(1, (per * used).max() if per.size else 1), 1 << 20))
+        if code != _ffi.PH_F64:
+            raise TypeError("weights must be float64")
+        if len(shapes[0]) != 2 or shapes[0] != shapes[1] or shapes[0][0] != W or shapes[2] != (W,) or shapes[0][1] < 1:
+            raise ValueError("periods and rows must be (W, pcap) with pcap >= 1, counts (W,), weights (W, kcap)")
+        pcap, ccap = int(shapes[0][1]), int(ccap)
+        out = mk.empty((W, ccap), np.float64)
+        status = mk.empty((W,), np.int32)
+        self._call(mk, W, self._lib.ph_qo_get_periods, mk.addr(per), mk.addr(rws), mk.addr(cnt), W, pcap, mk.addr(wts),
+                   int(kcap), int(max_period), ccap, fl, mk.addr(out), mk.addr(status))
+        return out, status
 
     def fold_sums(self, x, p_list, keep):
         """W = A x for natural-basis rows (QOPeriods.py:782): (W, sum(keep)) float64."""

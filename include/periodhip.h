@@ -59,6 +59,7 @@ extern "C" {
 #define PH_FLAG_DEVICE 8u /* array arguments are device pointers, call is asynchronous */
 #define PH_FLAG_NOSYNC 16u /* with PH_FLAG_DEVICE: never synchronise, not even to report PH_E_CAP */
 #define PH_FLAG_KEEP_WEIGHTS 32u /* ph_qo_find_periods: update_weights=False (QOPeriods.py:645-714) */
+#define PH_FLAG_OLA_NORM 64u /* ph_overlap_add: divide by the overlap-added window product */
 
 /* sweep modes */
 #define PH_SWEEP_NORM 0       /* periodic_norm(project(x,p))        Periods.py:507-508 */
@@ -519,6 +520,30 @@ int ph_fold_sums(ph_ctx* ctx, const void* x, int dtype, int64_t W, int N,
                  double* out);
 int ph_tile_sum(ph_ctx* ctx, const double* wts, int64_t W, int N, const int32_t* p_list,
                 const int32_t* keep, int n_p, int dtype, unsigned flags, void* out);
+
+/* ---- short-time analysis: frame a long signal, overlap-add a framed result (no counterpart in the reference, which
+ * takes one window per call) ----------------------------------------------------------------------
+ * ph_frames: frames (W, N) row-major contiguous of out_dtype from a signal of L samples of in_dtype:
+ *   frames[f, i] = (out_dtype)((double)signal[f * hop + i] * window[i])   if f * hop + i < L, else 0
+ * window (N) float64 or NULL (no product: a same-dtype call copies exactly).  hop >= 1, hop > N is allowed; W >= 1 and
+ * (W - 1) * hop < L, so every frame starts inside the signal.  W * N may exceed 2^31.  The host-pointer form uploads
+ * the signal once (L elements, not W * N).  One launch (k_frames): 16-byte stores whenever `frames` is 16-byte aligned,
+ * for every N; scalar accesses otherwise.
+ * ph_overlap_add: y (W, K, N) of dtype -> out (L) float64,
+ *   num[n] = sum_f sum_{k < K_f} win_s[n - f * hop] * y[f, k, n - f * hop]
+ *   den[n] = sum_f win_a[n - f * hop] * win_s[n - f * hop]          both over the frames f < W with 0 <= n - f * hop < N
+ *   out[n] = num[n], or with PH_FLAG_OLA_NORM num[n] / den[n] where den[n] > 0 and exactly 0.0 elsewhere (samples no frame
+ *   covers, or a zero window product).
+ * K_f = counts[f] clipped to [0, K] (counts (W) int32 or NULL = K); rows k >= K_f are never read.  win_a / win_s (N) float64
+ * or NULL = all ones.  One launch (k_overlap_add): one lane per output sample, float64 accumulation in one fixed order,
+ * no atomics -- the same bits on every run.
+ * Both: every array follows PH_FLAG_DEVICE (window, counts included); PH_E_ARG for a NULL ctx / signal / frames / y / out,
+ * an unknown dtype, a size < 1, or (W - 1) * hop >= L, before any HIP call. */
+int ph_frames(ph_ctx* ctx, const void* signal, int in_dtype, int64_t L, int N, int hop, int64_t W,
+              const double* window /* N or NULL */, int out_dtype, unsigned flags, void* frames);
+int ph_overlap_add(ph_ctx* ctx, const void* y, int dtype, int64_t W, int K, int N, int hop, int64_t L,
+                   const int32_t* counts /* W or NULL */, const double* win_a, const double* win_s,
+                   unsigned flags /* PH_FLAG_DEVICE | PH_FLAG_OLA_NORM */, double* out);
 
 #ifdef __cplusplus
 }

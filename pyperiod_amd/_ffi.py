@@ -17,6 +17,7 @@ PH_OK, PH_E_ARG, PH_E_HIP, PH_E_NOMEM, PH_E_CAP, PH_E_UNSUPPORTED = 0, -1, -2, -
 PH_F64, PH_F32 = 0, 1
 PH_FLAG_TRUNC, PH_FLAG_ORTH, PH_FLAG_SINGLE, PH_FLAG_DEVICE, PH_FLAG_NOSYNC = 1, 2, 4, 8, 16
 PH_FLAG_KEEP_WEIGHTS = 32  # ph_qo_find_periods: update_weights=False
+PH_FLAG_OLA_NORM = 64  # ph_overlap_add: divide by the overlap-added window product
 PH_STREAM_DEFAULT = 1  # ph_set_stream handle of the device default stream (its real handle, 0, means "own stream")
 PH_SWEEP_NORM, PH_SWEEP_NORM_GAMMA, PH_SWEEP_MAXABS = 0, 1, 2
 PH_ST_OK, PH_ST_NO_PERIOD, PH_ST_ITER_CAP, PH_ST_CAP = 0, 1, 2, 3
@@ -75,6 +76,8 @@ SIGNATURES = {
     "ph_qo_get_periods": [_vp, _pi32, _pi32, _pi32, _i64, _i, _vp, _i, _i, _i, _u, _vp, _vp],
     "ph_fold_sums": [_vp, _vp, _i, _i64, _i, _pi32, _pi32, _i, _u, _vp],
     "ph_tile_sum": [_vp, _vp, _i64, _i, _pi32, _pi32, _i, _i, _u, _vp],
+    "ph_frames": [_vp, _vp, _i, _i64, _i, _i, _i64, _vp, _i, _u, _vp],
+    "ph_overlap_add": [_vp, _vp, _i, _i64, _i, _i, _i, _i64, _pi32, _vp, _vp, _u, _vp],
 }
 
 

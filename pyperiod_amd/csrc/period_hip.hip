@@ -14,6 +14,7 @@
 #include "../../include/periodhip.h"
 #include "ph_kernels.h"
 #include "ph_fit.h"
+#include "ph_frames.h"
 
 namespace {
 
@@ -2469,6 +2470,105 @@ int ph_qo_get_periods(ph_ctx* c, const int32_t* periods, const int32_t* rows, co
   };
   PH_TRY(k.second == PH_PLAN_LDS ? launch(std::true_type{}) : launch(std::false_type{}));
   PH_TRY(launch_check("k_qo_extract"));
+  return st.finish();
+}
+
+
+}  // extern "C"
+
+// ----------------------------------------------------------------------------- short-time framing / overlap-add
+namespace {
+
+// checks shared by ph_frames and ph_overlap_add: positive sizes, every frame starts inside the signal, and the element
+// count W * rows * N (times 8 bytes) stays inside int64 -- it may well pass 2^31
+int check_framing(const char* what, int64_t W, int rows, int N, int hop, int64_t L) {
+  if (W < 1 || rows < 1 || N < 1 || hop < 1 || L < 1)
+    return fail(PH_E_ARG, "%s: W=%lld, K=%d, N=%d, hop=%d, L=%lld must all be >= 1", what, (long long)W, rows, N, hop,
+                (long long)L);
+  if (W - 1 > (L - 1) / hop)
+    return fail(PH_E_ARG, "%s: frame %lld starts at or behind the end of the signal ((W - 1) * hop >= L = %lld)", what,
+                (long long)(W - 1), (long long)L);
+  if (W > (INT64_MAX / 8) / ((int64_t)rows * N)) return fail(PH_E_ARG, "%s: W * K * N does not fit 64 bits", what);
+  return PH_OK;
+}
+
+// workgroups of a flat grid-stride kernel over `items` lanes' worth of work
+unsigned flat_grid(const ph_ctx* c, int64_t items) {
+  const int64_t want = (items + ph::kFramesBlock - 1) / ph::kFramesBlock;
+  const int64_t cap = (int64_t)std::max(1, c->num_cu) * 64;
+  return (unsigned)std::max<int64_t>(1, std::min(want, cap));
+}
+
+template <typename Tin, typename Tout>
+void launch_frames(ph_ctx* c, const void* ds, int64_t L, int N, int hop, int64_t W, const double* dwin, void* dout) {
+  constexpr int V = 16 / (int)sizeof(Tout);
+  const int64_t total = W * (int64_t)N;
+  ProfScope ps_(c, "k_frames");
+  if (reinterpret_cast<uintptr_t>(dout) % 16 == 0)
+    hipLaunchKernelGGL((ph::k_frames<Tin, Tout, V>), dim3(flat_grid(c, total / V)),
+                       dim3(ph::kFramesBlock), 0, c->stream, (const Tin*)ds, L, N, hop, W, dwin, (Tout*)dout);
+  else
+    hipLaunchKernelGGL((ph::k_frames<Tin, Tout, 1>), dim3(flat_grid(c, total)), dim3(ph::kFramesBlock), 0, c->stream,
+                       (const Tin*)ds, L, N, hop, W, dwin, (Tout*)dout);
+}
+
+}  // namespace
+
+extern "C" {
+
+int ph_frames(ph_ctx* c, const void* signal, int in_dtype, int64_t L, int N, int hop, int64_t W, const double* window,
+              int out_dtype, unsigned flags, void* frames) {
+  if (!c) return fail(PH_E_ARG, "ctx is NULL");
+  if (!signal || !frames) return fail(PH_E_ARG, "signal / frames is NULL");
+  if ((in_dtype != PH_F64 && in_dtype != PH_F32) || (out_dtype != PH_F64 && out_dtype != PH_F32))
+    return fail(PH_E_ARG, "in_dtype and out_dtype must be PH_F64 or PH_F32");
+  PH_TRY(check_framing("ph_frames", W, 1, N, hop, L));
+  PH_HIP(hipSetDevice(c->device));
+  Stage st(c, flags);
+  const void *ds, *dwin = nullptr;
+  void* dout;
+  PH_TRY(st.in(signal, (size_t)L * elem_size(in_dtype), &ds));  // the signal once: L elements, not W * N
+  if (window) PH_TRY(st.in(window, (size_t)N * sizeof(double), &dwin, B_GWIN));
+  PH_TRY(st.out(B_OUT0, frames, (size_t)W * N * elem_size(out_dtype), &dout));
+  if (in_dtype == PH_F64 && out_dtype == PH_F64)
+    launch_frames<double, double>(c, ds, L, N, hop, W, (const double*)dwin, dout);
+  else if (in_dtype == PH_F64)
+    launch_frames<double, float>(c, ds, L, N, hop, W, (const double*)dwin, dout);
+  else if (out_dtype == PH_F64)
+    launch_frames<float, double>(c, ds, L, N, hop, W, (const double*)dwin, dout);
+  else
+    launch_frames<float, float>(c, ds, L, N, hop, W, (const double*)dwin, dout);
+  PH_TRY(launch_check("k_frames"));
+  return st.finish();
+}
+
+int ph_overlap_add(ph_ctx* c, const void* y, int dtype, int64_t W, int K, int N, int hop, int64_t L,
+                   const int32_t* counts, const double* win_a, const double* win_s, unsigned flags, double* out) {
+  if (!c) return fail(PH_E_ARG, "ctx is NULL");
+  if (!y || !out) return fail(PH_E_ARG, "y / out is NULL");
+  if (dtype != PH_F64 && dtype != PH_F32) return fail(PH_E_ARG, "dtype must be PH_F64 or PH_F32");
+  PH_TRY(check_framing("ph_overlap_add", W, K, N, hop, L));
+  PH_HIP(hipSetDevice(c->device));
+  Stage st(c, flags);
+  const void *dy, *dcnt = nullptr, *dwa = nullptr, *dws = nullptr;
+  void* dout;
+  PH_TRY(st.in(y, (size_t)W * K * N * elem_size(dtype), &dy));
+  if (counts) PH_TRY(st.in(counts, (size_t)W * sizeof(int32_t), &dcnt, B_GBUF));
+  if (win_a) PH_TRY(st.in(win_a, (size_t)N * sizeof(double), &dwa, B_GWIN));
+  if (win_s) PH_TRY(st.in(win_s, (size_t)N * sizeof(double), &dws, B_WS1));
+  PH_TRY(st.out(B_OUT0, out, (size_t)L * sizeof(double), &dout));
+  const dim3 grid(flat_grid(c, L));
+  const int norm = (flags & PH_FLAG_OLA_NORM) ? 1 : 0;
+  {
+    ProfScope ps_(c, "k_overlap_add");
+    if (dtype == PH_F64)
+      hipLaunchKernelGGL(ph::k_overlap_add<double>, grid, dim3(ph::kFramesBlock), 0, c->stream, (const double*)dy, W, K, N,
+                         hop, L, (const int*)dcnt, (const double*)dwa, (const double*)dws, norm, (double*)dout);
+    else
+      hipLaunchKernelGGL(ph::k_overlap_add<float>, grid, dim3(ph::kFramesBlock), 0, c->stream, (const float*)dy, W, K, N,
+                         hop, L, (const int*)dcnt, (const double*)dwa, (const double*)dws, norm, (double*)dout);
+  }
+  PH_TRY(launch_check("k_overlap_add"));
   return st.finish();
 }
 

@@ -1,0 +1,149 @@
+// Short-time framing and overlap-add on the device: k_frames cuts a signal of L samples into the (W, N) batch every
+// other entry point takes, k_overlap_add folds a (W, K, N) result back onto the L samples of the signal.  Both are
+// memory-bound element-wise kernels without LDS; all index arithmetic is int64 (f * hop and f * N pass 2^31 for real
+// recordings).  Included by period_hip.hip behind ph_fit.h.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace ph {
+
+constexpr int kFramesBlock = 256;
+
+template <typename T, int V>
+struct alignas(sizeof(T) * V) FrameVec {
+  T v[V];
+};
+
+// ======================================================================================
+// frames[f, i] = Tout((double)s[f * hop + i] * win[i]) if f * hop + i < L else 0          (win == nullptr: no product,
+// a same-dtype copy is exact).  frames is (W, N) row-major contiguous = one flat array of W * N elements, and the kernel
+// walks it flat: a lane owns V consecutive elements, V * sizeof(Tout) = 16 bytes, and stores them with one 16-byte
+// access.  A flat vector is 16-byte aligned whenever the base pointer is, whatever N is (an odd N only makes it straddle
+// two rows, which costs a wrap of (f, i) and nothing else), so the host picks V > 1 exactly when `frames` is 16-byte
+// aligned and V = 1 -- every access scalar, correct for every N, hop and alignment -- otherwise.  The elements behind the
+// last whole vector (W * N mod V of them) are stored one by one.
+// The source address s + f * hop + i has no alignment to speak of (odd hop, float32): the V samples are read with one
+// vector load only when they lie in one row, inside the signal, and the real address is aligned to the vector;
+// otherwise one by one.  Overlapping frames re-read the signal from L2 (the signal is hop / N of the output's size).
+// Grid: flat over the vectors with a grid-stride loop, so W never sits in a 16-bit grid dimension; (f, i) of a lane's
+// first vector costs one 64-bit division, every further step adds the precomputed quotient and remainder of the stride.
+// ======================================================================================
+template <typename Tin, typename Tout, int V>
+__global__ __launch_bounds__(kFramesBlock) void k_frames(const Tin* __restrict__ s, int64_t L, int N, int hop, int64_t W,
+                                                        const double* __restrict__ win, Tout* __restrict__ frames) {
+  const int64_t total = W * (int64_t)N;
+  const int64_t n_vec = total / V;
+  const int64_t stride = (int64_t)gridDim.x * kFramesBlock;  // in vectors
+  const int64_t step = stride * V;                           // in elements
+  const int64_t step_f = step / N;
+  const int step_i = (int)(step % N);
+  int64_t vec = (int64_t)blockIdx.x * kFramesBlock + threadIdx.x;
+  int64_t f = 0;
+  int i = 0;
+  if (vec < n_vec) {
+    const int64_t e0 = vec * V;
+    f = e0 / N;
+    i = (int)(e0 - f * N);
+  }
+  for (; vec < n_vec; vec += stride) {
+    FrameVec<Tout, V> o;
+    const int64_t src = f * hop + i;
+    bool done = false;
+    if constexpr (V > 1) {
+      // one row, inside the signal, and the real source address aligned to the vector
+      if (i + V <= N && src + V <= L && (reinterpret_cast<uintptr_t>(s + src) % (sizeof(Tin) * V)) == 0) {
+        const FrameVec<Tin, V> in = *reinterpret_cast<const FrameVec<Tin, V>*>(s + src);
+#pragma unroll
+        for (int j = 0; j < V; ++j) o.v[j] = win ? (Tout)((double)in.v[j] * win[i + j]) : (Tout)(double)in.v[j];
+        done = true;
+      }
+    }
+    if (!done) {
+      int64_t ff = f;
+      int ii = i;
+#pragma unroll
+      for (int j = 0; j < V; ++j) {
+        const int64_t a = ff * hop + ii;
+        Tout r = (Tout)0;
+        if (a < L) r = win ? (Tout)((double)s[a] * win[ii]) : (Tout)(double)s[a];
+        o.v[j] = r;
+        if (++ii == N) {
+          ii = 0;
+          ++ff;
+        }
+      }
+    }
+    *reinterpret_cast<FrameVec<Tout, V>*>(frames + vec * V) = o;
+    f += step_f;
+    i += step_i;
+    if (i >= N) {
+      i -= N;
+      ++f;
+    }
+  }
+  // the elements behind the last whole vector
+  if constexpr (V > 1) {
+    const int64_t e = n_vec * V + (int64_t)blockIdx.x * kFramesBlock + threadIdx.x;
+    if (e < total) {
+      const int64_t ff = e / N;
+      const int ii = (int)(e - ff * N);
+      const int64_t a = ff * hop + ii;
+      Tout r = (Tout)0;
+      if (a < L) r = win ? (Tout)((double)s[a] * win[ii]) : (Tout)(double)s[a];
+      frames[e] = r;
+    }
+  }
+}
+
+// ======================================================================================
+// Overlap-add in the gather form: y (W, K, N) of T -> out (L) float64.
+//   num[n] = sum_f sum_{k < K_f} ws[n - f hop] * y[f, k, n - f hop]     over the frames f < W with 0 <= n - f hop < N
+//   den[n] = sum_f wa[n - f hop] * ws[n - f hop]                        over the same frames
+//   out[n] = num[n], or with `norm`: num[n] / den[n] where den[n] > 0 and exactly 0.0 elsewhere
+// K_f = counts[f] clipped to [0, K] (counts == nullptr: K); rows k >= K_f are never read.  wa / ws == nullptr: all ones.
+// Every output sample is owned by one lane, which walks its at most ceil(N / hop) frames in ascending f and their rows in
+// ascending k, accumulating in float64: one fixed order per sample, no atomics, so the result is the same bits on every
+// run.  Lanes of a wavefront take consecutive n, so for one (f, k) they read consecutive elements of one row: every load
+// is coalesced, and the grid as a whole reads each element of y with f hop + i < L exactly once.  den comes from the
+// same walk.  Flat grid with a grid-stride loop over n.
+// ======================================================================================
+template <typename T>
+__global__ __launch_bounds__(kFramesBlock) void k_overlap_add(const T* __restrict__ y, int64_t W, int K, int N, int hop,
+                                                             int64_t L, const int* __restrict__ counts,
+                                                             const double* __restrict__ wa, const double* __restrict__ ws,
+                                                             int norm, double* __restrict__ out) {
+  const int64_t stride = (int64_t)gridDim.x * kFramesBlock;
+  for (int64_t n = (int64_t)blockIdx.x * kFramesBlock + threadIdx.x; n < L; n += stride) {
+    const int64_t f_lo = n < N ? 0 : (n - N) / hop + 1;
+    int64_t f_hi = n / hop;
+    if (f_hi > W - 1) f_hi = W - 1;
+    double num = 0.0, den = 0.0;
+    for (int64_t f = f_lo; f <= f_hi; ++f) {
+      const int i = (int)(n - f * hop);
+      int kf = K;
+      if (counts) {
+        kf = counts[f];
+        kf = kf < 0 ? 0 : kf > K ? K : kf;
+      }
+      const double s = ws ? ws[i] : 1.0;
+      den += (wa ? wa[i] : 1.0) * s;
+      const T* row = y + (f * K) * (int64_t)N + i;
+      int k = 0;
+      for (; k + 4 <= kf; k += 4) {  // four loads in flight, added in ascending k
+        const double a0 = (double)row[(int64_t)(k + 0) * N], a1 = (double)row[(int64_t)(k + 1) * N];
+        const double a2 = (double)row[(int64_t)(k + 2) * N], a3 = (double)row[(int64_t)(k + 3) * N];
+        num += s * a0;
+        num += s * a1;
+        num += s * a2;
+        num += s * a3;
+      }
+      for (; k < kf; ++k) num += s * (double)row[(int64_t)k * N];
+    }
+    out[n] = norm ? (den > 0.0 ? num / den : 0.0) : num;
+  }
+}
+
+}  // namespace ph

@@ -628,6 +628,76 @@ class PeriodEngine:
                    int(kcap), int(max_period), ccap, fl, mk.addr(out), mk.addr(status))
         return out, status
 
+    # ------------------------------------------------------------------ short-time framing
+    def _dtype_code(self, mk, dtype, default):
+        """PH_F64 / PH_F32 for a numpy or torch dtype (None: `default`)."""
+        if dtype is None:
+            return default
+        if mk.torch and isinstance(dtype, mk._t.dtype):
+            code = {mk._t.float64: _ffi.PH_F64, mk._t.float32: _ffi.PH_F32}.get(dtype)
+        else:
+            code = _NP_DTYPES.get(np.dtype(dtype))
+        if code is None:
+            raise TypeError(f"unsupported dtype {dtype}")
+        return code
+
+    def frames(self, signal, frame_length, hop, count=None, window=None, out_dtype=None):
+        """Cut a 1-D signal of L samples into overlapping frames (ph_frames, one launch): -> (W, frame_length) with
+        frames[f, i] = signal[f * hop + i] * window[i], zero behind the end of the signal, in `out_dtype` (default: the
+        signal's).  `count` = W; default 1 + ceil((L - frame_length) / hop) (the last frame zero-padded), 1 when the
+        signal is shorter than a frame.  `window`: None or frame_length float64 samples (with torch input a float64
+        tensor on the signal's device).  A numpy signal is uploaded once (L elements) and numpy frames come back; a
+        torch tensor on the engine's device gives a tensor, on torch's current stream."""
+        if getattr(signal, "ndim", None) != 1:
+            raise ValueError("expected a 1-D signal")
+        x, code, _, L, fl, mk = self._prep(signal.reshape(1, -1))
+        N, hop = int(frame_length), int(hop)
+        if count is None:
+            if N < 1 or hop < 1:
+                raise ValueError("frame_length and hop must be >= 1")
+            count = 1 + -((N - L) // hop) if L >= N else 1
+        W = int(count)
+        if W < 0:
+            raise ValueError("count must be >= 0")
+        ocode = self._dtype_code(mk, out_dtype, code)
+        win = None if window is None else self._window(mk, x, window, N)
+        out = mk.empty((W, N), self._np_dtype(ocode))
+        self._call(mk, W, self._lib.ph_frames, mk.addr(x), code, L, N, hop, W, mk.addr(win), ocode, fl, mk.addr(out))
+        return out
+
+    def overlap_add(self, y, hop, length, counts=None, win_a=None, win_s=None, normalize=True):
+        """Overlap-add a framed result (ph_overlap_add, one launch): y (W, N) or (W, K, N) -> (length,) float64,
+        out[n] = sum over the frames f covering n and the rows k < counts[f] (default: all K) of
+        win_s[n - f hop] * y[f, k, n - f hop]; with `normalize` divided by sum_f win_a * win_s where that is > 0 and
+        exactly 0.0 elsewhere.  `counts` (W) int32, `win_a` / `win_s` (N) float64 or None (all ones): numpy arrays, or
+        with torch input tensors on y's device."""
+        if getattr(y, "ndim", None) not in (2, 3):
+            raise ValueError("expected y of shape (W, N) or (W, K, N)")
+        K, N = (1, y.shape[1]) if y.ndim == 2 else (y.shape[1], y.shape[2])
+        hop, L = int(hop), int(length)
+        if L < 0:
+            raise ValueError("length must be >= 0")
+        x, code, W, _, fl, mk = self._prep(y.reshape(y.shape[0], K * N))
+        cnt = None
+        if counts is not None:
+            if mk.torch:
+                cnt = counts.contiguous()
+                if cnt.dtype != mk._t.int32 or cnt.device != x.device:
+                    raise TypeError("counts must be an int32 tensor on the device of y")
+            else:
+                cnt = np.ascontiguousarray(counts, dtype=np.int32)
+            if tuple(cnt.shape) != (W,):
+                raise ValueError("counts must hold one entry per frame")
+        wa = None if win_a is None else self._window(mk, x, win_a, N)
+        ws = None if win_s is None else self._window(mk, x, win_s, N)
+        out = mk.empty((L,), np.float64)
+        if W == 0 or L == 0:  # nothing to add: no call
+            out[...] = 0.0
+            return out
+        self._call(mk, W, self._lib.ph_overlap_add, mk.addr(x), code, W, K, N, hop, L, mk.addr(cnt), mk.addr(wa),
+                   mk.addr(ws), fl | (_ffi.PH_FLAG_OLA_NORM if normalize else 0), mk.addr(out))
+        return out
+
     def fold_sums(self, x, p_list, keep):
         """W = A x for natural-basis rows (QOPeriods.py:782): (W, sum(keep)) float64."""
         x, code, W, N, fl, mk = self._prep(x)

@@ -320,24 +320,66 @@ __device__ __forceinline__ float scalar_select_lt(int x, int y, float a, float b
 //            both periods cross their cut in the SAME column at the same lane -- the columns in front of it feed the
 //            1 / R sums of both, the columns behind it the 1 / (R - 1) sums of both;
 //   loads    row r, column c is read only while 64 c + r q < N, and only up to column ceil(q / 64) + r, the last one
-//            q + 64 needs of it.  Every sample either period owns is read, what lies behind the window is a zero of the
-//            pad, and no read goes past index N + 62.
+//            q + 64 needs of it (rows up to R - 2 reach that column inside the window: pair_duo_tail).  Every sample
+//            either period owns is read, what lies behind the window is a zero of the pad, and no read goes past
+//            index N + 62.
 // The wavefront streams over the columns and carries the R - 1 unfinished sums of q + 64 in `pend` (pend[k]: rows
 // 0 ... k of chunk c - k), rotated by unrolling.  Everything is straight-line code in the manner of pair_rows_group (U
-// columns of loads, one lgkmcnt(0), then the adds): R rows per column in front of the cut, R - 1 behind it; the column
-// that holds the cut and the last column of q classify per lane (LANES); in the first R - 1 columns, where no chunk of
-// q + 64 is complete yet, the unfinished sum is multiplied by a wave-uniform 0 (PRO); the R - 1 columns behind the last
-// one of q bring the rows that q + 64 still lacks (pair_duo_tail).  Adds and squares per period are those of two
-// single passes; the reads are ~0.63 x (45 281 -> 28 669 wavefront loads per sweep at N = 4096, p = 683 ... 1365).
+// columns of loads, one lgkmcnt(0), then the adds): R rows per column in front of the cut, R - 1 behind it; what a side
+// has left after its full groups is one group of 1 ... U - 1 columns.  In the first R - 1 columns no chunk of q + 64 is
+// complete yet: the groups that hold them stand at compile-time positions and leave the square out there (the
+// wave-uniform 0 / 1 factor remains where the peeling stops early).  The column that holds the cut and the last column
+// of q classify their lanes -- wave-uniform intervals, so the squares run under lane masks from the scalar unit
+// (pair_duo_edge) instead of per-lane selects.  The R - 1 columns behind the last one of q bring the rows that q + 64
+// still lacks (pair_duo_tail).  Adds and squares per period are those of two single passes, in the same order in
+// every variant; the reads are ~0.63 x (45 281 -> 28 669 wavefront loads per sweep at N = 4096, p = 683 ... 1365).
 // (the window address of the lane is recomputed in front of every loop, as pair_lane() is: kept live across the pass it
 // is spilled around the groups)
 __device__ __forceinline__ pair_ptr pair_at(const f2* __restrict__ xs) { return (pair_ptr)xs + pair_lane(); }
 
-template <int R, int NR, int U, bool PRO, bool LANES>
-__device__ __forceinline__ void pair_duo_group(pair_ptr ptr, int q, int c, int cut, f2 (&pend)[R - 1], f2& sa, f2& pa, f2& sb,
-                                               f2& pb) {
+// acc += v * v in the lanes of `lanes` (a wave-uniform bit mask) only: the packed FMA runs under EXEC & lanes, the
+// other lanes keep their sum.  The lane sets of a pass are intervals the scalar unit knows (pair_lanes_below); a select
+// per lane and operand in front of an unconditional FMA cost 30 vector instructions per classified column.  EXEC is
+// back in place at the end of the statement, in front of any LDS or cross-lane instruction.
+__device__ __forceinline__ unsigned long pair_lanes_below(int n) { return ~0ul >> (64 - n); }  // lanes 0 ... n - 1, 1 <= n <= 64
+__device__ __forceinline__ void f2_sq_acc_lanes(f2& acc, f2 v, unsigned long lanes) {
+  unsigned long keep;
+  asm volatile(
+      "s_and_saveexec_b64 %[keep], %[m]\n\t"
+      "v_pk_fma_f32 %[acc], %[v], %[v], %[acc]\n\t"
+      "s_mov_b64 exec, %[keep]"
+      : [acc] "+v"(acc), [keep] "=&s"(keep)
+      : [v] "v"(v), [m] "s"(lanes)
+      : "scc");
+}
+// the column that holds the cut: lanes of `below` are residues in front of it (sums sa, pa), the others lie behind it
+// (pb), and those of them in `inq` are residues of q as well (sb)
+__device__ __forceinline__ void f2_sq_acc_cut(f2& sa, f2& pa, f2& sb, f2& pb, f2 t, f2 d, unsigned long below, unsigned long inq) {
+  unsigned long keep;
+  asm volatile(
+      "s_and_saveexec_b64 %[keep], %[below]\n\t"
+      "v_pk_fma_f32 %[sa], %[t], %[t], %[sa]\n\t"
+      "v_pk_fma_f32 %[pa], %[d], %[d], %[pa]\n\t"
+      "s_andn2_b64 exec, %[keep], %[below]\n\t"
+      "v_pk_fma_f32 %[pb], %[d], %[d], %[pb]\n\t"
+      "s_and_b64 exec, exec, %[inq]\n\t"
+      "v_pk_fma_f32 %[sb], %[t], %[t], %[sb]\n\t"
+      "s_mov_b64 exec, %[keep]"
+      : [sa] "+v"(sa), [pa] "+v"(pa), [sb] "+v"(sb), [pb] "+v"(pb), [keep] "=&s"(keep)
+      : [t] "v"(t), [d] "v"(d), [below] "s"(below), [inq] "s"(inq)
+      : "scc");
+}
+
+// U columns from column c on, NR rows each.  PRO says what becomes of the sums of q + 64 that complete here -- in the
+// first R - 1 columns of a pass none is complete:
+//   0       every column is at R - 1 or behind it: all of them are squared;
+//   k > 0   the group stands at a position known at compile time and its first k columns are in front of R - 1: they
+//           simply have no square;
+//   -1      the position is not static: the sum is multiplied by a wave-uniform 0 or 1.
+template <int R, int NR, int U, int PRO>
+__device__ __forceinline__ void pair_duo_group(pair_ptr ptr, int q, int c, f2 (&pend)[R - 1], f2& sa, f2& pa, f2& sb, f2& pb) {
   static_assert(NR == R || NR == R - 1, "all rows (in front of the cut), or all but the last (behind it)");
-  static_assert(!LANES || U == 1, "a column that is cut comes alone");
+  static_assert(PRO >= -1 && PRO <= U, "columns without a square are columns of the group");
   f2 v[NR][U];
 #pragma unroll
   for (int r = 0; r < NR; ++r)
@@ -350,27 +392,14 @@ __device__ __forceinline__ void pair_duo_group(pair_ptr ptr, int q, int c, int c
     f2 t = v[0][u];
 #pragma unroll
     for (int r = 1; r < NR; ++r) t += v[r][u];
-    f2 d = pend[R - 2];  // chunk c + u - (R - 1) of q + 64
-    if (NR == R) d += v[NR - 1][u];
-    if (PRO || LANES) d *= scalar_select_lt(c + u, R - 1, 0.0f, 1.0f);
-    if (LANES) {
-      const int j = 64 * c + pair_lane();  // residue of q; that of q + 64 is j - 64 (R - 1) and lies below q
-      if (NR == R) {
-        const bool full = j < cut;
-        sa = f2_fma(full ? t : f2_zero(), t, sa);
-        sb = f2_fma((!full && j < q) ? t : f2_zero(), t, sb);
-        pa = f2_fma(full ? d : f2_zero(), d, pa);
-        pb = f2_fma(full ? f2_zero() : d, d, pb);
-      } else {
-        sb = f2_fma(j < q ? t : f2_zero(), t, sb);
-        pb = f2_fma(d, d, pb);
-      }
-    } else if (NR == R) {
-      sa = f2_fma(t, t, sa);
-      pa = f2_fma(d, d, pa);
-    } else {
-      sb = f2_fma(t, t, sb);
-      pb = f2_fma(d, d, pb);
+    if (NR == R) sa = f2_fma(t, t, sa);
+    else sb = f2_fma(t, t, sb);
+    if (u >= PRO) {
+      f2 d = pend[R - 2];  // chunk c + u - (R - 1) of q + 64
+      if (NR == R) d += v[NR - 1][u];
+      if (PRO < 0) d *= scalar_select_lt(c + u, R - 1, 0.0f, 1.0f);
+      if (NR == R) pa = f2_fma(d, d, pa);
+      else pb = f2_fma(d, d, pb);
     }
 #pragma unroll
     for (int k = R - 2; k >= 1; --k) pend[k] = pend[k - 1] + v[k][u];
@@ -378,45 +407,49 @@ __device__ __forceinline__ void pair_duo_group(pair_ptr ptr, int q, int c, int c
   }
 }
 
-// one load of the tail that may lie behind the window: skipped as a whole (wave-uniform), its register keeps the zero
-template <int OFF>
-__device__ __forceinline__ void pair_duo_load_if(f2& val, unsigned addr, int index, int N) {
-  asm volatile(
-      "s_cmp_lt_i32 %2, %3\n\t"
-      "s_cbranch_scc0 .Lduo_skip_%=\n\t"
-      "ds_read_b64 %0, %1 offset:%4\n"
-      ".Lduo_skip_%=:"
-      : "+v"(val)
-      : "v"(addr), "s"(index + OFF / 8), "s"(N), "n"(OFF)
-      : "scc");
+// A column whose lanes are classified: the one that holds the cut (NR = R; `below` = its lanes in front of the cut), and
+// the last column of q (`inq` = its lanes that are residues of q; the others belong to q + 64 alone).  Both lie at
+// column R - 1 or behind it (pair_duo_rows), so the sum of q + 64 that completes here is always squared.
+template <int R, int NR>
+__device__ __forceinline__ void pair_duo_edge(pair_ptr ptr, int q, unsigned long below, unsigned long inq, f2 (&pend)[R - 1],
+                                              f2& sa, f2& pa, f2& sb, f2& pb) {
+  static_assert(NR == R || NR == R - 1, "all rows (in front of the cut), or all but the last (behind it)");
+  f2 v[NR];
+#pragma unroll
+  for (int r = 0; r < NR; ++r) v[r] = ptr[r * q];
+  __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
+  __builtin_amdgcn_sched_barrier(0);
+  f2 t = v[0];
+#pragma unroll
+  for (int r = 1; r < NR; ++r) t += v[r];
+  f2 d = pend[R - 2];
+  if (NR == R) d += v[NR - 1];
+  if (NR == R) {
+    f2_sq_acc_cut(sa, pa, sb, pb, t, d, below, inq);
+  } else {
+    f2_sq_acc_lanes(sb, t, inq);
+    pb = f2_fma(d, d, pb);
+  }
+#pragma unroll
+  for (int k = R - 2; k >= 1; --k) pend[k] = pend[k - 1] + v[k];
+  pend[0] = v[0];
 }
 
 // The columns ncb + t, t = T0 ... T1 - 1 of 0 ... R - 2, behind the last column of q (ncb = ceil(q / 64)): q + 64 needs
-// the rows t ... R - 2 of them.  Rows up to R - 3 lie inside the window (q > 64 R), row R - 2 only while
-// 64 (ncb + t) + (R - 2) q < N.  Every chunk of q + 64 that completes here lies behind its cut; the last one, chunk ncb,
-// is cut at q + 64 (after column R - 2).  Six rows take the columns in two batches (15 loads would cost the registers).
+// the rows t ... R - 2 of them.  All of them lie inside the window: row R - 2 of column ncb + t starts at index
+// 64 (ncb + t) + (R - 2) q, which is below N because 64 ncb - q + 64 t <= 63 + 64 (R - 2) < cut = N - (R - 1) q (the
+// partner has R rows: cut > 64 (R - 1), see pair_duo_rows), and its lanes end below N + 63.  Every chunk of q + 64 that
+// completes here lies behind its cut; the last one, chunk ncb, is cut at q + 64 (after column R - 2).  Six rows take the
+// columns in two batches (15 loads would cost the registers).
 template <int R, int T0, int T1>
-__device__ __forceinline__ void pair_duo_tail(const f2* __restrict__ xs, int N, int q, int ncb, f2 (&pend)[R - 1], f2& pb) {
+__device__ __forceinline__ void pair_duo_tail(const f2* __restrict__ xs, int q, int ncb, f2 (&pend)[R - 1], f2& pb) {
   const pair_ptr at = pair_at(xs) + 64 * ncb;
   f2 v[R - 1][R - 1];  // [row][t]
 #pragma unroll
-  for (int t = T0; t < T1; ++t) v[R - 2][t] = f2_zero();
-#pragma unroll
   for (int t = T0; t < T1; ++t)
 #pragma unroll
-    for (int r = t; r < R - 2; ++r) v[r][t] = at[r * q + 64 * t];
-  {
-    const int first = 64 * ncb + (R - 2) * q;  // index of row R - 2 in column ncb, lane 0
-    const unsigned addr = (unsigned)(unsigned long)(at + (R - 2) * q);
-    if (T0 <= 0 && 0 < T1) pair_duo_load_if<0>(v[R - 2][0], addr, first, N);
-    if (T0 <= 1 && 1 < T1) pair_duo_load_if<512>(v[R - 2][1], addr, first, N);
-    if (T0 <= 2 && 2 < T1) pair_duo_load_if<1024>(v[R - 2][2 % (R - 1)], addr, first, N);
-    if (T0 <= 3 && 3 < T1) pair_duo_load_if<1536>(v[R - 2][3 % (R - 1)], addr, first, N);
-    if (T0 <= 4 && 4 < T1) pair_duo_load_if<2048>(v[R - 2][4 % (R - 1)], addr, first, N);
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-  for (int t = T0; t < T1; ++t) asm volatile("" : "+v"(v[R - 2][t]));  // every use of these comes behind the wait
+    for (int r = t; r < R - 1; ++r) v[r][t] = at[r * q + 64 * t];
+  __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
   __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
   for (int t = T0; t < T1; ++t) {
@@ -425,16 +458,15 @@ __device__ __forceinline__ void pair_duo_tail(const f2* __restrict__ xs, int N, 
     for (int k = R - 2; k >= 1; --k) pend[k] = k >= t ? pend[k - 1] + v[k][t] : pend[k - 1];
     if (t == 0) pend[0] = v[0][0];
   }
-  if (T1 == R - 1) {
-    const f2 d = (64 * (ncb - 1) + pair_lane() < q) ? pend[R - 2] : f2_zero();  // chunk ncb: residues q ... q + 63
-    pb = f2_fma(d, d, pb);
-  }
+  if (T1 == R - 1) f2_sq_acc_lanes(pb, pend[R - 2], pair_lanes_below(q - 64 * (ncb - 1)));  // chunk ncb: residues q ... q + 63
 }
 
 template <int R>
 __device__ __forceinline__ void pair_duo_rows(const f2* __restrict__ xs, int N, int q, const PGeomF g, f2& base, f2& partner) {
   // loads in flight: 12 / 16 / 10 / 12 in front of the cut (R = 3 ... 6), 8 / 12 / 12 / 10 behind it
   constexpr int UA = R <= 4 ? 4 : 2, UB = R <= 4 ? 4 : R == 5 ? 3 : 2;
+  constexpr int A3 = UA < 4 ? 1 : 3, A2 = UA < 3 ? 1 : 2, B3 = UB < 4 ? 1 : 3, B2 = UB < 3 ? 1 : 2;  // widths of the remainder groups
+  constexpr int P0 = R - 1 < UA ? R - 1 : UA, P1 = R - 1 - UA < UA ? R - 1 - UA : UA, P2 = R - 1 - 2 * UA;  // columns in front of R - 1 in the first groups
   const int cut = g.nfull, ncb = (q + 63) >> 6, last = ncb - 1;  // the last column of q is cut at q
   f2 pend[R - 1];
 #pragma unroll
@@ -444,42 +476,71 @@ __device__ __forceinline__ void pair_duo_rows(const f2* __restrict__ xs, int N, 
   {
     const int whole = min(cut >> 6, last);
     const pair_ptr at = pair_at(xs);
-    for (; c + UA <= whole; c += UA) {
-      if (c < R - 1) pair_duo_group<R, R, UA, true, false>(at + 64 * c, q, c, cut, pend, sa, pa, sb, pb);
-      else pair_duo_group<R, R, UA, false, false>(at + 64 * c, q, c, cut, pend, sa, pa, sb, pb);
+    // the groups that hold the first R - 1 columns stand at fixed positions: peeled, their columns in front of R - 1
+    // have no square of q + 64
+    if (UA <= whole) {
+      pair_duo_group<R, R, UA, P0>(at, q, 0, pend, sa, pa, sb, pb);
+      c = UA;
+      if constexpr (P1 > 0) {
+        if (2 * UA <= whole) {
+          pair_duo_group<R, R, UA, P1>(at + 64 * UA, q, UA, pend, sa, pa, sb, pb);
+          c = 2 * UA;
+          if constexpr (P2 > 0) {
+            if (3 * UA <= whole) {
+              pair_duo_group<R, R, UA, P2>(at + 128 * UA, q, 2 * UA, pend, sa, pa, sb, pb);
+              c = 3 * UA;
+            }
+          }
+        }
+      }
     }
-    for (; c < whole; ++c) {
+    for (; c + UA <= whole; c += UA) pair_duo_group<R, R, UA, 0>(at + 64 * c, q, c, pend, sa, pa, sb, pb);
+    // what is left, fewer than UA columns, in one group with one drain
+    const int rem = whole - c;
+    if (rem > 0) {
       asm volatile("" ::: "memory");
-      pair_duo_group<R, R, 1, true, false>(at + 64 * c, q, c, cut, pend, sa, pa, sb, pb);
+      if (c < R - 1) {  // (the peeling stopped in front of column R - 1: the position is not static)
+        if (UA > 3 && rem == 3) pair_duo_group<R, R, A3, -1>(at + 64 * c, q, c, pend, sa, pa, sb, pb);
+        else if (UA > 2 && rem == 2) pair_duo_group<R, R, A2, -1>(at + 64 * c, q, c, pend, sa, pa, sb, pb);
+        else pair_duo_group<R, R, 1, -1>(at + 64 * c, q, c, pend, sa, pa, sb, pb);
+      } else {
+        if (UA > 3 && rem == 3) pair_duo_group<R, R, A3, 0>(at + 64 * c, q, c, pend, sa, pa, sb, pb);
+        else if (UA > 2 && rem == 2) pair_duo_group<R, R, A2, 0>(at + 64 * c, q, c, pend, sa, pa, sb, pb);
+        else pair_duo_group<R, R, 1, 0>(at + 64 * c, q, c, pend, sa, pa, sb, pb);
+      }
+      c = whole;
     }
   }
   sb = pb = f2_zero();  // (not live in front of the cut)
+  // From here on every column lies at R - 1 or behind it: the partner has R rows as well, (R - 1) (q + 64) < N, so
+  // cut = N - (R - 1) q > 64 (R - 1) -- `whole` >= R - 1, and q has more than R chunk columns.
+  const unsigned long inq = pair_lanes_below(q - 64 * last);  // lanes of the last column that are residues of q
   if (c < last && 64 * c < cut) {  // the column that holds the cut
     asm volatile("" ::: "memory");
-    pair_duo_group<R, R, 1, true, true>(pair_at(xs) + 64 * c, q, c, cut, pend, sa, pa, sb, pb);
+    pair_duo_edge<R, R>(pair_at(xs) + 64 * c, q, pair_lanes_below(cut - 64 * c), ~0ul, pend, sa, pa, sb, pb);
     c += 1;
   }
   {
     const pair_ptr at = pair_at(xs);
-    for (; c + UB <= last; c += UB) {
-      if (c < R - 1) pair_duo_group<R, R - 1, UB, true, false>(at + 64 * c, q, c, cut, pend, sa, pa, sb, pb);
-      else pair_duo_group<R, R - 1, UB, false, false>(at + 64 * c, q, c, cut, pend, sa, pa, sb, pb);
-    }
-    for (; c < last; ++c) {
+    for (; c + UB <= last; c += UB) pair_duo_group<R, R - 1, UB, 0>(at + 64 * c, q, c, pend, sa, pa, sb, pb);
+    const int rem = last - c;
+    if (rem > 0) {  // fewer than UB columns: one group, one drain
       asm volatile("" ::: "memory");
-      pair_duo_group<R, R - 1, 1, true, false>(at + 64 * c, q, c, cut, pend, sa, pa, sb, pb);
+      if (UB > 3 && rem == 3) pair_duo_group<R, R - 1, B3, 0>(at + 64 * c, q, c, pend, sa, pa, sb, pb);
+      else if (UB > 2 && rem == 2) pair_duo_group<R, R - 1, B2, 0>(at + 64 * c, q, c, pend, sa, pa, sb, pb);
+      else pair_duo_group<R, R - 1, 1, 0>(at + 64 * c, q, c, pend, sa, pa, sb, pb);
     }
   }
   asm volatile("" ::: "memory");
-  if (64 * last < cut) pair_duo_group<R, R, 1, true, true>(pair_at(xs) + 64 * last, q, last, cut, pend, sa, pa, sb, pb);
-  else pair_duo_group<R, R - 1, 1, true, true>(pair_at(xs) + 64 * last, q, last, cut, pend, sa, pa, sb, pb);
+  if (64 * last < cut) pair_duo_edge<R, R>(pair_at(xs) + 64 * last, q, pair_lanes_below(cut - 64 * last), inq, pend, sa, pa, sb, pb);
+  else pair_duo_edge<R, R - 1>(pair_at(xs) + 64 * last, q, 0ul, inq, pend, sa, pa, sb, pb);
   const f2 wf = f2_make(g.w_full, g.w_full);
   base = f2_fma(sa, wf, sb * g.w_short);  // (complete: two registers fewer across the tail)
   if (R == 6) {
-    pair_duo_tail<R, 0, 2>(xs, N, q, ncb, pend, pb);
-    pair_duo_tail<R, 2, R - 1>(xs, N, q, ncb, pend, pb);
+    pair_duo_tail<R, 0, 2>(xs, q, ncb, pend, pb);
+    pair_duo_tail<R, 2, R - 1>(xs, q, ncb, pend, pb);
   } else {
-    pair_duo_tail<R, 0, R - 1>(xs, N, q, ncb, pend, pb);
+    pair_duo_tail<R, 0, R - 1>(xs, q, ncb, pend, pb);
   }
   partner = f2_fma(pa, wf, pb * g.w_short);
 }

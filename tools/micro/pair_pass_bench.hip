@@ -7,6 +7,7 @@
 // (3 ... 6 rows, q > 64 rows), as the plan of k_mbest_step1_pair pairs them; its passes are counted per base.  Time from hipEvents;
 // instruction counts per pass with tools/micro/pair_pass_pmc.sh.  profiles/r4_study/pair_pass_bench.txt holds the
 // numbers of the round-3 passes (one loop over the two segments) next to these.
+// Arguments: variant, q_lo, q_hi, N (default 4096).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Wno-unused-value -I../../pyperiod_amd/csrc pair_pass_bench.hip -o pair_pass_bench
 #include "ph_pair.h"
 #include <cstdio>
@@ -55,8 +56,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
 int main(int argc, char** argv) {
   setvbuf(stdout, NULL, _IONBF, 0);
   const int v = argc > 1 ? atoi(argv[1]) : 1;
-  const int N = 4096, q_lo = argc > 2 ? atoi(argv[2]) : 64, q_hi = argc > 3 ? atoi(argv[3]) : 2048, reps = 2, blocks = 2048;
+  const int N = argc > 4 ? atoi(argv[4]) : 4096;  // window length (the edge shapes of the shared-load pass occur at small N already)
+  const int q_lo = argc > 2 ? atoi(argv[2]) : 64, q_hi = argc > 3 ? atoi(argv[3]) : 2048, reps = 2, blocks = 2048;
   if (v != 1 && v != 2 && v != 3 && v != 4) return 2;
+  if (N < 256 || N > 4096) return 2;  // (the window pair and its pad must fit the LDS of a workgroup at this occupancy)
   if (q_lo < 64 || (v == 3 ? q_hi - 1 + 64 >= N : v * (q_hi - 1) > N)) return 2;  // the passes need q >= 64 and whole class cycles inside the window
   std::vector<PGeomF> g(N + 1);
   for (int p = 1; p <= N; ++p) {
@@ -130,6 +133,7 @@ int main(int argc, char** argv) {
       }
     printf("%d screen values against the fp64 fold: largest |error| / (pair_radius x sum of squares) = %.3f (period %d; must be < 1), largest relative error %.2e\n",
            checked, worst, at, worst_rel);
+    printf("N = %d: every value inside its radius: %s\n", N, worst <= 1.0 ? "yes" : "NO");
   }
   if (v == 3)
     printf("shared-load pass (q, q + 64): %.3f ms for %.0f passes (%d bases in [%d, %d)): %.1f ns per pass per CU\n", best, passes, bases,

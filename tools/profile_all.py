@@ -5,6 +5,8 @@ the source of the per-kernel HIP-event timings.
 
 usage: profile_all.py [--reps R] [--json OUT] [kernel-group ...]
 groups: mbest sweep s2l bc ram k1 qo bf orth fold misc   (default: all)
+        mbest_plain   (never part of the default: config 2 through plain m_best alone, for counter captures of
+                       k_mbest_step1_pair that must not mix plain and gamma launches)
 """
 import argparse
 import json
@@ -56,13 +58,15 @@ def main():
         print(tag, json.dumps(rec), flush=True)
 
     x4k = None
-    if set(which) & {"mbest", "sweep", "bc", "k1", "bf", "orth", "misc"}:
+    if set(which) & {"mbest", "mbest_plain", "sweep", "bc", "k1", "bf", "orth", "misc"}:
         x4k = torch.from_numpy(multi_sinusoid_batch(0, 1024, 4096)).to(dev)
     if "mbest" in which:  # config 2
         out = eng.m_best(x4k, 10, want_sweeps=True)
         sw = int(out[4].sum().item())
         run("c2_m_best_1024x4096", lambda: eng.m_best(x4k, 10), sw * 1364, "window_proj", sw * 1364 * 32768)
         run("c2_m_best_gamma_1024x4096", lambda: eng.m_best(x4k, 10, gamma=True))
+    if "mbest_plain" in which:
+        run("c2_m_best_1024x4096_plain_only", lambda: eng.m_best(x4k, 10))
     if "sweep" in which:
         for mode, nm in ((0, "norm"), (2, "maxabs")):
             run(f"sweep_{nm}_1024x4096", lambda: eng.sweep(x4k, 2, 1365, mode), 1024 * 1364, "window_proj", 1024 * 1364 * 32768)

@@ -545,6 +545,21 @@ int ph_overlap_add(ph_ctx* ctx, const void* y, int dtype, int64_t W, int K, int 
                    const int32_t* counts /* W or NULL */, const double* win_a, const double* win_s,
                    unsigned flags /* PH_FLAG_DEVICE | PH_FLAG_OLA_NORM */, double* out);
 
+/* ph_overlap_add_tracks: the routed overlap-add -- y (W, K, N) of dtype -> out (T, L) float64,
+ *   num[t, n] = sum_f win_s[n - f * hop] * sum_{k < K_f, bit k of masks[t, f] set} y[f, k, n - f * hop]
+ *   den[n], K_f, the frames of a sample, win_a / win_s and PH_FLAG_OLA_NORM as in ph_overlap_add; a track without a term
+ *   at n is exactly 0.0 there.
+ * masks (T, W) 64-bit words: bit k of masks[t, f] routes row k of frame f to track t, so K <= 64.  Bits at or above K_f
+ * are ignored; rows behind K_f or in no mask are never read; masks may overlap (the row is added to every track that names
+ * it).  One launch (k_overlap_add_tracks): one lane per (t, n), float64 accumulation in ascending f, then ascending k, no
+ * atomics -- the same bits on every run.  T * L and W * K * N may exceed 2^31.
+ * Every array follows PH_FLAG_DEVICE.  PH_E_ARG for a NULL ctx / y / masks / out, an unknown dtype, what ph_overlap_add
+ * refuses, T < 1, K > 64, or T * L * 8 / T * W * 8 beyond 64 bits, before any HIP call. */
+int ph_overlap_add_tracks(ph_ctx* ctx, const void* y, int dtype, int64_t W, int K, int N, int hop, int64_t L,
+                          const int32_t* counts /* W or NULL */, const uint64_t* masks /* (T, W) */, int64_t T,
+                          const double* win_a, const double* win_s,
+                          unsigned flags /* PH_FLAG_DEVICE | PH_FLAG_OLA_NORM */, double* out /* (T, L) */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,12 @@ and the ``(W, K, N)`` bases never leave the device.
     st = ShortTime(4096, 512, window=np.sqrt(np.hanning(4096)))
     res = st.analyze(recording, method="m_best", num=10)
     res.periodic, res.residual            # (L,) float64 each
+
+``decompose`` splits the periodic part by period: the same pipeline, then one routed overlap-add
+(``PeriodEngine.overlap_add_tracks``) of the same bases onto one waveform per track.
+
+    dec = st.decompose(recording, method="m_best", num=10, max_tracks=8)
+    dec.track_periods, dec.tracks, dec.other, dec.activity
 """
 
 from __future__ import annotations
@@ -35,6 +41,27 @@ class ShortTimeResult(NamedTuple):
     periodic: np.ndarray
     residual: np.ndarray
     counts: Optional[np.ndarray] = None
+
+
+class ShortTimeTracks(NamedTuple):
+    """What ``ShortTime.decompose`` returns.  ``periods`` / ``powers`` / ``counts`` / ``periodic`` / ``residual`` are
+    those of ``analyze``.  ``track_periods`` lists the T tracks, each a tuple of periods; ``tracks[t]`` (T, L) is the
+    overlap-added, window-normalised sum of the bases whose period is in ``track_periods[t]``; ``other`` (L,) is the
+    same sum over every used basis that is in no track (period-0 rows included) -- computed as a track of its own, not
+    as a difference; ``activity[t, f]`` (T, W) is the sum of the ``powers`` of the track's bases in frame f."""
+
+    periods: np.ndarray
+    powers: np.ndarray
+    periodic: np.ndarray
+    residual: np.ndarray
+    track_periods: list
+    tracks: np.ndarray
+    other: np.ndarray
+    activity: np.ndarray
+    counts: Optional[np.ndarray] = None
+
+
+_MAX_ROWS = 64  # rows per frame a 64-bit routing mask can name
 
 
 def _first(mask):
@@ -120,6 +147,28 @@ class ShortTime:
         """Frame `signal`, run ``Periods.<method>`` (its keyword arguments in **kwargs) over the frames and overlap-add
         the bases: -> ShortTimeResult.  One upload of the signal, one download of the results; status words raise what
         the ``Periods`` method raises, with the first offending frame named."""
+        x64, L, W, eng, win, num, per, pw, bases, counts = self._run(signal, method, kwargs)
+        if num == 0:  # the reference's loops do not run: empty per-frame arrays, nothing periodic
+            return ShortTimeResult(np.zeros((W, 0), np.uint32), np.zeros((W, 0)), np.zeros(L), x64)
+        periodic = eng.overlap_add(bases, self.hop, L, counts, win, win, True).cpu().numpy()
+        per, pw, counts = self._host_results(per, pw, counts)
+        return ShortTimeResult(per, pw, periodic, x64 - periodic, counts)
+
+    @staticmethod
+    def _host_results(per, pw, counts):
+        """The per-frame device results as analyze returns them: (W, num) uint32 periods, or for small_to_large int32
+        periods and powers with zeros behind counts[f]."""
+        per, pw = per.cpu().numpy(), pw.cpu().numpy()
+        if counts is None:
+            return per.view(np.uint32), pw, None
+        counts = counts.cpu().numpy()
+        used = np.arange(per.shape[1])[None, :] < counts[:, None]
+        return np.where(used, per, 0), np.where(used, pw, 0.0), counts
+
+    def _run(self, signal, method, kwargs):
+        """The pipeline analyze and decompose share: one upload of the signal, frames, the engine method, the status
+        check.  -> (float64 signal, L, W, engine, device window, num, periods, powers, bases, counts) with the last four
+        on the device (None when num == 0: nothing ran)."""
         if method not in _METHODS:
             raise ValueError(f"method must be one of {_METHODS}")
         import torch  # lazily, as QOPeriods.solve_quadratic does
@@ -176,16 +225,144 @@ class ShortTime:
             num = 1
             counts, per, pw, bases, st = eng.small_to_large(fr, thresh, n_periods, trunc, orth)
         x64 = x.astype(np.float64)
-        if num == 0:  # the reference's loops do not run: empty per-frame arrays, nothing periodic
-            return ShortTimeResult(np.zeros((W, 0), np.uint32), np.zeros((W, 0)), np.zeros(L), x64)
+        if num == 0:
+            return x64, L, W, eng, win, 0, None, None, None, None
         self._raise_status(st.cpu().numpy(), method)
-        periodic = eng.overlap_add(bases, self.hop, L, counts, win, win, True).cpu().numpy()
-        per, pw = per.cpu().numpy(), pw.cpu().numpy()
+        return x64, L, W, eng, win, num, per, pw, bases, counts
+
+    def decompose(self, signal, method="m_best", tracks=None, max_tracks=8, **kwargs):
+        """``analyze``, and the periodic part split by period: -> ShortTimeTracks.  `tracks`: None -- the `max_tracks`
+        strongest periods of the recording, one track each (``rank_periods``) -- or a list whose entries are a period or
+        an iterable of periods, e.g. ``[12, (17, 34)]``.  The pipeline is that of ``analyze`` (same methods, keyword
+        arguments and exceptions); afterwards only the per-frame periods / powers / counts come down, the routing masks
+        (``track_masks``) go up, and one routed overlap-add (``PeriodEngine.overlap_add_tracks``) folds the bases onto
+        T + 1 rows: the tracks and ``other``.  The ``(W, K, N)`` bases never leave the device.  K <= 64 bases per
+        frame: `num` > 64 raises ValueError before anything is launched; for small_to_large K is known only once the
+        method has run, so there the check comes after the method's kernels and before the two overlap-adds."""
+        if method not in _METHODS:
+            raise ValueError(f"method must be one of {_METHODS}")
+        wanted = None if tracks is None else self._track_list(tracks)
+        max_tracks = int(max_tracks)
+        if max_tracks < 0:
+            raise ValueError("max_tracks must be >= 0")
+        if method != "small_to_large" and int(kwargs.get("num", 5)) > _MAX_ROWS:
+            raise ValueError(f"num={int(kwargs['num'])} bases per frame: decompose routes at most {_MAX_ROWS}")
+        x64, L, W, eng, win, num, per, pw, bases, counts = self._run(signal, method, kwargs)
+        if num == 0:
+            wanted = wanted or []
+            return ShortTimeTracks(np.zeros((W, 0), np.uint32), np.zeros((W, 0)), np.zeros(L), x64, wanted,
+                                   np.zeros((len(wanted), L)), np.zeros(L), np.zeros((len(wanted), W)))
+        if bases.shape[1] > _MAX_ROWS:
+            raise ValueError(f"{bases.shape[1]} bases per frame: decompose routes at most {_MAX_ROWS}")
+        import torch
+
+        counts_d = counts
+        per, pw, counts = self._host_results(per, pw, counts)  # the small per-frame arrays down
+        if wanted is None:
+            wanted = [(p,) for p in self.rank_periods(per, pw, counts, max_tracks)]
+        masks = self.track_masks(per, counts, wanted)
+        T = len(wanted)
+        masks_d = torch.as_tensor(masks.view(np.int64), device=bases.device)  # (T + 1) * W words up
+        routed = eng.overlap_add_tracks(bases, masks_d, self.hop, L, counts_d, win, win, True)
+        periodic = eng.overlap_add(bases, self.hop, L, counts_d, win, win, True).cpu().numpy()
+        routed = routed.cpu().numpy()
+        activity = np.zeros((T, W))
+        for k in range(per.shape[1]):  # ascending k, as the kernel adds
+            bit = (masks[:T] >> np.uint64(k)) & np.uint64(1)
+            activity += np.where(bit != 0, pw[None, :, k], 0.0)
+        return ShortTimeTracks(per, pw, periodic, x64 - periodic, wanted, routed[:T], routed[T], activity, counts)
+
+    @staticmethod
+    def _track_list(tracks):
+        """[12, (17, 34)] -> [(12,), (17, 34)]; ValueError for an empty list or entry, a period < 1 or a period in two
+        tracks (twice in one track counts once)."""
+        def walk(obj):  # the items of a non-str iterable, None for anything else (a str, a number, a 0-d array)
+            if isinstance(obj, (str, bytes)):
+                return None
+            try:
+                return list(obj)
+            except TypeError:
+                return None
+
+        entries = walk(tracks)
+        if entries is None:
+            raise ValueError("tracks must be a list of periods or of iterables of periods")
+        out, seen = [], set()
+        for entry in entries:
+            group = walk(entry)
+            if group is None:
+                group = [entry.item() if isinstance(entry, np.ndarray) else entry]
+            if not group:
+                raise ValueError("a track needs at least one period")
+            ps = []
+            for p in group:
+                if isinstance(p, bool) or not isinstance(p, (int, np.integer)):
+                    raise ValueError(f"track period {p!r} is not an integer")
+                p = int(p)
+                if p < 1:
+                    raise ValueError(f"track period {p} must be >= 1")
+                if p not in ps:
+                    ps.append(p)
+            if seen.intersection(ps):
+                raise ValueError(f"period {sorted(seen.intersection(ps))[0]} is in two tracks")
+            seen.update(ps)
+            out.append(tuple(ps))
+        if not out:
+            raise ValueError("tracks must name at least one track")
+        return out
+
+    @staticmethod
+    def _used(periods, counts):
+        """(W, K) int64 periods and the mask of the entries in use (k < counts[f], counts clipped to [0, K])."""
+        per = np.asarray(periods)
+        if per.ndim != 2:
+            raise ValueError("periods must be (W, K)")
+        per = per.astype(np.int64)
+        W, K = per.shape
         if counts is None:
-            return ShortTimeResult(per.view(np.uint32), pw, periodic, x64 - periodic)
-        counts = counts.cpu().numpy()
-        used = np.arange(per.shape[1])[None, :] < counts[:, None]
-        return ShortTimeResult(np.where(used, per, 0), np.where(used, pw, 0.0), periodic, x64 - periodic, counts)
+            return per, np.ones((W, K), bool)
+        cnt = np.asarray(counts)
+        if cnt.shape != (W,):
+            raise ValueError("counts must hold one entry per frame")
+        return per, np.arange(K)[None, :] < np.clip(cnt.astype(np.int64), 0, K)[:, None]
+
+    @staticmethod
+    def rank_periods(periods, powers, counts=None, max_tracks=8):
+        """The `max_tracks` strongest periods of a recording: over the distinct non-zero periods among the used entries
+        of `periods` (W, K), the sum of their `powers` (NaN counts as 0), in descending order, ties to the smaller
+        period.  -> list of ints."""
+        per, used = ShortTime._used(periods, counts)
+        pw = np.asarray(powers, dtype=np.float64)
+        if pw.shape != per.shape:
+            raise ValueError("powers must have the shape of periods")
+        used = used & (per != 0)
+        uniq, inv = np.unique(per[used], return_inverse=True)
+        score = np.bincount(inv.ravel(), weights=np.nan_to_num(pw[used], nan=0.0, posinf=np.inf, neginf=-np.inf),
+                            minlength=uniq.size)
+        order = sorted(range(uniq.size), key=lambda j: (-score[j], uniq[j]))
+        return [int(uniq[j]) for j in order[: max(int(max_tracks), 0)]]
+
+    @staticmethod
+    def track_masks(periods, counts, track_periods):
+        """The routing masks of ``PeriodEngine.overlap_add_tracks`` for T tracks: (T + 1, W) uint64 with bit k of
+        [t, f] set when entry k of frame f is in use (k < counts[f]; None: all) and periods[f, k] is in
+        track_periods[t]; row T takes every used entry that is in no track, period 0 included.  K <= 64."""
+        per, used = ShortTime._used(periods, counts)
+        W, K = per.shape
+        if K > _MAX_ROWS:
+            raise ValueError(f"{K} entries per frame do not fit a 64-bit mask")
+        groups = ShortTime._track_list(track_periods) if len(track_periods) else []
+        T = len(groups)
+        masks = np.zeros((T + 1, W), np.uint64)
+        for k in range(K):
+            bit = np.uint64(1) << np.uint64(k)
+            taken = np.zeros(W, bool)
+            for t, group in enumerate(groups):
+                hit = used[:, k] & np.isin(per[:, k], group)
+                masks[t, hit] |= bit
+                taken |= hit
+            masks[T, used[:, k] & ~taken] |= bit
+        return masks
 
     @staticmethod
     def _no_more(kwargs, method):

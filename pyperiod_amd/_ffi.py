@@ -78,6 +78,7 @@ SIGNATURES = {
     "ph_tile_sum": [_vp, _vp, _i64, _i, _pi32, _pi32, _i, _i, _u, _vp],
     "ph_frames": [_vp, _vp, _i, _i64, _i, _i, _i64, _vp, _i, _u, _vp],
     "ph_overlap_add": [_vp, _vp, _i, _i64, _i, _i, _i, _i64, _pi32, _vp, _vp, _u, _vp],
+    "ph_overlap_add_tracks": [_vp, _vp, _i, _i64, _i, _i, _i, _i64, _pi32, _vp, _i64, _vp, _vp, _u, _vp],
 }
 
 

@@ -2572,4 +2572,42 @@ int ph_overlap_add(ph_ctx* c, const void* y, int dtype, int64_t W, int K, int N,
   return st.finish();
 }
 
+int ph_overlap_add_tracks(ph_ctx* c, const void* y, int dtype, int64_t W, int K, int N, int hop, int64_t L,
+                          const int32_t* counts, const uint64_t* masks, int64_t T, const double* win_a,
+                          const double* win_s, unsigned flags, double* out) {
+  if (!c) return fail(PH_E_ARG, "ctx is NULL");
+  if (!y || !masks || !out) return fail(PH_E_ARG, "y / masks / out is NULL");
+  if (dtype != PH_F64 && dtype != PH_F32) return fail(PH_E_ARG, "dtype must be PH_F64 or PH_F32");
+  PH_TRY(check_framing("ph_overlap_add_tracks", W, K, N, hop, L));
+  if (T < 1) return fail(PH_E_ARG, "ph_overlap_add_tracks: T=%lld must be >= 1", (long long)T);
+  if (K > 64) return fail(PH_E_ARG, "ph_overlap_add_tracks: K=%d rows per frame do not fit a 64-bit mask", K);
+  if (T > (INT64_MAX / 8) / L || T > (INT64_MAX / 8) / W)
+    return fail(PH_E_ARG, "ph_overlap_add_tracks: T * L or T * W does not fit 64 bits");
+  PH_HIP(hipSetDevice(c->device));
+  Stage st(c, flags);
+  const void *dy, *dmask, *dcnt = nullptr, *dwa = nullptr, *dws = nullptr;
+  void* dout;
+  PH_TRY(st.in(y, (size_t)W * K * N * elem_size(dtype), &dy));
+  PH_TRY(st.in(masks, (size_t)T * W * sizeof(uint64_t), &dmask, B_WS0));
+  if (counts) PH_TRY(st.in(counts, (size_t)W * sizeof(int32_t), &dcnt, B_GBUF));
+  if (win_a) PH_TRY(st.in(win_a, (size_t)N * sizeof(double), &dwa, B_GWIN));
+  if (win_s) PH_TRY(st.in(win_s, (size_t)N * sizeof(double), &dws, B_WS1));
+  PH_TRY(st.out(B_OUT0, out, (size_t)T * L * sizeof(double), &dout));
+  const dim3 grid(flat_grid(c, T * L));
+  const int norm = (flags & PH_FLAG_OLA_NORM) ? 1 : 0;
+  {
+    ProfScope ps_(c, "k_overlap_add_tracks");
+    if (dtype == PH_F64)
+      hipLaunchKernelGGL(ph::k_overlap_add_tracks<double>, grid, dim3(ph::kFramesBlock), 0, c->stream, (const double*)dy, W,
+                         K, N, hop, L, (const int*)dcnt, (const unsigned long long*)dmask, T, (const double*)dwa,
+                         (const double*)dws, norm, (double*)dout);
+    else
+      hipLaunchKernelGGL(ph::k_overlap_add_tracks<float>, grid, dim3(ph::kFramesBlock), 0, c->stream, (const float*)dy, W,
+                         K, N, hop, L, (const int*)dcnt, (const unsigned long long*)dmask, T, (const double*)dwa,
+                         (const double*)dws, norm, (double*)dout);
+  }
+  PH_TRY(launch_check("k_overlap_add_tracks"));
+  return st.finish();
+}
+
 }  // extern "C"

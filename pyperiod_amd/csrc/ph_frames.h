@@ -1,5 +1,6 @@
 // Short-time framing and overlap-add on the device: k_frames cuts a signal of L samples into the (W, N) batch every
-// other entry point takes, k_overlap_add folds a (W, K, N) result back onto the L samples of the signal.  Both are
+// other entry point takes, k_overlap_add folds a (W, K, N) result back onto the L samples of the signal, and
+// k_overlap_add_tracks folds it onto several tracks of L samples, the rows of each chosen by a mask.  All are
 // memory-bound element-wise kernels without LDS; all index arithmetic is int64 (f * hop and f * N pass 2^31 for real
 // recordings).  Included by period_hip.hip behind ph_fit.h.
 #pragma once
@@ -143,6 +144,78 @@ __global__ __launch_bounds__(kFramesBlock) void k_overlap_add(const T* __restric
       for (; k < kf; ++k) num += s * (double)row[(int64_t)k * N];
     }
     out[n] = norm ? (den > 0.0 ? num / den : 0.0) : num;
+  }
+}
+
+// ======================================================================================
+// Routed overlap-add: the same y (W, K, N), folded onto NT tracks of L samples each -> out (NT, L) float64.
+//   num[t, n] = sum_f ws[n - f hop] * sum_{k < K_f, bit k of masks[t, f] set} y[f, k, n - f hop]
+//   den[n] and the frames f of a sample as in k_overlap_add; out[t, n] = num, or with `norm` num / den where den > 0 and
+//   exactly 0.0 elsewhere.  A track with no term at n gives num = 0.0 and so exactly 0.0.
+// masks (NT, W) 64-bit words: bit k of masks[t, f] routes row k of frame f to track t (K <= 64, checked on the host).  A
+// mask instead of a (W, K) label array: with labels a lane would compare all K labels of a frame for the ~K / NT rows it
+// loads; with a mask it is one 8-byte load per frame -- the same address for every lane of a wavefront unless the
+// wavefront straddles two frames' worth of n or two tracks -- and then a walk over the set bits.  The word is unsigned
+// throughout: bits at or above K_f are cut off with a logical mask ((1 << K_f) - 1, skipped for K_f = 64), the walk takes
+// the lowest set bit with ctz and clears it with m & (m - 1), so bit 63 is a row like any other.  Masks may overlap (the
+// row is added to every track that names it); rows behind K_f or in no mask are never read.
+// One lane owns one (t, n) and walks frames in ascending f, rows in ascending k, accumulating in float64: one fixed
+// order, no atomics, the same bits on every run.  Items are flat over NT * L, so the lanes of a wavefront may lie in two
+// tracks (L not a multiple of 64): every lane derives its own (t, n) and loads its own mask word.  Grid-stride loop.
+// ======================================================================================
+template <typename T>
+__global__ __launch_bounds__(kFramesBlock) void k_overlap_add_tracks(const T* __restrict__ y, int64_t W, int K, int N, int hop,
+                                                                    int64_t L, const int* __restrict__ counts,
+                                                                    const unsigned long long* __restrict__ masks,
+                                                                    int64_t NT, const double* __restrict__ wa,
+                                                                    const double* __restrict__ ws, int norm,
+                                                                    double* __restrict__ out) {
+  const int64_t total = NT * L;
+  const int64_t stride = (int64_t)gridDim.x * kFramesBlock;
+  for (int64_t item = (int64_t)blockIdx.x * kFramesBlock + threadIdx.x; item < total; item += stride) {
+    const int64_t t = item / L;
+    const int64_t n = item - t * L;
+    const int64_t f_lo = n < N ? 0 : (n - N) / hop + 1;
+    int64_t f_hi = n / hop;
+    if (f_hi > W - 1) f_hi = W - 1;
+    const unsigned long long* mrow = masks + t * W;
+    double num = 0.0, den = 0.0;
+    for (int64_t f = f_lo; f <= f_hi; ++f) {
+      const int i = (int)(n - f * hop);
+      int kf = K;
+      if (counts) {
+        kf = counts[f];
+        kf = kf < 0 ? 0 : kf > K ? K : kf;
+      }
+      const double s = ws ? ws[i] : 1.0;
+      den += (wa ? wa[i] : 1.0) * s;
+      unsigned long long m = mrow[f];
+      if (kf < 64) m &= (1ull << kf) - 1ull;  // (kf = 0: no row at all)
+      const T* row = y + (f * K) * (int64_t)N + i;
+      int left = __builtin_popcountll(m);
+      for (; left >= 4; left -= 4) {  // four loads in flight, added in ascending k
+        const int k0 = __builtin_ctzll(m);
+        m &= m - 1ull;
+        const int k1 = __builtin_ctzll(m);
+        m &= m - 1ull;
+        const int k2 = __builtin_ctzll(m);
+        m &= m - 1ull;
+        const int k3 = __builtin_ctzll(m);
+        m &= m - 1ull;
+        const double a0 = (double)row[(int64_t)k0 * N], a1 = (double)row[(int64_t)k1 * N];
+        const double a2 = (double)row[(int64_t)k2 * N], a3 = (double)row[(int64_t)k3 * N];
+        num += s * a0;
+        num += s * a1;
+        num += s * a2;
+        num += s * a3;
+      }
+      for (; left > 0; --left) {
+        const int k = __builtin_ctzll(m);
+        m &= m - 1ull;
+        num += s * (double)row[(int64_t)k * N];
+      }
+    }
+    out[item] = norm ? (den > 0.0 ? num / den : 0.0) : num;
   }
 }
 

@@ -665,12 +665,9 @@ class PeriodEngine:
         self._call(mk, W, self._lib.ph_frames, mk.addr(x), code, L, N, hop, W, mk.addr(win), ocode, fl, mk.addr(out))
         return out
 
-    def overlap_add(self, y, hop, length, counts=None, win_a=None, win_s=None, normalize=True):
-        """Overlap-add a framed result (ph_overlap_add, one launch): y (W, N) or (W, K, N) -> (length,) float64,
-        out[n] = sum over the frames f covering n and the rows k < counts[f] (default: all K) of
-        win_s[n - f hop] * y[f, k, n - f hop]; with `normalize` divided by sum_f win_a * win_s where that is > 0 and
-        exactly 0.0 elsewhere.  `counts` (W) int32, `win_a` / `win_s` (N) float64 or None (all ones): numpy arrays, or
-        with torch input tensors on y's device."""
+    def _ola_args(self, y, hop, length, counts, win_a, win_s):
+        """What overlap_add and overlap_add_tracks share: -> (x, code, W, K, N, hop, L, flags, out-factory, counts,
+        win_a, win_s), y flattened to (W, K * N) and the optional arrays checked against it."""
         if getattr(y, "ndim", None) not in (2, 3):
             raise ValueError("expected y of shape (W, N) or (W, K, N)")
         K, N = (1, y.shape[1]) if y.ndim == 2 else (y.shape[1], y.shape[2])
@@ -690,12 +687,46 @@ class PeriodEngine:
                 raise ValueError("counts must hold one entry per frame")
         wa = None if win_a is None else self._window(mk, x, win_a, N)
         ws = None if win_s is None else self._window(mk, x, win_s, N)
+        return x, code, W, K, N, hop, L, fl, mk, cnt, wa, ws
+
+    def overlap_add(self, y, hop, length, counts=None, win_a=None, win_s=None, normalize=True):
+        """Overlap-add a framed result (ph_overlap_add, one launch): y (W, N) or (W, K, N) -> (length,) float64,
+        out[n] = sum over the frames f covering n and the rows k < counts[f] (default: all K) of
+        win_s[n - f hop] * y[f, k, n - f hop]; with `normalize` divided by sum_f win_a * win_s where that is > 0 and
+        exactly 0.0 elsewhere.  `counts` (W) int32, `win_a` / `win_s` (N) float64 or None (all ones): numpy arrays, or
+        with torch input tensors on y's device."""
+        x, code, W, K, N, hop, L, fl, mk, cnt, wa, ws = self._ola_args(y, hop, length, counts, win_a, win_s)
         out = mk.empty((L,), np.float64)
         if W == 0 or L == 0:  # nothing to add: no call
             out[...] = 0.0
             return out
         self._call(mk, W, self._lib.ph_overlap_add, mk.addr(x), code, W, K, N, hop, L, mk.addr(cnt), mk.addr(wa),
                    mk.addr(ws), fl | (_ffi.PH_FLAG_OLA_NORM if normalize else 0), mk.addr(out))
+        return out
+
+    def overlap_add_tracks(self, y, masks, hop, length, counts=None, win_a=None, win_s=None, normalize=True):
+        """Routed overlap-add (ph_overlap_add_tracks, one launch): y (W, N) or (W, K, N), K <= 64 -> (T, length) float64,
+        out[t, n] = what overlap_add gives for the rows k < counts[f] of frame f whose bit k is set in masks[t, f].
+        `masks` (T, W): np.uint64 or np.int64 (the same bits), or with torch input a torch.int64 tensor on y's device;
+        masks may overlap, a row in no mask is never read.  `counts`, `win_a`, `win_s`, `normalize` as in overlap_add."""
+        x, code, W, K, N, hop, L, fl, mk, cnt, wa, ws = self._ola_args(y, hop, length, counts, win_a, win_s)
+        if mk.torch:
+            if not _is_torch(masks) or masks.dtype != mk._t.int64 or masks.device != x.device:
+                raise TypeError("masks must be an int64 tensor on the device of y")
+            msk = masks.contiguous()
+        else:
+            if not isinstance(masks, np.ndarray) or masks.dtype not in (np.dtype(np.uint64), np.dtype(np.int64)):
+                raise TypeError("masks must be a uint64 or int64 array")
+            msk = np.ascontiguousarray(masks)
+        if msk.ndim != 2 or msk.shape[1] != W:
+            raise ValueError("masks must be (T, W): one word per track and frame")
+        T = int(msk.shape[0])
+        out = mk.empty((T, L), np.float64)
+        if W == 0 or L == 0:  # nothing to add: no call
+            out[...] = 0.0
+            return out
+        self._call(mk, W, self._lib.ph_overlap_add_tracks, mk.addr(x), code, W, K, N, hop, L, mk.addr(cnt), mk.addr(msk),
+                   T, mk.addr(wa), mk.addr(ws), fl | (_ffi.PH_FLAG_OLA_NORM if normalize else 0), mk.addr(out))
         return out
 
     def fold_sums(self, x, p_list, keep):

@@ -560,6 +560,27 @@ int ph_overlap_add_tracks(ph_ctx* ctx, const void* y, int dtype, int64_t W, int 
                           const double* win_a, const double* win_s,
                           unsigned flags /* PH_FLAG_DEVICE | PH_FLAG_OLA_NORM */, double* out /* (T, L) */);
 
+/* ph_overlap_add_periodic: the routed overlap-add of periodic segments -- seg (W, ccap) float64 in the
+ * layout ph_qo_get_periods writes (block a of frame f is p(f, a) = periods[f, a] doubles at off(f, a) = sum of periods[f, :a])
+ * -> out (T, L) float64, every block tiled to the frame on the fly.  With i = n - f * hop over the frames f < W, 0 <= i < N:
+ *   num[t, n] = sum_f win_s[i] * sum_{a < C_f, bit a of masks[t, f] set} seg[f, off(f, a) + (i mod p(f, a))]
+ *   C_f = counts[f] clipped to [0, min(pcap, 64)]; den[n], win_a / win_s, PH_FLAG_OLA_NORM and the exact 0.0 of a track
+ *   without a term as in ph_overlap_add_tracks.
+ * periods (W, pcap) int32, counts (W) int32, masks (T, W) 64-bit words: bit a of masks[t, f] routes block a of frame f to
+ * track t (blocks at or above 64 cannot be routed); masks may overlap.  The offsets are derived in the kernel from
+ * `periods`.  The walk of a frame stops at the first block with p < 1 or off + p > ccap: that block and the ones behind it
+ * contribute nothing, so no read leaves the frame's row of seg whatever the arrays hold; elements behind sum(p), blocks
+ * behind C_f and blocks in no mask of the track are never read.  i mod p is exact for N < 2^31 and p <= ccap <= 2^24
+ * (p > N, p = N and p = 1 included).  One launch (k_overlap_add_periodic): one lane per (t, n), float64 accumulation in
+ * ascending f, then ascending a, no atomics -- the same bits on every run.  T * L may exceed 2^31.
+ * Every array follows PH_FLAG_DEVICE.  PH_E_ARG for a NULL ctx / seg / periods / counts / masks / out, W, N, hop, T, pcap,
+ * ccap or L < 1, pcap > 2^20, ccap > 2^24, (W - 1) * hop >= L, or T * L * 8 / T * W * 8 / W * ccap * 8 / W * pcap * 4 beyond
+ * 64 bits, before any HIP call. */
+int ph_overlap_add_periodic(ph_ctx* ctx, const double* seg /* (W, ccap) */, const int32_t* periods /* (W, pcap) */,
+                            const int32_t* counts /* W */, const uint64_t* masks /* (T, W) */, int64_t W, int pcap,
+                            int ccap, int64_t T, int N, int hop, int64_t L, const double* win_a, const double* win_s,
+                            unsigned flags /* PH_FLAG_DEVICE | PH_FLAG_OLA_NORM */, double* out /* (T, L) */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,13 @@ and the ``(W, K, N)`` bases never leave the device.
 
     dec = st.decompose(recording, method="m_best", num=10, max_tracks=8)
     dec.track_periods, dec.tracks, dec.other, dec.activity
+
+``decompose_qo`` is the same split by ``QOPeriods``: ``find_periods`` and ``get_periods`` on every frame -- one waveform
+of p samples per period -- and one routed overlap-add that tiles those waveforms on the fly
+(``PeriodEngine.overlap_add_periodic``), so no ``(W, K, N)`` array exists even on the device.
+
+    dq = st.decompose_qo(recording, num=4, thresh=0.1)
+    dq.track_periods, dq.tracks, dq.other, dq.periodic, dq.residual
 """
 
 from __future__ import annotations
@@ -271,6 +278,243 @@ class ShortTime:
             bit = (masks[:T] >> np.uint64(k)) & np.uint64(1)
             activity += np.where(bit != 0, pw[None, :, k], 0.0)
         return ShortTimeTracks(per, pw, periodic, x64 - periodic, wanted, routed[:T], routed[T], activity, counts)
+
+    def decompose_qo(self, signal, num, thresh, min_length=2, max_length=None, update_weights=True, tracks=None,
+                     max_tracks=8, max_rows=2048):
+        """``QOPeriods.find_periods`` followed by ``get_periods`` on every frame, and the per-period waveforms
+        overlap-added onto tracks: -> ShortTimeTracks.  Plain selection, default test function, natural basis, no
+        analysis window inside the fit (the ``ShortTime`` window shapes the frames); `trunc_to_integer_multiple` is the
+        constructor's flag, `update_weights` either value; ``orthogonalize=True`` raises ValueError (that loop is stepped
+        from the host).  `num` in 1 .. 64 is required (a 64-bit mask routes 64 blocks), `max_length` defaults to
+        ``frame_length // 3``, `tracks` / `max_tracks` are those of ``decompose``.  `max_rows` caps the dictionary rows
+        (weights) per frame the device loop is given room for.
+
+        Everything runs on device tensors: ``frames`` -> ``qo_find_periods`` (frames that end PH_ST_CAP are re-run at
+        the next capacity as a gathered sub-batch and scattered back, while that capacity is feasible and <= `max_rows`)
+        -> ``qo_get_periods`` (one period per block, ``(W, ccap)``) -> per-block powers -> ONE
+        ``overlap_add_periodic`` launch with T + 2 mask rows: the tracks, ``other`` and all blocks (``periodic``).  L
+        samples go up, (T + 2) L doubles and the per-frame periods / counts / powers come down; no ``(W, K, N)`` array
+        exists anywhere.  A frame the device loop does not finish (still not PH_ST_OK, or without a block) is downloaded,
+        run through the 1-D ``QOPeriods.find_periods`` and packed back into the device arrays; such frames are named in
+        a warning.  A frame with sum |x| <= 1e-16 (the reference's fixed all-zero answer) has no block.
+        With ``update_weights=False`` the loop fits a period again whenever it is the strongest of the running residual
+        (and once more when the test function stops it); the blocks of one period are added into one before the
+        extraction (``_merge_repeats``: the tiles of a sum are the sum of the tiles), so every period of a frame is
+        listed once, in the order first fitted.
+
+        Result: ``periods`` / ``powers`` (W, K) are the blocks' periods and the mean square of each block's waveform over
+        its period, zeros behind ``counts`` (blocks per frame); ``activity[t, f]`` sums the powers of the track's blocks
+        in ascending block order; ``residual = float64(signal) - periodic``."""
+        import torch
+
+        from .QOPeriods import QOPeriods
+
+        if self._orthogonalize:
+            raise ValueError("decompose_qo: orthogonal selection is stepped from the host and not offered here")
+        if isinstance(num, bool) or not isinstance(num, (int, np.integer)) or not 1 <= int(num) <= _MAX_ROWS:
+            raise ValueError(f"num={num!r}: decompose_qo needs 1 <= num <= {_MAX_ROWS} blocks per frame")
+        num, max_rows, max_tracks = int(num), int(max_rows), int(max_tracks)
+        if max_rows < 1:
+            raise ValueError("max_rows must be >= 1")
+        if max_tracks < 0:
+            raise ValueError("max_tracks must be >= 0")
+        wanted = None if tracks is None else self._track_list(tracks)
+        x = self._signal(signal)
+        if type(x).__module__.startswith("torch"):
+            x = x.detach().cpu().numpy()
+        L, N, hop = x.shape[0], self.frame_length, self.hop
+        W = self.frame_count(L)
+        max_length = N // 3 if max_length is None else int(max_length)
+        min_length = int(min_length)
+        trunc, uw = self._trunc_to_integer_multiple, bool(update_weights)
+        eng = default_engine()
+        dev = torch.device("cuda", eng.device)
+        xd = torch.as_tensor(x, device=dev)  # the one upload: L samples
+        win = None if self.window is None else torch.as_tensor(self.window, device=dev)
+        fr = eng.frames(xd, N, hop, W, win, torch.float64 if self.dtype == np.float64 else torch.float32)
+        silent = (fr.to(torch.float64).abs().sum(dim=1) <= 1e-16).cpu().numpy()
+
+        # ---- the fit: the capacities of QOPeriods._find_periods_device_batch, capped at max_rows
+        bound = num * max_length
+        if uw:
+            kcap, kmax = (min(2048, max(64, -(-bound // 64) * 64)) if bound <= 2048 else 512), 2048
+            kcap = min(kcap, max_rows)
+            while kcap > 64 and not eng.qo_feasible(N, self.dtype, kcap, max_length):
+                kcap //= 2
+            if not eng.qo_feasible(N, self.dtype, kcap, max_length):
+                kcap = 0  # no capacity fits: every frame goes the way of the unfinished ones
+        else:
+            kcap, kmax = min(4096, max(64, -(-bound // 64) * 64), max_rows), 1 << 20
+        kmax = min(kmax, max_rows)
+        per = torch.zeros((W, num), dtype=torch.int32, device=dev)
+        keeps = torch.zeros((W, num), dtype=torch.int32, device=dev)
+        nb = torch.zeros((W,), dtype=torch.int32, device=dev)
+        wts = torch.zeros((W, max(kcap, 1)), dtype=torch.float64, device=dev)
+        st = np.full(W, _ffi.PH_ST_CAP, dtype=np.int32)
+        todo = np.arange(W)
+        while kcap and todo.size:
+            whole = todo.size == W
+            idx = None if whole else torch.as_tensor(todo, device=dev)
+            p2, _, k2, c2, w2, _, s2 = eng.qo_find_periods(fr if whole else fr[idx], num, thresh, min_length, max_length,
+                                                           kcap, trunc=trunc, update_weights=uw)
+            if wts.shape[1] < kcap:
+                wts = torch.cat([wts, wts.new_zeros((W, kcap - wts.shape[1]))], dim=1)
+            if whole:
+                per, keeps, nb = p2, k2, c2[:, 1].contiguous()
+                wts[:, :kcap] = w2
+            else:
+                per[idx], keeps[idx], nb[idx] = p2, k2, c2[:, 1]
+                wts[idx, :kcap] = w2
+            st[todo] = s2.cpu().numpy()
+            grow = st[todo] == _ffi.PH_ST_CAP
+            nxt = kcap * (2 if uw else 4)
+            if not grow.any() or nxt > kmax or (uw and not eng.qo_feasible(N, self.dtype, nxt, max_length)):
+                break
+            kcap, todo = nxt, todo[grow]
+        if not uw:  # a keeps entry of 0 stands for `period` rows
+            keeps = torch.where(keeps == 0, per, keeps)
+
+        # ---- frames the device loop did not finish: the 1-D call, packed into the device arrays
+        nb_h = nb.cpu().numpy()
+        unfinished = np.flatnonzero(~silent & ((st != _ffi.PH_ST_OK) | (nb_h == 0)))
+        if unfinished.size:
+            rows_h = fr[torch.as_tensor(unfinished, device=dev)].cpu().numpy()
+            qo = QOPeriods(trunc_to_integer_multiple=trunc)
+            packed = []
+            for f, row in zip(unfinished, rows_h):
+                out, _ = qo.find_periods(row, num, thresh, min_length, max_length, uw)
+                wt = np.asarray(out["weights"], dtype=np.float64).reshape(-1)
+                blocks = self._pack_dictionary(wt, out["basis_dictionary"], not uw)
+                if sum(blocks[1]) != wt.size:
+                    # (the fixed-weight loop fitted a period twice: the dictionary keeps one entry, the weights both
+                    # blocks, and which rows belong to which cannot be told from the two)
+                    raise ValueError(f"decompose_qo: the 1-D result of frame {int(f)} has {wt.size} weights for the "
+                                     f"{sum(blocks[1])} rows of its dictionary")
+                packed.append(blocks)
+            pcap = max([num] + [len(p[0]) for p in packed])
+            if pcap > _MAX_ROWS:
+                raise ValueError(f"{pcap} blocks in frame {int(unfinished[0])}: decompose_qo routes at most {_MAX_ROWS}")
+            kneed = max([wts.shape[1]] + [p[2].size for p in packed])
+            if pcap > num:
+                per = torch.cat([per, per.new_zeros((W, pcap - num))], dim=1)
+                keeps = torch.cat([keeps, keeps.new_zeros((W, pcap - num))], dim=1)
+            if kneed > wts.shape[1]:
+                wts = torch.cat([wts, wts.new_zeros((W, kneed - wts.shape[1]))], dim=1)
+            hp = np.zeros((unfinished.size, pcap), np.int32)
+            hk = np.zeros((unfinished.size, pcap), np.int32)
+            hw = np.zeros((unfinished.size, wts.shape[1]))
+            hn = np.zeros(unfinished.size, np.int32)
+            for j, (ps, ks, ws_) in enumerate(packed):
+                hn[j] = len(ps)
+                hp[j, : len(ps)], hk[j, : len(ps)], hw[j, : ws_.size] = ps, ks, ws_
+            idx = torch.as_tensor(unfinished, device=dev)
+            per[idx], keeps[idx] = torch.as_tensor(hp, device=dev), torch.as_tensor(hk, device=dev)
+            wts[idx], nb[idx] = torch.as_tensor(hw, device=dev), torch.as_tensor(hn, device=dev)
+            warn(f"decompose_qo: frames {unfinished.tolist()} were not finished by the device loop and ran on the host")
+        if silent.any():
+            nb[torch.as_tensor(np.flatnonzero(silent), device=dev)] = 0
+        if not uw:  # the fixed-weight loop lists a period once per fit: one block per period for the extraction
+            per, keeps, nb, wts = self._merge_repeats(torch, per, keeps, nb, wts, max(max_length, 1))
+        per, keeps, nb, wts = per.contiguous(), keeps.contiguous(), nb.contiguous(), wts.contiguous()
+        pcap = per.shape[1]
+
+        # ---- one period per block, and its power
+        slot = torch.arange(pcap, device=dev)[None, :]
+        used = slot < nb[:, None]
+        ends = torch.cumsum((per.clamp(min=0) * used).to(torch.int64), dim=1)  # (W, pcap): end of block a
+        ccap = max(1, int(ends[:, -1].max().item()))  # the one word read back
+        seg, gst = eng.qo_get_periods(per, keeps, nb, wts, ccap=ccap)
+        gst = gst.cpu().numpy()
+        nb_h = nb.cpu().numpy()
+        bad = (gst != _ffi.PH_ST_OK) & ~((gst == _ffi.PH_ST_NO_PERIOD) & (nb_h <= 0))
+        if bad.any():
+            raise ValueError(f"decompose_qo: the dictionary of frame {_first(bad)} cannot be extracted "
+                             f"(status {int(gst[_first(bad)])})")
+        col = torch.arange(ccap, device=dev)[None, :]
+        sq = seg * seg
+        powers = torch.zeros((W, pcap), dtype=torch.float64, device=dev)
+        for a in range(pcap):  # one pass over seg per block index
+            hi = ends[:, a : a + 1]
+            lo = hi - per[:, a : a + 1].clamp(min=0)
+            inside = (col >= lo) & (col < hi) & used[:, a : a + 1]
+            powers[:, a] = torch.where(inside, sq, sq.new_zeros(())).sum(dim=1) / per[:, a].clamp(min=1)
+        per_h = np.where(used.cpu().numpy(), per.cpu().numpy(), 0)
+        pw_h = np.where(per_h > 0, powers.cpu().numpy(), 0.0)
+        counts_h = np.clip(nb_h, 0, pcap).astype(np.int32)
+
+        # ---- tracks: T rows, `other`, and every block (`periodic`) in one launch
+        if wanted is None:
+            wanted = [(p,) for p in self.rank_periods(per_h, pw_h, counts_h, max_tracks)]
+        T = len(wanted)
+        masks = np.empty((T + 2, W), np.uint64)
+        masks[: T + 1] = self.track_masks(per_h, counts_h, wanted)
+        low = (np.uint64(1) << np.minimum(counts_h, 63).astype(np.uint64)) - np.uint64(1)
+        masks[T + 1] = np.where(counts_h >= 64, np.uint64(2**64 - 1), low)  # every block in use
+        masks_d = torch.as_tensor(masks.view(np.int64), device=dev)
+        routed = eng.overlap_add_periodic(seg, per, nb, masks_d, N, hop, L, win, win, True).cpu().numpy()
+        activity = np.zeros((T, W))
+        for a in range(pcap):  # ascending a, as the kernel adds
+            bit = (masks[:T] >> np.uint64(a)) & np.uint64(1)
+            activity += np.where(bit != 0, pw_h[None, :, a], 0.0)
+        periodic = routed[T + 1]
+        return ShortTimeTracks(per_h, pw_h, periodic, x.astype(np.float64) - periodic, wanted, routed[:T], routed[T],
+                               activity, counts_h)
+
+    @staticmethod
+    def _merge_repeats(torch, per, keeps, nb, wts, max_block):
+        """The blocks of the fixed-weight loop with every period listed once: that loop fits a period again whenever
+        it is the strongest of the running residual (and once more when the test function stops it), each time as a
+        block of its own, and ``qo_get_periods`` refuses a period listed twice.  Blocks of one period are added -- the
+        tiles of a sum are the sum of the tiles, so the reconstruction is unchanged -- into the slot of the first, in
+        ascending block order; rows = the most any of them has.  Device tensors in, device tensors out; `max_block`
+        bounds the rows of one block.  One word is read back (does anything repeat?)."""
+        W, P = per.shape
+        Kc = wts.shape[1]
+        ar = torch.arange(P, device=per.device)
+        used = ar[None, :] < nb[:, None]
+        same = (per[:, :, None] == per[:, None, :]) & used[:, :, None] & used[:, None, :]
+        first = same.to(torch.int8).argmax(dim=2)  # [f, a]: the first block with the period of block a
+        lead = used & (first == ar[None, :])
+        if bool((lead == used).all()):
+            return per, keeps, nb, wts
+        # new index of every used block (a frame without blocks has no first one: 0, an index like any other -- it is
+        # used to gather below -- and no row of such a frame is moved)
+        slot = torch.gather(torch.cumsum(lead.to(torch.int64), dim=1) - 1, 1, first).clamp(min=0)
+        rows = (keeps * used).to(torch.int64)
+        old_off = torch.cumsum(rows, dim=1) - rows
+        where = torch.where(used, slot, torch.full_like(slot, P))  # unused blocks land in a column that is dropped
+        new_per = per.new_zeros((W, P + 1)).scatter_(1, where, per)[:, :P]
+        new_rows = rows.new_zeros((W, P + 1)).scatter_reduce_(1, where, rows, "amax")[:, :P]
+        new_off = torch.cumsum(new_rows, dim=1) - new_rows
+        new_wts = torch.zeros_like(wts)
+        j = torch.arange(min(int(max_block), Kc), device=per.device)[None, :]
+        for a in range(P):  # ascending a: one fixed order of addition; inside one a no two rows share a target
+            valid = j < rows[:, a : a + 1]
+            src = (old_off[:, a : a + 1] + j).clamp(max=Kc - 1)
+            dst = (torch.gather(new_off, 1, slot[:, a : a + 1]) + j).clamp(max=Kc - 1)
+            vals = torch.where(valid, torch.gather(wts, 1, src), wts.new_zeros(()))
+            new_wts.scatter_add_(1, dst, vals)
+        return new_per, new_rows.to(torch.int32), lead.sum(dim=1).to(torch.int32), new_wts
+
+    @staticmethod
+    def _pack_dictionary(weights, dictionary, zero_is_period=False):
+        """A 1-D find_periods result as the blocks qo_get_periods takes: -> (periods, rows, weights) with the slice
+        semantics of ``QOPeriods.get_periods`` (an entry with more rows than its period keeps `period` of them).
+        `zero_is_period`: the fixed-weight loop writes 0 for a block that kept all `period` rows (``Pp(keep=0)``)."""
+        from .QOPeriods import QOPeriods
+
+        ps, ks, blocks, read = [], [], [], 0
+        for q, r in dictionary.items():
+            q, r = int(q), int(r)
+            if zero_is_period and r == 0:
+                r = q
+            v = QOPeriods.concatenate_periods(weights[read:], {str(q): r})
+            k = r if 0 <= r <= q else q
+            read += r
+            ps.append(q)
+            ks.append(k)
+            blocks.append(v[:k])
+        return ps, ks, (np.concatenate(blocks) if blocks else np.zeros(0))
 
     @staticmethod
     def _track_list(tracks):

@@ -79,6 +79,7 @@ SIGNATURES = {
     "ph_frames": [_vp, _vp, _i, _i64, _i, _i, _i64, _vp, _i, _u, _vp],
     "ph_overlap_add": [_vp, _vp, _i, _i64, _i, _i, _i, _i64, _pi32, _vp, _vp, _u, _vp],
     "ph_overlap_add_tracks": [_vp, _vp, _i, _i64, _i, _i, _i, _i64, _pi32, _vp, _i64, _vp, _vp, _u, _vp],
+    "ph_overlap_add_periodic": [_vp, _vp, _pi32, _pi32, _vp, _i64, _i, _i, _i64, _i, _i, _i64, _vp, _vp, _u, _vp],
 }
 
 

@@ -2610,4 +2610,47 @@ int ph_overlap_add_tracks(ph_ctx* c, const void* y, int dtype, int64_t W, int K,
   return st.finish();
 }
 
+int ph_overlap_add_periodic(ph_ctx* c, const double* seg, const int32_t* periods, const int32_t* counts,
+                            const uint64_t* masks, int64_t W, int pcap, int ccap, int64_t T, int N, int hop, int64_t L,
+                            const double* win_a, const double* win_s, unsigned flags, double* out) {
+  if (!c) return fail(PH_E_ARG, "ctx is NULL");
+  if (!seg || !periods || !counts || !masks || !out)
+    return fail(PH_E_ARG, "ph_overlap_add_periodic: seg / periods / counts / masks / out is NULL");
+  // (not check_framing: there is no W * K * N array here, so no product of that size to refuse)
+  if (W < 1 || N < 1 || hop < 1 || L < 1)
+    return fail(PH_E_ARG, "ph_overlap_add_periodic: W=%lld, N=%d, hop=%d, L=%lld must all be >= 1", (long long)W, N, hop,
+                (long long)L);
+  if (W - 1 > (L - 1) / hop)
+    return fail(PH_E_ARG, "ph_overlap_add_periodic: frame %lld starts at or behind the end of the signal ((W - 1) * hop >= L = %lld)",
+                (long long)(W - 1), (long long)L);
+  if (T < 1) return fail(PH_E_ARG, "ph_overlap_add_periodic: T=%lld must be >= 1", (long long)T);
+  if (pcap < 1 || pcap > (1 << 20)) return fail(PH_E_ARG, "ph_overlap_add_periodic: pcap=%d must be in [1, 2^20]", pcap);
+  if (ccap < 1 || ccap > (1 << 24)) return fail(PH_E_ARG, "ph_overlap_add_periodic: ccap=%d must be in [1, 2^24]", ccap);
+  if (T > (INT64_MAX / 8) / L || T > (INT64_MAX / 8) / W)
+    return fail(PH_E_ARG, "ph_overlap_add_periodic: T * L or T * W does not fit 64 bits");
+  if (W > (INT64_MAX / 8) / ccap || W > (INT64_MAX / 4) / pcap)
+    return fail(PH_E_ARG, "ph_overlap_add_periodic: W * ccap or W * pcap does not fit 64 bits");
+  PH_HIP(hipSetDevice(c->device));
+  Stage st(c, flags);
+  const void *dseg, *dper, *dcnt, *dmask, *dwa = nullptr, *dws = nullptr;
+  void* dout;
+  PH_TRY(st.in(seg, (size_t)W * ccap * sizeof(double), &dseg));
+  PH_TRY(st.in(periods, (size_t)W * pcap * sizeof(int32_t), &dper, B_GEN0));
+  PH_TRY(st.in(counts, (size_t)W * sizeof(int32_t), &dcnt, B_GBUF));
+  PH_TRY(st.in(masks, (size_t)T * W * sizeof(uint64_t), &dmask, B_WS0));
+  if (win_a) PH_TRY(st.in(win_a, (size_t)N * sizeof(double), &dwa, B_GWIN));
+  if (win_s) PH_TRY(st.in(win_s, (size_t)N * sizeof(double), &dws, B_WS1));
+  PH_TRY(st.out(B_OUT0, out, (size_t)T * L * sizeof(double), &dout));
+  const dim3 grid(flat_grid(c, T * L));
+  const int norm = (flags & PH_FLAG_OLA_NORM) ? 1 : 0;
+  {
+    ProfScope ps_(c, "k_overlap_add_periodic");
+    hipLaunchKernelGGL(ph::k_overlap_add_periodic, grid, dim3(ph::kFramesBlock), 0, c->stream, (const double*)dseg,
+                       (const int*)dper, (const int*)dcnt, (const unsigned long long*)dmask, W, pcap, ccap, T, N, hop, L,
+                       (const double*)dwa, (const double*)dws, norm, (double*)dout);
+  }
+  PH_TRY(launch_check("k_overlap_add_periodic"));
+  return st.finish();
+}
+
 }  // extern "C"

@@ -1,6 +1,7 @@
 // Short-time framing and overlap-add on the device: k_frames cuts a signal of L samples into the (W, N) batch every
 // other entry point takes, k_overlap_add folds a (W, K, N) result back onto the L samples of the signal, and
-// k_overlap_add_tracks folds it onto several tracks of L samples, the rows of each chosen by a mask.  All are
+// k_overlap_add_tracks folds it onto several tracks of L samples, the rows of each chosen by a mask;
+// k_overlap_add_periodic does the same from one period per row (the segments of k_qo_extract), tiled on the fly.  All are
 // memory-bound element-wise kernels without LDS; all index arithmetic is int64 (f * hop and f * N pass 2^31 for real
 // recordings).  Included by period_hip.hip behind ph_fit.h.
 #pragma once
@@ -213,6 +214,67 @@ __global__ __launch_bounds__(kFramesBlock) void k_overlap_add_tracks(const T* __
         const int k = __builtin_ctzll(m);
         m &= m - 1ull;
         num += s * (double)row[(int64_t)k * N];
+      }
+    }
+    out[item] = norm ? (den > 0.0 ? num / den : 0.0) : num;
+  }
+}
+
+// ======================================================================================
+// Routed overlap-add of periodic segments: seg (W, ccap) float64 holds ONE period of every block -- the layout
+// k_qo_extract writes: block a of frame f is p(f, a) = periods[f, a] doubles at off(f, a) = sum_{b < a} p(f, b) -- and is
+// tiled on the fly onto NT tracks of L samples -> out (NT, L) float64.  With i = n - f hop:
+//   num[t, n] = sum_f ws[i] * sum_{a < C_f, bit a of masks[t, f] set} seg[f, off(f, a) + (i mod p(f, a))]
+//   C_f = counts[f] clipped to [0, min(pcap, 64)]; den, norm, the frames of a sample and the mask word as in
+//   k_overlap_add_tracks.  The dense (W, K, N) rows that kernel reads never exist: a frame costs sum p doubles, not K N.
+// One lane owns one (t, n) and walks frames in ascending f, blocks in ascending a, accumulating in float64: the order
+// of k_overlap_add_tracks, no atomics, the same bits on every run.  Flat grid-stride loop over NT * L, int64 addressing.
+// The offsets are the running sum of the periods the walk has passed, so a lane reads periods[f, a] for every a up to
+// the highest bit of its (cut) mask word -- the same address for every lane of a wavefront that lies in one frame and
+// track, one cache line per 16 blocks -- and seg only for the blocks its mask names.
+// Stop rule: the device arrays are whatever the caller left there, so the walk of a frame ends at the first block with
+// p < 1 or off + p > ccap; that block and the ones behind it contribute nothing.  Every read of seg is therefore at
+// off + r with 0 <= r < p and off + p <= ccap: inside the frame's row.  Elements behind sum p, blocks behind C_f and
+// blocks in no mask of the lane's track are never read.
+// i mod p: 0 <= i < N < 2^31 and, by the stop rule, 1 <= p <= ccap <= 2^24, so the unsigned 32-bit remainder is exact
+// (p > N gives i).  It is the compiler's expansion (a float reciprocal and two corrections, ~20 VALU instructions per
+// term): measured against the gathers in tools/short_time_qo_bench.py, DESIGN.md 4.2h.
+// ======================================================================================
+__global__ __launch_bounds__(kFramesBlock) void k_overlap_add_periodic(const double* __restrict__ seg, const int* __restrict__ periods,
+                                                                      const int* __restrict__ counts,
+                                                                      const unsigned long long* __restrict__ masks, int64_t W,
+                                                                      int pcap, int ccap, int64_t NT, int N, int hop, int64_t L,
+                                                                      const double* __restrict__ wa, const double* __restrict__ ws,
+                                                                      int norm, double* __restrict__ out) {
+  const int64_t total = NT * L;
+  const int64_t stride = (int64_t)gridDim.x * kFramesBlock;
+  const int cmax = pcap < 64 ? pcap : 64;
+  for (int64_t item = (int64_t)blockIdx.x * kFramesBlock + threadIdx.x; item < total; item += stride) {
+    const int64_t t = item / L;
+    const int64_t n = item - t * L;
+    const int64_t f_lo = n < N ? 0 : (n - N) / hop + 1;
+    int64_t f_hi = n / hop;
+    if (f_hi > W - 1) f_hi = W - 1;
+    const unsigned long long* mrow = masks + t * W;
+    double num = 0.0, den = 0.0;
+    for (int64_t f = f_lo; f <= f_hi; ++f) {
+      const unsigned i = (unsigned)(n - f * hop);
+      int cf = counts[f];
+      cf = cf < 0 ? 0 : cf > cmax ? cmax : cf;
+      const double s = ws ? ws[i] : 1.0;
+      den += (wa ? wa[i] : 1.0) * s;
+      unsigned long long m = mrow[f];
+      if (cf < 64) m &= (1ull << cf) - 1ull;  // (cf = 0: no block at all)
+      if (m == 0ull) continue;
+      const int last = 63 - __builtin_clzll(m);  // < cf <= pcap
+      const int* prow = periods + f * (int64_t)pcap;
+      const double* srow = seg + f * (int64_t)ccap;
+      int64_t off = 0;
+      for (int a = 0; a <= last; ++a) {
+        const int p = prow[a];
+        if (p < 1 || off + p > ccap) break;  // the stop rule
+        if ((m >> a) & 1ull) num += s * srow[off + (int64_t)(i % (unsigned)p)];
+        off += p;
       }
     }
     out[item] = norm ? (den > 0.0 ? num / den : 0.0) : num;

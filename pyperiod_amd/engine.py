@@ -729,6 +729,59 @@ class PeriodEngine:
                    T, mk.addr(wa), mk.addr(ws), fl | (_ffi.PH_FLAG_OLA_NORM if normalize else 0), mk.addr(out))
         return out
 
+    def overlap_add_periodic(self, seg, periods, counts, masks, frame_length, hop, length, win_a=None, win_s=None,
+                             normalize=True):
+        """Routed overlap-add of periodic segments (ph_overlap_add_periodic, one launch): -> (T, length) float64,
+        out[t, n] = what overlap_add_tracks gives for the blocks of `seg` tiled to `frame_length` samples, without the
+        tiled (W, K, N) array.  `seg` (W, ccap) float64 and `periods` (W, pcap <= 64) int32 as qo_get_periods takes and
+        returns them (block a of frame f is periods[f, a] doubles at sum(periods[f, :a])), `counts` (W) int32 blocks in
+        use, `masks` (T, W) np.uint64 / np.int64 or a torch.int64 tensor: bit a of masks[t, f] routes block a of frame f
+        to track t.  A frame's blocks from the first with a period < 1 or running past ccap on contribute nothing.
+        numpy arrays, or torch tensors on the engine's device (on torch's current stream; the result is then a tensor);
+        `win_a` / `win_s` (frame_length) float64 or None, `normalize` as in overlap_add."""
+        N, hop, L = int(frame_length), int(hop), int(length)
+        if L < 0:
+            raise ValueError("length must be >= 0")
+        if getattr(seg, "ndim", None) != 2:
+            raise ValueError("expected seg of shape (W, ccap)")
+        x, code, W, ccap, fl, mk = self._prep(seg)
+        if code != _ffi.PH_F64:
+            raise TypeError("seg must be float64")
+        if mk.torch:
+            t = mk._t
+            for a, what in ((periods, "periods"), (counts, "counts")):
+                if not _is_torch(a) or a.dtype != t.int32 or a.device != x.device:
+                    raise TypeError(f"{what} must be an int32 tensor on the device of seg")
+            if not _is_torch(masks) or masks.dtype != t.int64 or masks.device != x.device:
+                raise TypeError("masks must be an int64 tensor on the device of seg")
+            per, cnt, msk = periods.contiguous(), counts.contiguous(), masks.contiguous()
+        else:
+            if not isinstance(masks, np.ndarray) or masks.dtype not in (np.dtype(np.uint64), np.dtype(np.int64)):
+                raise TypeError("masks must be a uint64 or int64 array")
+            per = np.ascontiguousarray(periods, dtype=np.int32)
+            cnt = np.ascontiguousarray(counts, dtype=np.int32)
+            msk = np.ascontiguousarray(masks)
+        if per.ndim != 2 or per.shape[0] != W or per.shape[1] < 1:
+            raise ValueError("periods must be (W, pcap) with pcap >= 1")
+        pcap = int(per.shape[1])
+        if pcap > 64:
+            raise ValueError(f"pcap={pcap} blocks per frame do not fit a 64-bit mask")
+        if tuple(cnt.shape) != (W,):
+            raise ValueError("counts must hold one entry per frame")
+        if msk.ndim != 2 or msk.shape[1] != W:
+            raise ValueError("masks must be (T, W): one word per track and frame")
+        T = int(msk.shape[0])
+        wa = None if win_a is None else self._window(mk, x, win_a, N)
+        ws = None if win_s is None else self._window(mk, x, win_s, N)
+        out = mk.empty((T, L), np.float64)
+        if W == 0 or L == 0:  # nothing to add: no call
+            out[...] = 0.0
+            return out
+        self._call(mk, W, self._lib.ph_overlap_add_periodic, mk.addr(x), mk.addr(per), mk.addr(cnt), mk.addr(msk), W, pcap,
+                   int(ccap), T, N, hop, L, mk.addr(wa), mk.addr(ws),
+                   fl | (_ffi.PH_FLAG_OLA_NORM if normalize else 0), mk.addr(out))
+        return out
+
     def fold_sums(self, x, p_list, keep):
         """W = A x for natural-basis rows (QOPeriods.py:782): (W, sum(keep)) float64."""
         x, code, W, N, fl, mk = self._prep(x)

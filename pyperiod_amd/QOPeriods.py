@@ -7,11 +7,8 @@ even be constructed (QOPeriods.py:190) and only its non-orthogonal ``find_period
   * plain projection, default test function: the whole greedy loop (gamma sweep, phi-mass row
     bookkeeping, right-hand side by folds, matrix-free conjugate-gradient solve, reconstruction,
     residual) runs in ONE kernel launch per window batch -> ph_qo_find_periods
-  * a (W, N) batch: the default, update_weights=False and trunc variants run in one launch per batch
-    (ph_qo_find_periods, PH_FLAG_KEEP_WEIGHTS / PH_FLAG_TRUNC), update_weights=False under an analysis window too
-    (ph_qo_greedy_win); with re-solved weights under an analysis window and under orthogonal (Muresan-Parks) selection
-    -- with or without a window -- the greedy loop is stepped from the host for the whole batch, two launches per round
-    (ph_sweep + ph_qo_fit_win; ph_qo_orth_select + ph_qo_fit or ph_qo_fit_win); the other settings run row by row
+  * a (W, N) batch: one launch per batch, a greedy loop stepped from the host with two launches per round, or the
+    1-D call row by row -- the table in ``QOPeriods._batch_path`` says which settings run where
   * other 1-D settings (custom test_function, update_weights=False, trunc, window, Ramanujan basis):
     the loop is driven from the host with the heavy pieces on the GPU -- the sweep (ph_sweep,
     QOPeriods.py:470-478), W = A x and A A^T as folds (ph_fold_sums, :781-782), A^T w
@@ -104,6 +101,41 @@ def _device_window(window, n):
     return win if win.shape == (n,) and np.all(np.isfinite(win)) else None
 
 
+_PICKED, _NOTHING_LEFT, _HAND_BACK = range(3)  # what a selector of QOPeriods._find_periods_stepped says of a row
+
+
+def _hand_back_all(w):
+    """A selector's answer when its precondition fails: (period, norm, fate) with all `w` rows handed back."""
+    return np.zeros(w, dtype=np.int32), np.zeros(w), np.full(w, _HAND_BACK)
+
+
+def _qo_capacities(eng, n, dtype, num, max_length, update_weights, max_rows=None):
+    """The dictionary-row capacities (kcap) ph_qo_find_periods is given for windows of `n` samples, one after the other:
+    the caller launches at each and asks for the next while rows end PH_ST_CAP.  Nothing is yielded when no capacity is
+    feasible.  A block adds at most `max_length` rows, so the start has room for all `num` of them when that is at most
+    2048 rows.  Re-solved weights live in LDS: the start is halved until the plan query accepts it, and doubles while
+    that holds, up to 2048.  The fixed-weight loop keeps its weights in HBM only, where every capacity is feasible: up
+    to 2^20 rows in steps of 4.  `max_rows` caps the start and the limit (the start may then be below 64, or no
+    multiple of 64)."""
+    bound = int(num) * int(max_length)
+    room = max(64, -(-bound // 64) * 64)
+    if update_weights:
+        kcap, limit, step = (min(2048, room) if bound <= 2048 else 512), 2048, 2
+    else:
+        kcap, limit, step = min(4096, room), 1 << 20, 4
+    if max_rows is not None:
+        kcap, limit = min(kcap, max_rows), min(limit, max_rows)
+
+    def feasible(k):
+        return not update_weights or eng.qo_feasible(n, dtype, k, max_length)
+
+    while kcap > 64 and not feasible(kcap):
+        kcap //= 2
+    while kcap <= limit and feasible(kcap):
+        yield kcap
+        kcap *= step
+
+
 class _LazyBases(dict):
     """The output_bases dict of one row of a batched find_periods.  Its "subspaces" entry -- the stacked
     natural-basis rows of the dictionary blocks, rows x N doubles -- is built from the blocks on first read and
@@ -191,8 +223,7 @@ class QOPeriods(Periods):
     def find_periods(self, data, num=None, thresh=None, min_length=2, max_length=None, update_weights=True, **kwargs):
         """Greedy period selection with re-solved weights (QOPeriods.py:313-596).
         Returns ``(dict(periods, norms, subspaces, weights, basis_dictionary), residual)``; a ``(W, N)``
-        ndarray returns a list of W such tuples (see ``_find_periods_batch``: one launch per batch -- also for
-        ``update_weights=False`` under ``self.window`` -- or two per round, with ``subspaces`` built on first read).
+        ndarray returns a list of W such tuples (see ``_find_periods_batch``; ``subspaces`` is built on first read).
 
         ``orthogonalize=True``: the v1 reference dies on this branch (``best_base`` is never
         assigned, QOPeriods.py:427-448).  Offered here as its commented-out lines intend: the
@@ -222,58 +253,61 @@ class QOPeriods(Periods):
             update_weights and custom_test is None and thresh is not None and not self._orthogonalize
             and not self._trunc_to_integer_multiple and self._basis_type == "natural" and not windowed
         )
-        if on_device:
-            done = self._find_periods_device(default_engine(), data, N, num, thresh, min_length, max_length)
-            if done is not None:
-                return done
+        if on_device:  # the whole greedy loop in one launch, as a batch of one
+            done = self._find_periods_device_batch(default_engine(), data[None, :], num, thresh, min_length, max_length, True)[0]
+            if done is not None:  # (None: the dictionary does not fit the kernel's LDS layout or workspace)
+                bases, residual = done
+                # a plain dict, with "subspaces" built and the views into the launch's arrays copied
+                self._output_bases = {k: v.copy() if k in ("periods", "norms", "weights") else v for k, v in bases.items()}
+                return (self._output_bases, residual.copy())
         return self._find_periods_host(data, N, num, thresh, min_length, max_length, update_weights, custom_test)
+
+    def _batch_path(self, W, windowed, win, thresh, update_weights, kwargs):
+        """Where a (W, N) batch runs.  ``common`` = default test function, `thresh` set, natural basis, not verbose;
+        "device window" = ``self.window`` is a finite 1-D array of N samples (`win`):
+
+            settings                                                              path
+            common, orthogonal, update_weights, no window or device window        "orthogonal": stepped, ph_qo_orth_select
+            common, plain, update_weights, device window                          "gamma": stepped, ph_sweep
+            common, plain, no window -- or device window with fixed weights       "one launch"
+            anything else                                                         None: the 1-D call on every row
+        """
+        common = kwargs.get("test_function") is None and thresh is not None and self._basis_type == "natural" and not self._verbose
+        if not common or W == 0 or (windowed and win is None):
+            return None
+        if self._orthogonalize:
+            return "orthogonal" if update_weights else None
+        return "gamma" if windowed and update_weights else "one launch"
 
     def _find_periods_batch(self, data, num, thresh, min_length, max_length, update_weights, kwargs):
         """find_periods over a (W, N) batch: a list of W ``(output_bases, residual)`` tuples, each what the
-        1-D call on that row returns (``output_bases`` becomes the list of the per-row dicts).
-
-        Rows whose settings the device loops cover -- default test function, ``thresh`` set, natural basis,
-        no analysis window, plain selection, either ``trunc_to_integer_multiple`` and either
-        ``update_weights`` -- run in ONE launch of ph_qo_find_periods per batch (float32 batches in the fp32
-        kernels, residuals returned as float64).  Under an analysis window (``self.window`` a finite 1-D array
-        of N samples) the same settings with ``update_weights=True`` run a batched greedy loop stepped from the host
-        (``_find_periods_window_batch``: one ph_sweep and one ph_qo_fit_win launch per round), and with
-        ``update_weights=False`` the whole fixed-weight loop in ONE launch of ph_qo_greedy_win per batch (each block
-        fitted under the window).  ``orthogonalize=True`` with ``update_weights=True`` runs the same kind of
-        host-stepped loop (``_find_periods_orth_batch``: one ph_qo_orth_select and one ph_qo_fit launch per round,
-        ph_qo_fit_win under such a window); ``update_weights=False`` under orthogonal selection stays on the 1-D path,
-        and so does every setting under a window that is not a finite 1-D array of N samples.  Everything else (custom ``test_function``,
-        Ramanujan basis, ``verbose``, ``thresh=None``) and every row the kernels hand back
-        with a fallback status or a dictionary beyond the device's capacity runs the 1-D call on that row;
-        all-zero rows get the reference's fixed answer.
+        1-D call on that row returns (``output_bases`` becomes the list of the per-row dicts).  ``_batch_path`` has the
+        table of which settings run where: in ONE launch per batch (``_find_periods_device_batch``: float32 batches in
+        the fp32 kernels, residuals returned as float64), in a greedy loop stepped from the host with two launches per
+        round (``_find_periods_stepped``), or row by row.  Every row a device path hands back -- a fallback status, a
+        dictionary beyond the device's capacity -- runs the 1-D call too; all-zero rows get the reference's fixed
+        answer there.
 
         ``"subspaces"`` of a device row is built from its ``basis_dictionary`` blocks on first read (W x rows
         x N doubles for the whole batch would not fit the host's memory at scale); reading it gives the array
         of the 1-D result."""
         W, N = data.shape
         windowed = not (self.window is None or self.window is False)
-        common = kwargs.get("test_function") is None and thresh is not None and self._basis_type == "natural" and not self._verbose
-        on_device_settings = common and not self._orthogonalize
-        on_device = on_device_settings and not windowed
-        out = [None] * W
         win = _device_window(self.window, N) if windowed else None
-        if common and self._orthogonalize and update_weights and (not windowed or win is not None) and W > 0:
+        path = self._batch_path(W, windowed, win, thresh, update_weights, kwargs)
+        out = [None] * W
+        if path is not None:
+            eng = default_engine()
             ml = int(np.floor(N / 3)) if max_length is None else int(max_length)
             n = N if num is None else int(num)
-            x = np.ascontiguousarray(data, dtype=np.float64)  # (the 1-D call works on the float64 copy of a row)
-            out = self._find_periods_orth_batch(default_engine(), x, n, thresh, ml, window=win)
-        if win is not None and update_weights and on_device_settings and W > 0:
-            ml = int(np.floor(N / 3)) if max_length is None else int(max_length)
-            n = N if num is None else int(num)
-            x = np.ascontiguousarray(data, dtype=np.float64)
-            out = self._find_periods_window_batch(default_engine(), x, win, n, thresh, int(min_length), ml)
-        if (on_device or (win is not None and on_device_settings and not update_weights)) and W > 0:
-            x = data if data.dtype in (np.float32, np.float64) else data.astype(np.float64)
-            x = np.ascontiguousarray(x)
-            ml = int(np.floor(N / 3)) if max_length is None else int(max_length)
-            n = N if num is None else int(num)
-            for w, r in enumerate(self._find_periods_device_batch(default_engine(), x, n, thresh, min_length, ml, update_weights,
-                                                                  window=win)):
+            # (the 1-D call works on the float64 copy of a row; only the one-launch kernels have an fp32 form)
+            x = np.ascontiguousarray(data, dtype=np.float32 if path == "one launch" and data.dtype == np.float32 else np.float64)
+        if path == "orthogonal":
+            out = self._find_periods_stepped(eng, x, self._select_orthogonal(eng, ml), n, thresh, ml, window=win)
+        elif path == "gamma":
+            out = self._find_periods_stepped(eng, x, self._select_gamma(eng, int(min_length), ml), n, thresh, ml, window=win)
+        elif path == "one launch":
+            for w, r in enumerate(self._find_periods_device_batch(eng, x, n, thresh, min_length, ml, update_weights, window=win)):
                 # all-zero rows (QOPeriods.py:394-406) go to the 1-D call.  A gamma norm is at most rms(x) <=
                 # sum|x| / sqrt(N), so only rows whose first norm is <= 1e-16 need the sum of the 1-D test.
                 if r is not None:
@@ -287,24 +321,20 @@ class QOPeriods(Periods):
         self._output_bases = [r[0] for r in out]
         return out
 
+    def _row_bases(self, blocks, n, periods, norms, weights):
+        """The output_bases of one device row from its (period, rows kept) `blocks`."""
+        return _LazyBases(blocks, n, self._basis_type, periods=periods, norms=norms, weights=weights,
+                          basis_dictionary={str(q): k for q, k in blocks})
+
     def _find_periods_device_batch(self, eng, x, num, thresh, min_length, max_length, update_weights, window=None):
-        """One ph_qo_find_periods launch for the batch `x` (and one more per capacity doubling, for the rows that
-        needed it); with the float64 analysis window `window` (N, ``update_weights=False`` only) the launch is
+        """One ph_qo_find_periods launch for the batch `x` (and one more per capacity of ``_qo_capacities``, for the rows
+        that needed it); with the float64 analysis window `window` (N, ``update_weights=False`` only) the launch is
         ph_qo_greedy_win.  -> list of (output_bases, residual) or None (the row goes to the 1-D call)."""
         W, N = x.shape
         trunc = bool(self._trunc_to_integer_multiple)
-        bound = int(num) * int(max_length)  # a block adds at most max_length rows
-        if update_weights:
-            kcap, kmax = (min(2048, max(64, -(-bound // 64) * 64)) if bound <= 2048 else 512), 2048
-            while kcap > 64 and not eng.qo_feasible(N, x.dtype, kcap, max_length):
-                kcap //= 2
-            if not eng.qo_feasible(N, x.dtype, kcap, max_length):
-                return [None] * W
-        else:  # the fixed-weight loop keeps its weights in HBM only: room for every row it can fit
-            kcap, kmax = min(4096, max(64, -(-bound // 64) * 64)), 1 << 20
         results = [None] * W
         todo = np.arange(W)
-        while todo.size:
+        for kcap in _qo_capacities(eng, N, x.dtype, num, max_length, update_weights):
             xs = x if todo.size == W else x[todo]
             per, nrm, keeps, counts, wts, resid, st = eng.qo_find_periods(
                 xs, num, thresh, min_length, max_length, kcap, trunc=trunc, update_weights=update_weights, window=window
@@ -317,103 +347,61 @@ class QOPeriods(Periods):
                 n_report, n_blocks = int(counts[i, 0]), int(counts[i, 1])
                 blocks = [(int(per[i, b]), int(keeps[i, b])) for b in range(n_blocks)]
                 n_rows = sum(k if k else q for q, k in blocks)
-                result = _LazyBases(  # (views into the batch's output arrays)
-                    blocks, N, self._basis_type,
-                    periods=per[i, :n_report],
-                    norms=nrm[i, :n_report],
-                    weights=wts[i, :n_rows],
-                    basis_dictionary={str(q): k for q, k in blocks},
-                )
-                results[w] = (result, resid[i])
-            grow = st == _ffi.PH_ST_CAP
-            if not grow.any():
+                # (views into the batch's output arrays)
+                results[w] = (self._row_bases(blocks, N, per[i, :n_report], nrm[i, :n_report], wts[i, :n_rows]), resid[i])
+            todo = todo[st == _ffi.PH_ST_CAP]
+            if not todo.size:
                 break
-            nxt = kcap * (2 if update_weights else 4)
-            if nxt > kmax or (update_weights and not eng.qo_feasible(N, x.dtype, nxt, max_length)):
-                break
-            kcap, todo = nxt, todo[grow]
         return results
 
-    def _find_periods_window_batch(self, eng, x, win, num, thresh, min_length, max_length):
-        """The greedy loop under the analysis window `win` for the float64 batch `x`, stepped from the host: per round
-        one ph_sweep launch (gamma norms of the residuals of the rows still active, the selection rule of
-        ``_strongest_period``) and one ph_qo_fit_win launch (those rows, each with its list so far), instead of one
-        dense dictionary, two uploads of it and a host solve per row and round.  A row stops when
-        ``rms(reconstruction) > rms(data) * thresh`` fails -- its result is the last fit with one period fewer
-        reported (QOPeriods.py:560-594) -- when no gamma norm is positive, or after `num` rounds.
-        -> per row (output_bases, residual), or None: the row is rerun whole by the 1-D call (all-zero rows, a fit that
-        came back not PH_ST_OK -- a block without rows, an indefinite matrix, more than 64 periods, a dictionary beyond
-        the largest feasible capacity)."""
-        W, N = x.shape
+    def _select_gamma(self, eng, min_length, max_length):
+        """The selector of the plain branch for ``_find_periods_stepped``: one ph_sweep launch, the gamma norms of the
+        residuals over min_length .. max_length, and per row the first maximum if it is > 0 (NaN ordered below every
+        number: the strict '>' scan of ``_strongest_period``), else nothing left."""
         trunc = bool(self._trunc_to_integer_multiple)
-        out = [None] * W
-        if max_length < min_length or min_length < 1:
-            return out
-        per = np.zeros((W, 64), dtype=np.int32)
-        counts = np.zeros(W, dtype=np.int32)
-        gnorm = np.zeros((W, 64))
-        fits = [None] * W  # (blocks, weights, residual) of the row's last fit
-        res = x.copy()
-        rms_data = np.sqrt(np.sum(x * x, axis=1) / N)
-        active = np.flatnonzero(np.sum(np.abs(x), axis=1) > 1e-16)  # (QOPeriods.py:394-406: the 1-D call's fixed answer)
 
-        def finish(w, n_report):
-            blocks, wts, resid = fits[w]
-            out[w] = (_LazyBases(blocks, N, self._basis_type, periods=per[w, :n_report].astype(np.uint32),
-                                 norms=gnorm[w, :n_report].copy(), weights=wts,
-                                 basis_dictionary={str(q): k for q, k in blocks}), resid)
-
-        for i in range(num):
-            if i > 0:  # the test function on the reconstruction of the last fit
-                rec = x[active] - res[active]
-                go = np.sqrt(np.sum(rec * rec, axis=1) / N) > rms_data[active] * thresh
-                for w in active[~go]:
-                    finish(w, int(counts[w]) - 1)
-                active = active[go]
-            if active.size == 0:
-                break
-            vals = eng.sweep(np.ascontiguousarray(res[active]), min_length, max_length, _ffi.PH_SWEEP_NORM_GAMMA, trunc, False)
+        def select(res):
+            if max_length < min_length or min_length < 1:
+                return _hand_back_all(res.shape[0])
+            rows = np.arange(res.shape[0])
+            vals = eng.sweep(res, min_length, max_length, _ffi.PH_SWEEP_NORM_GAMMA, trunc, False)
             order = np.where(np.isnan(vals), -np.inf, vals)
             k = np.argmax(order, axis=1)
-            found = order[np.arange(active.size), k] > 0
-            for w in active[~found]:  # no period left: every later round repeats this one
-                if fits[w] is not None:
-                    finish(w, int(counts[w]))
-            found &= counts[active] < 64  # (a 65th period: the 1-D call)
-            active, k, vals = active[found], k[found], vals[found]
-            if active.size == 0:
-                break
-            per[active, counts[active]] = min_length + k
-            gnorm[active, counts[active]] = vals[np.arange(active.size), k]
-            counts[active] += 1
-            fit = self._fit_lists_device(eng, np.ascontiguousarray(x[active]), np.ascontiguousarray(per[active]),
-                                         np.ascontiguousarray(counts[active]), max_length, window=win)
-            for w, r in zip(active, fit):
-                if r is not None:
-                    fits[w] = r
-                    res[w] = r[2]
-            active = active[np.array([r is not None for r in fit], dtype=bool)]
-        for w in active:
-            finish(w, int(counts[w]))
-        return out
+            return min_length + k, vals[rows, k], np.where(order[rows, k] > 0, _PICKED, _NOTHING_LEFT)
 
-    def _find_periods_orth_batch(self, eng, x, num, thresh, max_length, window=None):
-        """The greedy loop under orthogonal (Muresan-Parks) selection with re-solved weights for the float64
-        batch `x`, stepped from the host: per round one ph_qo_orth_select launch on the residuals of the rows still active
-        (the period by the normalised orthogonal powers over q < max_length and the norm of the orthogonalised
-        projection: ``_strongest_period`` for every row at once; ``min_length`` does not enter, as in the 1-D call) and
-        one ph_qo_fit launch on those rows with their lists so far -- ph_qo_fit_win under the float64 analysis window
-        `window` (N), which only the fit sees -- instead of three launches, a dense dictionary, its upload and a host
-        solve per row and round.  A row stops when ``rms(reconstruction) > rms(data) * thresh``
-        fails -- its result is the last fit with one period fewer reported (QOPeriods.py:560-594) -- or after `num`
-        rounds.  -> per row (output_bases, residual), or None: the row is rerun whole by the 1-D call (all-zero rows,
-        a select or fit that came back not PH_ST_OK -- a non-finite power, a block without rows such as a period picked
-        twice, a dictionary beyond the largest feasible capacity -- and a 65th period)."""
+        return select
+
+    def _select_orthogonal(self, eng, max_length):
+        """The selector of orthogonal (Muresan-Parks) selection for ``_find_periods_stepped``: one ph_qo_orth_select
+        launch, per row the period by the normalised orthogonal powers over q < max_length and the norm of the
+        orthogonalised projection (``_strongest_period`` for every row at once; ``min_length`` does not enter, as in the
+        1-D call).  A status that is not PH_ST_OK (a non-finite power) hands the row back."""
+        trunc = bool(self._trunc_to_integer_multiple)
+
+        def select(res):
+            if max_length < 2:  # (ph_qo_orth_select needs max_p >= 2)
+                return _hand_back_all(res.shape[0])
+            p, g, st = eng.qo_orth_select(res, max_length, trunc)
+            return p, g, np.where(st == _ffi.PH_ST_OK, _PICKED, _HAND_BACK)
+
+        return select
+
+    def _find_periods_stepped(self, eng, x, select, num, thresh, max_length, window=None):
+        """The greedy loop with re-solved weights for the float64 batch `x`, stepped from the host: per round one launch
+        of `select` on the residuals of the rows still active and one ph_qo_fit launch on those rows with their lists so
+        far -- ph_qo_fit_win under the float64 analysis window `window` (N), which only the fit sees -- instead of a
+        dense dictionary, its uploads and a host solve per row and round.  ``select(residuals)`` -> (period, norm, fate)
+        per row: _PICKED, _NOTHING_LEFT (the row is finished with the fit it has) or _HAND_BACK.  A row also stops when
+        ``rms(reconstruction) > rms(data) * thresh`` fails -- its result is the last fit with one period fewer reported
+        (QOPeriods.py:560-594) -- or after `num` rounds.
+        -> per row (output_bases, residual), or None: the row is rerun whole by the 1-D call (all-zero rows, `num` < 1,
+        a row handed back or with nothing left before its first fit, a fit that came back not PH_ST_OK -- a block
+        without rows such as a period picked twice, an indefinite matrix, a dictionary beyond the largest feasible
+        capacity -- and a 65th period, which is tested after the select)."""
         W, N = x.shape
         out = [None] * W
-        if max_length < 2 or num < 1:  # (ph_qo_orth_select needs max_p >= 2)
+        if num < 1:
             return out
-        trunc = bool(self._trunc_to_integer_multiple)
         per = np.zeros((W, 64), dtype=np.int32)
         counts = np.zeros(W, dtype=np.int32)
         gnorm = np.zeros((W, 64))
@@ -424,9 +412,7 @@ class QOPeriods(Periods):
 
         def finish(w, n_report):
             blocks, wts, resid = fits[w]
-            out[w] = (_LazyBases(blocks, N, self._basis_type, periods=per[w, :n_report].astype(np.uint32),
-                                 norms=gnorm[w, :n_report].copy(), weights=wts,
-                                 basis_dictionary={str(q): k for q, k in blocks}), resid)
+            out[w] = (self._row_bases(blocks, N, per[w, :n_report].astype(np.uint32), gnorm[w, :n_report].copy(), wts), resid)
 
         for i in range(num):
             if i > 0:  # the test function on the reconstruction of the last fit
@@ -435,12 +421,14 @@ class QOPeriods(Periods):
                 for w in active[~go]:
                     finish(w, int(counts[w]) - 1)
                 active = active[go]
-            active = active[counts[active] < 64]  # (a 65th period: the 1-D call)
             if active.size == 0:
                 break
-            p, g, st = eng.qo_orth_select(np.ascontiguousarray(res[active]), max_length, trunc)
-            ok = st == _ffi.PH_ST_OK
-            active, p, g = active[ok], p[ok], g[ok]
+            p, g, fate = select(np.ascontiguousarray(res[active]))
+            for w in active[fate == _NOTHING_LEFT]:  # every later round would repeat this one
+                if fits[w] is not None:
+                    finish(w, int(counts[w]))
+            picked = (fate == _PICKED) & (counts[active] < 64)  # (a 65th period: the 1-D call)
+            active, p, g = active[picked], p[picked], g[picked]
             if active.size == 0:
                 break
             per[active, counts[active]] = p
@@ -532,39 +520,6 @@ class QOPeriods(Periods):
             result = report(active, len(active))
             self._output_bases = result
         return (result, res)
-
-    def _find_periods_device(self, eng, data, N, num, thresh, min_length, max_length):
-        """The whole greedy loop in one kernel launch (ph_qo_find_periods); None when the window /
-        dictionary does not fit the kernel's LDS layout or workspace -- the host-driven loop then runs."""
-        # a block adds at most max_length rows: start with room for all of them when that fits
-        bound = int(num) * int(max_length if max_length is not None else N // 3)
-        kcap = min(2048, max(64, -(-bound // 64) * 64)) if bound <= 2048 else 512
-        while kcap > 64 and not eng.qo_feasible(N, np.float64, kcap, max_length):
-            kcap //= 2
-        if not eng.qo_feasible(N, np.float64, kcap, max_length):
-            return None
-        while True:
-            per, nrm, keeps, counts, wts, resid, st = eng.qo_find_periods(data[None, :], num, thresh, min_length, max_length, kcap)
-            if st[0] == _ffi.PH_ST_CAP and kcap < 2048 and eng.qo_feasible(N, np.float64, 2 * kcap, max_length):
-                kcap *= 2
-                continue
-            break
-        if st[0] != _ffi.PH_ST_OK:
-            return None  # dictionary larger than the device workspace: host-driven loop
-        n_report, n_blocks = int(counts[0, 0]), int(counts[0, 1])
-        if n_blocks == 0:
-            return None
-        blocks = [(int(per[0, b]), int(keeps[0, b])) for b in range(n_blocks)]
-        rows = np.vstack([self.Pp(q, N, k, self._basis_type) for q, k in blocks])
-        result = {
-            "periods": per[0, :n_report].copy(),
-            "norms": nrm[0, :n_report].copy(),
-            "subspaces": rows,
-            "weights": wts[0, : rows.shape[0]].copy(),
-            "basis_dictionary": {str(q): k for q, k in blocks},
-        }
-        self._output_bases = result
-        return (result, resid[0].copy())
 
     def _solve_structured(self, x, basis_matrix, dictionary):
         """solve_quadratic for a natural-basis dictionary without touching the dense matrix

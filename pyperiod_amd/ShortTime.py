@@ -307,7 +307,7 @@ class ShortTime:
         in ascending block order; ``residual = float64(signal) - periodic``."""
         import torch
 
-        from .QOPeriods import QOPeriods
+        from .QOPeriods import QOPeriods, _qo_capacities
 
         if self._orthogonalize:
             raise ValueError("decompose_qo: orthogonal selection is stepped from the host and not offered here")
@@ -334,43 +334,29 @@ class ShortTime:
         fr = eng.frames(xd, N, hop, W, win, torch.float64 if self.dtype == np.float64 else torch.float32)
         silent = (fr.to(torch.float64).abs().sum(dim=1) <= 1e-16).cpu().numpy()
 
-        # ---- the fit: the capacities of QOPeriods._find_periods_device_batch, capped at max_rows
-        bound = num * max_length
-        if uw:
-            kcap, kmax = (min(2048, max(64, -(-bound // 64) * 64)) if bound <= 2048 else 512), 2048
-            kcap = min(kcap, max_rows)
-            while kcap > 64 and not eng.qo_feasible(N, self.dtype, kcap, max_length):
-                kcap //= 2
-            if not eng.qo_feasible(N, self.dtype, kcap, max_length):
-                kcap = 0  # no capacity fits: every frame goes the way of the unfinished ones
-        else:
-            kcap, kmax = min(4096, max(64, -(-bound // 64) * 64), max_rows), 1 << 20
-        kmax = min(kmax, max_rows)
+        # ---- the fit: frames that end PH_ST_CAP run again at the next capacity; without a feasible capacity every
+        # frame goes the way of the unfinished ones
         per = torch.zeros((W, num), dtype=torch.int32, device=dev)
         keeps = torch.zeros((W, num), dtype=torch.int32, device=dev)
         nb = torch.zeros((W,), dtype=torch.int32, device=dev)
-        wts = torch.zeros((W, max(kcap, 1)), dtype=torch.float64, device=dev)
+        wts = torch.zeros((W, 1), dtype=torch.float64, device=dev)
         st = np.full(W, _ffi.PH_ST_CAP, dtype=np.int32)
         todo = np.arange(W)
-        while kcap and todo.size:
+        for kcap in _qo_capacities(eng, N, self.dtype, num, max_length, uw, max_rows):
             whole = todo.size == W
             idx = None if whole else torch.as_tensor(todo, device=dev)
             p2, _, k2, c2, w2, _, s2 = eng.qo_find_periods(fr if whole else fr[idx], num, thresh, min_length, max_length,
                                                            kcap, trunc=trunc, update_weights=uw)
-            if wts.shape[1] < kcap:
-                wts = torch.cat([wts, wts.new_zeros((W, kcap - wts.shape[1]))], dim=1)
             if whole:
-                per, keeps, nb = p2, k2, c2[:, 1].contiguous()
-                wts[:, :kcap] = w2
+                per, keeps, nb, wts = p2, k2, c2[:, 1].contiguous(), w2
             else:
+                wts = torch.cat([wts, wts.new_zeros((W, kcap - wts.shape[1]))], dim=1)
                 per[idx], keeps[idx], nb[idx] = p2, k2, c2[:, 1]
-                wts[idx, :kcap] = w2
+                wts[idx] = w2
             st[todo] = s2.cpu().numpy()
-            grow = st[todo] == _ffi.PH_ST_CAP
-            nxt = kcap * (2 if uw else 4)
-            if not grow.any() or nxt > kmax or (uw and not eng.qo_feasible(N, self.dtype, nxt, max_length)):
+            todo = todo[st[todo] == _ffi.PH_ST_CAP]
+            if not todo.size:
                 break
-            kcap, todo = nxt, todo[grow]
         if not uw:  # a keeps entry of 0 stands for `period` rows
             keeps = torch.where(keeps == 0, per, keeps)
 

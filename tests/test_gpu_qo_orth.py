@@ -278,7 +278,8 @@ def test_batch_equals_rows(engines):
             QOPeriods(trunc_to_integer_multiple=trunc, orthogonalize=True).find_periods(x[15], **kw)
         with pytest.raises(ValueError, match="keep"):
             qo.find_periods(x, **kw)
-        stepped = qo._find_periods_orth_batch(engines[0], x, kw["num"], kw["thresh"], kw["max_length"])
+        stepped = qo._find_periods_stepped(engines[0], x, qo._select_orthogonal(engines[0], kw["max_length"]), kw["num"],
+                                           kw["thresh"], kw["max_length"])
         assert stepped[14] is None and stepped[15] is None and all(r is not None for r in stepped[:14])
         batch = qo.find_periods(x[:15], **kw)
         for w in range(15):

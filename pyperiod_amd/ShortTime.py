@@ -33,7 +33,7 @@ from warnings import warn
 import numpy as np
 
 from . import _ffi
-from .engine import default_engine
+from .engine import _is_torch, default_engine
 
 _METHODS = ("m_best", "m_best_gamma", "best_correlation", "best_frequency", "small_to_large")
 
@@ -119,7 +119,7 @@ class ShortTime:
 
     @staticmethod
     def _signal(signal):
-        if type(signal).__module__.startswith("torch"):
+        if _is_torch(signal):
             if signal.dim() != 1:
                 raise ValueError("expected a 1-D signal")
             return signal
@@ -131,7 +131,7 @@ class ShortTime:
         return np.ascontiguousarray(arr)
 
     def _device_window(self, like):
-        if self.window is None or not type(like).__module__.startswith("torch"):
+        if self.window is None or not _is_torch(like):
             return self.window
         import torch
 
@@ -172,26 +172,42 @@ class ShortTime:
         used = np.arange(per.shape[1])[None, :] < counts[:, None]
         return np.where(used, per, 0), np.where(used, pw, 0.0), counts
 
+    def _device_frames(self, signal):
+        """The start of every pipeline: the signal as a host array, uploaded once, and its frames on the device.
+        -> (host signal, L, W, engine, device, device window, frames)."""
+        import torch  # lazily, as QOPeriods.solve_quadratic does
+
+        x = self._signal(signal)
+        if _is_torch(x):
+            x = x.detach().cpu().numpy()
+        L = x.shape[0]
+        W = self.frame_count(L)
+        eng = default_engine()
+        dev = torch.device("cuda", eng.device)
+        xd = torch.as_tensor(x, device=dev)  # the one upload: L samples
+        win = None if self.window is None else torch.as_tensor(self.window, device=dev)
+        tdt = torch.float64 if self.dtype == np.float64 else torch.float32
+        return x, L, W, eng, dev, win, eng.frames(xd, self.frame_length, self.hop, W, win, tdt)
+
+    @staticmethod
+    def _activity(masks, powers, T):
+        """activity[t, f]: the powers of the rows of frame f that masks[t, f] names, added in ascending row order (the
+        order of the kernels)."""
+        activity = np.zeros((T, powers.shape[0]))
+        for k in range(powers.shape[1]):
+            bit = (masks[:T] >> np.uint64(k)) & np.uint64(1)
+            activity += np.where(bit != 0, powers[None, :, k], 0.0)
+        return activity
+
     def _run(self, signal, method, kwargs):
         """The pipeline analyze and decompose share: one upload of the signal, frames, the engine method, the status
         check.  -> (float64 signal, L, W, engine, device window, num, periods, powers, bases, counts) with the last four
         on the device (None when num == 0: nothing ran)."""
         if method not in _METHODS:
             raise ValueError(f"method must be one of {_METHODS}")
-        import torch  # lazily, as QOPeriods.solve_quadratic does
-
-        x = self._signal(signal)
-        if type(x).__module__.startswith("torch"):
-            x = x.detach().cpu().numpy()
-        L, N = x.shape[0], self.frame_length
-        W = self.frame_count(L)
-        eng = default_engine()
-        dev = torch.device("cuda", eng.device)
+        x, L, W, eng, _, win, fr = self._device_frames(signal)
+        N = self.frame_length
         trunc, orth = self._trunc_to_integer_multiple, self._orthogonalize
-        xd = torch.as_tensor(x, device=dev)  # the one upload: L samples
-        win = None if self.window is None else torch.as_tensor(self.window, device=dev)
-        tdt = torch.float64 if self.dtype == np.float64 else torch.float32
-        fr = eng.frames(xd, N, self.hop, W, win, tdt)
         counts = None
         if method in ("m_best", "m_best_gamma"):
             if orth:
@@ -273,11 +289,8 @@ class ShortTime:
         routed = eng.overlap_add_tracks(bases, masks_d, self.hop, L, counts_d, win, win, True)
         periodic = eng.overlap_add(bases, self.hop, L, counts_d, win, win, True).cpu().numpy()
         routed = routed.cpu().numpy()
-        activity = np.zeros((T, W))
-        for k in range(per.shape[1]):  # ascending k, as the kernel adds
-            bit = (masks[:T] >> np.uint64(k)) & np.uint64(1)
-            activity += np.where(bit != 0, pw[None, :, k], 0.0)
-        return ShortTimeTracks(per, pw, periodic, x64 - periodic, wanted, routed[:T], routed[T], activity, counts)
+        return ShortTimeTracks(per, pw, periodic, x64 - periodic, wanted, routed[:T], routed[T],
+                               self._activity(masks, pw, T), counts)
 
     def decompose_qo(self, signal, num, thresh, min_length=2, max_length=None, update_weights=True, tracks=None,
                      max_tracks=8, max_rows=2048):
@@ -307,8 +320,6 @@ class ShortTime:
         in ascending block order; ``residual = float64(signal) - periodic``."""
         import torch
 
-        from .QOPeriods import QOPeriods, _qo_capacities
-
         if self._orthogonalize:
             raise ValueError("decompose_qo: orthogonal selection is stepped from the host and not offered here")
         if isinstance(num, bool) or not isinstance(num, (int, np.integer)) or not 1 <= int(num) <= _MAX_ROWS:
@@ -319,23 +330,29 @@ class ShortTime:
         if max_tracks < 0:
             raise ValueError("max_tracks must be >= 0")
         wanted = None if tracks is None else self._track_list(tracks)
-        x = self._signal(signal)
-        if type(x).__module__.startswith("torch"):
-            x = x.detach().cpu().numpy()
-        L, N, hop = x.shape[0], self.frame_length, self.hop
-        W = self.frame_count(L)
-        max_length = N // 3 if max_length is None else int(max_length)
-        min_length = int(min_length)
-        trunc, uw = self._trunc_to_integer_multiple, bool(update_weights)
-        eng = default_engine()
-        dev = torch.device("cuda", eng.device)
-        xd = torch.as_tensor(x, device=dev)  # the one upload: L samples
-        win = None if self.window is None else torch.as_tensor(self.window, device=dev)
-        fr = eng.frames(xd, N, hop, W, win, torch.float64 if self.dtype == np.float64 else torch.float32)
+        max_length = self.frame_length // 3 if max_length is None else int(max_length)
+        fit = (num, thresh, int(min_length), max_length, bool(update_weights))
+        x, L, W, eng, dev, win, fr = self._device_frames(signal)
         silent = (fr.to(torch.float64).abs().sum(dim=1) <= 1e-16).cpu().numpy()
+        blocks, st = self._qo_fit(torch, eng, fr, fit, max_rows)
+        blocks = self._qo_host_route(torch, fr, silent, st, blocks, fit)
+        seg, per_h, pw_h, counts_h = self._qo_segments(torch, eng, blocks)
+        if wanted is None:
+            wanted = [(p,) for p in self.rank_periods(per_h, pw_h, counts_h, max_tracks)]
+        T = len(wanted)
+        masks, routed = self._qo_route(torch, eng, seg, blocks, per_h, counts_h, wanted, L, win)
+        periodic = routed[T + 1]
+        return ShortTimeTracks(per_h, pw_h, periodic, x.astype(np.float64) - periodic, wanted, routed[:T], routed[T],
+                               self._activity(masks, pw_h, T), counts_h)
 
-        # ---- the fit: frames that end PH_ST_CAP run again at the next capacity; without a feasible capacity every
-        # frame goes the way of the unfinished ones
+    def _qo_fit(self, torch, eng, fr, fit, max_rows):
+        """The device fit: frames that end PH_ST_CAP run again at the next capacity; without a feasible capacity every
+        frame goes the way of the unfinished ones.  -> (periods, rows, blocks per frame, weights) on the device and the
+        host status words."""
+        from .QOPeriods import _qo_capacities
+
+        num, thresh, min_length, max_length, uw = fit
+        (W, N), dev, trunc = fr.shape, fr.device, self._trunc_to_integer_multiple
         per = torch.zeros((W, num), dtype=torch.int32, device=dev)
         keeps = torch.zeros((W, num), dtype=torch.int32, device=dev)
         nb = torch.zeros((W,), dtype=torch.int32, device=dev)
@@ -359,8 +376,16 @@ class ShortTime:
                 break
         if not uw:  # a keeps entry of 0 stands for `period` rows
             keeps = torch.where(keeps == 0, per, keeps)
+        return (per, keeps, nb, wts), st
 
-        # ---- frames the device loop did not finish: the 1-D call, packed into the device arrays
+    def _qo_host_route(self, torch, fr, silent, st, blocks, fit):
+        """Frames the device loop did not finish: the 1-D call, packed into the device arrays.  Then the blocks as the
+        extraction takes them: none for a silent frame, every period once, contiguous."""
+        from .QOPeriods import QOPeriods
+
+        num, thresh, min_length, max_length, uw = fit
+        per, keeps, nb, wts = blocks
+        W, dev, trunc = fr.shape[0], fr.device, self._trunc_to_integer_multiple
         nb_h = nb.cpu().numpy()
         unfinished = np.flatnonzero(~silent & ((st != _ffi.PH_ST_OK) | (nb_h == 0)))
         if unfinished.size:
@@ -402,9 +427,14 @@ class ShortTime:
         if not uw:  # the fixed-weight loop lists a period once per fit: one block per period for the extraction
             per, keeps, nb, wts = self._merge_repeats(torch, per, keeps, nb, wts, max(max_length, 1))
         per, keeps, nb, wts = per.contiguous(), keeps.contiguous(), nb.contiguous(), wts.contiguous()
-        pcap = per.shape[1]
+        return per, keeps, nb, wts
 
-        # ---- one period per block, and its power
+    @staticmethod
+    def _qo_segments(torch, eng, blocks):
+        """One period per block (``qo_get_periods``) and its power.  -> the (W, ccap) segments on the device and the
+        host periods, powers (zeros behind the blocks in use) and blocks per frame."""
+        per, keeps, nb, wts = blocks
+        (W, pcap), dev = per.shape, per.device
         slot = torch.arange(pcap, device=dev)[None, :]
         used = slot < nb[:, None]
         ends = torch.cumsum((per.clamp(min=0) * used).to(torch.int64), dim=1)  # (W, pcap): end of block a
@@ -427,24 +457,19 @@ class ShortTime:
         per_h = np.where(used.cpu().numpy(), per.cpu().numpy(), 0)
         pw_h = np.where(per_h > 0, powers.cpu().numpy(), 0.0)
         counts_h = np.clip(nb_h, 0, pcap).astype(np.int32)
+        return seg, per_h, pw_h, counts_h
 
-        # ---- tracks: T rows, `other`, and every block (`periodic`) in one launch
-        if wanted is None:
-            wanted = [(p,) for p in self.rank_periods(per_h, pw_h, counts_h, max_tracks)]
-        T = len(wanted)
+    def _qo_route(self, torch, eng, seg, blocks, per_h, counts_h, wanted, L, win):
+        """T mask rows for the tracks, one for `other` and one with every block (`periodic`), folded in one launch."""
+        per, _, nb, _ = blocks
+        T, W = len(wanted), per.shape[0]
         masks = np.empty((T + 2, W), np.uint64)
         masks[: T + 1] = self.track_masks(per_h, counts_h, wanted)
         low = (np.uint64(1) << np.minimum(counts_h, 63).astype(np.uint64)) - np.uint64(1)
         masks[T + 1] = np.where(counts_h >= 64, np.uint64(2**64 - 1), low)  # every block in use
-        masks_d = torch.as_tensor(masks.view(np.int64), device=dev)
-        routed = eng.overlap_add_periodic(seg, per, nb, masks_d, N, hop, L, win, win, True).cpu().numpy()
-        activity = np.zeros((T, W))
-        for a in range(pcap):  # ascending a, as the kernel adds
-            bit = (masks[:T] >> np.uint64(a)) & np.uint64(1)
-            activity += np.where(bit != 0, pw_h[None, :, a], 0.0)
-        periodic = routed[T + 1]
-        return ShortTimeTracks(per_h, pw_h, periodic, x.astype(np.float64) - periodic, wanted, routed[:T], routed[T],
-                               activity, counts_h)
+        masks_d = torch.as_tensor(masks.view(np.int64), device=per.device)
+        routed = eng.overlap_add_periodic(seg, per, nb, masks_d, self.frame_length, self.hop, L, win, win, True)
+        return masks, routed.cpu().numpy()
 
     @staticmethod
     def _merge_repeats(torch, per, keeps, nb, wts, max_block):

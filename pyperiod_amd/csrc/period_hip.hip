@@ -2479,18 +2479,56 @@ int ph_qo_get_periods(ph_ctx* c, const int32_t* periods, const int32_t* rows, co
 // ----------------------------------------------------------------------------- short-time framing / overlap-add
 namespace {
 
-// checks shared by ph_frames and ph_overlap_add: positive sizes, every frame starts inside the signal, and the element
-// count W * rows * N (times 8 bytes) stays inside int64 -- it may well pass 2^31
-int check_framing(const char* what, int64_t W, int rows, int N, int hop, int64_t L) {
-  if (W < 1 || rows < 1 || N < 1 || hop < 1 || L < 1)
-    return fail(PH_E_ARG, "%s: W=%lld, K=%d, N=%d, hop=%d, L=%lld must all be >= 1", what, (long long)W, rows, N, hop,
+// the frame walk every short-time entry point makes: positive sizes, and every frame starts inside the signal.  `rows`
+// points at K where the entry point has rows per frame (K is then checked and named with the rest), nullptr where not
+int check_frame_walk(const char* what, int64_t W, const int* rows, int N, int hop, int64_t L) {
+  if (rows && (W < 1 || *rows < 1 || N < 1 || hop < 1 || L < 1))
+    return fail(PH_E_ARG, "%s: W=%lld, K=%d, N=%d, hop=%d, L=%lld must all be >= 1", what, (long long)W, *rows, N, hop,
                 (long long)L);
+  if (W < 1 || N < 1 || hop < 1 || L < 1)
+    return fail(PH_E_ARG, "%s: W=%lld, N=%d, hop=%d, L=%lld must all be >= 1", what, (long long)W, N, hop, (long long)L);
   if (W - 1 > (L - 1) / hop)
     return fail(PH_E_ARG, "%s: frame %lld starts at or behind the end of the signal ((W - 1) * hop >= L = %lld)", what,
                 (long long)(W - 1), (long long)L);
+  return PH_OK;
+}
+
+// the element count W * rows * N (times 8 bytes) stays inside int64 -- it may well pass 2^31
+int check_framed_size(const char* what, int64_t W, int rows, int N) {
   if (W > (INT64_MAX / 8) / ((int64_t)rows * N)) return fail(PH_E_ARG, "%s: W * K * N does not fit 64 bits", what);
   return PH_OK;
 }
+
+// T tracks: at least one, and the (T, L) result and the (T, W) masks (times 8 bytes) stay inside int64.  Two calls,
+// because each routed entry point has limits of its own that it has always named between the two
+int check_tracks(const char* what, int64_t T) {
+  return T < 1 ? fail(PH_E_ARG, "%s: T=%lld must be >= 1", what, (long long)T) : (int)PH_OK;
+}
+int check_tracks_size(const char* what, int64_t T, int64_t W, int64_t L) {
+  if (T > (INT64_MAX / 8) / L || T > (INT64_MAX / 8) / W)
+    return fail(PH_E_ARG, "%s: T * L or T * W does not fit 64 bits", what);
+  return PH_OK;
+}
+
+// What the three overlap-add kernels take besides their rows: the optional counts and windows, the masks of the routed
+// ones (T = 0: none), and the `norm` flag -- staged into the same slots for all three.
+struct OlaSides {
+  const int* counts = nullptr;
+  const unsigned long long* masks = nullptr;
+  const double *wa = nullptr, *ws = nullptr;
+  int norm = 0;
+  int stage(Stage& st, unsigned flags, int64_t W, int N, const int32_t* h_counts, const uint64_t* h_masks, int64_t T,
+            const double* win_a, const double* win_s) {
+    const void *dc = nullptr, *dm = nullptr, *da = nullptr, *ds = nullptr;
+    if (h_counts) PH_TRY(st.in(h_counts, (size_t)W * sizeof(int32_t), &dc, B_GBUF));
+    if (h_masks) PH_TRY(st.in(h_masks, (size_t)T * W * sizeof(uint64_t), &dm, B_WS0));
+    if (win_a) PH_TRY(st.in(win_a, (size_t)N * sizeof(double), &da, B_GWIN));
+    if (win_s) PH_TRY(st.in(win_s, (size_t)N * sizeof(double), &ds, B_WS1));
+    counts = (const int*)dc, masks = (const unsigned long long*)dm, wa = (const double*)da, ws = (const double*)ds;
+    norm = (flags & PH_FLAG_OLA_NORM) ? 1 : 0;
+    return PH_OK;
+  }
+};
 
 // workgroups of a flat grid-stride kernel over `items` lanes' worth of work
 unsigned flat_grid(const ph_ctx* c, int64_t items) {
@@ -2522,7 +2560,9 @@ int ph_frames(ph_ctx* c, const void* signal, int in_dtype, int64_t L, int N, int
   if (!signal || !frames) return fail(PH_E_ARG, "signal / frames is NULL");
   if ((in_dtype != PH_F64 && in_dtype != PH_F32) || (out_dtype != PH_F64 && out_dtype != PH_F32))
     return fail(PH_E_ARG, "in_dtype and out_dtype must be PH_F64 or PH_F32");
-  PH_TRY(check_framing("ph_frames", W, 1, N, hop, L));
+  const int one = 1;
+  PH_TRY(check_frame_walk("ph_frames", W, &one, N, hop, L));
+  PH_TRY(check_framed_size("ph_frames", W, 1, N));
   PH_HIP(hipSetDevice(c->device));
   Stage st(c, flags);
   const void *ds, *dwin = nullptr;
@@ -2547,26 +2587,25 @@ int ph_overlap_add(ph_ctx* c, const void* y, int dtype, int64_t W, int K, int N,
   if (!c) return fail(PH_E_ARG, "ctx is NULL");
   if (!y || !out) return fail(PH_E_ARG, "y / out is NULL");
   if (dtype != PH_F64 && dtype != PH_F32) return fail(PH_E_ARG, "dtype must be PH_F64 or PH_F32");
-  PH_TRY(check_framing("ph_overlap_add", W, K, N, hop, L));
+  PH_TRY(check_frame_walk("ph_overlap_add", W, &K, N, hop, L));
+  PH_TRY(check_framed_size("ph_overlap_add", W, K, N));
   PH_HIP(hipSetDevice(c->device));
   Stage st(c, flags);
-  const void *dy, *dcnt = nullptr, *dwa = nullptr, *dws = nullptr;
+  OlaSides sd;
+  const void* dy;
   void* dout;
   PH_TRY(st.in(y, (size_t)W * K * N * elem_size(dtype), &dy));
-  if (counts) PH_TRY(st.in(counts, (size_t)W * sizeof(int32_t), &dcnt, B_GBUF));
-  if (win_a) PH_TRY(st.in(win_a, (size_t)N * sizeof(double), &dwa, B_GWIN));
-  if (win_s) PH_TRY(st.in(win_s, (size_t)N * sizeof(double), &dws, B_WS1));
+  PH_TRY(sd.stage(st, flags, W, N, counts, nullptr, 0, win_a, win_s));
   PH_TRY(st.out(B_OUT0, out, (size_t)L * sizeof(double), &dout));
   const dim3 grid(flat_grid(c, L));
-  const int norm = (flags & PH_FLAG_OLA_NORM) ? 1 : 0;
   {
     ProfScope ps_(c, "k_overlap_add");
     if (dtype == PH_F64)
       hipLaunchKernelGGL(ph::k_overlap_add<double>, grid, dim3(ph::kFramesBlock), 0, c->stream, (const double*)dy, W, K, N,
-                         hop, L, (const int*)dcnt, (const double*)dwa, (const double*)dws, norm, (double*)dout);
+                         hop, L, sd.counts, sd.wa, sd.ws, sd.norm, (double*)dout);
     else
       hipLaunchKernelGGL(ph::k_overlap_add<float>, grid, dim3(ph::kFramesBlock), 0, c->stream, (const float*)dy, W, K, N,
-                         hop, L, (const int*)dcnt, (const double*)dwa, (const double*)dws, norm, (double*)dout);
+                         hop, L, sd.counts, sd.wa, sd.ws, sd.norm, (double*)dout);
   }
   PH_TRY(launch_check("k_overlap_add"));
   return st.finish();
@@ -2578,33 +2617,28 @@ int ph_overlap_add_tracks(ph_ctx* c, const void* y, int dtype, int64_t W, int K,
   if (!c) return fail(PH_E_ARG, "ctx is NULL");
   if (!y || !masks || !out) return fail(PH_E_ARG, "y / masks / out is NULL");
   if (dtype != PH_F64 && dtype != PH_F32) return fail(PH_E_ARG, "dtype must be PH_F64 or PH_F32");
-  PH_TRY(check_framing("ph_overlap_add_tracks", W, K, N, hop, L));
-  if (T < 1) return fail(PH_E_ARG, "ph_overlap_add_tracks: T=%lld must be >= 1", (long long)T);
+  PH_TRY(check_frame_walk("ph_overlap_add_tracks", W, &K, N, hop, L));
+  PH_TRY(check_framed_size("ph_overlap_add_tracks", W, K, N));
+  PH_TRY(check_tracks("ph_overlap_add_tracks", T));
   if (K > 64) return fail(PH_E_ARG, "ph_overlap_add_tracks: K=%d rows per frame do not fit a 64-bit mask", K);
-  if (T > (INT64_MAX / 8) / L || T > (INT64_MAX / 8) / W)
-    return fail(PH_E_ARG, "ph_overlap_add_tracks: T * L or T * W does not fit 64 bits");
+  PH_TRY(check_tracks_size("ph_overlap_add_tracks", T, W, L));
   PH_HIP(hipSetDevice(c->device));
   Stage st(c, flags);
-  const void *dy, *dmask, *dcnt = nullptr, *dwa = nullptr, *dws = nullptr;
+  OlaSides sd;
+  const void* dy;
   void* dout;
   PH_TRY(st.in(y, (size_t)W * K * N * elem_size(dtype), &dy));
-  PH_TRY(st.in(masks, (size_t)T * W * sizeof(uint64_t), &dmask, B_WS0));
-  if (counts) PH_TRY(st.in(counts, (size_t)W * sizeof(int32_t), &dcnt, B_GBUF));
-  if (win_a) PH_TRY(st.in(win_a, (size_t)N * sizeof(double), &dwa, B_GWIN));
-  if (win_s) PH_TRY(st.in(win_s, (size_t)N * sizeof(double), &dws, B_WS1));
+  PH_TRY(sd.stage(st, flags, W, N, counts, masks, T, win_a, win_s));
   PH_TRY(st.out(B_OUT0, out, (size_t)T * L * sizeof(double), &dout));
   const dim3 grid(flat_grid(c, T * L));
-  const int norm = (flags & PH_FLAG_OLA_NORM) ? 1 : 0;
   {
     ProfScope ps_(c, "k_overlap_add_tracks");
     if (dtype == PH_F64)
       hipLaunchKernelGGL(ph::k_overlap_add_tracks<double>, grid, dim3(ph::kFramesBlock), 0, c->stream, (const double*)dy, W,
-                         K, N, hop, L, (const int*)dcnt, (const unsigned long long*)dmask, T, (const double*)dwa,
-                         (const double*)dws, norm, (double*)dout);
+                         K, N, hop, L, sd.counts, sd.masks, T, sd.wa, sd.ws, sd.norm, (double*)dout);
     else
       hipLaunchKernelGGL(ph::k_overlap_add_tracks<float>, grid, dim3(ph::kFramesBlock), 0, c->stream, (const float*)dy, W,
-                         K, N, hop, L, (const int*)dcnt, (const unsigned long long*)dmask, T, (const double*)dwa,
-                         (const double*)dws, norm, (double*)dout);
+                         K, N, hop, L, sd.counts, sd.masks, T, sd.wa, sd.ws, sd.norm, (double*)dout);
   }
   PH_TRY(launch_check("k_overlap_add_tracks"));
   return st.finish();
@@ -2616,38 +2650,29 @@ int ph_overlap_add_periodic(ph_ctx* c, const double* seg, const int32_t* periods
   if (!c) return fail(PH_E_ARG, "ctx is NULL");
   if (!seg || !periods || !counts || !masks || !out)
     return fail(PH_E_ARG, "ph_overlap_add_periodic: seg / periods / counts / masks / out is NULL");
-  // (not check_framing: there is no W * K * N array here, so no product of that size to refuse)
-  if (W < 1 || N < 1 || hop < 1 || L < 1)
-    return fail(PH_E_ARG, "ph_overlap_add_periodic: W=%lld, N=%d, hop=%d, L=%lld must all be >= 1", (long long)W, N, hop,
-                (long long)L);
-  if (W - 1 > (L - 1) / hop)
-    return fail(PH_E_ARG, "ph_overlap_add_periodic: frame %lld starts at or behind the end of the signal ((W - 1) * hop >= L = %lld)",
-                (long long)(W - 1), (long long)L);
-  if (T < 1) return fail(PH_E_ARG, "ph_overlap_add_periodic: T=%lld must be >= 1", (long long)T);
+  // (there is no W * K * N array here, so no product of that size to refuse)
+  PH_TRY(check_frame_walk("ph_overlap_add_periodic", W, nullptr, N, hop, L));
+  PH_TRY(check_tracks("ph_overlap_add_periodic", T));
   if (pcap < 1 || pcap > (1 << 20)) return fail(PH_E_ARG, "ph_overlap_add_periodic: pcap=%d must be in [1, 2^20]", pcap);
   if (ccap < 1 || ccap > (1 << 24)) return fail(PH_E_ARG, "ph_overlap_add_periodic: ccap=%d must be in [1, 2^24]", ccap);
-  if (T > (INT64_MAX / 8) / L || T > (INT64_MAX / 8) / W)
-    return fail(PH_E_ARG, "ph_overlap_add_periodic: T * L or T * W does not fit 64 bits");
+  PH_TRY(check_tracks_size("ph_overlap_add_periodic", T, W, L));
   if (W > (INT64_MAX / 8) / ccap || W > (INT64_MAX / 4) / pcap)
     return fail(PH_E_ARG, "ph_overlap_add_periodic: W * ccap or W * pcap does not fit 64 bits");
   PH_HIP(hipSetDevice(c->device));
   Stage st(c, flags);
-  const void *dseg, *dper, *dcnt, *dmask, *dwa = nullptr, *dws = nullptr;
+  OlaSides sd;
+  const void *dseg, *dper;
   void* dout;
   PH_TRY(st.in(seg, (size_t)W * ccap * sizeof(double), &dseg));
   PH_TRY(st.in(periods, (size_t)W * pcap * sizeof(int32_t), &dper, B_GEN0));
-  PH_TRY(st.in(counts, (size_t)W * sizeof(int32_t), &dcnt, B_GBUF));
-  PH_TRY(st.in(masks, (size_t)T * W * sizeof(uint64_t), &dmask, B_WS0));
-  if (win_a) PH_TRY(st.in(win_a, (size_t)N * sizeof(double), &dwa, B_GWIN));
-  if (win_s) PH_TRY(st.in(win_s, (size_t)N * sizeof(double), &dws, B_WS1));
+  PH_TRY(sd.stage(st, flags, W, N, counts, masks, T, win_a, win_s));
   PH_TRY(st.out(B_OUT0, out, (size_t)T * L * sizeof(double), &dout));
   const dim3 grid(flat_grid(c, T * L));
-  const int norm = (flags & PH_FLAG_OLA_NORM) ? 1 : 0;
   {
     ProfScope ps_(c, "k_overlap_add_periodic");
     hipLaunchKernelGGL(ph::k_overlap_add_periodic, grid, dim3(ph::kFramesBlock), 0, c->stream, (const double*)dseg,
-                       (const int*)dper, (const int*)dcnt, (const unsigned long long*)dmask, W, pcap, ccap, T, N, hop, L,
-                       (const double*)dwa, (const double*)dws, norm, (double*)dout);
+                       (const int*)dper, sd.counts, sd.masks, W, pcap, ccap, T, N, hop, L, sd.wa, sd.ws, sd.norm,
+                       (double*)dout);
   }
   PH_TRY(launch_check("k_overlap_add_periodic"));
   return st.finish();

@@ -100,12 +100,38 @@ __global__ __launch_bounds__(kFramesBlock) void k_frames(const Tin* __restrict__
   }
 }
 
+// ---- the pieces of the walk every overlap-add kernel below makes for its sample n
+// the frames f < W with 0 <= n - f hop < N: f_lo .. f_hi (none when f_lo > f_hi)
+__device__ __forceinline__ void ola_frame_span(int64_t n, int64_t N, int64_t hop, int64_t W, int64_t& f_lo, int64_t& f_hi) {
+  f_lo = n < N ? 0 : (n - N) / hop + 1;
+  f_hi = n / hop;
+  if (f_hi > W - 1) f_hi = W - 1;
+}
+// a count as the caller left it, clipped to [0, cap]
+__device__ __forceinline__ int ola_clip(int count, int cap) { return count < 0 ? 0 : count > cap ? cap : count; }
+// the synthesis weight of offset i (nullptr: all ones); its product with the analysis weight is added to den
+template <typename I>
+__device__ __forceinline__ double ola_window(I i, const double* __restrict__ wa, const double* __restrict__ ws, double& den) {
+  const double s = ws ? ws[i] : 1.0;
+  den += (wa ? wa[i] : 1.0) * s;
+  return s;
+}
+// the lowest kf bits of a mask word: unsigned throughout, and no shift by 64 (kf = 0: no bit at all)
+__device__ __forceinline__ unsigned long long ola_cut(unsigned long long m, int kf) {
+  if (kf < 64) m &= (1ull << kf) - 1ull;
+  return m;
+}
+// num, or with `norm` num / den where den > 0 and exactly 0.0 elsewhere
+__device__ __forceinline__ double ola_result(double num, double den, int norm) {
+  return norm ? (den > 0.0 ? num / den : 0.0) : num;
+}
+
 // ======================================================================================
 // Overlap-add in the gather form: y (W, K, N) of T -> out (L) float64.
 //   num[n] = sum_f sum_{k < K_f} ws[n - f hop] * y[f, k, n - f hop]     over the frames f < W with 0 <= n - f hop < N
 //   den[n] = sum_f wa[n - f hop] * ws[n - f hop]                        over the same frames
-//   out[n] = num[n], or with `norm`: num[n] / den[n] where den[n] > 0 and exactly 0.0 elsewhere
-// K_f = counts[f] clipped to [0, K] (counts == nullptr: K); rows k >= K_f are never read.  wa / ws == nullptr: all ones.
+//   out[n] = ola_result(num[n], den[n], norm)
+// K_f = counts[f] clipped to [0, K] (counts == nullptr: K); rows k >= K_f are never read.
 // Every output sample is owned by one lane, which walks its at most ceil(N / hop) frames in ascending f and their rows in
 // ascending k, accumulating in float64: one fixed order per sample, no atomics, so the result is the same bits on every
 // run.  Lanes of a wavefront take consecutive n, so for one (f, k) they read consecutive elements of one row: every load
@@ -119,19 +145,13 @@ __global__ __launch_bounds__(kFramesBlock) void k_overlap_add(const T* __restric
                                                              int norm, double* __restrict__ out) {
   const int64_t stride = (int64_t)gridDim.x * kFramesBlock;
   for (int64_t n = (int64_t)blockIdx.x * kFramesBlock + threadIdx.x; n < L; n += stride) {
-    const int64_t f_lo = n < N ? 0 : (n - N) / hop + 1;
-    int64_t f_hi = n / hop;
-    if (f_hi > W - 1) f_hi = W - 1;
+    int64_t f_lo, f_hi;
+    ola_frame_span(n, N, hop, W, f_lo, f_hi);
     double num = 0.0, den = 0.0;
     for (int64_t f = f_lo; f <= f_hi; ++f) {
       const int i = (int)(n - f * hop);
-      int kf = K;
-      if (counts) {
-        kf = counts[f];
-        kf = kf < 0 ? 0 : kf > K ? K : kf;
-      }
-      const double s = ws ? ws[i] : 1.0;
-      den += (wa ? wa[i] : 1.0) * s;
+      const int kf = counts ? ola_clip(counts[f], K) : K;
+      const double s = ola_window(i, wa, ws, den);
       const T* row = y + (f * K) * (int64_t)N + i;
       int k = 0;
       for (; k + 4 <= kf; k += 4) {  // four loads in flight, added in ascending k
@@ -144,22 +164,21 @@ __global__ __launch_bounds__(kFramesBlock) void k_overlap_add(const T* __restric
       }
       for (; k < kf; ++k) num += s * (double)row[(int64_t)k * N];
     }
-    out[n] = norm ? (den > 0.0 ? num / den : 0.0) : num;
+    out[n] = ola_result(num, den, norm);
   }
 }
 
 // ======================================================================================
 // Routed overlap-add: the same y (W, K, N), folded onto NT tracks of L samples each -> out (NT, L) float64.
 //   num[t, n] = sum_f ws[n - f hop] * sum_{k < K_f, bit k of masks[t, f] set} y[f, k, n - f hop]
-//   den[n] and the frames f of a sample as in k_overlap_add; out[t, n] = num, or with `norm` num / den where den > 0 and
-//   exactly 0.0 elsewhere.  A track with no term at n gives num = 0.0 and so exactly 0.0.
+//   A track with no term at n gives num = 0.0 and so exactly 0.0.
 // masks (NT, W) 64-bit words: bit k of masks[t, f] routes row k of frame f to track t (K <= 64, checked on the host).  A
 // mask instead of a (W, K) label array: with labels a lane would compare all K labels of a frame for the ~K / NT rows it
 // loads; with a mask it is one 8-byte load per frame -- the same address for every lane of a wavefront unless the
-// wavefront straddles two frames' worth of n or two tracks -- and then a walk over the set bits.  The word is unsigned
-// throughout: bits at or above K_f are cut off with a logical mask ((1 << K_f) - 1, skipped for K_f = 64), the walk takes
-// the lowest set bit with ctz and clears it with m & (m - 1), so bit 63 is a row like any other.  Masks may overlap (the
-// row is added to every track that names it); rows behind K_f or in no mask are never read.
+// wavefront straddles two frames' worth of n or two tracks -- and then a walk over the set bits.  Bits at or above K_f
+// are cut off (ola_cut), the walk takes the lowest set bit with ctz and clears it with m & (m - 1), so bit 63 is a row
+// like any other.  Masks may overlap (the row is added to every track that names it); rows behind K_f or in no mask are
+// never read.
 // One lane owns one (t, n) and walks frames in ascending f, rows in ascending k, accumulating in float64: one fixed
 // order, no atomics, the same bits on every run.  Items are flat over NT * L, so the lanes of a wavefront may lie in two
 // tracks (L not a multiple of 64): every lane derives its own (t, n) and loads its own mask word.  Grid-stride loop.
@@ -176,22 +195,15 @@ __global__ __launch_bounds__(kFramesBlock) void k_overlap_add_tracks(const T* __
   for (int64_t item = (int64_t)blockIdx.x * kFramesBlock + threadIdx.x; item < total; item += stride) {
     const int64_t t = item / L;
     const int64_t n = item - t * L;
-    const int64_t f_lo = n < N ? 0 : (n - N) / hop + 1;
-    int64_t f_hi = n / hop;
-    if (f_hi > W - 1) f_hi = W - 1;
+    int64_t f_lo, f_hi;
+    ola_frame_span(n, N, hop, W, f_lo, f_hi);
     const unsigned long long* mrow = masks + t * W;
     double num = 0.0, den = 0.0;
     for (int64_t f = f_lo; f <= f_hi; ++f) {
       const int i = (int)(n - f * hop);
-      int kf = K;
-      if (counts) {
-        kf = counts[f];
-        kf = kf < 0 ? 0 : kf > K ? K : kf;
-      }
-      const double s = ws ? ws[i] : 1.0;
-      den += (wa ? wa[i] : 1.0) * s;
-      unsigned long long m = mrow[f];
-      if (kf < 64) m &= (1ull << kf) - 1ull;  // (kf = 0: no row at all)
+      const int kf = counts ? ola_clip(counts[f], K) : K;
+      const double s = ola_window(i, wa, ws, den);
+      unsigned long long m = ola_cut(mrow[f], kf);
       const T* row = y + (f * K) * (int64_t)N + i;
       int left = __builtin_popcountll(m);
       for (; left >= 4; left -= 4) {  // four loads in flight, added in ascending k
@@ -216,7 +228,7 @@ __global__ __launch_bounds__(kFramesBlock) void k_overlap_add_tracks(const T* __
         num += s * (double)row[(int64_t)k * N];
       }
     }
-    out[item] = norm ? (den > 0.0 ? num / den : 0.0) : num;
+    out[item] = ola_result(num, den, norm);
   }
 }
 
@@ -225,8 +237,8 @@ __global__ __launch_bounds__(kFramesBlock) void k_overlap_add_tracks(const T* __
 // k_qo_extract writes: block a of frame f is p(f, a) = periods[f, a] doubles at off(f, a) = sum_{b < a} p(f, b) -- and is
 // tiled on the fly onto NT tracks of L samples -> out (NT, L) float64.  With i = n - f hop:
 //   num[t, n] = sum_f ws[i] * sum_{a < C_f, bit a of masks[t, f] set} seg[f, off(f, a) + (i mod p(f, a))]
-//   C_f = counts[f] clipped to [0, min(pcap, 64)]; den, norm, the frames of a sample and the mask word as in
-//   k_overlap_add_tracks.  The dense (W, K, N) rows that kernel reads never exist: a frame costs sum p doubles, not K N.
+//   C_f = counts[f] clipped to [0, min(pcap, 64)].  The dense (W, K, N) rows k_overlap_add_tracks reads never exist: a
+//   frame costs sum p doubles, not K N.
 // One lane owns one (t, n) and walks frames in ascending f, blocks in ascending a, accumulating in float64: the order
 // of k_overlap_add_tracks, no atomics, the same bits on every run.  Flat grid-stride loop over NT * L, int64 addressing.
 // The offsets are the running sum of the periods the walk has passed, so a lane reads periods[f, a] for every a up to
@@ -252,19 +264,15 @@ __global__ __launch_bounds__(kFramesBlock) void k_overlap_add_periodic(const dou
   for (int64_t item = (int64_t)blockIdx.x * kFramesBlock + threadIdx.x; item < total; item += stride) {
     const int64_t t = item / L;
     const int64_t n = item - t * L;
-    const int64_t f_lo = n < N ? 0 : (n - N) / hop + 1;
-    int64_t f_hi = n / hop;
-    if (f_hi > W - 1) f_hi = W - 1;
+    int64_t f_lo, f_hi;
+    ola_frame_span(n, N, hop, W, f_lo, f_hi);
     const unsigned long long* mrow = masks + t * W;
     double num = 0.0, den = 0.0;
     for (int64_t f = f_lo; f <= f_hi; ++f) {
       const unsigned i = (unsigned)(n - f * hop);
-      int cf = counts[f];
-      cf = cf < 0 ? 0 : cf > cmax ? cmax : cf;
-      const double s = ws ? ws[i] : 1.0;
-      den += (wa ? wa[i] : 1.0) * s;
-      unsigned long long m = mrow[f];
-      if (cf < 64) m &= (1ull << cf) - 1ull;  // (cf = 0: no block at all)
+      const int cf = ola_clip(counts[f], cmax);
+      const double s = ola_window(i, wa, ws, den);
+      const unsigned long long m = ola_cut(mrow[f], cf);
       if (m == 0ull) continue;
       const int last = 63 - __builtin_clzll(m);  // < cf <= pcap
       const int* prow = periods + f * (int64_t)pcap;
@@ -277,7 +285,7 @@ __global__ __launch_bounds__(kFramesBlock) void k_overlap_add_periodic(const dou
         off += p;
       }
     }
-    out[item] = norm ? (den > 0.0 ? num / den : 0.0) : num;
+    out[item] = ola_result(num, den, norm);
   }
 }
 

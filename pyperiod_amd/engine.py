@@ -74,6 +74,28 @@ class KernelPlan(NamedTuple):
     pad: int
 
 
+def _side(mk, x, a, dtype, name, of="x", joint=False):
+    """A side array of a call next to its main array `x`: with torch input a contiguous `dtype` tensor on x's device, with
+    numpy input a contiguous numpy array (dtype None: as it is).  `joint`: `name` lists several arrays refused as one."""
+    if not mk.torch:
+        return np.ascontiguousarray(a, dtype=dtype)
+    tname = np.dtype(dtype).name
+    if not _is_torch(a) or a.dtype != getattr(mk._t, tname) or a.device != x.device:
+        kind = f"{tname} tensors" if joint else f"{'an' if tname[0] == 'i' else 'a'} {tname} tensor"
+        raise TypeError(f"{name} must be {kind} on the device of {of}")
+    return a.contiguous()
+
+
+def _masks(mk, x, masks, W, of):
+    """The (T, W) routing masks of a routed overlap-add: np.uint64 / np.int64, or with torch input torch.int64."""
+    if not mk.torch and (not isinstance(masks, np.ndarray) or masks.dtype not in (np.dtype(np.uint64), np.dtype(np.int64))):
+        raise TypeError("masks must be a uint64 or int64 array")
+    msk = _side(mk, x, masks, np.int64 if mk.torch else None, "masks", of)
+    if msk.ndim != 2 or msk.shape[1] != W:
+        raise ValueError("masks must be (T, W): one word per track and frame")
+    return msk
+
+
 def _i32(a):
     a = np.ascontiguousarray(a, dtype=np.int32)
     return a, a.ctypes.data
@@ -372,12 +394,7 @@ class PeriodEngine:
 
     def _window(self, mk, x, window, N):
         """One float64 analysis window of N samples for a batch: a numpy array, or with torch input a tensor on x's device."""
-        if mk.torch:
-            win = window.contiguous()
-            if win.dtype != mk._t.float64 or win.device != x.device:
-                raise TypeError("window must be a float64 tensor on the device of x")
-        else:
-            win = np.ascontiguousarray(window, dtype=np.float64)
+        win = _side(mk, x, window, np.float64, "window")
         if tuple(win.shape) != (N,):
             raise ValueError(f"window must hold N={N} samples")
         return win
@@ -485,26 +502,21 @@ class PeriodEngine:
         row (default: all pcap).  With torch input both are int32 tensors on x's device (n_periods required for 2-D
         lists) and `max_period` should be given (default N); for numpy it defaults to the largest entry."""
         x, code, W, N, fl, mk = self._prep(x)
+        per = _side(mk, x, periods, np.int32, "periods")
         if mk.torch:
-            per = periods.contiguous()
-            if per.dtype != mk._t.int32 or per.device != x.device:
-                raise TypeError("periods must be an int32 tensor on the device of x")
             if n_periods is None:
                 n_periods = mk._t.full((W if per.dim() == 2 else 1,), per.shape[-1], dtype=mk._t.int32, device=x.device)
-            npr = n_periods.contiguous()
-            if npr.dtype != mk._t.int32 or npr.device != x.device:
-                raise TypeError("n_periods must be an int32 tensor on the device of x")
+            npr = _side(mk, x, n_periods, np.int32, "n_periods")
             ndim, shape = per.dim(), tuple(per.shape)
             if max_period is None:
                 max_period = N
         else:
-            per = np.ascontiguousarray(periods, dtype=np.int32)
             if per.shape[-1] == 0:  # an empty list still needs one readable entry
                 per = np.zeros(per.shape[:-1] + (1,), dtype=np.int32)
                 n_periods = np.zeros(W if per.ndim == 2 else 1, dtype=np.int32)
             if n_periods is None:
                 n_periods = np.full(W if per.ndim == 2 else 1, per.shape[-1], dtype=np.int32)
-            npr = np.ascontiguousarray(np.atleast_1d(n_periods), dtype=np.int32)
+            npr = _side(mk, x, np.atleast_1d(n_periods), np.int32, "n_periods")
             ndim, shape = per.ndim, per.shape
             if max_period is None:
                 max_period = max(1, int(per.max()))
@@ -592,13 +604,11 @@ class PeriodEngine:
         means `period` rows and has to be replaced first).  `ccap` defaults to the largest sum of periods of the batch
         and `max_period` to the largest period (numpy) or ccap (torch); computing ccap from device tensors reads one
         word back, so pass it to stay asynchronous."""
-        if _is_torch(weights):
-            wts, code, W, kcap, fl, mk = self._prep(weights)
+        wts, code, W, kcap, fl, mk = self._prep(weights if _is_torch(weights) else np.asarray(weights, dtype=np.float64))
+        per, rws, cnt = (_side(mk, wts, a, np.int32, "periods, rows and counts", "weights", joint=True)
+                         for a in (periods, rows, counts))
+        if mk.torch:
             t = mk._t
-            per, rws, cnt = periods.contiguous(), rows.contiguous(), counts.contiguous()
-            for a in (per, rws, cnt):
-                if a.dtype != t.int32 or a.device != wts.device:
-                    raise TypeError("periods, rows and counts must be int32 tensors on the device of weights")
             shapes = tuple(per.shape), tuple(rws.shape), tuple(cnt.shape)
             if ccap is None:
                 used = t.arange(per.shape[1], device=per.device)[None, :] < cnt[:, None]
@@ -606,10 +616,6 @@ class PeriodEngine:
             if max_period is None:
                 max_period = min(int(ccap), 1 << 20)
         else:
-            wts, code, W, kcap, fl, mk = self._prep(np.asarray(weights, dtype=np.float64))
-            per = np.ascontiguousarray(periods, dtype=np.int32)
-            rws = np.ascontiguousarray(rows, dtype=np.int32)
-            cnt = np.ascontiguousarray(counts, dtype=np.int32)
             shapes = per.shape, rws.shape, cnt.shape
             if per.ndim == 2 and per.shape == rws.shape and cnt.shape == (W,):
                 used = np.arange(per.shape[1])[None, :] < cnt[:, None]
@@ -671,23 +677,30 @@ class PeriodEngine:
         if getattr(y, "ndim", None) not in (2, 3):
             raise ValueError("expected y of shape (W, N) or (W, K, N)")
         K, N = (1, y.shape[1]) if y.ndim == 2 else (y.shape[1], y.shape[2])
-        hop, L = int(hop), int(length)
-        if L < 0:
+        if int(length) < 0:
             raise ValueError("length must be >= 0")
         x, code, W, _, fl, mk = self._prep(y.reshape(y.shape[0], K * N))
+        return (x, code, W, K, N, int(hop), int(length), fl, mk) + self._ola_sides(mk, x, W, N, counts, win_a, win_s, "y")
+
+    def _ola_sides(self, mk, x, W, N, counts, win_a, win_s, of):
+        """The per-frame counts (None: all) and the two windows (None: all ones) of an overlap-add, checked against x."""
         cnt = None
         if counts is not None:
-            if mk.torch:
-                cnt = counts.contiguous()
-                if cnt.dtype != mk._t.int32 or cnt.device != x.device:
-                    raise TypeError("counts must be an int32 tensor on the device of y")
-            else:
-                cnt = np.ascontiguousarray(counts, dtype=np.int32)
+            cnt = _side(mk, x, counts, np.int32, "counts", of)
             if tuple(cnt.shape) != (W,):
                 raise ValueError("counts must hold one entry per frame")
         wa = None if win_a is None else self._window(mk, x, win_a, N)
         ws = None if win_s is None else self._window(mk, x, win_s, N)
-        return x, code, W, K, N, hop, L, fl, mk, cnt, wa, ws
+        return cnt, wa, ws
+
+    def _ola_call(self, mk, shape, W, L, fn, *args, fl, normalize):
+        """The float64 result of an overlap-add: one call of `fn` (flags and result last), or zeros when W or L is 0."""
+        out = mk.empty(shape, np.float64)
+        if W == 0 or L == 0:
+            out[...] = 0.0
+            return out
+        self._call(mk, W, fn, *args, fl | (_ffi.PH_FLAG_OLA_NORM if normalize else 0), mk.addr(out))
+        return out
 
     def overlap_add(self, y, hop, length, counts=None, win_a=None, win_s=None, normalize=True):
         """Overlap-add a framed result (ph_overlap_add, one launch): y (W, N) or (W, K, N) -> (length,) float64,
@@ -696,13 +709,8 @@ class PeriodEngine:
         exactly 0.0 elsewhere.  `counts` (W) int32, `win_a` / `win_s` (N) float64 or None (all ones): numpy arrays, or
         with torch input tensors on y's device."""
         x, code, W, K, N, hop, L, fl, mk, cnt, wa, ws = self._ola_args(y, hop, length, counts, win_a, win_s)
-        out = mk.empty((L,), np.float64)
-        if W == 0 or L == 0:  # nothing to add: no call
-            out[...] = 0.0
-            return out
-        self._call(mk, W, self._lib.ph_overlap_add, mk.addr(x), code, W, K, N, hop, L, mk.addr(cnt), mk.addr(wa),
-                   mk.addr(ws), fl | (_ffi.PH_FLAG_OLA_NORM if normalize else 0), mk.addr(out))
-        return out
+        return self._ola_call(mk, (L,), W, L, self._lib.ph_overlap_add, mk.addr(x), code, W, K, N, hop, L, mk.addr(cnt),
+                              mk.addr(wa), mk.addr(ws), fl=fl, normalize=normalize)
 
     def overlap_add_tracks(self, y, masks, hop, length, counts=None, win_a=None, win_s=None, normalize=True):
         """Routed overlap-add (ph_overlap_add_tracks, one launch): y (W, N) or (W, K, N), K <= 64 -> (T, length) float64,
@@ -710,24 +718,10 @@ class PeriodEngine:
         `masks` (T, W): np.uint64 or np.int64 (the same bits), or with torch input a torch.int64 tensor on y's device;
         masks may overlap, a row in no mask is never read.  `counts`, `win_a`, `win_s`, `normalize` as in overlap_add."""
         x, code, W, K, N, hop, L, fl, mk, cnt, wa, ws = self._ola_args(y, hop, length, counts, win_a, win_s)
-        if mk.torch:
-            if not _is_torch(masks) or masks.dtype != mk._t.int64 or masks.device != x.device:
-                raise TypeError("masks must be an int64 tensor on the device of y")
-            msk = masks.contiguous()
-        else:
-            if not isinstance(masks, np.ndarray) or masks.dtype not in (np.dtype(np.uint64), np.dtype(np.int64)):
-                raise TypeError("masks must be a uint64 or int64 array")
-            msk = np.ascontiguousarray(masks)
-        if msk.ndim != 2 or msk.shape[1] != W:
-            raise ValueError("masks must be (T, W): one word per track and frame")
+        msk = _masks(mk, x, masks, W, "y")
         T = int(msk.shape[0])
-        out = mk.empty((T, L), np.float64)
-        if W == 0 or L == 0:  # nothing to add: no call
-            out[...] = 0.0
-            return out
-        self._call(mk, W, self._lib.ph_overlap_add_tracks, mk.addr(x), code, W, K, N, hop, L, mk.addr(cnt), mk.addr(msk),
-                   T, mk.addr(wa), mk.addr(ws), fl | (_ffi.PH_FLAG_OLA_NORM if normalize else 0), mk.addr(out))
-        return out
+        return self._ola_call(mk, (T, L), W, L, self._lib.ph_overlap_add_tracks, mk.addr(x), code, W, K, N, hop, L,
+                              mk.addr(cnt), mk.addr(msk), T, mk.addr(wa), mk.addr(ws), fl=fl, normalize=normalize)
 
     def overlap_add_periodic(self, seg, periods, counts, masks, frame_length, hop, length, win_a=None, win_s=None,
                              normalize=True):
@@ -747,40 +741,19 @@ class PeriodEngine:
         x, code, W, ccap, fl, mk = self._prep(seg)
         if code != _ffi.PH_F64:
             raise TypeError("seg must be float64")
-        if mk.torch:
-            t = mk._t
-            for a, what in ((periods, "periods"), (counts, "counts")):
-                if not _is_torch(a) or a.dtype != t.int32 or a.device != x.device:
-                    raise TypeError(f"{what} must be an int32 tensor on the device of seg")
-            if not _is_torch(masks) or masks.dtype != t.int64 or masks.device != x.device:
-                raise TypeError("masks must be an int64 tensor on the device of seg")
-            per, cnt, msk = periods.contiguous(), counts.contiguous(), masks.contiguous()
-        else:
-            if not isinstance(masks, np.ndarray) or masks.dtype not in (np.dtype(np.uint64), np.dtype(np.int64)):
-                raise TypeError("masks must be a uint64 or int64 array")
-            per = np.ascontiguousarray(periods, dtype=np.int32)
-            cnt = np.ascontiguousarray(counts, dtype=np.int32)
-            msk = np.ascontiguousarray(masks)
+        per = _side(mk, x, periods, np.int32, "periods", "seg")
         if per.ndim != 2 or per.shape[0] != W or per.shape[1] < 1:
             raise ValueError("periods must be (W, pcap) with pcap >= 1")
         pcap = int(per.shape[1])
         if pcap > 64:
             raise ValueError(f"pcap={pcap} blocks per frame do not fit a 64-bit mask")
-        if tuple(cnt.shape) != (W,):
-            raise ValueError("counts must hold one entry per frame")
-        if msk.ndim != 2 or msk.shape[1] != W:
-            raise ValueError("masks must be (T, W): one word per track and frame")
+        cnt = _side(mk, x, counts, np.int32, "counts", "seg")  # (not optional here: None is refused like any non-array)
+        cnt, wa, ws = self._ola_sides(mk, x, W, N, cnt, win_a, win_s, "seg")
+        msk = _masks(mk, x, masks, W, "seg")
         T = int(msk.shape[0])
-        wa = None if win_a is None else self._window(mk, x, win_a, N)
-        ws = None if win_s is None else self._window(mk, x, win_s, N)
-        out = mk.empty((T, L), np.float64)
-        if W == 0 or L == 0:  # nothing to add: no call
-            out[...] = 0.0
-            return out
-        self._call(mk, W, self._lib.ph_overlap_add_periodic, mk.addr(x), mk.addr(per), mk.addr(cnt), mk.addr(msk), W, pcap,
-                   int(ccap), T, N, hop, L, mk.addr(wa), mk.addr(ws),
-                   fl | (_ffi.PH_FLAG_OLA_NORM if normalize else 0), mk.addr(out))
-        return out
+        return self._ola_call(mk, (T, L), W, L, self._lib.ph_overlap_add_periodic, mk.addr(x), mk.addr(per), mk.addr(cnt),
+                              mk.addr(msk), W, pcap, int(ccap), T, N, hop, L, mk.addr(wa), mk.addr(ws), fl=fl,
+                              normalize=normalize)
 
     def fold_sums(self, x, p_list, keep):
         """W = A x for natural-basis rows (QOPeriods.py:782): (W, sum(keep)) float64."""

@@ -3,24 +3,8 @@
 // tests/test_host_sanitizers.py: what is checked is that argument validation, pass plans, geometry / CSR / Bluestein
 // tables, staging copies and LDS layout arithmetic touch no byte out of bounds and hit no undefined behaviour.
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
 
-#include "../../include/periodhip.h"
-
-extern "C" void stub_reset_launches();
-extern "C" int stub_launches(int* block, long long* lds, int cap);
-
-static int fails = 0;
-#define EXPECT(call, want)                                                              \
-  do {                                                                                  \
-    const int rc_ = (call);                                                             \
-    if (rc_ != (want)) {                                                                \
-      std::printf("FAIL %s:%d %s -> %d (%s), want %d\n", __FILE__, __LINE__, #call, rc_, ph_last_error(), (want)); \
-      ++fails;                                                                          \
-    }                                                                                   \
-  } while (0)
+#include "driver_common.h"
 
 struct Csr {
   std::vector<int32_t> off, q;
@@ -305,10 +289,5 @@ int main() {
   for (int i = 0; i < cntp && i < 256; ++i) (void)ph_profile_name(c, i);
   EXPECT(ph_sync(c), PH_OK);
   EXPECT(ph_destroy(c), PH_OK);
-  if (fails) {
-    std::printf("host sanitizer driver: %d unexpected return codes\n", fails);
-    return 1;
-  }
-  std::printf("host sanitizer driver ok\n");
-  return 0;
+  return finish("");
 }

@@ -1,53 +1,10 @@
 // Drives ph_frames and ph_overlap_add through the HOST half of the library (hip_stub.cpp stands in for the runtime; kernels
-// do not run, outputs are not looked at).  Built with -fsanitize=address,undefined by tests/test_host_sanitizers_frames.py:
+// do not run, outputs are not looked at).  Built with -fsanitize=address,undefined by tests/test_host_sanitizers.py:
 // argument validation, the host-pointer staging (the signal once, L elements), the size arithmetic with W * N and
 // W * K * N beyond 2^31 (sizes only: those calls pass PH_FLAG_DEVICE, so nothing of that size is allocated or touched) and
 // W == 1 must touch no byte out of bounds and overflow no integer; every call is one launch of kFramesBlock threads
 // without LDS, named k_frames / k_overlap_add in the profile.
-#include <cstdio>
-#include <cstdlib>
-#include <string_view>
-#include <vector>
-
-#include "../../include/periodhip.h"
-
-extern "C" void stub_reset_launches();
-extern "C" int stub_launches(int* block, long long* lds, int cap);
-
-static int fails = 0;
-#define EXPECT(call, want)                                                              \
-  do {                                                                                  \
-    const int rc_ = (call);                                                             \
-    if (rc_ != (want)) {                                                                \
-      std::printf("FAIL %s:%d %s -> %d (%s), want %d\n", __FILE__, __LINE__, #call, rc_, ph_last_error(), (want)); \
-      ++fails;                                                                          \
-    }                                                                                   \
-  } while (0)
-
-static std::vector<const char*> expect_names;
-
-// one launch of 256 threads without LDS since the last reset
-static void one_launch(const char* name, int line) {
-  int block[4];
-  long long l[4];
-  const int n = stub_launches(block, l, 4);
-  if (n != 1 || block[0] != 256 || l[0] != 0) {
-    std::printf("FAIL line %d: %d launches, block %d, lds %lld\n", line, n, n ? block[0] : -1, n ? l[0] : -1LL);
-    ++fails;
-  }
-  expect_names.push_back(name);
-  stub_reset_launches();
-}
-
-static void no_launch(int line) {
-  int block[4];
-  long long l[4];
-  if (stub_launches(block, l, 4) != 0) {
-    std::printf("FAIL line %d: a refused call launched a kernel\n", line);
-    ++fails;
-  }
-  stub_reset_launches();
-}
+#include "driver_common.h"
 
 int main() {
   ph_ctx* c = nullptr;
@@ -153,25 +110,8 @@ int main() {
   float ms[300];
   int cntp = 0;
   EXPECT(ph_profile_read(c, ms, 300, &cntp), PH_OK);
-  const int want = (int)(expect_names.size() < 256 ? expect_names.size() : 256);
-  if (cntp != want) {
-    std::printf("FAIL %d profile entries for %zu launches\n", cntp, expect_names.size());
-    ++fails;
-  }
-  for (int i = 0; i < cntp && i < want; ++i) {
-    const char* nm = ph_profile_name(c, i);
-    if (!nm || std::string_view(nm) != expect_names[i]) {
-      std::printf("FAIL profile entry %d is %s, want %s\n", i, nm ? nm : "(null)", expect_names[i]);
-      ++fails;
-      break;
-    }
-  }
+  check_profile(c, cntp);
   EXPECT(ph_sync(c), PH_OK);
   EXPECT(ph_destroy(c), PH_OK);
-  if (fails) {
-    std::printf("host sanitizer driver (frames): %d unexpected results\n", fails);
-    return 1;
-  }
-  std::printf("host sanitizer driver frames ok\n");
-  return 0;
+  return finish("frames");
 }

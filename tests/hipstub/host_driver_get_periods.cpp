@@ -1,33 +1,14 @@
 // Drives ph_qo_get_periods through the HOST half of the library (hip_stub.cpp stands in for the runtime; kernels do not
-// run, outputs are not looked at).  Built with -fsanitize=address,undefined by tests/test_host_sanitizers_get_periods.py:
+// run, outputs are not looked at).  Built with -fsanitize=address,undefined by tests/test_host_sanitizers.py:
 // argument validation, the plan query, the Moebius tables, the staging of the three int32 lists beside the weights and
 // the workspaces must touch no byte out of bounds, and the one launch must ask for the LDS and the workgroup width that
 // ph_plan_info(PH_OP_QO_GET_PERIODS) names.
-#include <cstdio>
-#include <cstdlib>
-#include <string_view>
-#include <vector>
-
-#include "../../include/periodhip.h"
-
-extern "C" void stub_reset_launches();
-extern "C" int stub_launches(int* block, long long* lds, int cap);
-
-static int fails = 0;
-#define EXPECT(call, want)                                                              \
-  do {                                                                                  \
-    const int rc_ = (call);                                                             \
-    if (rc_ != (want)) {                                                                \
-      std::printf("FAIL %s:%d %s -> %d (%s), want %d\n", __FILE__, __LINE__, #call, rc_, ph_last_error(), (want)); \
-      ++fails;                                                                          \
-    }                                                                                   \
-  } while (0)
+#include "driver_common.h"
 
 int main() {
   ph_ctx* c = nullptr;
   EXPECT(ph_create(0, &c), PH_OK);
   EXPECT(ph_profile_enable(c, 1), PH_OK);
-  int launches = 0;
   // {W, pcap, largest period}: sum(p) from a few doubles (LDS) to far beyond the LDS (HBM workspace)
   const int sizes[][3] = {{1, 1, 1}, {3, 2, 18}, {5, 5, 100}, {2, 3, 5461}, {1, 4, 20000}, {2, 64, 1 << 20}};
   for (const auto& sz : sizes) {
@@ -69,7 +50,7 @@ int main() {
                     n, n ? l[0] : -1LL, n ? block[0] : -1, plan[PH_PLAN_K0 + PH_PLAN_LDS_BYTES], plan[PH_PLAN_K0 + PH_PLAN_BLOCK]);
         ++fails;
       }
-      launches += 1;
+      launched("k_qo_extract");
       // a few doubles fit the LDS, a sum of periods beyond it does not
       const int where = plan[PH_PLAN_K0 + PH_PLAN_WINDOW];
       if ((ccap <= 1000 && where != PH_PLAN_LDS) || (ccap >= 20000 && where != PH_PLAN_HBM)) {
@@ -112,24 +93,8 @@ int main() {
   float ms[300];
   int cntp = 0;
   EXPECT(ph_profile_read(c, ms, 300, &cntp), PH_OK);
-  if (cntp != launches) {
-    std::printf("FAIL %d profile entries for %d launches\n", cntp, launches);
-    ++fails;
-  }
-  for (int i = 0; i < cntp && i < 256; ++i) {
-    const char* nm = ph_profile_name(c, i);
-    if (!nm || std::string_view(nm) != "k_qo_extract") {
-      std::printf("FAIL profile entry %d is %s\n", i, nm ? nm : "(null)");
-      ++fails;
-      break;
-    }
-  }
+  check_profile(c, cntp);
   EXPECT(ph_sync(c), PH_OK);
   EXPECT(ph_destroy(c), PH_OK);
-  if (fails) {
-    std::printf("host sanitizer driver (get_periods): %d unexpected results\n", fails);
-    return 1;
-  }
-  std::printf("host sanitizer driver get_periods ok\n");
-  return 0;
+  return finish("get_periods");
 }

@@ -1,27 +1,10 @@
 // Drives ph_qo_greedy_win through the HOST half of the library (hip_stub.cpp stands in for the runtime; kernels do not
-// run, outputs are not looked at).  Built with -fsanitize=address,undefined by tests/test_host_sanitizers_greedy_win.py:
+// run, outputs are not looked at).  Built with -fsanitize=address,undefined by tests/test_host_sanitizers.py:
 // argument validation, the staging of the analysis window beside the batch, the divisor tables and the LDS layout must
 // touch no byte out of bounds, and the one launch must ask for the LDS that ph_qo_plan_info(PH_FLAG_KEEP_WEIGHTS) names.
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <string_view>
-#include <vector>
 
-#include "../../include/periodhip.h"
-
-extern "C" void stub_reset_launches();
-extern "C" int stub_launches(int* block, long long* lds, int cap);
-
-static int fails = 0;
-#define EXPECT(call, want)                                                              \
-  do {                                                                                  \
-    const int rc_ = (call);                                                             \
-    if (rc_ != (want)) {                                                                \
-      std::printf("FAIL %s:%d %s -> %d (%s), want %d\n", __FILE__, __LINE__, #call, rc_, ph_last_error(), (want)); \
-      ++fails;                                                                          \
-    }                                                                                   \
-  } while (0)
+#include "driver_common.h"
 
 int main() {
   ph_ctx* c = nullptr;
@@ -93,20 +76,8 @@ int main() {
   float ms[300];
   int cntp = 0;
   EXPECT(ph_profile_read(c, ms, 300, &cntp), PH_OK);
-  for (int i = 0; i < cntp && i < 256; ++i) {
-    const char* nm = ph_profile_name(c, i);
-    if (!nm || std::string_view(nm) != "k_qo_greedy_win") {
-      std::printf("FAIL profile entry %d is %s\n", i, nm ? nm : "(null)");
-      ++fails;
-      break;
-    }
-  }
+  check_profile(c, cntp, "k_qo_greedy_win");
   EXPECT(ph_sync(c), PH_OK);
   EXPECT(ph_destroy(c), PH_OK);
-  if (fails) {
-    std::printf("host sanitizer driver (greedy_win): %d unexpected results\n", fails);
-    return 1;
-  }
-  std::printf("host sanitizer driver greedy_win ok\n");
-  return 0;
+  return finish("greedy_win");
 }

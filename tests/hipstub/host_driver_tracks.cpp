@@ -1,62 +1,10 @@
 // Drives ph_overlap_add_tracks through the HOST half of the library (hip_stub.cpp stands in for the runtime; kernels do
-// not run, outputs are not looked at).  Built with -fsanitize=address,undefined by tests/test_host_sanitizers_tracks.py:
+// not run, outputs are not looked at).  Built with -fsanitize=address,undefined by tests/test_host_sanitizers.py:
 // every refusal, K = 64 against K = 65, the host-pointer staging of y, masks, counts and both windows with exact-size
 // vectors, NULL optional pointers, and the size arithmetic with T * L and W * K * N beyond 2^31 (sizes only: those calls
 // pass PH_FLAG_DEVICE, so nothing of that size is allocated or touched) must touch no byte out of bounds and overflow no
 // integer; every accepted call is one launch of kFramesBlock threads without LDS, named k_overlap_add_tracks.
-#include <cstdio>
-#include <cstdlib>
-#include <string_view>
-#include <vector>
-
-#include "../../include/periodhip.h"
-
-extern "C" void stub_reset_launches();
-extern "C" int stub_launches(int* block, long long* lds, int cap);
-
-static int fails = 0;
-#define EXPECT(call, want)                                                              \
-  do {                                                                                  \
-    const int rc_ = (call);                                                             \
-    if (rc_ != (want)) {                                                                \
-      std::printf("FAIL %s:%d %s -> %d (%s), want %d\n", __FILE__, __LINE__, #call, rc_, ph_last_error(), (want)); \
-      ++fails;                                                                          \
-    }                                                                                   \
-  } while (0)
-
-static int launches = 0;
-
-// one launch of 256 threads without LDS since the last reset
-static void one_launch(int line) {
-  int block[4];
-  long long l[4];
-  const int n = stub_launches(block, l, 4);
-  if (n != 1 || block[0] != 256 || l[0] != 0) {
-    std::printf("FAIL line %d: %d launches, block %d, lds %lld\n", line, n, n ? block[0] : -1, n ? l[0] : -1LL);
-    ++fails;
-  }
-  ++launches;
-  stub_reset_launches();
-}
-
-static void no_launch(int line) {
-  int block[4];
-  long long l[4];
-  if (stub_launches(block, l, 4) != 0) {
-    std::printf("FAIL line %d: a refused call launched a kernel\n", line);
-    ++fails;
-  }
-  stub_reset_launches();
-}
-
-// the message of a refusal names what was refused
-static void said(const char* word, int line) {
-  const char* msg = ph_last_error();
-  if (!msg || std::string_view(msg).find(word) == std::string_view::npos) {
-    std::printf("FAIL line %d: message '%s' does not name %s\n", line, msg ? msg : "(null)", word);
-    ++fails;
-  }
-}
+#include "driver_common.h"
 
 int main() {
   ph_ctx* c = nullptr;
@@ -77,13 +25,13 @@ int main() {
       // NULL optional pointers
       EXPECT(ph_overlap_add_tracks(c, y.data(), dt, W, K, N, hop, L, nullptr, masks.data(), T, nullptr, nullptr, 0, out.data()),
              PH_OK);
-      one_launch(__LINE__);
+      one_launch("k_overlap_add_tracks", __LINE__);
       EXPECT(ph_overlap_add_tracks(c, y.data(), dt, W, K, N, hop, L, cnt.data(), masks.data(), T, win.data(), win.data(),
                                    PH_FLAG_OLA_NORM, out.data()), PH_OK);
-      one_launch(__LINE__);
+      one_launch("k_overlap_add_tracks", __LINE__);
       EXPECT(ph_overlap_add_tracks(c, y.data(), dt, W, K, N, hop, L, cnt.data(), masks.data(), T, nullptr, win.data(),
                                    PH_FLAG_DEVICE | PH_FLAG_OLA_NORM, out.data()), PH_OK);
-      one_launch(__LINE__);
+      one_launch("k_overlap_add_tracks", __LINE__);
     }
   }
 
@@ -95,19 +43,19 @@ int main() {
     const int N = 4096, hop = 512, K = 5;
     const int64_t L = (W - 1) * hop + N;  // > 2^30: T * L > 2^31 from T = 3 on
     EXPECT(ph_overlap_add_tracks(c, tiny, PH_F64, W, K, N, hop, L, nullptr, tm, 9, nullptr, nullptr, PH_FLAG_DEVICE, tiny), PH_OK);
-    one_launch(__LINE__);
+    one_launch("k_overlap_add_tracks", __LINE__);
     EXPECT(ph_overlap_add_tracks(c, tiny, PH_F32, W, 64, N, hop, L, nullptr, tm, 3, nullptr, nullptr,
                                  PH_FLAG_DEVICE | PH_FLAG_OLA_NORM, tiny), PH_OK);
-    one_launch(__LINE__);
+    one_launch("k_overlap_add_tracks", __LINE__);
     // T * W beyond 2^31 with a small L
     EXPECT(ph_overlap_add_tracks(c, tiny, PH_F64, 70000, 1, 8, 1, 70007, nullptr, tm, 40000, nullptr, nullptr, PH_FLAG_DEVICE,
                                  tiny), PH_OK);
-    one_launch(__LINE__);
+    one_launch("k_overlap_add_tracks", __LINE__);
     // f * hop beyond 2^31 as well: hop of 2^20 over 2^12 frames
     const int64_t W2 = 4096, L2 = (W2 - 1) * ((int64_t)1 << 20) + 1;
     EXPECT(ph_overlap_add_tracks(c, tiny, PH_F32, W2, 1, 8, 1 << 20, L2, nullptr, tm, 2, nullptr, nullptr, PH_FLAG_DEVICE, tiny),
            PH_OK);
-    one_launch(__LINE__);
+    one_launch("k_overlap_add_tracks", __LINE__);
     // byte counts that do not fit 64 bits are refused, not wrapped: W * K * N, T * L, T * W
     EXPECT(ph_overlap_add_tracks(c, tiny, PH_F64, INT64_MAX / 2, 64, INT32_MAX, 1, INT64_MAX, nullptr, tm, 1, nullptr, nullptr,
                                  PH_FLAG_DEVICE, tiny), PH_E_ARG);
@@ -121,7 +69,7 @@ int main() {
     // the largest counts that pass
     EXPECT(ph_overlap_add_tracks(c, tiny, PH_F64, 4, 2, 16, 8, INT64_MAX / 64, nullptr, tm, 8, nullptr, nullptr, PH_FLAG_DEVICE,
                                  tiny), PH_OK);
-    one_launch(__LINE__);
+    one_launch("k_overlap_add_tracks", __LINE__);
     no_launch(__LINE__);
   }
 
@@ -162,35 +110,18 @@ int main() {
     std::vector<double> y64(4 * 64 * 16);
     EXPECT(ph_overlap_add_tracks(c, y64.data(), PH_F64, 4, 64, 16, 8, 100, nullptr, masks.data(), 3, nullptr, nullptr, 0,
                                  out.data()), PH_OK);
-    one_launch(__LINE__);
+    one_launch("k_overlap_add_tracks", __LINE__);
     EXPECT(ph_overlap_add_tracks(c, y.data(), PH_F64, 4, 2, 16, 8, 25, nullptr, masks.data(), 3, nullptr, nullptr, 0, out.data()),
            PH_OK);
-    one_launch(__LINE__);
+    one_launch("k_overlap_add_tracks", __LINE__);
   }
 
   // ---- the profile name of every launch (the profile keeps the first 256)
   float ms[300];
   int cntp = 0;
   EXPECT(ph_profile_read(c, ms, 300, &cntp), PH_OK);
-  const int want = launches < 256 ? launches : 256;
-  if (cntp != want) {
-    std::printf("FAIL %d profile entries for %d launches\n", cntp, launches);
-    ++fails;
-  }
-  for (int i = 0; i < cntp && i < want; ++i) {
-    const char* nm = ph_profile_name(c, i);
-    if (!nm || std::string_view(nm) != "k_overlap_add_tracks") {
-      std::printf("FAIL profile entry %d is %s\n", i, nm ? nm : "(null)");
-      ++fails;
-      break;
-    }
-  }
+  check_profile(c, cntp);
   EXPECT(ph_sync(c), PH_OK);
   EXPECT(ph_destroy(c), PH_OK);
-  if (fails) {
-    std::printf("host sanitizer driver (tracks): %d unexpected results\n", fails);
-    return 1;
-  }
-  std::printf("host sanitizer driver tracks ok\n");
-  return 0;
+  return finish("tracks");
 }

@@ -183,6 +183,64 @@ def test_entry_points_reject_bad_arguments_without_gpu():
     assert b"ctx" in lib.ph_last_error()
 
 
+def cpu_engine():
+    """A PeriodEngine without a context that takes CPU tensors as if they lived on its device; reaching the library is
+    an error.  Everything the binding checks about its arguments runs before that."""
+    import torch
+
+    from pyperiod_amd import _ffi
+    from pyperiod_amd.engine import PeriodEngine, _Out
+
+    class Reached(Exception):
+        pass
+
+    def prep(x):
+        x = x.contiguous()
+        code = {torch.float64: _ffi.PH_F64, torch.float32: _ffi.PH_F32}[x.dtype]
+        return x, code, x.shape[0], x.shape[1], _ffi.PH_FLAG_DEVICE, _Out(x)
+
+    def call(*a, **k):
+        raise Reached
+
+    eng = object.__new__(PeriodEngine)
+    eng._prep, eng._call, eng._lib = prep, call, type("Lib", (), {"__getattr__": lambda self, name: name})()
+    return eng, Reached
+
+
+def test_numpy_side_array_next_to_a_tensor_is_a_type_error():
+    """With torch input every side array is a tensor of the right dtype: a numpy array (or a tensor of another dtype) in
+    its place raises TypeError in every method, before the library is called."""
+    import torch
+
+    eng, Reached = cpu_engine()
+    x, i32 = torch.zeros((4, 16), dtype=torch.float64), lambda *shape: torch.ones(shape, dtype=torch.int32)
+    win_t, win_n = torch.ones(16, dtype=torch.float64), np.ones(16)
+    with pytest.raises(Reached):
+        eng.overlap_add(x, 4, 28, i32(4), win_t, win_t)
+    with pytest.raises(Reached):
+        eng.frames(x[0], 16, 4, 1, win_t)
+    with pytest.raises(Reached):
+        eng.qo_fit(x, i32(4, 2), i32(4), max_period=5, window=win_t)
+    with pytest.raises(Reached):
+        eng.qo_get_periods(i32(4, 2), i32(4, 2), i32(4), x, ccap=4)
+    bad = [
+        lambda: eng.overlap_add(x, 4, 28, counts=np.ones(4, np.int32)),
+        lambda: eng.overlap_add(x, 4, 28, counts=torch.ones(4, dtype=torch.int64)),
+        lambda: eng.overlap_add(x, 4, 28, win_a=win_n),
+        lambda: eng.overlap_add(x, 4, 28, win_s=win_n),
+        lambda: eng.frames(x[0], 16, 4, 1, win_n),
+        lambda: eng.qo_fit(x, np.ones((4, 2), np.int32), i32(4)),
+        lambda: eng.qo_fit(x, i32(4, 2), np.ones(4, np.int32)),
+        lambda: eng.qo_fit(x, i32(4, 2), i32(4), window=win_n),
+        lambda: eng.qo_get_periods(np.ones((4, 2), np.int32), i32(4, 2), i32(4), x, ccap=4),
+        lambda: eng.qo_get_periods(i32(4, 2), np.ones((4, 2), np.int32), i32(4), x, ccap=4),
+        lambda: eng.qo_get_periods(i32(4, 2), i32(4, 2), np.ones(4, np.int32), x, ccap=4),
+    ]
+    for call in bad:
+        with pytest.raises(TypeError, match="on the device of"):
+            call()
+
+
 @pytest.mark.parametrize("L,N,hop", ROUND_TRIP)
 def test_restatement_round_trip(L, N, hop):
     from pyperiod_amd import ShortTime

@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-from test_short_time_cpu import ola_bound, sqrt_hann
+from test_short_time_cpu import cpu_engine, ola_bound, sqrt_hann
 from test_short_time_tracks_cpu import overlap_add_tracks_ref
 
 
@@ -221,6 +221,23 @@ def test_entry_point_rejects_bad_arguments_without_gpu():
         assert call(flags=dev, W=1 << 40, N=1, hop=1, L=1 << 40, T=1, ccap=1 << 24) == E  # W ccap 8
         assert b"W * ccap" in lib.ph_last_error()
         assert call(flags=dev, W=1 << 42, N=1, hop=1, L=1 << 42, T=1, ccap=1, pcap=1 << 20) == E  # W pcap 4
+
+
+def test_numpy_side_array_next_to_a_tensor_is_a_type_error():
+    import torch
+
+    eng, Reached = cpu_engine()
+    seg, masks = torch.zeros((4, 8), dtype=torch.float64), torch.ones((3, 4), dtype=torch.int64)
+    per, cnt = torch.ones((4, 2), dtype=torch.int32), torch.ones(4, dtype=torch.int32)
+    with pytest.raises(Reached):
+        eng.overlap_add_periodic(seg, per, cnt, masks, 16, 4, 28)
+    for call in (lambda: eng.overlap_add_periodic(seg, per.numpy(), cnt, masks, 16, 4, 28),
+                 lambda: eng.overlap_add_periodic(seg, per, cnt.numpy(), masks, 16, 4, 28),
+                 lambda: eng.overlap_add_periodic(seg, per, None, masks, 16, 4, 28),
+                 lambda: eng.overlap_add_periodic(seg, per, cnt, masks.numpy(), 16, 4, 28),
+                 lambda: eng.overlap_add_periodic(seg, per, cnt, masks, 16, 4, 28, win_a=np.ones(16))):
+        with pytest.raises(TypeError, match="on the device of"):
+            call()
 
 
 def test_merge_repeats_against_a_loop():

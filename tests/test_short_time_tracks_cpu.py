@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-from test_short_time_cpu import ola_bound, overlap_add_ref, sqrt_hann
+from test_short_time_cpu import cpu_engine, ola_bound, overlap_add_ref, sqrt_hann
 
 
 # ------------------------------------------------------------------ restatement
@@ -222,6 +222,21 @@ def test_decompose_validates_before_touching_the_gpu(monkeypatch):
                                        "activity", "counts")
     assert ShortTime._track_list([12, (17, 34), {5}, np.int64(7), [8, 8], np.array(9),
                                   np.array([3, 6])]) == [(12,), (17, 34), (5,), (7,), (8,), (9,), (3, 6)]
+
+
+def test_numpy_side_array_next_to_a_tensor_is_a_type_error():
+    import torch
+
+    eng, Reached = cpu_engine()
+    y, masks = torch.zeros((4, 2, 16), dtype=torch.float64), torch.ones((3, 4), dtype=torch.int64)
+    with pytest.raises(Reached):
+        eng.overlap_add_tracks(y, masks, 4, 28, torch.ones(4, dtype=torch.int32))
+    for call in (lambda: eng.overlap_add_tracks(y, masks.numpy(), 4, 28),
+                 lambda: eng.overlap_add_tracks(y, masks.to(torch.int32), 4, 28),
+                 lambda: eng.overlap_add_tracks(y, masks, 4, 28, counts=np.ones(4, np.int32)),
+                 lambda: eng.overlap_add_tracks(y, masks, 4, 28, win_s=np.ones(16))):
+        with pytest.raises(TypeError, match="on the device of"):
+            call()
 
 
 def test_symbol_in_binding_and_header():

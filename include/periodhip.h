@@ -117,6 +117,11 @@ int ph_max_window(ph_ctx* ctx, int dtype, unsigned flags, int* max_n);
  * and 4p).  n_pass * N * sizeof(T) is the number of bytes one sweep reads from LDS. */
 int ph_sweep_plan_info(ph_ctx* ctx, int p_lo, int p_hi, int* n_pass, int* n_periods);
 
+/* The radius table of the window-pair screen of ph_m_best, as the host uploads it for windows of N samples: out[q],
+ * q = 1 ... max_p <= N (out[0] = 0; max_p + 1 doubles), bounds |float screen value - fp64 value| of period q in units
+ * of the window's sum of squares.  Host arithmetic only: needs no context and no device. */
+int ph_pair_radius_table(int N, int max_p, double* out);
+
 /* Measurement helper: which step-1 kernel ph_m_best runs for these arguments.  fp64 windows in plain mode
  * that fit the LDS twice are screened two windows per workgroup in packed float (windows_per_workgroup = 2,
  * one 8-byte LDS element carries a sample of both windows, lds_bytes_per_sample = 8 per PAIR) and only the

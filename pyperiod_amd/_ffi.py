@@ -49,6 +49,7 @@ SIGNATURES = {
     "ph_device_info": [_vp, C.POINTER(_i), C.POINTER(_i)],
     "ph_max_window": [_vp, _i, _u, C.POINTER(_i)],
     "ph_sweep_plan_info": [_vp, _i, _i, C.POINTER(_i), C.POINTER(_i)],
+    "ph_pair_radius_table": [_i, _i, C.POINTER(_d)],
     "ph_m_best_info": [_vp, _i, _i, _i, _i, _i, _u, C.POINTER(_i), C.POINTER(_i)],
     "ph_m_best_plan_info": [_vp, _i, _i, _i, _i, _i, _u, C.POINTER(_i), C.POINTER(_i)],
     "ph_m_best_screen_info": [_vp, _i, _i, _i, _i, _i, _u, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_longlong)],

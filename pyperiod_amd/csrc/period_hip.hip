@@ -72,6 +72,7 @@ struct ph_ctx {
   // per-period fold geometry for the tuned sweeps, cached for the last (N, max_p)
   DevBuf geom;
   DevBuf geomf;  // the same table in float (ph::PGeomF), for the window-pair screen
+  DevBuf radq;   // radius of that screen per period: ph::pair_radius(ceil(N / q), q) (pair_radius_table)
   DevBuf kapf;   // kappa_q of k_small_to_large_pair's flag test (ph::s2l_kappa, rounded up to float)
   int geom_n = -1, geom_max_p = -1;
   bool step1_pair = true;  // PH_STEP1_PAIR=0: always the one-window fp64 kernel for m_best step 1
@@ -248,6 +249,14 @@ int prepare_plan(ph_ctx* c, int p_lo, int p_hi, const ph::PassPlan** out, int* n
   return PH_OK;
 }
 
+// Radius of the window-pair screen per period, in units of the sum of squares: radq[q] = pair_radius(ceil(N / q), q),
+// the bound ph_pair.h proves (k_mbest_step1_pair reads it in its survivor scan instead of estimating the row count).
+std::vector<double> pair_radius_table(int N, int max_p) {
+  std::vector<double> host((size_t)max_p + 1, 0.0);
+  for (int q = 1; q <= max_p; ++q) host[q] = ph::pair_radius((N + q - 1) / q, q);
+  return host;
+}
+
 // Dense table geom[p], p in [0, max_p]: rows, nfull and the reciprocal counts of period p.
 int prepare_geom(ph_ctx* c, int N, int max_p, const ph::PGeom** out) {
   if (c->geom.p && c->geom_n == N && c->geom_max_p >= max_p) {
@@ -269,6 +278,9 @@ int prepare_geom(ph_ctx* c, int N, int max_p, const ph::PGeom** out) {
     hostf[p] = ph::PGeomF{host[p].rows, host[p].nfull, (float)host[p].w_full, (float)host[p].w_short};
   PH_TRY(ensure(c, c->geomf, hostf.size() * sizeof(ph::PGeomF)));
   PH_HIP(hipMemcpyAsync(c->geomf.p, hostf.data(), hostf.size() * sizeof(ph::PGeomF), hipMemcpyHostToDevice, c->stream));
+  const std::vector<double> hostr = pair_radius_table(N, max_p);
+  PH_TRY(ensure(c, c->radq, hostr.size() * sizeof(double)));
+  PH_HIP(hipMemcpyAsync(c->radq.p, hostr.data(), hostr.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
   std::vector<float> hostk(host.size(), 0.0f);
   for (size_t p = 1; p < host.size(); ++p) {
     const double k = ph::s2l_kappa(N, host[p].rows, (int)p);
@@ -1029,6 +1041,7 @@ int ph_destroy(ph_ctx* c) {
     if (t.dev.p) (void)hipFree(t.dev.p);
   if (c->geom.p) (void)hipFree(c->geom.p);
   if (c->geomf.p) (void)hipFree(c->geomf.p);
+  if (c->radq.p) (void)hipFree(c->radq.p);
   if (c->kapf.p) (void)hipFree(c->kapf.p);
   if (c->plan.p) (void)hipFree(c->plan.p);
   if (c->twid.p) (void)hipFree(c->twid.p);
@@ -1063,6 +1076,14 @@ int ph_sweep_plan_info(ph_ctx* c, int p_lo, int p_hi, int* n_pass, int* n_period
   if (p_lo < 1 || p_hi < p_lo) return fail(PH_E_ARG, "need 1 <= p_lo <= p_hi (got %d, %d)", p_lo, p_hi);
   *n_pass = (int)build_plan(p_lo, p_hi, c->plan_max_m, true, c->pair_chain).size();  // the plan ph_sweep's norm modes run
   *n_periods = p_hi - p_lo + 1;
+  return PH_OK;
+}
+
+int ph_pair_radius_table(int N, int max_p, double* out) {
+  if (!out) return fail(PH_E_ARG, "NULL argument");
+  if (N < 1 || max_p < 1 || max_p > N) return fail(PH_E_ARG, "need 1 <= max_p <= N (got %d, %d)", max_p, N);
+  const std::vector<double> host = pair_radius_table(N, max_p);
+  std::copy(host.begin(), host.end(), out);
   return PH_OK;
 }
 
@@ -1475,7 +1496,7 @@ int ph_m_best(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int num, in
     ProfScope ps_(c, "k_mbest_step1");
     hipLaunchKernelGGL(kernel, dim3((unsigned)((W + 1) / 2)), dim3(s1.block), s1.lds, c->stream, (const double*)dx, (int)W, N,
                        num, min_length, max_length, p_scr, gamma, tb.fac_off, tb.fac_q, geom,
-                       static_cast<const ph::PGeomF*>(c->geomf.p), plan, n_pass,
+                       static_cast<const ph::PGeomF*>(c->geomf.p), static_cast<const double*>(c->radq.p), plan, n_pass,
                        static_cast<double*>(c->buf[B_GWIN].p), max_iters, (uint32_t*)dper, (double*)dpow, (double*)drows,
                        row_stride, dnorm, (int*)dstat, (int*)dsweeps);
   } else

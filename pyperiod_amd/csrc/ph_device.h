@@ -213,6 +213,8 @@ struct Fold {
     nfull = p_ - shortn;
     trows = shortn == 0 ? rows : rows - 1;
   }
+  // from a table entry of the period (PGeom: rows, nfull of the same N)
+  __device__ __forceinline__ Fold(int p_, int rows_, int nfull_) : p(p_), rows(rows_), nfull(nfull_), trows(nfull_ == p_ ? rows_ : rows_ - 1) {}
   __device__ __forceinline__ int count(int j) const { return j < nfull ? rows : rows - 1; }
 };
 

@@ -437,7 +437,7 @@ __device__ __forceinline__ double pair_exact_part(const double* __restrict__ xs,
 
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_WAVES, 8))) void k_mbest_step1_pair(
     const double* __restrict__ x, int W, int N, int num, int p_lo, int p_hi, int p_scr, int gamma,
-    const int* __restrict__ fac_off, const int* __restrict__ fac_q, const PGeom* __restrict__ geom, const PGeomF* __restrict__ geomf, const PassPlan* __restrict__ plan, int n_pass,
+    const int* __restrict__ fac_off, const int* __restrict__ fac_q, const PGeom* __restrict__ geom, const PGeomF* __restrict__ geomf, const double* __restrict__ radq, const PassPlan* __restrict__ plan, int n_pass,
     double* __restrict__ gres, int max_iters, uint32_t* __restrict__ periods_out, double* __restrict__ norms_out,
     double* __restrict__ rows_out, int row_stride, double* __restrict__ dnorm_out, int* __restrict__ status_out,
     int* __restrict__ sweeps_out) {
@@ -513,7 +513,6 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
 #else
 #define PH_PAIR_MARK(k)
 #endif
-  const float fn = (float)N;
 #ifdef PH_CLOCKS
   const long long ck0 = clock64(), wk0 = wall_clock64();
 #endif
@@ -540,7 +539,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
     const int tid = (wv << 6) + pair_lane();
     const int lane = tid & (kWave - 1);
     if (tid == 0) ctl[14] = nw;  // the pass queue of the next screen (barriers in between)
-    // ---- 2. survivors of both windows: two passes over the screened values (a thread sees the same <= 2 entries twice)
+    // ---- 2. survivors of both windows: two passes over the screened values
     {
       const bool scr0 = act0 && !__builtin_amdgcn_readfirstlane(ctl[12]), scr1 = act1 && !__builtin_amdgcn_readfirstlane(ctl[13]);
       if (scr0 || scr1) {
@@ -554,20 +553,39 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
         uint32_t* seen = reinterpret_cast<uint32_t*>(stg);
         for (int k = tid; k < 2 * SD; k += blockDim.x) seen[k] = 0u;
         const double slack = cover ? pair_cover_slack(N) : 0.0;
-        double lo0 = -1.0 / 0.0, lo1 = -1.0 / 0.0;
-        for (int idx = i0 + tid; idx < P; idx += blockDim.x) {
+        // One screened entry as both passes need it: the two values, the radius -- radq[q] = pair_radius(ceil(N / q), q)
+        // from the host table next to geomf, the bound the proof in ph_pair.h states -- 1 / q in gamma mode and the skip
+        // bits.  At most blockDim.x entries (683 of 1024 threads at N = 4096) means one entry per thread: it is read
+        // once and stays in registers across the barrier.
+        struct Entry {
+          f2 v;
+          double rad, rq;
+          bool skip0, skip1;
+        };
+        auto entry = [&](int idx) {
+          Entry e;
           const int q = p_lo + idx;
-          const f2 v = vals[idx];
-          const double rad = pair_radius(pair_rows_upper(fn, q), q);
           const uint32_t bit = 1u << (idx & 31);
-          double a = (double)v.x - rad * unit0, b = (double)v.y - rad * unit1;
+          e.v = vals[idx];
+          e.rad = radq[q];
+          e.rq = gamma ? 1.0 / (double)q : 1.0;
+          e.skip0 = (skip[idx >> 5] & bit) != 0;
+          e.skip1 = (skip[SK + (idx >> 5)] & bit) != 0;
+          return e;
+        };
+        const int idx_own = i0 + tid;
+        Entry own = {f2_zero(), 0.0, 1.0, true, true};
+        if (idx_own < P) own = entry(idx_own);
+        double lo0 = -1.0 / 0.0, lo1 = -1.0 / 0.0;
+        for (int idx = idx_own; idx < P; idx += blockDim.x) {
+          const Entry e = idx == idx_own ? own : entry(idx);
+          double a = (double)e.v.x - e.rad * unit0, b = (double)e.v.y - e.rad * unit1;
           if (gamma) {
-            const double rq = 1.0 / (double)q;
-            a *= rq;
-            b *= rq;
+            a *= e.rq;
+            b *= e.rq;
           }
-          if (!(skip[idx >> 5] & bit) && a > lo0) lo0 = a;
-          if (!(skip[SK + (idx >> 5)] & bit) && b > lo1) lo1 = b;
+          if (!e.skip0 && a > lo0) lo0 = a;
+          if (!e.skip1 && b > lo1) lo1 = b;
         }
         lo0 = wave_max(lo0);
         lo1 = wave_max(lo1);
@@ -584,23 +602,21 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
         if (tid == 0 && none1) ctl[1] = kPairListCap + 1;
         // periods that tie with the winner in the ROUNDED norm survive too
         const double thr0 = lo0 - fabs(lo0) * 1e-9, thr1 = lo1 - fabs(lo1) * 1e-9;
-        for (int idx = i0 + tid; idx < P; idx += blockDim.x) {
+        for (int idx = idx_own; idx < P; idx += blockDim.x) {
+          const Entry e = idx == idx_own ? own : entry(idx);
           const int q = p_lo + idx;
-          const f2 v = vals[idx];
-          const double rad = pair_radius(pair_rows_upper(fn, q), q) + slack;
-          const uint32_t bit = 1u << (idx & 31);
-          double a = (double)v.x + rad * unit0, b = (double)v.y + rad * unit1;
+          const double rad = e.rad + slack;
+          double a = (double)e.v.x + rad * unit0, b = (double)e.v.y + rad * unit1;
           if (gamma) {
-            const double rq = 1.0 / (double)q;
-            a *= rq;
-            b *= rq;
+            a *= e.rq;
+            b *= e.rq;
           }
           const bool hit0 = scr0 && !none0 && a >= thr0, hit1 = scr1 && !none1 && b >= thr1;
-          if (hit0 && !(skip[idx >> 5] & bit)) {
+          if (hit0 && !e.skip0) {
             const int k = atomicAdd(&ctl[0], 1);
             if (k < kPairListCap) list[k] = q;
           }
-          if (hit1 && !(skip[SK + (idx >> 5)] & bit)) {
+          if (hit1 && !e.skip1) {
             const int k = atomicAdd(&ctl[1], 1);
             if (k < kPairListCap) list[kPairListCap + k] = q;
           }
@@ -744,9 +760,12 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
           status = 1;
         } else {
           // bookkeeping (Periods.py:518-535); identical in every thread
+          // (the row that holds the winner already: 64 rows per ballot instead of `num` LDS reads in every thread)
           int row = -1;
-          for (int k = 0; k < num; ++k)
-            if (per[k] == (uint32_t)bestp) row = k;
+          for (int k0 = 0; k0 < num; k0 += kWave) {
+            const unsigned long long hit = __ballot(k0 + lane < num && per[k0 + lane] == (uint32_t)bestp);
+            if (hit) row = k0 + 63 - __clzll(hit);
+          }
           int action;  // 0 = subtract only, 1 = store new row, 2 = accumulate into existing row
           __syncthreads();
           if (row >= 0 && repeats < 10) {
@@ -775,7 +794,8 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
           const double sc = uniform_f64(dst2[2 + w]);
           double* dst = gres + gw * gstride;
           double acc = 0.0;
-          const Fold f(N, bestp);
+          const PGeom gb = geom[__builtin_amdgcn_readfirstlane(bestp)];  // (a scalar load; Fold(N, p) divides in every thread)
+          const Fold f(bestp, gb.rows, gb.nfull);
           if (bestp <= kPairSmallP) {
             // a short period: its few residues have hundreds of rows each -- means through LDS, the subtraction is spread
             // over the workgroup

@@ -326,9 +326,10 @@ __device__ __forceinline__ float scalar_select_lt(int x, int y, float a, float b
 // The wavefront streams over the columns and carries the R - 1 unfinished sums of q + 64 in `pend` (pend[k]: rows
 // 0 ... k of chunk c - k), rotated by unrolling.  Everything is straight-line code in the manner of pair_rows_group (U
 // columns of loads, one lgkmcnt(0), then the adds): R rows per column in front of the cut, R - 1 behind it; what a side
-// has left after its full groups is one group of 1 ... U - 1 columns.  In the first R - 1 columns no chunk of q + 64 is
-// complete yet: the groups that hold them stand at compile-time positions and leave the square out there (the
-// wave-uniform 0 / 1 factor remains where the peeling stops early).  The column that holds the cut and the last column
+// has besides its full groups is one group of 1 ... U - 1 columns -- behind the cut it comes last, in front of the cut
+// FIRST, at column 0.  In the first R - 1 columns no chunk of q + 64 is complete yet: with the odd group in front, every
+// group that holds one of them stands at a compile-time position and leaves the square out there (pair_duo_front; the
+// columns keep their order, so every sum is the one of the other order bit for bit).  The column that holds the cut and the last column
 // of q classify their lanes -- wave-uniform intervals, so the squares run under lane masks from the scalar unit
 // (pair_duo_edge) instead of per-lane selects.  The R - 1 columns behind the last one of q bring the rows that q + 64
 // still lacks (pair_duo_tail).  Adds and squares per period are those of two single passes, in the same order in
@@ -370,16 +371,15 @@ __device__ __forceinline__ void f2_sq_acc_cut(f2& sa, f2& pa, f2& sb, f2& pb, f2
       : "scc");
 }
 
-// U columns from column c on, NR rows each.  PRO says what becomes of the sums of q + 64 that complete here -- in the
-// first R - 1 columns of a pass none is complete:
+// U columns, NR rows each.  PRO says what becomes of the sums of q + 64 that complete here -- in the first R - 1
+// columns of a pass none is complete.  Every group in front of column R - 1 stands at a position known at compile time
+// (pair_duo_front), so the count is static:
 //   0       every column is at R - 1 or behind it: all of them are squared;
-//   k > 0   the group stands at a position known at compile time and its first k columns are in front of R - 1: they
-//           simply have no square;
-//   -1      the position is not static: the sum is multiplied by a wave-uniform 0 or 1.
+//   k > 0   the first k columns of the group are in front of R - 1: they simply have no square.
 template <int R, int NR, int U, int PRO>
-__device__ __forceinline__ void pair_duo_group(pair_ptr ptr, int q, int c, f2 (&pend)[R - 1], f2& sa, f2& pa, f2& sb, f2& pb) {
+__device__ __forceinline__ void pair_duo_group(pair_ptr ptr, int q, f2 (&pend)[R - 1], f2& sa, f2& pa, f2& sb, f2& pb) {
   static_assert(NR == R || NR == R - 1, "all rows (in front of the cut), or all but the last (behind it)");
-  static_assert(PRO >= -1 && PRO <= U, "columns without a square are columns of the group");
+  static_assert(PRO >= 0 && PRO <= U, "columns without a square are columns of the group");
   f2 v[NR][U];
 #pragma unroll
   for (int r = 0; r < NR; ++r)
@@ -395,9 +395,8 @@ __device__ __forceinline__ void pair_duo_group(pair_ptr ptr, int q, int c, f2 (&
     if (NR == R) sa = f2_fma(t, t, sa);
     else sb = f2_fma(t, t, sb);
     if (u >= PRO) {
-      f2 d = pend[R - 2];  // chunk c + u - (R - 1) of q + 64
+      f2 d = pend[R - 2];  // the chunk of q + 64 that lies R - 1 columns back
       if (NR == R) d += v[NR - 1][u];
-      if (PRO < 0) d *= scalar_select_lt(c + u, R - 1, 0.0f, 1.0f);
       if (NR == R) pa = f2_fma(d, d, pa);
       else pb = f2_fma(d, d, pb);
     }
@@ -461,55 +460,57 @@ __device__ __forceinline__ void pair_duo_tail(const f2* __restrict__ xs, int q, 
   if (T1 == R - 1) f2_sq_acc_lanes(pb, pend[R - 2], pair_lanes_below(q - 64 * (ncb - 1)));  // chunk ncb: residues q ... q + 63
 }
 
+// The columns in front of the cut, up to the first group boundary at or behind column R - 1.  The pairing rule gives
+// whole >= R - 1 (pair_duo_rows), and the first group has F = whole mod UA columns (UA when that is 0), so whole - F is a
+// multiple of UA: a full group that starts at S = F + k UA < R - 1 <= whole ends at S + UA <= whole.  The groups peeled
+// here therefore always exist, and each knows at compile time how many of its columns lie in front of R - 1.
+template <int R, int UA, int S>
+__device__ __forceinline__ void pair_duo_peel(pair_ptr at, int q, f2 (&pend)[R - 1], f2& sa, f2& pa, f2& sb, f2& pb) {
+  if constexpr (S < R - 1) {
+    pair_duo_group<R, R, UA, (R - 1 - S < UA ? R - 1 - S : UA)>(at + 64 * S, q, pend, sa, pa, sb, pb);
+    pair_duo_peel<R, UA, S + UA>(at, q, pend, sa, pa, sb, pb);
+  }
+}
+// returns the column the main loop starts at
+template <int R, int UA, int F>
+__device__ __forceinline__ int pair_duo_front(pair_ptr at, int q, f2 (&pend)[R - 1], f2& sa, f2& pa, f2& sb, f2& pb) {
+  static_assert(F >= 1 && F <= UA, "the first group is the remainder, or a full group");
+  pair_duo_group<R, R, F, (R - 1 < F ? R - 1 : F)>(at, q, pend, sa, pa, sb, pb);
+  pair_duo_peel<R, UA, F>(at, q, pend, sa, pa, sb, pb);
+  return F >= R - 1 ? F : F + (R - 1 - F + UA - 1) / UA * UA;
+}
+
 template <int R>
 __device__ __forceinline__ void pair_duo_rows(const f2* __restrict__ xs, int N, int q, const PGeomF g, f2& base, f2& partner) {
   // loads in flight: 12 / 16 / 10 / 12 in front of the cut (R = 3 ... 6), 8 / 12 / 12 / 10 behind it
   constexpr int UA = R <= 4 ? 4 : 2, UB = R <= 4 ? 4 : R == 5 ? 3 : 2;
-  constexpr int A3 = UA < 4 ? 1 : 3, A2 = UA < 3 ? 1 : 2, B3 = UB < 4 ? 1 : 3, B2 = UB < 3 ? 1 : 2;  // widths of the remainder groups
-  constexpr int P0 = R - 1 < UA ? R - 1 : UA, P1 = R - 1 - UA < UA ? R - 1 - UA : UA, P2 = R - 1 - 2 * UA;  // columns in front of R - 1 in the first groups
+  constexpr int B3 = UB < 4 ? 1 : 3, B2 = UB < 3 ? 1 : 2;  // widths of the remainder groups behind the cut
   const int cut = g.nfull, ncb = (q + 63) >> 6, last = ncb - 1;  // the last column of q is cut at q
   f2 pend[R - 1];
 #pragma unroll
   for (int k = 0; k < R - 1; ++k) pend[k] = f2_zero();
   f2 sa = f2_zero(), pa = f2_zero(), sb, pb;
-  int c = 0;
+  int c;
   {
+    // In front of the cut the group of odd size comes FIRST, at column 0, and full groups follow: every group that holds
+    // one of the first R - 1 columns then stands at a compile-time position, and the main loop ends exactly at `whole`.
     const int whole = min(cut >> 6, last);
     const pair_ptr at = pair_at(xs);
-    // the groups that hold the first R - 1 columns stand at fixed positions: peeled, their columns in front of R - 1
-    // have no square of q + 64
-    if (UA <= whole) {
-      pair_duo_group<R, R, UA, P0>(at, q, 0, pend, sa, pa, sb, pb);
-      c = UA;
-      if constexpr (P1 > 0) {
-        if (2 * UA <= whole) {
-          pair_duo_group<R, R, UA, P1>(at + 64 * UA, q, UA, pend, sa, pa, sb, pb);
-          c = 2 * UA;
-          if constexpr (P2 > 0) {
-            if (3 * UA <= whole) {
-              pair_duo_group<R, R, UA, P2>(at + 128 * UA, q, 2 * UA, pend, sa, pa, sb, pb);
-              c = 3 * UA;
-            }
-          }
-        }
+    const int rem = whole & (UA - 1);
+    if (UA > 3 && rem == 3) c = pair_duo_front<R, UA, (UA > 3 ? 3 : 1)>(at, q, pend, sa, pa, sb, pb);
+    else if (UA > 2 && rem == 2) c = pair_duo_front<R, UA, (UA > 2 ? 2 : 1)>(at, q, pend, sa, pa, sb, pb);
+    else if (rem == 1) c = pair_duo_front<R, UA, 1>(at, q, pend, sa, pa, sb, pb);
+    else c = pair_duo_front<R, UA, UA>(at, q, pend, sa, pa, sb, pb);
+    // Two groups per trip: the second takes its loads from the row addresses of the first (512 UA bytes further on, an
+    // offset in the instruction), which halves the address arithmetic of the loop.  In front of the cut only up to four
+    // rows: at five and six the addresses kept across both groups cost the kernel one more spilled register.
+    if constexpr (R <= 4) {
+      for (; c + 2 * UA <= whole; c += 2 * UA) {
+        pair_duo_group<R, R, UA, 0>(at + 64 * c, q, pend, sa, pa, sb, pb);
+        pair_duo_group<R, R, UA, 0>(at + 64 * c + 64 * UA, q, pend, sa, pa, sb, pb);
       }
     }
-    for (; c + UA <= whole; c += UA) pair_duo_group<R, R, UA, 0>(at + 64 * c, q, c, pend, sa, pa, sb, pb);
-    // what is left, fewer than UA columns, in one group with one drain
-    const int rem = whole - c;
-    if (rem > 0) {
-      asm volatile("" ::: "memory");
-      if (c < R - 1) {  // (the peeling stopped in front of column R - 1: the position is not static)
-        if (UA > 3 && rem == 3) pair_duo_group<R, R, A3, -1>(at + 64 * c, q, c, pend, sa, pa, sb, pb);
-        else if (UA > 2 && rem == 2) pair_duo_group<R, R, A2, -1>(at + 64 * c, q, c, pend, sa, pa, sb, pb);
-        else pair_duo_group<R, R, 1, -1>(at + 64 * c, q, c, pend, sa, pa, sb, pb);
-      } else {
-        if (UA > 3 && rem == 3) pair_duo_group<R, R, A3, 0>(at + 64 * c, q, c, pend, sa, pa, sb, pb);
-        else if (UA > 2 && rem == 2) pair_duo_group<R, R, A2, 0>(at + 64 * c, q, c, pend, sa, pa, sb, pb);
-        else pair_duo_group<R, R, 1, 0>(at + 64 * c, q, c, pend, sa, pa, sb, pb);
-      }
-      c = whole;
-    }
+    for (; c + UA <= whole; c += UA) pair_duo_group<R, R, UA, 0>(at + 64 * c, q, pend, sa, pa, sb, pb);
   }
   sb = pb = f2_zero();  // (not live in front of the cut)
   // From here on every column lies at R - 1 or behind it: the partner has R rows as well, (R - 1) (q + 64) < N, so
@@ -522,13 +523,17 @@ __device__ __forceinline__ void pair_duo_rows(const f2* __restrict__ xs, int N, 
   }
   {
     const pair_ptr at = pair_at(xs);
-    for (; c + UB <= last; c += UB) pair_duo_group<R, R - 1, UB, 0>(at + 64 * c, q, c, pend, sa, pa, sb, pb);
+    for (; c + 2 * UB <= last; c += 2 * UB) {  // (two groups per trip, as in front of the cut)
+      pair_duo_group<R, R - 1, UB, 0>(at + 64 * c, q, pend, sa, pa, sb, pb);
+      pair_duo_group<R, R - 1, UB, 0>(at + 64 * c + 64 * UB, q, pend, sa, pa, sb, pb);
+    }
+    for (; c + UB <= last; c += UB) pair_duo_group<R, R - 1, UB, 0>(at + 64 * c, q, pend, sa, pa, sb, pb);
     const int rem = last - c;
     if (rem > 0) {  // fewer than UB columns: one group, one drain
       asm volatile("" ::: "memory");
-      if (UB > 3 && rem == 3) pair_duo_group<R, R - 1, B3, 0>(at + 64 * c, q, c, pend, sa, pa, sb, pb);
-      else if (UB > 2 && rem == 2) pair_duo_group<R, R - 1, B2, 0>(at + 64 * c, q, c, pend, sa, pa, sb, pb);
-      else pair_duo_group<R, R - 1, 1, 0>(at + 64 * c, q, c, pend, sa, pa, sb, pb);
+      if (UB > 3 && rem == 3) pair_duo_group<R, R - 1, B3, 0>(at + 64 * c, q, pend, sa, pa, sb, pb);
+      else if (UB > 2 && rem == 2) pair_duo_group<R, R - 1, B2, 0>(at + 64 * c, q, pend, sa, pa, sb, pb);
+      else pair_duo_group<R, R - 1, 1, 0>(at + 64 * c, q, pend, sa, pa, sb, pb);
     }
   }
   asm volatile("" ::: "memory");
@@ -818,7 +823,7 @@ __device__ __forceinline__ void pair_sweep_plan(const f2* __restrict__ xs, int N
 // gamma_{q/64 + 10}.  First order: (2 R + q/64 + 16) u; the factor 1.5 and the +32 cover the second-order terms
 // (R u <= 2^-13 for R <= 2048), the error of the fp64 value itself (<= (2R + q/64 + 16) 2^-53) and the error of ssq.
 // Underflow: the windows are scaled to RMS ~ 1, so denormal roundings (<= 2^-149 each) are far below the radius.
-__device__ __forceinline__ double pair_radius(int rows, int q) {
+__host__ __device__ __forceinline__ double pair_radius(int rows, int q) {
   return 1.5 * (2.0 * (double)rows + (double)(q >> 6) + 32.0) * 5.9604644775390625e-08;
 }
 

@@ -246,7 +246,12 @@ def best_frequency(data, win_size=None, num=5, trunc=False, orth=False):
 
 def m_best(data, num=5, max_length=None, min_length=2, gamma=False, trunc=False, orth=False, trace=None):
     """m_best (gamma=False, Periods.py:408-430) / m_best_gamma (gamma=True, :432-454).
-    `trace` (a dict, test tooling only) receives the step-1 picks before step 2 reshuffles them."""
+    `trace` (a dict, test tooling only) receives the step-1 picks before step 2 reshuffles them, and under "step2" one
+    record per iteration of the step-2 loop: position `i`, the row's `period` (all rows' `periods` as the iteration finds them), its `divisors` in the order scanned, the
+    winning factor `top_f` with its norm `n_big`, `n_small` (the norm of the LAST factor's projection), `lead` (the
+    relative lead of the top factor norm over the runner-up), the `outcome` -- "prime" (nothing to test), "present"
+    (:565), "nosplit" or "split" -- and, for the last two, `margins`: the relative distances of the three inequalities
+    of :573-575 from equality, |lhs - rhs| / rhs, with `holds` saying which of them hold."""
     n = len(data)
     if max_length is None:
         max_length = n // 3  # :485-486
@@ -296,20 +301,33 @@ def m_best(data, num=5, max_length=None, min_length=2, gamma=False, trunc=False,
     stale_p = max_length  # the loop variable `p` of :501 read again at :559,572
     base = None
     i = 0
+    steps = []  # test tooling (trace) only: one record per loop iteration
     while i < num:
         top_norm, top_f, top_base = 0, None, None
-        for f in factor_set(periods[i], True):  # set order, :548-549
+        second = 0.0
+        divisors = list(factor_set(periods[i], True))  # set order, :548-549
+        for f in divisors:
             base = project(bases[i], f, trunc, orth)
             nrm = periodic_norm(base, stale_p if gamma else None)
+            second = max(second, min(nrm, top_norm)) if nrm == nrm else second
             if nrm > top_norm:
                 top_f, top_norm, top_base = f, nrm, base
+        rec = {"i": i, "period": int(periods[i]), "periods": periods.copy(), "divisors": divisors, "top_f": top_f, "n_big": float(top_norm),
+               "n_small": None, "lead": (top_norm - second) / top_norm if top_norm > 0 else 1.0, "outcome": "prime",
+               "margins": None, "holds": None}
+        steps.append(rec)
         if top_f is not None and not np.any(periods == top_f):  # :565
             x_q = bases[i] - top_base
             n_big = top_norm
             # :569-572 -- the norm of the LAST factor's projection, not of x_q
             n_small = periodic_norm(base, stale_p if gamma else None)
             floor = min(norms)
+            pair = norms[num - 1] + norms[i]
+            rec["n_small"] = float(n_small)
+            rec["margins"] = (abs((n_small + n_big) - pair) / pair, abs(n_small - floor) / floor, abs(n_big - floor) / floor)
+            rec["holds"] = ((n_small + n_big) > pair, n_small > floor, n_big > floor)
             if (n_small + n_big) > (norms[num - 1] + norms[i]) and n_small > floor and n_big > floor:
+                rec["outcome"] = "split"
                 bases[i] = x_q
                 norms[i] = n_small
                 bases = np.insert(bases, i, top_base, 0)[:num]
@@ -317,9 +335,15 @@ def m_best(data, num=5, max_length=None, min_length=2, gamma=False, trunc=False,
                 periods = np.insert(periods, i, top_f)[:num]
                 # i is NOT advanced (:581-594)
             else:
+                rec["outcome"] = "nosplit"
                 i += 1
         else:
+            if top_f is not None:
+                rec["outcome"] = "present"
+                rec["n_small"] = float(periodic_norm(base, stale_p if gamma else None))
             i += 1
+    if trace is not None:
+        trace["step2"] = steps
 
     return periods, norms / periodic_norm(data), bases  # :600-601
 

@@ -313,6 +313,12 @@ int check_lds(const ph_ctx* c, size_t bytes, int N, const char* what) {
   return PH_OK;
 }
 
+// f(T{}) for the runtime element type.
+template <typename F>
+int dispatch(int dtype, F&& f) {
+  return dtype == PH_F64 ? f(double{}) : f(float{});
+}
+
 // f(T{}, std::bool_constant<window in LDS>{}) for the runtime element type / window placement.
 template <typename F>
 int dispatch(int dtype, bool lds_window, F&& f) {
@@ -362,6 +368,25 @@ int launch_check(const char* what) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(PH_E_HIP, "launch of %s failed: %s", what, hipGetErrorString(e));
   return PH_OK;
+}
+
+// One kernel launch on the context's stream, its profile bracket around the launch alone; a failure is reported under
+// `name`, the kernel that was launched.  The kernel's LDS limit must already allow `lds` (launch does both).
+template <typename K, typename... A>
+int enqueue(ph_ctx* c, const char* name, K kernel, dim3 grid, int block, size_t lds, A... args) {
+  {
+    ProfScope ps_(c, name);
+    hipLaunchKernelGGL(kernel, grid, dim3(block), lds, c->stream, args...);
+  }
+  return launch_check(name);
+}
+
+// The launch sequence of every kernel: raise its LDS limit to `lds`, then enqueue.  (ph_best_frequency raises the
+// limits of its kernels once and enqueues them `num` times.)
+template <typename K, typename... A>
+int launch(ph_ctx* c, const char* name, K kernel, dim3 grid, int block, size_t lds, A... args) {
+  PH_TRY(allow_lds(kernel, lds));
+  return enqueue(c, name, kernel, grid, block, lds, args...);
 }
 
 // Orth tables (only when PH_FLAG_ORTH) and validation of their content.
@@ -938,6 +963,123 @@ int plan_qo_extract(const ph_ctx* c, int ccap, int max_period, Plan* pl) {
   return PH_OK;
 }
 
+// ----------------------------------------------------------------------------- argument resolvers
+// One per entry point, as qo_plan and fit_prepare are for theirs: the defaults and refusals of the entry point's own
+// arguments, then its plan_* function.  The entry point and its ph_plan_info case both call it and state no argument rule
+// themselves; what only a launch can check (NULL outputs, the content of tables, W) stays with the launch.
+int resolve_project(const ph_ctx* c, int dtype, int N, int pmax, unsigned flags, Plan* pl, int* scratch_len) {
+  if (pmax < 1) return fail(PH_E_ARG, "p_list max %d must be >= 1", pmax);
+  return plan_project(c, dtype, N, pmax, flags, pl, scratch_len);
+}
+
+int check_sweep_range(int p_lo, int p_hi) {
+  if (p_lo < 1 || p_hi < p_lo) return fail(PH_E_ARG, "need 1 <= p_lo <= p_hi (got %d, %d)", p_lo, p_hi);
+  return PH_OK;
+}
+
+int resolve_sweep(const ph_ctx* c, int dtype, int N, int p_lo, int p_hi, int mode, unsigned flags, Plan* pl) {
+  PH_TRY(check_sweep_range(p_lo, p_hi));
+  if (mode < 0 || mode > 2) return fail(PH_E_ARG, "mode %d unknown", mode);
+  return plan_sweep(c, dtype, N, mode, flags, pl);
+}
+
+// Most proper divisors (1 and p removed) any period up to max_length has: the longest row of the caller's factor table
+// (CSR offsets, covering max_length), or without one the same count by sieve, as _factors.factor_tables makes the rows.
+int max_proper_divisors(const int32_t* fac_off, int max_length) {
+  int max_fac = 1;
+  if (fac_off) {
+    for (int q = 0; q <= max_length; ++q) max_fac = std::max(max_fac, fac_off[q + 1] - fac_off[q]);
+    return max_fac;
+  }
+  std::vector<int32_t> nd((size_t)max_length + 1, 0);
+  for (int d = 2; d <= max_length; ++d)
+    for (int q = 2 * d; q <= max_length; q += d) ++nd[q];
+  return std::max(max_fac, *std::max_element(nd.begin(), nd.end()));
+}
+
+// m_best: max_length < 0 means N / 3 (Periods.py:485-486); max_fac < 0 means "count them" (max_proper_divisors over
+// fac_off, which may be NULL).  `pair` is the plan's step-1 variant and p_scr the first period that kernel screens, so
+// the launch and the ph_m_best_*_info queries cannot disagree on either.
+struct MBestArgs {
+  int max_length, max_fac, p_scr;
+  bool pair;
+  Plan pl;
+};
+
+int resolve_m_best(const ph_ctx* c, int dtype, int N, int num, int min_length, int max_length, int gamma,
+                   const int32_t* fac_off, int table_max_p, int max_fac, unsigned flags, MBestArgs* a) {
+  if (num < 1 || num > 4096) return fail(PH_E_ARG, "num=%d must be in [1, 4096]", num);
+  if (max_length < 0) max_length = N / 3;
+  if (min_length < 1 || max_length < min_length)
+    return fail(PH_E_ARG, "need 1 <= min_length <= max_length (got %d, %d)", min_length, max_length);
+  if (fac_off && table_max_p < max_length)
+    return fail(PH_E_ARG, "factor tables cover p <= %d, need %d", table_max_p, max_length);
+  a->max_length = max_length;
+  a->max_fac = max_fac < 0 ? max_proper_divisors(fac_off, max_length) : max_fac;
+  PH_TRY(plan_m_best(c, dtype, N, num, min_length, max_length, a->max_fac, flags, &a->pl));
+  a->pair = a->pl.k[0].variant == PH_PLAN_PAIR;
+  a->p_scr = a->pair ? pair_screen_lo(c, min_length, max_length, gamma) : min_length;
+  return PH_OK;
+}
+
+// what the ph_m_best_*_info queries ask: ph_m_best's resolver without a factor table (the divisor count by sieve)
+int m_best_query(const ph_ctx* c, int dtype, int N, int num, int min_length, int max_length, int gamma, unsigned flags,
+                 MBestArgs* a) {
+  if (dtype != PH_F64 && dtype != PH_F32) return fail(PH_E_ARG, "dtype must be PH_F64 or PH_F32");
+  if (N < 1) return fail(PH_E_ARG, "N=%d must be >= 1", N);
+  return resolve_m_best(c, dtype, N, num, min_length, max_length, gamma, nullptr, 0, -1, flags, a);
+}
+
+// n_periods < 0 means N / 2 (Periods.py:271-272)
+int resolve_small_to_large(const ph_ctx* c, int dtype, int N, int* n_periods_io, unsigned flags, Plan* pl) {
+  if (*n_periods_io < 0) *n_periods_io = N / 2;
+  return plan_small_to_large(c, dtype, N, *n_periods_io, flags, pl);
+}
+
+// max_length < 0 means N / 3 (Periods.py:311-312)
+int resolve_best_correlation(const ph_ctx* c, int dtype, int N, int* max_length_io, unsigned flags, Plan* pl) {
+  if (*max_length_io < 0) *max_length_io = N / 3;
+  return plan_best_correlation(c, dtype, N, *max_length_io, flags, pl);
+}
+
+// win_size < 1 means N (Periods.py:381-382); *L receives the value used
+int resolve_best_frequency(const ph_ctx* c, int dtype, int N, int win_size, int* L, Plan* pl, BfShape* g) {
+  *L = win_size < 1 ? N : win_size;
+  if (*L < 2 || *L > (1 << 24)) return fail(PH_E_ARG, "win_size=%d out of range", *L);
+  return plan_best_frequency(c, dtype, N, *L, pl, g);
+}
+
+int resolve_ramanujan(const ph_ctx* c, int dtype, int N, int q_lo, int q_hi, Plan* pl) {
+  if (q_lo < 1 || q_hi < 1) return fail(PH_E_ARG, "need q_lo, q_hi >= 1 (got %d, %d)", q_lo, q_hi);
+  return plan_ramanujan(c, dtype, N, q_hi, pl);
+}
+
+// max_p < 0 means N / 2 (QOPeriods.py:1204-1207)
+int resolve_orth_powers(const ph_ctx* c, int dtype, int N, int* max_p_io, Plan* pl) {
+  if (*max_p_io < 0) *max_p_io = N / 2;
+  if (*max_p_io < 2) return fail(PH_E_ARG, "max_p=%d must be >= 2", *max_p_io);
+  plan_orth_powers(c, dtype, N, *max_p_io, pl);
+  return PH_OK;
+}
+
+// (ph_qo_orth_select has no default or refusal beside plan_qo_orth_select's own max_p >= 2: that function is its resolver)
+
+// What the window-pair kernels take beside the one-window arguments: one fp64 row of win_stride(N) per window in the
+// B_GWIN workspace, and the float tables prepare_geom keeps next to geom.
+struct PairWs {
+  double* gwin;
+  const ph::PGeomF* geomf;
+  const double* radq;
+  const float* kapf;
+};
+
+int pair_workspace(ph_ctx* c, int64_t W, int N, PairWs* ws) {
+  PH_TRY(ensure(c, c->buf[B_GWIN], (size_t)W * ph::win_stride((size_t)N) * sizeof(double)));
+  *ws = PairWs{static_cast<double*>(c->buf[B_GWIN].p), static_cast<const ph::PGeomF*>(c->geomf.p),
+               static_cast<const double*>(c->radq.p), static_cast<const float*>(c->kapf.p)};
+  return PH_OK;
+}
+
 }  // namespace
 
 
@@ -1073,7 +1215,7 @@ int ph_set_stream(ph_ctx* c, void* hip_stream) {
 
 int ph_sweep_plan_info(ph_ctx* c, int p_lo, int p_hi, int* n_pass, int* n_periods) {
   if (!c || !n_pass || !n_periods) return fail(PH_E_ARG, "NULL argument");
-  if (p_lo < 1 || p_hi < p_lo) return fail(PH_E_ARG, "need 1 <= p_lo <= p_hi (got %d, %d)", p_lo, p_hi);
+  PH_TRY(check_sweep_range(p_lo, p_hi));
   *n_pass = (int)build_plan(p_lo, p_hi, c->plan_max_m, true, c->pair_chain).size();  // the plan ph_sweep's norm modes run
   *n_periods = p_hi - p_lo + 1;
   return PH_OK;
@@ -1090,26 +1232,21 @@ int ph_pair_radius_table(int N, int max_p, double* out) {
 int ph_m_best_info(ph_ctx* c, int dtype, int N, int num, int min_length, int max_length, unsigned flags,
                    int* windows_per_workgroup, int* lds_bytes_per_sample) {
   if (!c || !windows_per_workgroup || !lds_bytes_per_sample) return fail(PH_E_ARG, "NULL argument");
-  if (dtype != PH_F64 && dtype != PH_F32) return fail(PH_E_ARG, "dtype must be PH_F64 or PH_F32");
-  if (max_length < 0) max_length = N / 3;
-  const bool pair = pair_eligible(c, dtype, N, num, min_length, max_length, flags);
-  *windows_per_workgroup = pair ? 2 : 1;
-  *lds_bytes_per_sample = pair ? 8 : (int)elem_size(dtype);
+  MBestArgs a;
+  PH_TRY(m_best_query(c, dtype, N, num, min_length, max_length, 0, flags, &a));
+  *windows_per_workgroup = a.pair ? 2 : 1;
+  *lds_bytes_per_sample = a.pair ? 8 : (int)elem_size(dtype);
   return PH_OK;
 }
 
 int ph_m_best_plan_info(ph_ctx* c, int dtype, int N, int num, int min_length, int max_length, unsigned flags, int* n_pass,
                         int* n_periods) {
   if (!c || !n_pass || !n_periods) return fail(PH_E_ARG, "NULL argument");
-  if (dtype != PH_F64 && dtype != PH_F32) return fail(PH_E_ARG, "dtype must be PH_F64 or PH_F32");
-  if (max_length < 0) max_length = N / 3;
-  if (min_length < 1 || max_length < min_length)
-    return fail(PH_E_ARG, "need 1 <= min_length <= max_length (got %d, %d)", min_length, max_length);
-  const bool pair = pair_eligible(c, dtype, N, num, min_length, max_length, flags);
   // the passes plain m_best runs: the pair kernel screens [pair_screen_lo, max_length] only (m_best_gamma: every period)
-  const int p_scr = pair ? pair_screen_lo(c, min_length, max_length, 0) : min_length;
-  *n_pass = (int)build_plan(p_scr, max_length, c->plan_max_m, false, pair && c->pair_chain).size();
-  *n_periods = max_length - min_length + 1;
+  MBestArgs a;
+  PH_TRY(m_best_query(c, dtype, N, num, min_length, max_length, 0, flags, &a));
+  *n_pass = (int)build_plan(a.p_scr, a.max_length, c->plan_max_m, false, a.pair && c->pair_chain).size();
+  *n_periods = a.max_length - min_length + 1;
   return PH_OK;
 }
 
@@ -1142,17 +1279,13 @@ long long plan_entry_elements(const ph::PassPlan& e, int N) {
 int ph_m_best_screen_info(ph_ctx* c, int dtype, int N, int num, int min_length, int max_length, unsigned flags, int gamma,
                           int* n_entries, int* n_screened, long long* lds_elements) {
   if (!c || !n_entries || !n_screened || !lds_elements) return fail(PH_E_ARG, "NULL argument");
-  if (dtype != PH_F64 && dtype != PH_F32) return fail(PH_E_ARG, "dtype must be PH_F64 or PH_F32");
-  if (max_length < 0) max_length = N / 3;
-  if (min_length < 1 || max_length < min_length)
-    return fail(PH_E_ARG, "need 1 <= min_length <= max_length (got %d, %d)", min_length, max_length);
   // (the one-window kernel folds every period of [min_length, max_length] in its own precision: same accounting)
-  const bool pair = pair_eligible(c, dtype, N, num, min_length, max_length, flags);
-  const int p_scr = pair ? pair_screen_lo(c, min_length, max_length, gamma) : min_length;
+  MBestArgs a;
+  PH_TRY(m_best_query(c, dtype, N, num, min_length, max_length, gamma, flags, &a));
   const std::vector<ph::PassPlan> plan =
-      build_plan(p_scr, max_length, c->plan_max_m, false, pair && c->pair_chain, pair && c->pair_duo ? N : 0);
+      build_plan(a.p_scr, a.max_length, c->plan_max_m, false, a.pair && c->pair_chain, a.pair && c->pair_duo ? N : 0);
   *n_entries = (int)plan.size();
-  *n_screened = max_length - p_scr + 1;
+  *n_screened = a.max_length - a.p_scr + 1;
   *lds_elements = 0;
   for (const ph::PassPlan& e : plan) *lds_elements += plan_entry_elements(e, N);
   return PH_OK;
@@ -1236,66 +1369,41 @@ int ph_plan_info(ph_ctx* c, int op, int dtype, int N, const int32_t* params, int
   Plan pl;
   switch (op) {
     case PH_OP_PROJECT: {
-      const int pmax = prm(0, N);
-      if (pmax < 1) return fail(PH_E_ARG, "p_list max %d must be >= 1", pmax);
       int scratch_len;
-      PH_TRY(plan_project(c, dtype, N, pmax, flags, &pl, &scratch_len));
+      PH_TRY(resolve_project(c, dtype, N, prm(0, N), flags, &pl, &scratch_len));
       break;
     }
-    case PH_OP_SWEEP: {
-      const int p_lo = prm(0, 1), p_hi = prm(1, N / 3), mode = prm(2, PH_SWEEP_NORM);
-      if (p_lo < 1 || p_hi < p_lo) return fail(PH_E_ARG, "need 1 <= p_lo <= p_hi (got %d, %d)", p_lo, p_hi);
-      if (mode < 0 || mode > 2) return fail(PH_E_ARG, "mode %d unknown", mode);
-      PH_TRY(plan_sweep(c, dtype, N, mode, flags, &pl));
+    case PH_OP_SWEEP:
+      PH_TRY(resolve_sweep(c, dtype, N, prm(0, 1), prm(1, N / 3), prm(2, PH_SWEEP_NORM), flags, &pl));
       break;
-    }
     case PH_OP_M_BEST: {
-      const int num = prm(0, 5), min_length = prm(1, 2);
-      int max_length = prm(2, -1), max_fac = prm(3, -1);
-      if (num < 1 || num > 4096) return fail(PH_E_ARG, "num=%d must be in [1, 4096]", num);
-      if (max_length < 0) max_length = N / 3;  // Periods.py:485-486
-      if (min_length < 1 || max_length < min_length)
-        return fail(PH_E_ARG, "need 1 <= min_length <= max_length (got %d, %d)", min_length, max_length);
-      if (max_fac < 0) {  // proper divisors (1 and p removed) of the candidate periods, as _factors.factor_tables
-        std::vector<int32_t> nd((size_t)max_length + 1, 0);
-        for (int d = 2; d <= max_length; ++d)
-          for (int q = 2 * d; q <= max_length; q += d) ++nd[q];
-        max_fac = std::max(1, *std::max_element(nd.begin(), nd.end()));
-      }
-      PH_TRY(plan_m_best(c, dtype, N, num, min_length, max_length, max_fac, flags, &pl));
+      MBestArgs a;
+      PH_TRY(resolve_m_best(c, dtype, N, prm(0, 5), prm(1, 2), prm(2, -1), 0, nullptr, 0, prm(3, -1), flags, &a));
+      pl = a.pl;
       break;
     }
     case PH_OP_SMALL_TO_LARGE: {
       int n_periods = prm(0, -1);
-      if (n_periods < 0) n_periods = N / 2;  // Periods.py:271-272
-      PH_TRY(plan_small_to_large(c, dtype, N, n_periods, flags, &pl));
+      PH_TRY(resolve_small_to_large(c, dtype, N, &n_periods, flags, &pl));
       break;
     }
     case PH_OP_BEST_CORRELATION: {
       int max_length = prm(0, -1);
-      if (max_length < 0) max_length = N / 3;  // Periods.py:311-312
-      PH_TRY(plan_best_correlation(c, dtype, N, max_length, flags, &pl));
+      PH_TRY(resolve_best_correlation(c, dtype, N, &max_length, flags, &pl));
       break;
     }
     case PH_OP_BEST_FREQUENCY: {
-      const int win_size = prm(0, -1);
-      const int L = win_size < 1 ? N : win_size;  // Periods.py:381-382
-      if (L < 2 || L > (1 << 24)) return fail(PH_E_ARG, "win_size=%d out of range", L);
+      int L;
       BfShape g;
-      PH_TRY(plan_best_frequency(c, dtype, N, L, &pl, &g));
+      PH_TRY(resolve_best_frequency(c, dtype, N, prm(0, -1), &L, &pl, &g));
       break;
     }
-    case PH_OP_RAMANUJAN: {
-      const int q_lo = prm(0, 2), q_hi = prm(1, N / 3);
-      if (q_lo < 1 || q_hi < 1) return fail(PH_E_ARG, "need q_lo, q_hi >= 1 (got %d, %d)", q_lo, q_hi);
-      PH_TRY(plan_ramanujan(c, dtype, N, q_hi, &pl));
+    case PH_OP_RAMANUJAN:
+      PH_TRY(resolve_ramanujan(c, dtype, N, prm(0, 2), prm(1, N / 3), &pl));
       break;
-    }
     case PH_OP_ORTH_POWERS: {
       int max_p = prm(0, -1);
-      if (max_p < 0) max_p = N / 2;  // QOPeriods.py:1204-1207
-      if (max_p < 2) return fail(PH_E_ARG, "max_p=%d must be >= 2", max_p);
-      plan_orth_powers(c, dtype, N, max_p, &pl);
+      PH_TRY(resolve_orth_powers(c, dtype, N, &max_p, &pl));
       break;
     }
     case PH_OP_FOLD_SUMS:
@@ -1351,7 +1459,7 @@ int ph_project_batch(ph_ctx* c, const void* x, int dtype, int64_t W, int N, cons
   const size_t sz = elem_size(dtype);
   Plan pl;
   int scratch_len;
-  PH_TRY(plan_project(c, dtype, N, pmax, flags, &pl, &scratch_len));
+  PH_TRY(resolve_project(c, dtype, N, pmax, flags, &pl, &scratch_len));
   const size_t lds = pl.k[0].lds;
   const int chunks = pick_chunks(c, W, n_p, 1);
   void *gbuf, *gwin;
@@ -1371,14 +1479,9 @@ int ph_project_batch(ph_ctx* c, const void* x, int dtype, int64_t W, int N, cons
   const dim3 grid((unsigned)(W * chunks));
   PH_TRY(dispatch(dtype, !gwin, [&](auto t, auto lw) {
     using T = decltype(t);
-    auto kernel = ph::k_project_batch<T, decltype(lw)::value>;
-    PH_TRY(allow_lds(kernel, lds));
-    ProfScope ps_(c, "k_project_batch");
-    hipLaunchKernelGGL(kernel, grid, dim3(kBlock), lds, c->stream, (const T*)dx, N, d_plist, n_p, chunks, kflags, tb,
-                       scratch_len, (T*)gbuf, (T*)gwin, (T*)dout);
-    return (int)PH_OK;
+    return launch(c, "k_project_batch", ph::k_project_batch<T, decltype(lw)::value>, grid, kBlock, lds, (const T*)dx, N,
+                  d_plist, n_p, chunks, kflags, tb, scratch_len, (T*)gbuf, (T*)gwin, (T*)dout);
   }));
-  PH_TRY(launch_check("k_project_batch"));
   return st.finish();
 }
 
@@ -1387,12 +1490,10 @@ int ph_sweep(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int p_lo, in
              const int32_t* orth_off, const int32_t* orth_q, int table_max_p, unsigned flags, double* out) {
   PH_TRY(check_common(c, x, dtype, W, N));
   if (!out) return fail(PH_E_ARG, "out is NULL");
-  if (p_lo < 1 || p_hi < p_lo) return fail(PH_E_ARG, "need 1 <= p_lo <= p_hi (got %d, %d)", p_lo, p_hi);
-  if (mode < 0 || mode > 2) return fail(PH_E_ARG, "mode %d unknown", mode);
+  Plan pl;
+  PH_TRY(resolve_sweep(c, dtype, N, p_lo, p_hi, mode, flags, &pl));
   PH_HIP(hipSetDevice(c->device));
   const size_t sz = elem_size(dtype);
-  Plan pl;
-  PH_TRY(plan_sweep(c, dtype, N, mode, flags, &pl));
   const bool general = pl.k[0].second != PH_PLAN_NONE;
   const size_t lds = pl.k[0].lds;
   const int P = p_hi - p_lo + 1;
@@ -1418,14 +1519,9 @@ int ph_sweep(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int p_lo, in
   const dim3 grid((unsigned)(W * chunks));
   PH_TRY(dispatch(dtype, !gwin, [&](auto t, auto lw) {
     using T = decltype(t);
-    auto kernel = ph::k_sweep<T, decltype(lw)::value>;
-    PH_TRY(allow_lds(kernel, lds));
-    ProfScope ps_(c, "k_sweep");
-    hipLaunchKernelGGL(kernel, grid, dim3(sweep_block), lds, c->stream, (const T*)dx, N, p_lo, p_hi, mode, chunks,
-                       kflags, tb, geom, plan, n_pass, (T*)gbuf, (T*)gwin, (double*)dout);
-    return (int)PH_OK;
+    return launch(c, "k_sweep", ph::k_sweep<T, decltype(lw)::value>, grid, sweep_block, lds, (const T*)dx, N, p_lo, p_hi,
+                  mode, chunks, kflags, tb, geom, plan, n_pass, (T*)gbuf, (T*)gwin, (double*)dout);
   }));
-  PH_TRY(launch_check("k_sweep"));
   return st.finish();
 }
 
@@ -1436,22 +1532,16 @@ int ph_m_best(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int num, in
               void* bases, int32_t* status, int32_t* n_sweeps) {
   PH_TRY(check_common(c, x, dtype, W, N));
   if (!periods || !powers || !bases || !status) return fail(PH_E_ARG, "output pointer is NULL");
-  if (num < 1 || num > 4096) return fail(PH_E_ARG, "num=%d must be in [1, 4096]", num);
-  if (max_length < 0) max_length = N / 3;  // Periods.py:485-486
-  if (min_length < 1 || max_length < min_length)
-    return fail(PH_E_ARG, "need 1 <= min_length <= max_length (got %d, %d)", min_length, max_length);
+  if (!fac_off || !fac_q) return fail(PH_E_ARG, "fac_off/fac_q tables are required");
+  MBestArgs a;
+  PH_TRY(resolve_m_best(c, dtype, N, num, min_length, max_length, gamma, fac_off, table_max_p, -1, flags, &a));
+  max_length = a.max_length;
+  const int max_fac = a.max_fac, p_scr = a.p_scr;
+  const bool pair = a.pair;
+  const KernelPlan &s1 = a.pl.k[0], &s2 = a.pl.k[1];
   PH_HIP(hipSetDevice(c->device));
   const size_t sz = elem_size(dtype);
   const int P = max_length - min_length + 1;
-  if (!fac_off || !fac_q) return fail(PH_E_ARG, "fac_off/fac_q tables are required");
-  if (table_max_p < max_length)
-    return fail(PH_E_ARG, "factor tables cover p <= %d, need %d", table_max_p, max_length);
-  int max_fac = 1;  // most proper divisors any candidate period has
-  for (int q = 0; q <= max_length; ++q) max_fac = std::max(max_fac, fac_off[q + 1] - fac_off[q]);
-  Plan pl;
-  PH_TRY(plan_m_best(c, dtype, N, num, min_length, max_length, max_fac, flags, &pl));
-  const KernelPlan &s1 = pl.k[0], &s2 = pl.k[1];
-  const bool pair = s1.variant == PH_PLAN_PAIR;
   // the two kernels run back to back on one stream and may share the workspaces
   void *gbuf1, *gbuf2, *gwin1, *gwin2;
   PH_TRY(place(c, s1.second, B_GBUF, (size_t)W * N * sz, &gbuf1));
@@ -1466,7 +1556,6 @@ int ph_m_best(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int num, in
   const ph::PassPlan* plan;
   int n_pass;
   // (the cached plan is keyed by its first period: the top-half plan of m_best and the full plan of m_best_gamma differ there)
-  const int p_scr = pair ? pair_screen_lo(c, min_length, max_length, gamma) : min_length;
   PH_TRY(prepare_plan(c, p_scr, max_length, &plan, &n_pass, 4, false, pair, pair ? N : 0));
   Stage st(c, flags);
   const void* dx;
@@ -1489,40 +1578,27 @@ int ph_m_best(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int num, in
   const int max_iters = 12 * (P + num) + 64;
   const dim3 grid((unsigned)W);
   if (pair) {
-    const size_t gstride = ph::win_stride((size_t)N);
-    PH_TRY(ensure(c, c->buf[B_GWIN], (size_t)W * gstride * sizeof(double)));
-    auto kernel = ph::k_mbest_step1_pair;
-    PH_TRY(allow_lds(kernel, s1.lds));
-    ProfScope ps_(c, "k_mbest_step1");
-    hipLaunchKernelGGL(kernel, dim3((unsigned)((W + 1) / 2)), dim3(s1.block), s1.lds, c->stream, (const double*)dx, (int)W, N,
-                       num, min_length, max_length, p_scr, gamma, tb.fac_off, tb.fac_q, geom,
-                       static_cast<const ph::PGeomF*>(c->geomf.p), static_cast<const double*>(c->radq.p), plan, n_pass,
-                       static_cast<double*>(c->buf[B_GWIN].p), max_iters, (uint32_t*)dper, (double*)dpow, (double*)drows,
-                       row_stride, dnorm, (int*)dstat, (int*)dsweeps);
-  } else
-  PH_TRY(dispatch(dtype, !gwin1, [&](auto t, auto lw) {
-    using T = decltype(t);
-    auto kernel = ph::k_mbest_step1<T, decltype(lw)::value>;
-    PH_TRY(allow_lds(kernel, s1.lds));
-    ProfScope ps_(c, "k_mbest_step1");
-    hipLaunchKernelGGL(kernel, grid, dim3(s1.block), s1.lds, c->stream, (const T*)dx, N, num, min_length,
-                       max_length, gamma, kflags, tb, geom, plan, n_pass, (T*)gbuf1, (T*)gwin1, max_iters,
-                       (uint32_t*)dper, (double*)dpow, (T*)drows, row_stride, dnorm, (int*)dstat, (int*)dsweeps, s1.small_means);
-    return (int)PH_OK;
-  }));
-  PH_TRY(launch_check("k_mbest_step1"));
+    PairWs ws;
+    PH_TRY(pair_workspace(c, W, N, &ws));
+    PH_TRY(launch(c, "k_mbest_step1", ph::k_mbest_step1_pair, dim3((unsigned)((W + 1) / 2)), s1.block, s1.lds,
+                  (const double*)dx, (int)W, N, num, min_length, max_length, p_scr, gamma, tb.fac_off, tb.fac_q, geom, ws.geomf,
+                  ws.radq, plan, n_pass, ws.gwin, max_iters, (uint32_t*)dper, (double*)dpow, (double*)drows, row_stride, dnorm,
+                  (int*)dstat, (int*)dsweeps));
+  } else {
+    PH_TRY(dispatch(dtype, !gwin1, [&](auto t, auto lw) {
+      using T = decltype(t);
+      return launch(c, "k_mbest_step1", ph::k_mbest_step1<T, decltype(lw)::value>, grid, s1.block, s1.lds, (const T*)dx, N,
+                    num, min_length, max_length, gamma, kflags, tb, geom, plan, n_pass, (T*)gbuf1, (T*)gwin1, max_iters,
+                    (uint32_t*)dper, (double*)dpow, (T*)drows, row_stride, dnorm, (int*)dstat, (int*)dsweeps,
+                    s1.small_means);
+    }));
+  }
   PH_TRY(dispatch(dtype, !gwin2, [&](auto t, auto lw) {
     using T = decltype(t);
-    auto kernel = ph::k_mbest_step2<T, decltype(lw)::value>;
-    PH_TRY(allow_lds(kernel, s2.lds));
-    ProfScope ps_(c, "k_mbest_step2");
-    hipLaunchKernelGGL(kernel, grid, dim3(s2.block), s2.lds, c->stream, N, num, gamma,
-                       max_length, kflags, tb, geom,
-                       max_fac, (T*)gbuf2, (T*)gwin2, (uint32_t*)dper, (double*)dpow, (T*)dbases, dnorm,
-                       (const int*)dstat, (T*)drows, row_stride);
-    return (int)PH_OK;
+    return launch(c, "k_mbest_step2", ph::k_mbest_step2<T, decltype(lw)::value>, grid, s2.block, s2.lds, N, num, gamma,
+                  max_length, kflags, tb, geom, max_fac, (T*)gbuf2, (T*)gwin2, (uint32_t*)dper, (double*)dpow, (T*)dbases,
+                  dnorm, (const int*)dstat, (T*)drows, row_stride);
   }));
-  PH_TRY(launch_check("k_mbest_step2"));
   return st.finish();
 }
 
@@ -1533,11 +1609,10 @@ int ph_small_to_large(ph_ctx* c, const void* x, int dtype, int64_t W, int N, dou
   PH_TRY(check_common(c, x, dtype, W, N));
   if (!counts || !periods || !powers || !status) return fail(PH_E_ARG, "output pointer is NULL");
   if (cap < 1) return fail(PH_E_ARG, "cap=%d must be >= 1", cap);
-  if (n_periods < 0) n_periods = N / 2;  // Periods.py:271-272
+  Plan pl;
+  PH_TRY(resolve_small_to_large(c, dtype, N, &n_periods, flags, &pl));
   PH_HIP(hipSetDevice(c->device));
   const size_t sz = elem_size(dtype);
-  Plan pl;
-  PH_TRY(plan_small_to_large(c, dtype, N, n_periods, flags, &pl));
   const KernelPlan& k = pl.k[0];
   void *gbuf, *gwin;
   PH_TRY(place(c, k.second, B_GBUF, (size_t)W * N * sz, &gbuf));
@@ -1563,31 +1638,23 @@ int ph_small_to_large(ph_ctx* c, const void* x, int dtype, int64_t W, int N, dou
   const unsigned kflags = flags & (PH_FLAG_TRUNC | PH_FLAG_ORTH);
   const dim3 grid((unsigned)W);
   if (k.variant == PH_PLAN_PAIR) {
-    const size_t gstride = ph::win_stride((size_t)N);
-    PH_TRY(ensure(c, c->buf[B_GWIN], (size_t)W * gstride * sizeof(double)));
-    auto kernel = ph::k_small_to_large_pair;
-    PH_TRY(allow_lds(kernel, k.lds));
-    ProfScope ps_(c, "k_small_to_large");
+    PairWs ws;
+    PH_TRY(pair_workspace(c, W, N, &ws));
     // persistent workgroups: as many as are resident at once (LDS and the 32 wavefronts of a CU), pairs from a counter
     const int64_t npairs = (W + 1) / 2;
     const int per_cu = (int)std::max<size_t>(1, std::min<size_t>((size_t)c->lds_limit / k.lds, 2048 / (size_t)k.block));
     const unsigned grid_pairs = (unsigned)std::min<int64_t>(npairs, (int64_t)c->num_cu * per_cu);
-    hipLaunchKernelGGL(kernel, dim3(grid_pairs), dim3(k.block), k.lds, c->stream, (const double*)dx, (int)W, N,
-                       thresh, n_periods, static_cast<const ph::PGeomF*>(c->geomf.p), static_cast<const float*>(c->kapf.p),
-                       static_cast<double*>(c->buf[B_GWIN].p), cap, (int*)dcnt, (int*)dper, (double*)dpow, (double*)dbases,
-                       (int*)dstat, dmax, dmax + 1);
-  } else
-  PH_TRY(dispatch(dtype, !gwin, [&](auto t, auto lw) {
-    using T = decltype(t);
-    auto kernel = ph::k_small_to_large<T, decltype(lw)::value>;
-    PH_TRY(allow_lds(kernel, k.lds));
-    ProfScope ps_(c, "k_small_to_large");
-    hipLaunchKernelGGL(kernel, grid, dim3(k.block), k.lds, c->stream, (const T*)dx, N, thresh, n_periods, kflags,
-                       tb, geom, (T*)gbuf, (T*)gwin, cap, (int*)dcnt, (int*)dper, (double*)dpow, (T*)dbases,
-                       (int*)dstat, dmax);
-    return (int)PH_OK;
-  }));
-  PH_TRY(launch_check("k_small_to_large"));
+    PH_TRY(launch(c, "k_small_to_large", ph::k_small_to_large_pair, dim3(grid_pairs), k.block, k.lds, (const double*)dx,
+                  (int)W, N, thresh, n_periods, ws.geomf, ws.kapf, ws.gwin, cap, (int*)dcnt, (int*)dper, (double*)dpow,
+                  (double*)dbases, (int*)dstat, dmax, dmax + 1));
+  } else {
+    PH_TRY(dispatch(dtype, !gwin, [&](auto t, auto lw) {
+      using T = decltype(t);
+      return launch(c, "k_small_to_large", ph::k_small_to_large<T, decltype(lw)::value>, grid, k.block, k.lds, (const T*)dx,
+                    N, thresh, n_periods, kflags, tb, geom, (T*)gbuf, (T*)gwin, cap, (int*)dcnt, (int*)dper, (double*)dpow,
+                    (T*)dbases, (int*)dstat, dmax);
+    }));
+  }
   PH_TRY(st.finish());
   // Capacity overflow must be impossible to miss: host-pointer calls are synchronous anyway; a
   // device-pointer call reads the batch maximum back (one word, one stream synchronisation) unless
@@ -1608,11 +1675,10 @@ int ph_best_correlation(ph_ctx* c, const void* x, int dtype, int64_t W, int N, i
   PH_TRY(check_common(c, x, dtype, W, N));
   if (!periods || !norms || !bases || !status) return fail(PH_E_ARG, "output pointer is NULL");
   if (num < 1) return fail(PH_E_ARG, "num=%d must be >= 1", num);
-  if (max_length < 0) max_length = N / 3;  // Periods.py:311-312
+  Plan pl;
+  PH_TRY(resolve_best_correlation(c, dtype, N, &max_length, flags, &pl));
   PH_HIP(hipSetDevice(c->device));
   const size_t sz = elem_size(dtype);
-  Plan pl;
-  PH_TRY(plan_best_correlation(c, dtype, N, max_length, flags, &pl));
   const KernelPlan& k = pl.k[0];
   const bool pair = k.variant == PH_PLAN_PAIR;
   void *gbuf, *gwin;
@@ -1636,26 +1702,19 @@ int ph_best_correlation(ph_ctx* c, const void* x, int dtype, int64_t W, int N, i
   const unsigned kflags = flags & (PH_FLAG_TRUNC | PH_FLAG_ORTH);
   const dim3 grid((unsigned)W);
   if (pair) {
-    const size_t gstride = ph::win_stride((size_t)N);
-    PH_TRY(ensure(c, c->buf[B_GWIN], (size_t)W * gstride * sizeof(double)));
-    auto kernel = ph::k_best_correlation_pair;
-    PH_TRY(allow_lds(kernel, k.lds));
-    ProfScope ps_(c, "k_best_correlation");
-    hipLaunchKernelGGL(kernel, dim3((unsigned)((W + 1) / 2)), dim3(k.block), k.lds, c->stream, (const double*)dx, (int)W, N,
-                       num, max_length, ratio, geom, static_cast<const ph::PGeomF*>(c->geomf.p), plan, n_pass,
-                       static_cast<double*>(c->buf[B_GWIN].p), (uint32_t*)dper, (double*)dnrm, (double*)dbases, (int*)dstat);
-  } else
-  PH_TRY(dispatch(dtype, !gwin, [&](auto t, auto lw) {
-    using T = decltype(t);
-    auto kernel = ph::k_best_correlation<T, decltype(lw)::value>;
-    PH_TRY(allow_lds(kernel, k.lds));
-    ProfScope ps_(c, "k_best_correlation");
-    hipLaunchKernelGGL(kernel, grid, dim3(k.block), k.lds, c->stream, (const T*)dx, N, num, max_length, ratio,
-                       kflags, tb, geom, plan, n_pass, (T*)gbuf, (T*)gwin, (uint32_t*)dper, (double*)dnrm, (T*)dbases,
-                       (int*)dstat);
-    return (int)PH_OK;
-  }));
-  PH_TRY(launch_check("k_best_correlation"));
+    PairWs ws;
+    PH_TRY(pair_workspace(c, W, N, &ws));
+    PH_TRY(launch(c, "k_best_correlation", ph::k_best_correlation_pair, dim3((unsigned)((W + 1) / 2)), k.block, k.lds,
+                  (const double*)dx, (int)W, N, num, max_length, ratio, geom, ws.geomf, plan, n_pass, ws.gwin, (uint32_t*)dper,
+                  (double*)dnrm, (double*)dbases, (int*)dstat));
+  } else {
+    PH_TRY(dispatch(dtype, !gwin, [&](auto t, auto lw) {
+      using T = decltype(t);
+      return launch(c, "k_best_correlation", ph::k_best_correlation<T, decltype(lw)::value>, grid, k.block, k.lds,
+                    (const T*)dx, N, num, max_length, ratio, kflags, tb, geom, plan, n_pass, (T*)gbuf, (T*)gwin,
+                    (uint32_t*)dper, (double*)dnrm, (T*)dbases, (int*)dstat);
+    }));
+  }
   return st.finish();
 }
 
@@ -1666,14 +1725,13 @@ int ph_best_frequency(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int
   PH_TRY(check_common(c, x, dtype, W, N));
   if (!periods || !powers || !bases || !status) return fail(PH_E_ARG, "output pointer is NULL");
   if (num < 1) return fail(PH_E_ARG, "num=%d must be >= 1", num);
-  const int L = win_size < 1 ? N : win_size;  // Periods.py:381-382
-  if (L < 2 || L > (1 << 24)) return fail(PH_E_ARG, "win_size=%d out of range", L);
   if (W > 65535) return fail(PH_E_ARG, "ph_best_frequency: W=%lld exceeds 65535 windows per call", (long long)W);
-  PH_HIP(hipSetDevice(c->device));
-  const size_t sz = elem_size(dtype);
+  int L;
   Plan pl;
   BfShape g;
-  PH_TRY(plan_best_frequency(c, dtype, N, L, &pl, &g));
+  PH_TRY(resolve_best_frequency(c, dtype, N, win_size, &L, &pl, &g));
+  PH_HIP(hipSetDevice(c->device));
+  const size_t sz = elem_size(dtype);
   const bool use_fft = pl.k[0].variant == PH_PLAN_FFT, use_chirp = pl.k[0].variant == PH_PLAN_CHIRP;
   const bool lds_window = pl.k[1].window == PH_PLAN_LDS;
   const size_t lds = pl.k[1].lds, lds_spec = g.lds_spec, lds_fft = g.lds_fft, lds_chirp = g.lds_chirp;
@@ -1783,29 +1841,22 @@ int ph_best_frequency(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int
     if (use_fft) PH_TRY(allow_lds(ph::k_bf_fft<T>, lds_fft));
     if (use_chirp) PH_TRY(allow_lds(ph::k_bf_chirp<T>, lds_chirp));
     PH_TRY(allow_lds(ph::k_bf_update<T, LW>, lds));
+    // (the limits are raised once, above: the num iterations enqueue only)
+    const double2 *twid = (const double2*)c->twid.p, *twm = (const double2*)c->bs_tab.p;
     for (int it = 0; it < num; ++it) {
       if (use_fft) {
-        ProfScope ps_(c, "k_bf_fft");
-        hipLaunchKernelGGL((ph::k_bf_fft<T>), grid_u, dim3(pl.k[0].block), lds_fft, c->stream, (const T*)dres, N, L, logL,
-                           (const double2*)c->twid.p, (const int*)dstat, dpart, dpartk);
+        PH_TRY(enqueue(c, "k_bf_fft", ph::k_bf_fft<T>, grid_u, pl.k[0].block, lds_fft, (const T*)dres, N, L, logL, twid,
+                       (const int*)dstat, dpart, dpartk));
       } else if (use_chirp) {
-        const double2* twm = (const double2*)c->bs_tab.p;
-        ProfScope ps_(c, "k_bf_chirp");
-        hipLaunchKernelGGL((ph::k_bf_chirp<T>), grid_u, dim3(pl.k[0].block), lds_chirp, c->stream, (const T*)dres, N, L, M, logM,
-                           twm, twm + M, twm + M + wlen, (const int*)dstat, dpart, dpartk);
+        PH_TRY(enqueue(c, "k_bf_chirp", ph::k_bf_chirp<T>, grid_u, pl.k[0].block, lds_chirp, (const T*)dres, N, L, M, logM,
+                       twm, twm + M, twm + M + wlen, (const int*)dstat, dpart, dpartk));
       } else {
-        ProfScope ps_(c, "k_bf_spectrum");
-        hipLaunchKernelGGL((ph::k_bf_spectrum<T, LW>), grid_s, dim3(pl.k[0].block), lds_spec, c->stream, (const T*)dres, N, L,
-                           (const double2*)c->twid.p, (const int*)dstat, dpart, dpartk);
+        PH_TRY(enqueue(c, "k_bf_spectrum", ph::k_bf_spectrum<T, LW>, grid_s, pl.k[0].block, lds_spec, (const T*)dres, N, L,
+                       twid, (const int*)dstat, dpart, dpartk));
       }
-      PH_TRY(launch_check("k_bf_spectrum"));
-      {
-        ProfScope ps_(c, "k_bf_update");
-        hipLaunchKernelGGL((ph::k_bf_update<T, LW>), grid_u, dim3(pl.k[1].block), lds, c->stream, (T*)dres, N, L, num, it,
-                           kflags, tb, (T*)gbuf, nchunk, (const double*)dpart, (const int*)dpartk, dnrm,
-                           (uint32_t*)dper, (double*)dpow, (T*)dbases, (int*)dstat);
-      }
-      PH_TRY(launch_check("k_bf_update"));
+      PH_TRY(enqueue(c, "k_bf_update", ph::k_bf_update<T, LW>, grid_u, pl.k[1].block, lds, (T*)dres, N, L, num, it, kflags,
+                     tb, (T*)gbuf, nchunk, (const double*)dpart, (const int*)dpartk, dnrm, (uint32_t*)dper, (double*)dpow,
+                     (T*)dbases, (int*)dstat));
     }
     return (int)PH_OK;
   }));
@@ -1825,7 +1876,7 @@ struct RamLaunch {
 static int ram_prepare(ph_ctx* c, int dtype, int64_t W, int N, int q_lo, int q_hi, RamLaunch* rl) {
   const size_t sz = elem_size(dtype);
   Plan& pl = rl->pl;
-  PH_TRY(plan_ramanujan(c, dtype, N, q_hi, &pl));
+  PH_TRY(resolve_ramanujan(c, dtype, N, q_lo, q_hi, &pl));
   const KernelPlan& k = pl.k[0];
   void*& gwin = rl->gwin;
   PH_TRY(place(c, k.window, B_GWIN, (size_t)W * ph::win_stride(N + kPad) * sz, &gwin));
@@ -1922,14 +1973,9 @@ static int ram_enqueue(ph_ctx* c, const RamLaunch& rl, int dtype, int64_t W, int
     const ph::RamJob* d_roots = reinterpret_cast<const ph::RamJob*>(rl.d_tab);
     PH_TRY(dispatch(dtype, !gwin, [&](auto t, auto lw) {
       using T = decltype(t);
-      auto kernel = ph::k_ramanujan<T, decltype(lw)::value>;
-      PH_TRY(allow_lds(kernel, k.lds));
-      ProfScope ps_(c, "k_ramanujan");
-      hipLaunchKernelGGL(kernel, grid, dim3(k.block), k.lds, c->stream, (const T*)dx, N, q_hi, d_roots, n_root,
-                         d_roots + n_root, (T*)gwin, k.pad, (double*)dout);
-      return (int)PH_OK;
+      return launch(c, "k_ramanujan", ph::k_ramanujan<T, decltype(lw)::value>, grid, k.block, k.lds, (const T*)dx, N, q_hi,
+                    d_roots, n_root, d_roots + n_root, (T*)gwin, k.pad, (double*)dout);
     }));
-    PH_TRY(launch_check("k_ramanujan"));
   }
   return PH_OK;
 }
@@ -1938,7 +1984,6 @@ int ph_ramanujan_norms(ph_ctx* c, const void* x, int dtype, int64_t W, int N, in
                        unsigned flags, double* out) {
   PH_TRY(check_common(c, x, dtype, W, N));
   if (!out) return fail(PH_E_ARG, "out is NULL");
-  if (q_lo < 1 || q_hi < 1) return fail(PH_E_ARG, "need q_lo, q_hi >= 1 (got %d, %d)", q_lo, q_hi);
   PH_HIP(hipSetDevice(c->device));
   const size_t sz = elem_size(dtype);
   RamLaunch rl;
@@ -1991,14 +2036,9 @@ int ph_fold_sums(ph_ctx* c, const void* x, int dtype, int64_t W, int N, const in
   const dim3 grid((unsigned)W);
   PH_TRY(dispatch(dtype, lds_window, [&](auto t, auto lw) {
     using T = decltype(t);
-    auto kernel = ph::k_fold_sums<T, decltype(lw)::value>;
-    PH_TRY(allow_lds(kernel, lds));
-    ProfScope ps_(c, "k_fold_sums");
-    hipLaunchKernelGGL(kernel, grid, dim3(pl.k[0].block), lds, c->stream, (const T*)dx, N, d_p, d_keep, d_off, n_p, stride,
-                       (double*)dout);
-    return (int)PH_OK;
+    return launch(c, "k_fold_sums", ph::k_fold_sums<T, decltype(lw)::value>, grid, pl.k[0].block, lds, (const T*)dx, N, d_p,
+                  d_keep, d_off, n_p, stride, (double*)dout);
   }));
-  PH_TRY(launch_check("k_fold_sums"));
   return st.finish();
 }
 
@@ -2019,22 +2059,11 @@ int ph_tile_sum(ph_ctx* c, const double* wts, int64_t W, int N, const int32_t* p
   PH_TRY(st.in(wts, (size_t)W * stride * sizeof(double), &dw));
   PH_TRY(st.out(B_OUT0, out, (size_t)W * N * sz, &dout));
   const dim3 grid((unsigned)W);
-  if (dtype == PH_F64) {
-    PH_TRY(allow_lds(ph::k_tile_sum<double>, lds));
-    {
-      ProfScope ps_(c, "k_tile_sum");
-      hipLaunchKernelGGL(ph::k_tile_sum<double>, grid, dim3(kBlock), lds, c->stream, (const double*)dw, N, d_p,
-                         d_keep, d_off, n_p, stride, (double*)dout);
-    }
-  } else {
-    PH_TRY(allow_lds(ph::k_tile_sum<float>, lds));
-    {
-      ProfScope ps_(c, "k_tile_sum");
-      hipLaunchKernelGGL(ph::k_tile_sum<float>, grid, dim3(kBlock), lds, c->stream, (const double*)dw, N, d_p,
-                         d_keep, d_off, n_p, stride, (float*)dout);
-    }
-  }
-  PH_TRY(launch_check("k_tile_sum"));
+  PH_TRY(dispatch(dtype, [&](auto t) {
+    using T = decltype(t);
+    return launch(c, "k_tile_sum", ph::k_tile_sum<T>, grid, kBlock, lds, (const double*)dw, N, d_p, d_keep, d_off, n_p, stride,
+                  (T*)dout);
+  }));
   return st.finish();
 }
 
@@ -2052,19 +2081,10 @@ int ph_periodic_norm(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int 
   PH_TRY(st.in(x, (size_t)W * N * sz, &dx));
   PH_TRY(st.out(B_OUT0, out, (size_t)W * sizeof(double), &dout));
   const dim3 grid((unsigned)W);
-  if (dtype == PH_F64)
-    {
-      ProfScope ps_(c, "k_periodic_norm");
-      hipLaunchKernelGGL(ph::k_periodic_norm<double>, grid, dim3(kBlock), 0, c->stream, (const double*)dx, N, p,
-                         (double*)dout);
-    }
-  else
-    {
-      ProfScope ps_(c, "k_periodic_norm");
-      hipLaunchKernelGGL(ph::k_periodic_norm<float>, grid, dim3(kBlock), 0, c->stream, (const float*)dx, N, p,
-                         (double*)dout);
-    }
-  PH_TRY(launch_check("k_periodic_norm"));
+  PH_TRY(dispatch(dtype, [&](auto t) {
+    using T = decltype(t);
+    return launch(c, "k_periodic_norm", ph::k_periodic_norm<T>, grid, kBlock, 0, (const T*)dx, N, p, (double*)dout);
+  }));
   return st.finish();
 }
 
@@ -2087,11 +2107,7 @@ int ph_dict_project(ph_ctx* c, const double* x, const double* basis, int rows, i
     db = (const double*)c->buf[B_WS1].p;
     dout = (float*)c->buf[B_OUT0].p;
   }
-  {
-    ProfScope ps_(c, "k_dict_project");
-    hipLaunchKernelGGL(ph::k_dict_project, dim3((unsigned)rows), dim3(kBlock), 0, c->stream, dx, db, N, dout);
-  }
-  PH_TRY(launch_check("k_dict_project"));
+  PH_TRY(launch(c, "k_dict_project", ph::k_dict_project, dim3((unsigned)rows), kBlock, 0, dx, db, N, dout));
   if (!device) {
     PH_HIP(hipMemcpyAsync(out, dout, (size_t)rows * N * 4, hipMemcpyDeviceToHost, c->stream));
     PH_HIP(hipStreamSynchronize(c->stream));
@@ -2162,23 +2178,15 @@ static int qo_find_run(ph_ctx* c, const void* x, int dtype, int64_t W, int N, co
     if (keep_weights) {
       auto kernel = window ? (trunc ? ph::k_qo_greedy<T, LW, true, true> : ph::k_qo_greedy<T, LW, false, true>)
                            : (trunc ? ph::k_qo_greedy<T, LW, true> : ph::k_qo_greedy<T, LW, false>);
-      PH_TRY(allow_lds(kernel, lds));
-      ProfScope ps_(c, name);
-      hipLaunchKernelGGL(kernel, grid, dim3(c->qo_block), lds, c->stream, (const T*)dx, N, num, thresh, min_length,
-                         max_length, geom, plan, n_pass, d_phi, d_off, d_dq, kcap, (T*)gwin,
-                         (uint32_t*)c->buf[B_WS1].p, (uint32_t*)dper,
-                         (double*)dnrm, (int*)dkeep, (int*)dcnt, (double*)dwts, (T*)dres, (int*)dstat, (const double*)dwin);
-      return (int)PH_OK;
+      return launch(c, name, kernel, grid, c->qo_block, lds, (const T*)dx, N, num, thresh, min_length, max_length, geom, plan,
+                    n_pass, d_phi, d_off, d_dq, kcap, (T*)gwin, (uint32_t*)c->buf[B_WS1].p, (uint32_t*)dper, (double*)dnrm,
+                    (int*)dkeep, (int*)dcnt, (double*)dwts, (T*)dres, (int*)dstat, (const double*)dwin);
     }
     auto kernel = trunc ? ph::k_qo_find<T, LW, true> : ph::k_qo_find<T, LW>;
-    PH_TRY(allow_lds(kernel, lds));
-    ProfScope ps_(c, name);
-    hipLaunchKernelGGL(kernel, grid, dim3(c->qo_block), lds, c->stream, (const T*)dx, N, num, thresh, min_length,
-                       max_length, geom, plan, n_pass, d_phi, d_off, d_dq, kcap, overlay ? 1 : 0, (T*)gwin, (double*)c->buf[B_WS1].p,
-                       (uint32_t*)dper, (double*)dnrm, (int*)dkeep, (int*)dcnt, (double*)dwts, (T*)dres, (int*)dstat);
-    return (int)PH_OK;
+    return launch(c, name, kernel, grid, c->qo_block, lds, (const T*)dx, N, num, thresh, min_length, max_length, geom, plan,
+                  n_pass, d_phi, d_off, d_dq, kcap, overlay ? 1 : 0, (T*)gwin, (double*)c->buf[B_WS1].p, (uint32_t*)dper,
+                  (double*)dnrm, (int*)dkeep, (int*)dcnt, (double*)dwts, (T*)dres, (int*)dstat);
   }));
-  PH_TRY(launch_check(name));
   return st.finish();
 }
 
@@ -2248,19 +2256,11 @@ static int fit_enqueue(ph_ctx* c, const FitLaunch& fl, int dtype, int64_t W, int
                        void* dres, void* dstat) {
   const KernelPlan& k = fl.pl.k[0];
   const dim3 grid((unsigned)W);
-  ProfScope ps_(c, "k_qo_fit");
-  if (dtype == PH_F64) {
-    PH_TRY(allow_lds(ph::k_qo_fit<double>, k.lds));
-    hipLaunchKernelGGL(ph::k_qo_fit<double>, grid, dim3(k.block), k.lds, c->stream, (const double*)dx, N, dper, dnper, pcap,
-                       per_stride, max_period, fl.d_phi, fl.d_off, fl.d_dq, kcap, (int*)dkeep, (double*)dwts, (double*)dres,
-                       (int*)dstat);
-  } else {
-    PH_TRY(allow_lds(ph::k_qo_fit<float>, k.lds));
-    hipLaunchKernelGGL(ph::k_qo_fit<float>, grid, dim3(k.block), k.lds, c->stream, (const float*)dx, N, dper, dnper, pcap,
-                       per_stride, max_period, fl.d_phi, fl.d_off, fl.d_dq, kcap, (int*)dkeep, (double*)dwts, (float*)dres,
-                       (int*)dstat);
-  }
-  return launch_check("k_qo_fit");
+  return dispatch(dtype, [&](auto t) {
+    using T = decltype(t);
+    return launch(c, "k_qo_fit", ph::k_qo_fit<T>, grid, k.block, k.lds, (const T*)dx, N, dper, dnper, pcap, per_stride,
+                  max_period, fl.d_phi, fl.d_off, fl.d_dq, kcap, (int*)dkeep, (double*)dwts, (T*)dres, (int*)dstat);
+  });
 }
 
 // k_qo_fit_win: `dwin` the analysis window on the device, `dws` the HBM workspace of u (nullptr when the plan keeps u in LDS)
@@ -2269,16 +2269,12 @@ static int fit_win_enqueue(ph_ctx* c, const FitLaunch& fl, int dtype, int64_t W,
                            double* dws, void* dkeep, void* dwts, void* dres, void* dstat) {
   const KernelPlan& k = fl.pl.k[0];
   const dim3 grid((unsigned)W);
-  PH_TRY(dispatch(dtype, k.second == PH_PLAN_LDS, [&](auto t, auto ul) {
+  return dispatch(dtype, k.second == PH_PLAN_LDS, [&](auto t, auto ul) {
     using T = decltype(t);
-    auto kernel = ph::k_qo_fit_win<T, decltype(ul)::value>;
-    PH_TRY(allow_lds(kernel, k.lds));
-    ProfScope ps_(c, "k_qo_fit_win");
-    hipLaunchKernelGGL(kernel, grid, dim3(k.block), k.lds, c->stream, (const T*)dx, N, dwin, dper, dnper, pcap, per_stride,
-                       max_period, fl.d_phi, fl.d_off, fl.d_dq, kcap, dws, (int*)dkeep, (double*)dwts, (T*)dres, (int*)dstat);
-    return (int)PH_OK;
-  }));
-  return launch_check("k_qo_fit_win");
+    return launch(c, "k_qo_fit_win", ph::k_qo_fit_win<T, decltype(ul)::value>, grid, k.block, k.lds, (const T*)dx, N, dwin,
+                  dper, dnper, pcap, per_stride, max_period, fl.d_phi, fl.d_off, fl.d_dq, kcap, dws, (int*)dkeep,
+                  (double*)dwts, (T*)dres, (int*)dstat);
+  });
 }
 
 // ph_qo_fit (window == nullptr) and ph_qo_fit_win: one set of argument checks, tables and staging
@@ -2339,12 +2335,11 @@ int ph_ramanujan_fit(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int 
   PH_TRY(check_common(c, x, dtype, W, N));
   if (!norms || !periods || !counts || !keeps || !weights || !residual || !status)
     return fail(PH_E_ARG, "output pointer is NULL");
-  if (q_lo < 1 || q_hi < 1) return fail(PH_E_ARG, "need q_lo, q_hi >= 1 (got %d, %d)", q_lo, q_hi);
   PH_HIP(hipSetDevice(c->device));
-  FitLaunch fl;
-  PH_TRY(fit_prepare(c, N, false, pcap, q_hi, kcap, &fl));
   RamLaunch rl;
   PH_TRY(ram_prepare(c, dtype, W, N, q_lo, q_hi, &rl));
+  FitLaunch fl;
+  PH_TRY(fit_prepare(c, N, false, pcap, q_hi, kcap, &fl));
   const size_t sz = elem_size(dtype);
   Stage st(c, flags);
   const void* dx;
@@ -2359,12 +2354,8 @@ int ph_ramanujan_fit(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int 
   PH_TRY(st.out(B_GEN0, status, (size_t)W * sizeof(int32_t), &dstat));
   // three launches on the context's stream, no host round trip between them
   PH_TRY(ram_enqueue(c, rl, dtype, W, N, q_hi, dx, dnrm));
-  {
-    ProfScope ps_(c, "k_ram_select");
-    hipLaunchKernelGGL(ph::k_ram_select, dim3((unsigned)W), dim3(ph::kWave), 0, c->stream, (const double*)dnrm, q_hi, thresh,
-                       pcap, (int*)dper, (int*)dcnt);
-  }
-  PH_TRY(launch_check("k_ram_select"));
+  PH_TRY(launch(c, "k_ram_select", ph::k_ram_select, dim3((unsigned)W), ph::kWave, 0, (const double*)dnrm, q_hi, thresh, pcap,
+                (int*)dper, (int*)dcnt));
   PH_TRY(fit_enqueue(c, fl, dtype, W, N, dx, (const int*)dper, (const int*)dcnt, pcap, pcap, q_hi, kcap, dkeep, dwts, dres,
                      dstat));
   return st.finish();
@@ -2375,12 +2366,10 @@ int ph_orth_powers(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int ma
                    unsigned flags, double* autocorr, double* eq3, double* powers) {
   PH_TRY(check_common(c, x, dtype, W, N));
   if (!powers) return fail(PH_E_ARG, "powers is NULL");
-  if (max_p < 0) max_p = N / 2;  // QOPeriods.py:1204-1207
-  if (max_p < 2) return fail(PH_E_ARG, "max_p=%d must be >= 2", max_p);
+  Plan pl;
+  PH_TRY(resolve_orth_powers(c, dtype, N, &max_p, &pl));
   PH_HIP(hipSetDevice(c->device));
   const size_t sz = elem_size(dtype);
-  Plan pl;
-  plan_orth_powers(c, dtype, N, max_p, &pl);
   const bool lds_window = pl.k[0].window == PH_PLAN_LDS;
   const size_t lds = pl.k[0].lds;
   void* gws;
@@ -2397,14 +2386,9 @@ int ph_orth_powers(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int ma
   const dim3 grid((unsigned)W);
   PH_TRY(dispatch(dtype, lds_window, [&](auto t, auto lw) {
     using T = decltype(t);
-    auto kernel = ph::k_orth_powers<T, decltype(lw)::value>;
-    PH_TRY(allow_lds(kernel, lds));
-    ProfScope ps_(c, "k_orth_powers");
-    hipLaunchKernelGGL(kernel, grid, dim3(pl.k[0].block), lds, c->stream, (const T*)dx, N, max_p, normalize, d_off, d_d, d_mu,
-                       (double*)gws, (double*)dr, (double*)de, (double*)dp);
-    return (int)PH_OK;
+    return launch(c, "k_orth_powers", ph::k_orth_powers<T, decltype(lw)::value>, grid, pl.k[0].block, lds, (const T*)dx, N,
+                  max_p, normalize, d_off, d_d, d_mu, (double*)gws, (double*)dr, (double*)de, (double*)dp);
   }));
-  PH_TRY(launch_check("k_orth_powers"));
   return st.finish();
 }
 
@@ -2440,14 +2424,10 @@ int ph_qo_orth_select(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int
   const dim3 grid((unsigned)W);
   PH_TRY(dispatch(dtype, lds_window, [&](auto t, auto lw) {
     using T = decltype(t);
-    auto kernel = ph::k_qo_orth_select<T, decltype(lw)::value>;
-    PH_TRY(allow_lds(kernel, lds));
-    ProfScope ps_(c, "k_qo_orth_select");
-    hipLaunchKernelGGL(kernel, grid, dim3(pl.k[0].block), lds, c->stream, (const T*)dx, N, max_p, kflags, tb, d_off, d_d,
-                       d_mu, (double*)gws, (int*)dper, (double*)dnrm, (double*)dpow, (int*)dstat);
-    return (int)PH_OK;
+    return launch(c, "k_qo_orth_select", ph::k_qo_orth_select<T, decltype(lw)::value>, grid, pl.k[0].block, lds,
+                  (const T*)dx, N, max_p, kflags, tb, d_off, d_d, d_mu, (double*)gws, (int*)dper, (double*)dnrm, (double*)dpow,
+                  (int*)dstat);
   }));
-  PH_TRY(launch_check("k_qo_orth_select"));
   return st.finish();
 }
 
@@ -2480,17 +2460,12 @@ int ph_qo_get_periods(ph_ctx* c, const int32_t* periods, const int32_t* rows, co
   PH_TRY(st.out(B_OUT0, out, (size_t)W * ccap * sizeof(double), &dout));
   PH_TRY(st.out(B_GEN0, status, (size_t)W * sizeof(int32_t), &dstat));
   const dim3 grid((unsigned)W);
-  auto launch = [&](auto wl) {
-    auto kernel = ph::k_qo_extract<decltype(wl)::value>;
-    PH_TRY(allow_lds(kernel, k.lds));
-    ProfScope ps_(c, "k_qo_extract");
-    hipLaunchKernelGGL(kernel, grid, dim3(k.block), k.lds, c->stream, (const int*)dper, (const int*)drow, (const int*)dcnt, pcap,
-                       (const double*)dwts, kcap, max_period, ccap, d_off, d_d, d_mu, (int*)gidx, (double*)gws, (double*)dout,
-                       (int*)dstat);
-    return (int)PH_OK;
+  auto extract = [&](auto wl) {
+    return launch(c, "k_qo_extract", ph::k_qo_extract<decltype(wl)::value>, grid, k.block, k.lds, (const int*)dper,
+                  (const int*)drow, (const int*)dcnt, pcap, (const double*)dwts, kcap, max_period, ccap, d_off, d_d, d_mu,
+                  (int*)gidx, (double*)gws, (double*)dout, (int*)dstat);
   };
-  PH_TRY(k.second == PH_PLAN_LDS ? launch(std::true_type{}) : launch(std::false_type{}));
-  PH_TRY(launch_check("k_qo_extract"));
+  PH_TRY(k.second == PH_PLAN_LDS ? extract(std::true_type{}) : extract(std::false_type{}));
   return st.finish();
 }
 
@@ -2559,16 +2534,14 @@ unsigned flat_grid(const ph_ctx* c, int64_t items) {
 }
 
 template <typename Tin, typename Tout>
-void launch_frames(ph_ctx* c, const void* ds, int64_t L, int N, int hop, int64_t W, const double* dwin, void* dout) {
+int launch_frames(ph_ctx* c, const void* ds, int64_t L, int N, int hop, int64_t W, const double* dwin, void* dout) {
   constexpr int V = 16 / (int)sizeof(Tout);
   const int64_t total = W * (int64_t)N;
-  ProfScope ps_(c, "k_frames");
   if (reinterpret_cast<uintptr_t>(dout) % 16 == 0)
-    hipLaunchKernelGGL((ph::k_frames<Tin, Tout, V>), dim3(flat_grid(c, total / V)),
-                       dim3(ph::kFramesBlock), 0, c->stream, (const Tin*)ds, L, N, hop, W, dwin, (Tout*)dout);
-  else
-    hipLaunchKernelGGL((ph::k_frames<Tin, Tout, 1>), dim3(flat_grid(c, total)), dim3(ph::kFramesBlock), 0, c->stream,
-                       (const Tin*)ds, L, N, hop, W, dwin, (Tout*)dout);
+    return launch(c, "k_frames", ph::k_frames<Tin, Tout, V>, dim3(flat_grid(c, total / V)), ph::kFramesBlock, 0,
+                  (const Tin*)ds, L, N, hop, W, dwin, (Tout*)dout);
+  return launch(c, "k_frames", ph::k_frames<Tin, Tout, 1>, dim3(flat_grid(c, total)), ph::kFramesBlock, 0, (const Tin*)ds, L,
+                N, hop, W, dwin, (Tout*)dout);
 }
 
 }  // namespace
@@ -2591,15 +2564,11 @@ int ph_frames(ph_ctx* c, const void* signal, int in_dtype, int64_t L, int N, int
   PH_TRY(st.in(signal, (size_t)L * elem_size(in_dtype), &ds));  // the signal once: L elements, not W * N
   if (window) PH_TRY(st.in(window, (size_t)N * sizeof(double), &dwin, B_GWIN));
   PH_TRY(st.out(B_OUT0, frames, (size_t)W * N * elem_size(out_dtype), &dout));
-  if (in_dtype == PH_F64 && out_dtype == PH_F64)
-    launch_frames<double, double>(c, ds, L, N, hop, W, (const double*)dwin, dout);
-  else if (in_dtype == PH_F64)
-    launch_frames<double, float>(c, ds, L, N, hop, W, (const double*)dwin, dout);
-  else if (out_dtype == PH_F64)
-    launch_frames<float, double>(c, ds, L, N, hop, W, (const double*)dwin, dout);
-  else
-    launch_frames<float, float>(c, ds, L, N, hop, W, (const double*)dwin, dout);
-  PH_TRY(launch_check("k_frames"));
+  PH_TRY(dispatch(in_dtype, [&](auto ti) {
+    return dispatch(out_dtype, [&](auto to) {
+      return launch_frames<decltype(ti), decltype(to)>(c, ds, L, N, hop, W, (const double*)dwin, dout);
+    });
+  }));
   return st.finish();
 }
 
@@ -2619,16 +2588,11 @@ int ph_overlap_add(ph_ctx* c, const void* y, int dtype, int64_t W, int K, int N,
   PH_TRY(sd.stage(st, flags, W, N, counts, nullptr, 0, win_a, win_s));
   PH_TRY(st.out(B_OUT0, out, (size_t)L * sizeof(double), &dout));
   const dim3 grid(flat_grid(c, L));
-  {
-    ProfScope ps_(c, "k_overlap_add");
-    if (dtype == PH_F64)
-      hipLaunchKernelGGL(ph::k_overlap_add<double>, grid, dim3(ph::kFramesBlock), 0, c->stream, (const double*)dy, W, K, N,
-                         hop, L, sd.counts, sd.wa, sd.ws, sd.norm, (double*)dout);
-    else
-      hipLaunchKernelGGL(ph::k_overlap_add<float>, grid, dim3(ph::kFramesBlock), 0, c->stream, (const float*)dy, W, K, N,
-                         hop, L, sd.counts, sd.wa, sd.ws, sd.norm, (double*)dout);
-  }
-  PH_TRY(launch_check("k_overlap_add"));
+  PH_TRY(dispatch(dtype, [&](auto t) {
+    using T = decltype(t);
+    return launch(c, "k_overlap_add", ph::k_overlap_add<T>, grid, ph::kFramesBlock, 0, (const T*)dy, W, K, N, hop, L, sd.counts,
+                  sd.wa, sd.ws, sd.norm, (double*)dout);
+  }));
   return st.finish();
 }
 
@@ -2652,16 +2616,11 @@ int ph_overlap_add_tracks(ph_ctx* c, const void* y, int dtype, int64_t W, int K,
   PH_TRY(sd.stage(st, flags, W, N, counts, masks, T, win_a, win_s));
   PH_TRY(st.out(B_OUT0, out, (size_t)T * L * sizeof(double), &dout));
   const dim3 grid(flat_grid(c, T * L));
-  {
-    ProfScope ps_(c, "k_overlap_add_tracks");
-    if (dtype == PH_F64)
-      hipLaunchKernelGGL(ph::k_overlap_add_tracks<double>, grid, dim3(ph::kFramesBlock), 0, c->stream, (const double*)dy, W,
-                         K, N, hop, L, sd.counts, sd.masks, T, sd.wa, sd.ws, sd.norm, (double*)dout);
-    else
-      hipLaunchKernelGGL(ph::k_overlap_add_tracks<float>, grid, dim3(ph::kFramesBlock), 0, c->stream, (const float*)dy, W,
-                         K, N, hop, L, sd.counts, sd.masks, T, sd.wa, sd.ws, sd.norm, (double*)dout);
-  }
-  PH_TRY(launch_check("k_overlap_add_tracks"));
+  PH_TRY(dispatch(dtype, [&](auto t) {
+    using E = decltype(t);
+    return launch(c, "k_overlap_add_tracks", ph::k_overlap_add_tracks<E>, grid, ph::kFramesBlock, 0, (const E*)dy, W, K, N,
+                  hop, L, sd.counts, sd.masks, T, sd.wa, sd.ws, sd.norm, (double*)dout);
+  }));
   return st.finish();
 }
 
@@ -2689,13 +2648,8 @@ int ph_overlap_add_periodic(ph_ctx* c, const double* seg, const int32_t* periods
   PH_TRY(sd.stage(st, flags, W, N, counts, masks, T, win_a, win_s));
   PH_TRY(st.out(B_OUT0, out, (size_t)T * L * sizeof(double), &dout));
   const dim3 grid(flat_grid(c, T * L));
-  {
-    ProfScope ps_(c, "k_overlap_add_periodic");
-    hipLaunchKernelGGL(ph::k_overlap_add_periodic, grid, dim3(ph::kFramesBlock), 0, c->stream, (const double*)dseg,
-                       (const int*)dper, sd.counts, sd.masks, W, pcap, ccap, T, N, hop, L, sd.wa, sd.ws, sd.norm,
-                       (double*)dout);
-  }
-  PH_TRY(launch_check("k_overlap_add_periodic"));
+  PH_TRY(launch(c, "k_overlap_add_periodic", ph::k_overlap_add_periodic, grid, ph::kFramesBlock, 0, (const double*)dseg,
+                (const int*)dper, sd.counts, sd.masks, W, pcap, ccap, T, N, hop, L, sd.wa, sd.ws, sd.norm, (double*)dout));
   return st.finish();
 }
 

@@ -258,12 +258,16 @@ class PeriodEngine:
         _ffi.check(self._lib.ph_sweep_plan_info(self._ctx, int(p_lo), int(p_hi), C.byref(n_pass), C.byref(n_per)))
         return n_pass.value, n_per.value
 
+    def _m_best_query(self, n, num, max_length, min_length, dtype, trunc, orth):
+        """The arguments the three ph_m_best_*_info queries share (a missing max_length: the library's default)."""
+        return (self._ctx, _NP_DTYPES[np.dtype(dtype)], int(n), int(num), int(min_length),
+                -1 if max_length is None else int(max_length), self._flags(trunc, orth))
+
     def m_best_info(self, n, num=5, max_length=None, min_length=2, dtype=np.float64, trunc=False, orth=False):
         """(windows per workgroup, LDS bytes per sample and workgroup) of the step-1 kernel m_best would run:
         (2, 8) for the window-pair float screen, (1, itemsize) for the one-window fold."""
         wpw, bps = C.c_int(0), C.c_int(0)
-        _ffi.check(self._lib.ph_m_best_info(self._ctx, _NP_DTYPES[np.dtype(dtype)], int(n), int(num), int(min_length),
-                                            int(n // 3 if max_length is None else max_length), self._flags(trunc, orth),
+        _ffi.check(self._lib.ph_m_best_info(*self._m_best_query(n, num, max_length, min_length, dtype, trunc, orth),
                                             C.byref(wpw), C.byref(bps)))
         return wpw.value, bps.value
 
@@ -271,9 +275,8 @@ class PeriodEngine:
         """(passes, periods) of one sweep of the step-1 kernel m_best would run (the window-pair kernel takes the
         periods up to 64 in chains, so it needs fewer passes than sweep_plan_info reports for the fp64 sweeps)."""
         n_pass, n_per = C.c_int(0), C.c_int(0)
-        _ffi.check(self._lib.ph_m_best_plan_info(self._ctx, _NP_DTYPES[np.dtype(dtype)], int(n), int(num), int(min_length),
-                                                 int(n // 3 if max_length is None else max_length),
-                                                 self._flags(trunc, orth), C.byref(n_pass), C.byref(n_per)))
+        _ffi.check(self._lib.ph_m_best_plan_info(*self._m_best_query(n, num, max_length, min_length, dtype, trunc, orth),
+                                                 C.byref(n_pass), C.byref(n_per)))
         return n_pass.value, n_per.value
 
     def m_best_screen_info(self, n, num=5, max_length=None, min_length=2, gamma=False, dtype=np.float64, trunc=False,
@@ -282,10 +285,8 @@ class PeriodEngine:
         (gamma: m_best_gamma) would run.  The window-pair kernel folds p and p + 64 from one set of loads where it can,
         so it has fewer entries than periods (PH_PAIR_DUO=0: one pass per period)."""
         n_ent, n_scr, elems = C.c_int(0), C.c_int(0), C.c_longlong(0)
-        _ffi.check(self._lib.ph_m_best_screen_info(self._ctx, _NP_DTYPES[np.dtype(dtype)], int(n), int(num), int(min_length),
-                                                   int(n // 3 if max_length is None else max_length),
-                                                   self._flags(trunc, orth), int(bool(gamma)), C.byref(n_ent),
-                                                   C.byref(n_scr), C.byref(elems)))
+        _ffi.check(self._lib.ph_m_best_screen_info(*self._m_best_query(n, num, max_length, min_length, dtype, trunc, orth),
+                                                   int(bool(gamma)), C.byref(n_ent), C.byref(n_scr), C.byref(elems)))
         return n_ent.value, n_scr.value, elems.value
 
     def m_best(self, x, num=5, max_length=None, min_length=2, gamma=False, trunc=False, orth=False, want_sweeps=False):

@@ -162,6 +162,67 @@ static void plan_checks(ph_ctx* c) {
   }
 }
 
+static void expect_eq(long long got, long long want, const char* what, int line) {
+  if (got != want) {
+    std::printf("FAIL line %d: %s is %lld, want %lld\n", line, what, got, want);
+    ++fails;
+  }
+}
+
+// A context created under PH_HBM_WINDOW=1 keeps every window in HBM, so its m_best runs the one-window step 1 where a
+// default context runs the window pair: the plan record, the ph_m_best_*_info queries and the launch all have to say so.
+// The screen of that kernel is the one a context under PH_STEP1_PAIR=0 reports.
+static void hbm_window_checks() {
+  ph_ctx *hbm = nullptr, *one = nullptr;
+  setenv("PH_HBM_WINDOW", "1", 1);
+  EXPECT(ph_create(0, &hbm), PH_OK);
+  unsetenv("PH_HBM_WINDOW");
+  setenv("PH_STEP1_PAIR", "0", 1);
+  EXPECT(ph_create(0, &one), PH_OK);
+  unsetenv("PH_STEP1_PAIR");
+  const int N = 4096, num = 10, max_len = N / 3;
+  int32_t rec[PH_PLAN_LEN];
+  const int32_t prm[3] = {num, 2, -1};
+  EXPECT(ph_plan_info(hbm, PH_OP_M_BEST, PH_F64, N, prm, 3, 0, rec), PH_OK);
+  expect_eq(rec[PH_PLAN_K0 + PH_PLAN_VARIANT], PH_PLAN_ONE, "step-1 variant under PH_HBM_WINDOW", __LINE__);
+  expect_eq(rec[PH_PLAN_K0 + PH_PLAN_WINDOW], PH_PLAN_HBM, "step-1 window under PH_HBM_WINDOW", __LINE__);
+  int wpw = 0, bps = 0;
+  EXPECT(ph_m_best_info(hbm, PH_F64, N, num, 2, -1, 0, &wpw, &bps), PH_OK);
+  expect_eq(wpw, 1, "windows per workgroup under PH_HBM_WINDOW", __LINE__);
+  expect_eq(bps, 8, "LDS bytes per sample under PH_HBM_WINDOW", __LINE__);
+  for (int gamma : {0, 1}) {
+    int ent[2] = {0, 0}, scr[2] = {0, 0};
+    long long el[2] = {0, 0};
+    EXPECT(ph_m_best_screen_info(hbm, PH_F64, N, num, 2, -1, 0, gamma, &ent[0], &scr[0], &el[0]), PH_OK);
+    EXPECT(ph_m_best_screen_info(one, PH_F64, N, num, 2, -1, 0, gamma, &ent[1], &scr[1], &el[1]), PH_OK);
+    expect_eq(ent[0], ent[1], "screen entries under PH_HBM_WINDOW", __LINE__);
+    expect_eq(scr[0], scr[1], "screened periods under PH_HBM_WINDOW", __LINE__);
+    expect_eq(el[0], el[1], "screen LDS elements under PH_HBM_WINDOW", __LINE__);
+    expect_eq(scr[0], max_len - 1, "screened periods of the one-window kernel", __LINE__);
+  }
+  int np[2] = {0, 0}, nq[2] = {0, 0};
+  EXPECT(ph_m_best_plan_info(hbm, PH_F64, N, num, 2, -1, 0, &np[0], &nq[0]), PH_OK);
+  EXPECT(ph_m_best_plan_info(one, PH_F64, N, num, 2, -1, 0, &np[1], &nq[1]), PH_OK);
+  expect_eq(np[0], np[1], "plan passes under PH_HBM_WINDOW", __LINE__);
+  const Csr fac = factor_tables(max_len);
+  std::vector<double> x((size_t)N), pw(num), bases((size_t)num * N);
+  for (int i = 0; i < N; ++i) x[i] = std::sin(0.37 * i) + 0.25 * std::sin(0.05 * i);
+  std::vector<uint32_t> per(num);
+  std::vector<int32_t> st(1);
+  expect_plan(hbm, PH_OP_M_BEST, PH_F64, N, {num, 2, -1}, 0, __LINE__, [&] {
+    return ph_m_best(hbm, x.data(), PH_F64, 1, N, num, 2, -1, 0, nullptr, nullptr, fac.off.data(), fac.q.data(), max_len, 0,
+                     per.data(), pw.data(), bases.data(), st.data(), nullptr);
+  });
+  // the query refuses the lengths its siblings and the launch refuse, and says which
+  EXPECT(ph_m_best_info(one, PH_F64, N, num, 5, 4, 0, &wpw, &bps), PH_E_ARG);
+  said("min_length", __LINE__);
+  said("max_length", __LINE__);
+  said("5, 4", __LINE__);
+  EXPECT(ph_m_best_info(one, PH_F64, N, num, 0, 4, 0, &wpw, &bps), PH_E_ARG);
+  EXPECT(ph_destroy(hbm), PH_OK);
+  EXPECT(ph_destroy(one), PH_OK);
+}
+
 int main() {
   ph_ctx* c = nullptr;
   int n = 0;
@@ -283,6 +344,7 @@ int main() {
     EXPECT(ph_sweep(c, x.data(), PH_F64, 0, N, 2, 3, 0, nullptr, nullptr, 0, 0, out.data()), PH_E_ARG);
   }
   plan_checks(c);
+  hbm_window_checks();
   float ms[300];
   int cntp = 0;
   EXPECT(ph_profile_read(c, ms, 300, &cntp), PH_OK);

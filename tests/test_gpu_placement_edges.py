@@ -827,6 +827,14 @@ def test_max_window_is_the_sweep_switch(engines):
     assert engines["hbm"].max_window() == 0
 
 
+def test_m_best_queries_report_the_kernel_that_runs(engines):
+    """Host only: with every window in HBM m_best runs the one-window step 1, and the info query says so as the plan does
+    (a default engine answers (2, 8) and PH_PLAN_PAIR for the same arguments)."""
+    hbm = engines["hbm"]
+    assert hbm.m_best_info(4096, 10) == (1, 8)
+    assert hbm.plan_info("m_best", 4096, (10, 2, -1))[0].variant == _ffi().PH_PLAN_ONE
+
+
 def _bf_variant(eng, n, L, dtype=np.float64):
     return plan_of(eng, "best_frequency", n, (L,), dtype, "plain")[0].variant
 

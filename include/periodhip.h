@@ -183,7 +183,11 @@ int ph_sweep(ph_ctx* ctx, const void* x, int dtype, int64_t W, int N, int p_lo, 
  * get_factors(p, remove_1_and_n=True) at Periods.py:548-549.  Pass max_length < 0 for the
  * reference default floor(N/3).  With gamma = 0 step 1 of fp64 windows reads the same table to find the divisors
  * of the periods that survive its screen (ph_m_best_plan_info), so it must list EVERY proper divisor; with
- * gamma = 1 (m_best_gamma) the screen runs the full plan over every period and step 1 does not read it. */
+ * gamma = 1 (m_best_gamma) the screen runs the full plan over every period and step 1 does not read it.
+ * min_length = 1 offers period 1, whose row of fac_off is empty: a window that keeps it is returned PH_ST_OK with
+ * its numbers, while the reference dies there (get_factors(1, remove_1_and_n=True), KeyError at Periods.py:548).
+ * A caller that wants the reference's behaviour treats a PH_ST_OK row whose periods hold a 1 as failed; the Python
+ * engine does so (PeriodEngine.m_best sets such rows to PH_ST_NO_PERIOD, Periods raises KeyError). */
 int ph_m_best(ph_ctx* ctx, const void* x, int dtype, int64_t W, int N, int num,
               int min_length, int max_length, int gamma,
               const int32_t* orth_off, const int32_t* orth_q,

@@ -167,8 +167,11 @@ def sweep_maxabs(data, p_lo, p_hi) -> np.ndarray:
 # --------------------------------------------------------------------------------------
 
 
-def small_to_large(data, thresh=0.1, n_periods=None, trunc=False, orth=False):
+def small_to_large(data, thresh=0.1, n_periods=None, trunc=False, orth=False, trace=None):
+    """`trace` (a dict, test tooling only) receives under "min_margin" the smallest |imposed - thresh| / thresh over all
+    p (1.0 when no p gives a finite value): how far the closest accept/reject decision is from flipping."""
     periods, powers, bases = [], [], []
+    margin = 1.0
     data_norm = periodic_norm(data)  # :269
     residual = data.copy()
     if n_periods is None:
@@ -177,11 +180,15 @@ def small_to_large(data, thresh=0.1, n_periods=None, trunc=False, orth=False):
         base = project(residual, p, trunc, orth)
         trial = residual - base
         imposed = (periodic_norm(residual) - periodic_norm(trial)) / data_norm  # :278-280
+        if trace is not None and imposed == imposed and thresh:
+            margin = min(margin, abs(imposed - thresh) / abs(thresh))
         if imposed > thresh:  # strict, :281
             residual = trial
             periods.append(p)
             powers.append(imposed)
             bases.append(base)
+    if trace is not None:
+        trace["min_margin"] = float(margin)
     return periods, powers, bases
 
 
@@ -190,7 +197,9 @@ def small_to_large(data, thresh=0.1, n_periods=None, trunc=False, orth=False):
 # --------------------------------------------------------------------------------------
 
 
-def best_correlation(data, num=5, max_length=None, ratio=0.01, trunc=False, orth=False):
+def best_correlation(data, num=5, max_length=None, ratio=0.01, trunc=False, orth=False, trace=None):
+    """`trace` (a list, test tooling only) receives per round (lead, gap, best): the relative lead of the winning
+    max|S_p[s]| over the best other period, |gain - ratio|, and the winning value itself."""
     n = len(data)
     if max_length is None:
         max_length = n // 3
@@ -202,15 +211,20 @@ def best_correlation(data, num=5, max_length=None, ratio=0.01, trunc=False, orth
     work = data.copy()
     for i in range(num):
         best_cor, best_p = 0, None
+        second = 0.0  # test tooling (trace) only
         for p in range(2, max_length):  # EXCLUSIVE upper bound, :324
             col = np.abs(fold_sums(work, p))
             s = int(np.argmax(col))  # first maximum == strict '>' scan over s, :327-331
             if col[s] > best_cor:
-                best_cor, best_p = col[s], p
+                best_cor, best_p, second = col[s], p, best_cor
+            elif col[s] > second:
+                second = col[s]
         base = project(work, best_p, trunc, orth)  # :334-339
         work = work - base  # unconditional, :340
         this_norm = periodic_norm(work)
         gain = (old_norm - this_norm) / og_norm
+        if trace is not None:
+            trace.append((float((best_cor - second) / best_cor), float(abs(gain - ratio)), float(best_cor)))
         if gain > ratio:  # :343
             periods[i], norms[i], bases[i] = best_p, gain, base
             old_norm = this_norm
@@ -222,7 +236,9 @@ def best_correlation(data, num=5, max_length=None, ratio=0.01, trunc=False, orth
 # --------------------------------------------------------------------------------------
 
 
-def best_frequency(data, win_size=None, num=5, trunc=False, orth=False):
+def best_frequency(data, win_size=None, num=5, trunc=False, orth=False, trace=None):
+    """`trace` (a list, test tooling only) receives per round the relative lead of the spectral peak over the runner-up
+    bin."""
     n = len(data)
     if win_size is None:
         win_size = n
@@ -232,6 +248,9 @@ def best_frequency(data, win_size=None, num=5, trunc=False, orth=False):
     work = data.copy()
     for i in range(num):
         mags = np.abs(np.fft.rfft(work, win_size))
+        if trace is not None:
+            top2 = np.sort(mags)[-2:] if mags.size > 1 else np.array([0.0, mags[0]])
+            trace.append(float((top2[1] - top2[0]) / top2[1]) if top2[1] > 0 else 0.0)
         p = int(np.round((2 * win_size) / np.argmax(mags)))  # :387-388
         base = project(work, p, trunc, orth)
         periods[i], norms[i], bases[i] = p, periodic_norm(base), base

@@ -157,6 +157,8 @@ class Periods:
         per, pw, bs, st = default_engine().m_best(
             x, num, max_length, min_length, type is not None, self._trunc_to_integer_multiple, self._orthogonalize
         )
+        if min_length <= 1 and np.any((np.asarray(st) == _ffi.PH_ST_NO_PERIOD) & np.any(np.asarray(per) == 1, axis=1)):
+            raise KeyError(1)  # get_factors(1, remove_1_and_n=True) in step 2, Periods.py:548
         _raise_status(st, "m_best")
         return (per, pw, bs) if batched else (per[0], pw[0], bs[0])
 

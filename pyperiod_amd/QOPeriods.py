@@ -249,6 +249,13 @@ class QOPeriods(Periods):
             return (self._output, np.zeros(N))
         custom_test = kwargs.get("test_function")
         windowed = not (self.window is None or self.window is False)
+        if self._no_candidate(min_length, max_length, num, thresh, update_weights, windowed, kwargs):
+            # windows of fewer than 3 * min_length samples with the default range: the reference's selection loop finds
+            # nothing, fits an empty dictionary and stops at its second iteration (QOPeriods.py:470-478, :560-594) --
+            # nothing is launched
+            self._output_bases = {"periods": np.zeros(0, dtype=np.uint32), "norms": np.zeros(0), "subspaces": np.zeros((0, N)),
+                                  "weights": np.zeros(0), "basis_dictionary": {}}
+            return (self._output_bases, data.copy())
         on_device = (
             update_weights and custom_test is None and thresh is not None and not self._orthogonalize
             and not self._trunc_to_integer_multiple and self._basis_type == "natural" and not windowed
@@ -261,6 +268,12 @@ class QOPeriods(Periods):
                 self._output_bases = {k: v.copy() if k in ("periods", "norms", "weights") else v for k, v in bases.items()}
                 return (self._output_bases, residual.copy())
         return self._find_periods_host(data, N, num, thresh, min_length, max_length, update_weights, custom_test)
+
+    def _no_candidate(self, min_length, max_length, num, thresh, update_weights, windowed, kwargs):
+        """The plain route (re-solved weights, default test function, natural basis, no window, not orthogonal) with an
+        empty period range: the one case in which the reference returns its empty answer instead of selecting."""
+        return (max_length < min_length and num >= 1 and thresh is not None and kwargs.get("test_function") is None
+                and update_weights and not windowed and not self._orthogonalize and self._basis_type == "natural")
 
     def _batch_path(self, W, windowed, win, thresh, update_weights, kwargs):
         """Where a (W, N) batch runs.  ``common`` = default test function, `thresh` set, natural basis, not verbose;
@@ -295,6 +308,9 @@ class QOPeriods(Periods):
         windowed = not (self.window is None or self.window is False)
         win = _device_window(self.window, N) if windowed else None
         path = self._batch_path(W, windowed, win, thresh, update_weights, kwargs)
+        if self._no_candidate(min_length, int(np.floor(N / 3)) if max_length is None else int(max_length),
+                              N if num is None else int(num), thresh, update_weights, windowed, kwargs):
+            path = None  # every row takes the 1-D call's empty answer
         out = [None] * W
         if path is not None:
             eng = default_engine()

@@ -32,7 +32,12 @@ class RamanujanPeriods(QOPeriods):
         win = np.ascontiguousarray(arr, dtype=np.float64) if batched else _as_window(x)[None, :]
         if not max_length:
             max_length = win.shape[1] // 3
-        norms = default_engine().ramanujan_norms(win, int(min_length), int(max_length))
+        if int(max_length) < max(int(min_length), 1):
+            # windows of fewer than 3 * min_length samples: the reference's loop over q does not run and it returns its
+            # zero vector (RamanujanPeriods.py:73-75)
+            norms = np.zeros((win.shape[0], max(int(max_length), 0) + 1))
+        else:
+            norms = default_engine().ramanujan_norms(win, int(min_length), int(max_length))
         norms = norms if batched else norms[0]
         if select_periods:
             if hasattr(select_periods, "__call__"):

@@ -291,7 +291,8 @@ class PeriodEngine:
 
     def m_best(self, x, num=5, max_length=None, min_length=2, gamma=False, trunc=False, orth=False, want_sweeps=False):
         """-> periods (W,num) uint32, powers (W,num) f64, bases (W,num,N), status (W) int32
-        [, n_sweeps (W) int32 when want_sweeps]."""
+        [, n_sweeps (W) int32 when want_sweeps].  A row whose list holds period 1 ends PH_ST_NO_PERIOD: the reference
+        raises there."""
         x, code, W, N, fl, mk = self._prep(x)
         if max_length is None:
             max_length = N // 3
@@ -307,6 +308,14 @@ class PeriodEngine:
                    keep[2], keep[3], foff.ctypes.data, fq.ctypes.data, max(max_length, 1),
                    fl | self._flags(trunc, orth), mk.addr(periods), mk.addr(powers), mk.addr(bases), mk.addr(status),
                    mk.addr(sweeps))
+        if min_length <= 1 and W:
+            # a row that ends with period 1 (only min_length <= 1 offers it): the reference's step 2 asks for
+            # get_factors(1, remove_1_and_n=True) and dies with KeyError (Periods.py:548) -- no result, so a status
+            one = (periods == 1).any(1) & (status == _ffi.PH_ST_OK)
+            if mk.torch:
+                status.masked_fill_(one, _ffi.PH_ST_NO_PERIOD)  # (no read-back: the call stays asynchronous)
+            else:
+                status[one] = _ffi.PH_ST_NO_PERIOD
         if want_sweeps:
             return periods, powers, bases, status, sweeps
         return periods, powers, bases, status

@@ -1,4 +1,4 @@
-// libperiod_hip.so -- C ABI (include/periodhip.h) over the gfx950 kernels in ph_kernels.h.
+// libperiod_hip.so -- C ABI (include/periodhip.h) over the gfx950 kernels (ph_kernels.h: one header per algorithm).
 // Host side only: argument checks, device staging for host-pointer calls, small integer
 // tables, launch geometry.  No compute happens on the host.
 #include <hip/hip_runtime.h>
@@ -1569,7 +1569,7 @@ int ph_m_best(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int num, in
   PH_TRY(st.out(B_OUT4, n_sweeps, (size_t)W * sizeof(int32_t), &dsweeps));
   PH_TRY(ensure(c, c->buf[B_WS0], (size_t)W * sizeof(double)));
   double* dnorm = static_cast<double*>(c->buf[B_WS0].p);
-  // compact basis rows between the two kernels: the first p elements of every row (ph_kernels.h, step 2);
+  // compact basis rows between the two kernels: the first p elements of every row (ph_mbest.h, step 2);
   // 16-byte aligned rows of a whole number of 128-element LDS-DMA pieces
   const int row_stride = (max_length + 127) & ~127;
   PH_TRY(ensure(c, c->buf[B_WS1], (size_t)W * num * row_stride * sz));

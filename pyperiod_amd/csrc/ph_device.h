@@ -18,6 +18,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 namespace ph {
 
 constexpr int kWave = 64;
@@ -379,9 +381,12 @@ struct PGeom {
   double w_short;  // 1 / (R-1)   (0 when R == 1)
 };
 
-// Where a window lives: in LDS (the normal case; volatile LDS-address-space reads, see
-// fold_rows) or -- for windows longer than the LDS -- in a per-workgroup HBM workspace that the
-// same code reads through ordinary global loads (served by L2).
+// Where a window lives: in LDS (the normal case) or -- for windows longer than the LDS -- in a per-workgroup HBM
+// workspace that the same code reads through ordinary global loads (served by L2).  The LDS reads go through a
+// volatile LDS-address-space pointer: the chunks of a row share one address register (immediate offsets 512 c) and
+// hipcc cannot fuse chunk pairs into ds_read2st64_b64, which runs at half the LDS rate of ds_read_b64.  The folds
+// issue a block of U rows x C chunks of independent ds_read_b64 back to back, then ONE lgkmcnt(0) (the scalar issue
+// slot is as busy as the vector one here; the other waves of the CU cover the latency), then the adds.
 template <typename T, bool LDS>
 struct Win;
 template <typename T>
@@ -397,42 +402,6 @@ struct Win<T, false> {
 
 constexpr int kPad = 256;  // LDS windows are followed by kPad zeroed elements: a 4-chunk group reads up to
                            // 255 elements past the last row of the window (see seg_group)
-
-// s[c] += sum over `nrows` rows of the C chunks starting at `ptr` (row stride p).  U rows x C
-// chunks of independent ds_read_b64 are issued back to back, then ONE lgkmcnt(0) (the scalar
-// issue slot is as busy as the vector one here; the other waves of the CU cover the latency),
-// then the adds.  The reads go through a volatile LDS-address-space pointer: the chunks of a
-// row share one address register (immediate offsets 512 c) and hipcc cannot fuse chunk pairs
-// into ds_read2st64_b64, which runs at half the LDS rate of ds_read_b64.  Row order per
-// residue is preserved (bit-identical column sums).
-template <typename T, int C, int U, bool LDS = true>
-__device__ __forceinline__ void fold_rows(typename Win<T, LDS>::ptr ptr, int p, int nrows, double (&s)[C]) {
-  int r = 0;
-  for (; r + U <= nrows; r += U) {
-    T v[U][C];
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-#pragma unroll
-      for (int c = 0; c < C; ++c) v[u][c] = ptr[u * p + 64 * c];
-    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-#pragma unroll
-      for (int c = 0; c < C; ++c) s[c] += (double)v[u][c];
-    ptr += U * p;
-  }
-  if (U > 1) {
-    for (; r < nrows; ++r) {
-      T v[C];
-#pragma unroll
-      for (int c = 0; c < C; ++c) v[c] = ptr[64 * c];
-#pragma unroll
-      for (int c = 0; c < C; ++c) s[c] += (double)v[c];
-      ptr += p;
-    }
-  }
-}
 
 // p < 64, max|S| mode: one lane per residue, rows in order (bit-identical sums).
 template <typename T>
@@ -689,7 +658,7 @@ __device__ __forceinline__ void seg_group(typename Win<T, LDS>::ptr ptr, int p, 
     for (int u = 0; u < U; ++u)
 #pragma unroll
       for (int c = 0; c < C; ++c) v[u][c] = ptr[u * p + 64 * c];
-    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): one wait per block, see fold_rows
+    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): one wait per block, see Win
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int u = 0; u < U; ++u)
@@ -1095,5 +1064,124 @@ __device__ __forceinline__ void load_window(const T* __restrict__ g, T* __restri
     for (int i = threadIdx.x; i < N; i += blockDim.x) xs[i] = g[i];
   }
 }
+
+// Dynamic LDS carve-up; every piece starts 16-byte aligned (guide: Guideline 17).
+struct Carve {
+  unsigned char* base;
+  size_t off;
+  __device__ explicit Carve(unsigned char* b) : base(b), off(0) {}
+  template <typename U>
+  __device__ U* take(size_t n) {
+    U* p = reinterpret_cast<U*>(base + off);
+    off += (n * sizeof(U) + 15) & ~size_t(15);
+    return p;
+  }
+};
+
+__host__ __device__ inline size_t carve_bytes(size_t n, size_t elem) { return (n * elem + 15) & ~size_t(15); }
+
+// The window buffer of workgroup blockIdx.x: LDS normally; for windows longer than the LDS
+// (LW == false) a slice of the HBM workspace `gwin` (stride win_stride(len) elements).
+__host__ __device__ inline size_t win_stride(size_t len) { return (len + 3) & ~size_t(3); }
+
+template <typename T, bool LW>
+__device__ __forceinline__ T* window_buf(Carve& cv, T* gwin, size_t len) {
+  if constexpr (LW) {
+    return cv.take<T>(len);
+  } else {
+    return gwin + (size_t)blockIdx.x * win_stride(len);
+  }
+}
+
+constexpr int kRedDoubles = 2 * kMaxWaves;
+
+// The sweep kernels run 4 workgroups x 8 wavefronts per CU (LDS holds four 32 KiB windows), which
+// needs <= 64 VGPRs; measured +15 % over the 5 waves/SIMD the unconstrained allocation gives.
+#ifndef PH_STEP1_WAVES
+#define PH_STEP1_WAVES 8
+#endif
+
+// all lanes of a wavefront see each other's LDS writes
+__device__ __forceinline__ void ram_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// ---------------------------------------------------------------- diagnostic builds
+// The switches of the instrumented builds (-DPH_PAIR_TIMERS, ...: DESIGN.md, tools/*_timers.py, tools/clocks.py) as
+// constants: a kernel declares its instruments with the constant as template argument, and in a default build they are
+// the empty specialisations below -- no state, no code, no #ifdef inside a kernel body.
+// (-DNAME defines NAME as 1; a name that is not defined is spelled out by the # operator and begins with 'P')
+#define PH_SWITCH_STR(name) #name
+#define PH_SWITCH(name) (PH_SWITCH_STR(name)[0] == '1' || PH_SWITCH_STR(name)[0] == '\0')
+constexpr bool kPairTimers = PH_SWITCH(PH_PAIR_TIMERS);
+constexpr bool kStep2Timers = PH_SWITCH(PH_STEP2_TIMERS);
+constexpr bool kS2LTimers = PH_SWITCH(PH_S2L_TIMERS);
+constexpr bool kQoTimers = PH_SWITCH(PH_QO_TIMERS);
+constexpr bool kFitTimers = PH_SWITCH(PH_FIT_TIMERS);
+constexpr bool kClocks = PH_SWITCH(PH_CLOCKS);
+#ifndef PH_PAIR_TIMERS_WGS
+#define PH_PAIR_TIMERS_WGS 6  // workgroups of k_mbest_step1_pair that print their timers
+#endif
+
+// Stage clock of one thread: mark(k) adds the wall-clock ticks (100 MHz) since the previous mark to stage k of K;
+// count(c, by) keeps the C event counters that are printed beside the stage sums; marker() is mark() as a callable
+// for a helper that has stages of its own.
+struct NoMark {
+  __device__ __forceinline__ void operator()(int) const {}
+};
+template <bool ON, int K, int C = 1>
+struct StageClock {
+  struct Marker {
+    StageClock* clock;
+    __device__ __forceinline__ void operator()(int k) const { clock->mark(k); }
+  };
+  __device__ __forceinline__ Marker marker() { return Marker{this}; }
+  long long sum[K] = {};
+  int num[C] = {};
+  const long long start = wall_clock64();
+  long long last = start;
+  __device__ __forceinline__ void mark(int k) {
+    const long long now = wall_clock64();
+    sum[k] += now - last;
+    last = now;
+  }
+  __device__ __forceinline__ void count(int c, int by = 1) { num[c] += by; }
+  __device__ __forceinline__ long long ticks(int k) const { return sum[k]; }
+  __device__ __forceinline__ int counted(int c) const { return num[c]; }
+  __device__ __forceinline__ long long total() const { return wall_clock64() - start; }
+};
+template <int K, int C>
+struct StageClock<false, K, C> {
+  __device__ __forceinline__ NoMark marker() const { return NoMark(); }
+  __device__ __forceinline__ void mark(int) const {}
+  __device__ __forceinline__ void count(int, int = 1) const {}
+  __device__ __forceinline__ long long ticks(int) const { return 0; }
+  __device__ __forceinline__ int counted(int) const { return 0; }
+  __device__ __forceinline__ long long total() const { return 0; }
+};
+
+// Workgroup stamp of the -DPH_CLOCKS builds: shader clock and wall clock where it is declared; finish() adds both at
+// the end and the place the workgroup ran at (HW_ID, XCC_ID).
+template <bool ON>
+struct WgStamp {
+  const long long ck0 = clock64(), wk0 = wall_clock64();
+  long long ck1 = 0, wk1 = 0;
+  unsigned hwid = 0, xcc = 0;
+  __device__ __forceinline__ void finish() {
+    ck1 = clock64();
+    wk1 = wall_clock64();
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+    xcc &= 15;
+  }
+};
+template <>
+struct WgStamp<false> {
+  static constexpr long long ck0 = 0, wk0 = 0, ck1 = 0, wk1 = 0;
+  static constexpr unsigned hwid = 0, xcc = 0;
+  __device__ __forceinline__ void finish() const {}
+};
 
 }  // namespace ph

@@ -2,8 +2,8 @@
 // device: k_qo_fit runs get_subspaces' row bookkeeping, the right-hand side by folds and the matrix-free conjugate
 // gradients of k_qo_find for a list it is handed instead of one it selects greedily; k_qo_fit_win is the same fit under an
 // analysis window (its product goes through a staged sample-length vector); k_ram_select turns Ramanujan norms into that
-// list.  Included by period_hip.hip behind ph_kernels.h.  Reference citations are file:line into
-// /root/reference/pyPeriod/.
+// list.  Included by period_hip.hip behind ph_kernels.h (it uses qo_offdiag and qo_gcd of ph_qo.h).  Reference
+// citations are file:line into /root/reference/pyPeriod/.
 #pragma once
 
 #include "ph_kernels.h"
@@ -343,9 +343,7 @@ __global__ __launch_bounds__(1024) void k_qo_fit(const T* __restrict__ x, int N,
     }
     if (!(rr <= tol2)) failed = true;  // not finite, or the bound was hit: the host path solves as the reference does
   }
-#ifdef PH_FIT_TIMERS
-  if (w < 64 && tid == 0) printf("qo_fit window %d: blocks %d rows %d cg iterations %d %s\n", (int)w, nblk, K, iter, failed ? "FAILED" : "ok");
-#endif
+  if (kFitTimers && w < 64 && tid == 0) printf("qo_fit window %d: blocks %d rows %d cg iterations %d %s\n", (int)w, nblk, K, iter, failed ? "FAILED" : "ok");
   __syncthreads();
   if (failed) {
     if (tid == 0) status_out[w] = 2;
@@ -642,9 +640,7 @@ __global__ __launch_bounds__(1024) void k_qo_fit_win(const T* __restrict__ x, in
     }
     if (!(rr <= tol2)) failed = true;  // not finite, or the bound was hit: the host path solves as the reference does
   }
-#ifdef PH_FIT_TIMERS
-  if (w < 64 && tid == 0) printf("qo_fit_win window %d: blocks %d rows %d cg iterations %d %s\n", (int)w, nblk, K, iter, failed ? "FAILED" : "ok");
-#endif
+  if (kFitTimers && w < 64 && tid == 0) printf("qo_fit_win window %d: blocks %d rows %d cg iterations %d %s\n", (int)w, nblk, K, iter, failed ? "FAILED" : "ok");
   __syncthreads();
   if (failed) {
     if (tid == 0) status_out[w] = 2;

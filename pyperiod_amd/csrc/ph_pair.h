@@ -11,7 +11,7 @@
 //
 // The float values only SCREEN the candidates of an m_best iteration (Periods.py:501-515): a rigorous radius
 // (pair_radius) bounds |screen - exact|, and the periods whose upper bound reaches the best lower bound are
-// re-evaluated in fp64 by the kernel (k_mbest_step1_pair in ph_kernels.h), which decides on those values.
+// re-evaluated in fp64 by the kernel (k_mbest_step1_pair in ph_mbest.h), which decides on those values.
 //
 // Plain m_best screens only the periods in (p_hi / 2, p_hi]: the projection onto the d-periodic vectors is never
 // longer than the one onto the m-periodic vectors when d | m, so a period with a multiple in range needs a look (in
@@ -838,6 +838,43 @@ __host__ __device__ __forceinline__ double pair_radius(int rows, int q) {
 // either order, which no bound relative to E_m would cover.  Never less than 2^-40.
 __device__ __forceinline__ double pair_cover_slack(int N) {
   return fmax(9.094947017729282e-13, (2.0 * (double)N + 32.0) * 2.220446049250313e-16);
+}
+
+// ---------------------------------------------------------------- shared by the window-pair kernels
+// (k_mbest_step1_pair, k_best_correlation_pair, k_small_to_large_pair)
+#ifndef PH_PAIR_QUEUE
+#define PH_PAIR_QUEUE 1
+#endif
+constexpr int kPairListCap = 96;
+constexpr int kPairSmallP = 256;  // winners up to this period: means through LDS, subtraction by all threads
+constexpr int kPairSplitW = 512;  // threads that share the rows of a short winner's residues (split_row_means)
+
+__device__ __forceinline__ bool pair_usable(double rsq) { return rsq > 0.0 && rsq < 1.79e308; }
+
+// power of two that brings the RMS of a window into [0.7, 1.5)
+__device__ __forceinline__ double pair_pick_scale(double rsq, int N) {
+  if (!pair_usable(rsq)) return 1.0;
+  int e;
+  (void)frexp(rsq / (double)N, &e);
+  return ldexp(1.0, -(e >> 1));
+}
+
+// The scale of a float image only has to keep its RMS near 1: it is renewed (pair_pick_scale, then pair_rescale) when
+// the residual, sum of squares rsq at scale sc, has shrunk to an RMS below 2^-20.
+constexpr double kPairStaleMeanSq = 9.0e-13;  // (2^-20)^2, rounded down
+__device__ __forceinline__ bool pair_image_stale(double rsq, double sc, int N) {
+  return pair_usable(rsq) && rsq * sc * sc < kPairStaleMeanSq * (double)N;
+}
+
+// float image of window w of a pair times a power of two: the rescaled image is the image at the new scale
+// (tid: for a kernel that recomputes its thread index to keep it out of long-lived registers)
+__device__ __forceinline__ void pair_rescale(float* __restrict__ pwf, int w, int N, float up, int tid = threadIdx.x) {
+  for (int n = tid; n < N; n += blockDim.x) pwf[2 * n + w] *= up;
+}
+
+// upper bound of ceil(N / q) without an integer division (the radius only has to be an upper bound)
+__device__ __forceinline__ int pair_rows_upper(float fn, int q) {
+  return (int)(fn * __builtin_amdgcn_rcpf((float)q) * 1.000001f) + 1;
 }
 
 }  // namespace ph

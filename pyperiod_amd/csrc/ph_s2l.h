@@ -1,5 +1,5 @@
-// Periods.small_to_large (Periods.py:246-287), window-pair screen with a speculative in-order period QUEUE and an
-// fp64 staging buffer in LDS (round 4; gfx950 / CDNA4 only).  Included from ph_kernels.h.
+// Periods.small_to_large (Periods.py:246-287): the one-window kernel k_small_to_large and, below it, the window-pair
+// screen with a speculative in-order period QUEUE and an fp64 staging buffer in LDS (round 4; gfx950 / CDNA4 only).
 //
 //   Two fp64 windows share a workgroup and the pair window of ph_pair.h: the ascending screen of k_small_to_large
 //   (||r||^2 - ||P_q r||^2 as an estimate of the reference's norm drop, Periods.py:274-281) runs on the float images of
@@ -28,6 +28,9 @@
 //   staging copies), which keeps every sum in the order of k_small_to_large<double>.
 #pragma once
 
+#include "ph_device.h"
+#include "ph_pair.h"
+
 namespace ph {
 
 // Exact evaluation of a candidate period p <= kBlockWide (Periods.py:274-281), shared by the one-window and the
@@ -42,10 +45,7 @@ namespace ph {
 // defined order anyway.  Threads >= width do nothing; msm holds >= width elements.
 // `part` (>= width elements) takes the partial sums of split_row_means; it may be `msm` itself (one more barrier then).
 constexpr int kFlatBatch = 8;  // samples a thread takes per trip of the flat loops (N = 4096, 512 threads: one trip)
-struct S2LNoMark {
-  __device__ __forceinline__ void operator()(int) const {}
-};
-template <typename T, typename MK = S2LNoMark>
+template <typename T, typename MK = NoMark>
 __device__ __forceinline__ double s2l_flat_trial(const T* __restrict__ work, T* msm, T* part, int N, int p, int tid, int width,
                                                  MK&& mark = MK()) {
   split_row_means(work, msm, part, N, p, tid, width);
@@ -107,13 +107,177 @@ __device__ __forceinline__ void s2l_flat_update(T* __restrict__ work, const T* _
   }
 }
 
+// ======================================================================================
+// Periods.small_to_large  (Periods.py:246-287).  Sequential in p; one workgroup per window.
+//   Plain projection: screen every p with ||r - P r||^2 = ||r||^2 - ||P r||^2 (one LDS pass),
+//   and evaluate the reference's expression exactly (second pass) whenever the screen is
+//   within its own error bound of the threshold, so the accept decision is the exact one.
+// ======================================================================================
+// periods screened speculatively per round (8 waves x 4 periods).  Screens beyond an accepted
+// period are discarded, (batch - 1) / 2 of them per accept on average: 32 beats 64 (9.4 vs 9.9 ms
+// on the config-4 shard) and 16 / 24 / 48.
+constexpr int kS2LBatch = 32;
+
+template <typename T, bool LW>
+__global__ __launch_bounds__(kBlockWide) __attribute__((amdgpu_waves_per_eu(PH_STEP1_WAVES, 8))) void k_small_to_large(const T* __restrict__ x, int N, double thresh,
+                                                           int n_periods, unsigned flags, Tables tb,
+                                                           const PGeom* __restrict__ geom, T* __restrict__ gbuf,
+                                                           T* gwin, int cap, int* __restrict__ counts,
+                                                           int* __restrict__ periods_out,
+                                                           double* __restrict__ powers_out,
+                                                           T* __restrict__ bases_out, int* __restrict__ status_out,
+                                                           int* __restrict__ max_count) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  Carve cv(smem);
+  T* work = window_buf<T, LW>(cv, gwin, N + kPad);
+  const bool general = flags & (kTrunc | kOrth);
+  T* buf = !general ? nullptr : gbuf ? gbuf + (int64_t)blockIdx.x * N : cv.take<T>(N);
+  double* red = cv.take<double>(kRedDoubles);
+  double* psq = cv.take<double>(kS2LBatch);
+  int* cand_slot = cv.take<int>(4);
+  T* msm = general ? nullptr : cv.take<T>(kBlockWide);  // means of a candidate period <= kBlockWide (s2l_flat_* below)
+
+  const int64_t w = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int lane = tid & (kWave - 1);
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int nw = blockDim.x >> 6;
+  load_window(x + w * (int64_t)N, work, N);
+  zero_pad(work, N);
+  __syncthreads();
+  double rsq = block_sumsq(work, N, red);
+  const double sqrtN = uniform_f64(sqrt((double)N));
+  const double dn = uniform_f64(sqrt(rsq) / sqrtN);  // data_norm, Periods.py:269
+  double rn = dn;                                    // periodic_norm(residual)
+  int count = 0;
+
+  StageClock<kS2LTimers, 3> clk;  // stages: screen, exact, update
+  int p = 2;
+  while (p <= n_periods) {
+    int cand = p;  // the period that gets the exact evaluation of Periods.py:274-281
+    if (!general) {
+      // The residual only changes when a period is accepted, so a run of periods can be
+      // screened in parallel (wave-per-period): ||r - P r||^2 = ||r||^2 - ||P r||^2 gives an
+      // estimate of the reference's norm drop.  The first period whose estimate, plus a bound
+      // on its cancellation error, reaches the threshold is evaluated exactly below; results
+      // screened beyond an accepted period are discarded and recomputed.
+      const int hi = min(n_periods, p + kS2LBatch - 1);
+      wave_sweep<T, false, LW, true>(work, N, geom, p + wv, hi, nw, lane, [&](double ss, int q) {
+        if (lane == 0) psq[q - p] = ss;
+      });
+      __syncthreads();
+      if (wv == 0) {  // one lane per screened period; the first flagged one is the candidate
+        const int q = p + lane;
+        bool flag = false;
+        if (q <= hi) {
+          // The decision below is taken on t_e = fl(sum (r - m)^2), the screen has t_s = rsq - psq.
+          // Both approximate T = ||r||^2 - ||P r||^2:
+          //   |psq - ||P r||^2| <= (2 R + q/64 + 16) eps ||r||^2   (S_j: R-term sums, |S_j| A_j / cnt_j <= Q_j
+          //                                                         by Cauchy-Schwarz; then a positive sum)
+          //   |rsq - ||r||^2|, |t_e - T| <= (N / 512 + 16) eps ||r||^2 each (strided partial sums + tree)
+          // so |t_s - t_e| <= D = (1.5 N + 256) eps rsq for every q >= 2 (2 R <= N, q / 64 <= N / 128).
+          // float windows: the means and r - m are rounded to float, adding (4 + R^2 eps_f) eps_f rsq.
+          // |sqrt(t_s) - sqrt(t_e)| <= min(D / sqrt(t_s), sqrt(D)); the remaining operations of
+          // (rn - sqrt(t) / sqrtN) / dn are shared by both paths up to 8 eps (<= 1e-13).
+          const double tsq = fmax(rsq - psq[lane], 0.0);
+          const double est = (rn - sqrt(tsq) / sqrtN) / dn;
+          double kappa = (1.5 * (double)N + 256.0) * 2.220446049250313e-16;
+          if (sizeof(T) == 4) {
+            const double rf = (double)geom[q].rows * 5.9604644775390625e-08;
+            kappa += (4.0 + rf * (double)geom[q].rows) * 5.9604644775390625e-08;
+          }
+          const double D = kappa * rsq;
+          const double dsq = fmin(D / fmax(sqrt(tsq), 1e-300), sqrt(D));
+          const double err = dsq / sqrtN / dn + 1e-13;
+          flag = !(est + err <= thresh);  // NaN -> evaluate
+        }
+        const unsigned long long mask = __ballot(flag);
+        if (lane == 0) *cand_slot = mask ? p + __ffsll((long long)mask) - 1 : -1;
+      }
+      __syncthreads();  // also: psq is rewritten by the next round
+      clk.mark(0);
+      cand = *cand_slot;
+      if (cand < 0) {
+        p = hi + 1;
+        continue;
+      }
+    }
+    // exact evaluation (row-order means, direct sum of squares of the trial residual)
+    double tsq = 0.0;
+    const bool flat = !general && cand <= kBlockWide;
+    if (flat) {
+      tsq = s2l_flat_trial(work, msm, msm, N, cand, tid, (int)blockDim.x);
+    } else if (!general) {
+      const Fold f(N, cand);
+      for (int j = tid; j < cand; j += blockDim.x) {
+        const T m = residue_mean(work, f, j, false);
+        const int cnt = f.count(j);
+        for (int r = 0; r < cnt; ++r) {
+          const double t = (double)(work[r * cand + j] - m);
+          tsq += t * t;
+        }
+      }
+    } else {
+      project_lds(work, buf, N, cand, flags, tb);
+      for (int n = tid; n < N; n += blockDim.x) {
+        const double t = (double)(work[n] - buf[n]);
+        tsq += t * t;
+      }
+    }
+    tsq = block_sum(tsq, red);
+    clk.mark(1);
+    const double tn = uniform_f64(sqrt(tsq) / sqrtN);
+    const double imposed = uniform_f64((rn - tn) / dn);
+    if (imposed > thresh) {  // strict, Periods.py:281
+      T* brow = (bases_out && count < cap) ? bases_out + (w * cap + count) * (int64_t)N : nullptr;
+      if (flat) {
+        s2l_flat_update(work, msm, N, cand, tid, (int)blockDim.x, brow, [](int, T) {});
+      } else if (!general) {
+        const Fold f(N, cand);
+        for (int j = tid; j < cand; j += blockDim.x) {
+          const T m = residue_mean(work, f, j, false);
+          const int cnt = f.count(j);
+          for (int r = 0; r < cnt; ++r) {
+            const int n = r * cand + j;
+            if (brow) brow[n] = m;
+            work[n] -= m;
+          }
+        }
+      } else {
+        for (int n = tid; n < N; n += blockDim.x) {
+          const T m = buf[n];
+          if (brow) brow[n] = m;
+          work[n] -= m;
+        }
+      }
+      if (tid == 0 && count < cap) {
+        periods_out[w * cap + count] = cand;
+        powers_out[w * cap + count] = imposed;
+      }
+      count += 1;
+      rsq = tsq;
+      rn = tn;
+    }
+    __syncthreads();
+    clk.mark(2);
+    p = cand + 1;
+  }
+  if (kS2LTimers && w < 6 && tid == 0)
+    printf("s2l timers (100 MHz ticks) screen %lld exact %lld update %lld  accepts %d\n", clk.ticks(0), clk.ticks(1), clk.ticks(2), count);
+  if (tid == 0) {
+    counts[w] = count;
+    status_out[w] = count > cap ? 3 : 0;
+    if (count > cap) atomicMax(max_count, count);  // rare: the host retries with this capacity
+  }
+}
+
 #ifdef PH_CLOCKS
 constexpr int kStampCap = 65536;
 __device__ long long g_ph_stamps[4 * kStampCap];  // diagnostic build only (tools/s2l_clocks.py)
 #endif
 constexpr int kS2LInf = 0x7fffffff;
 
-enum { S2L_TICK = 0, S2L_LIMIT, S2L_STOP0, S2L_STOP1, S2L_SKIP, S2L_QWORDS = 8 };
+enum { S2L_TICK = 0, S2L_LIMIT, S2L_STOP0, S2L_STOP1, S2L_SKIP, S2L_PASSES /* executed: timer builds */, S2L_NEXT_PAIR, S2L_QWORDS = 8 };
 
 // LDS of one workgroup (host and device agree through this one function)
 __host__ __device__ inline size_t s2l_pair_lds_bytes(int N) {
@@ -125,11 +289,6 @@ __host__ __device__ inline size_t s2l_pair_lds_bytes(int N) {
 __host__ __device__ inline double s2l_kappa(int N, int rows, int q) {
   return 1.5 * (2.0 * (double)rows + (double)(q >> 6) + 32.0) * 5.9604644775390625e-08 * (1.0 + 1e-9) +
          ((double)N / 256.0 + 32.0) * 2.220446049250313e-16;
-}
-
-// float image of window w of a pair times a power of two (its scale is renewed when the residual has collapsed)
-__device__ __forceinline__ void s2l_pair_rescale(float* __restrict__ pwf, int w, int N, float up) {
-  for (int n = threadIdx.x; n < N; n += blockDim.x) pwf[2 * n + w] *= up;
 }
 
 // staging copies by the whole workgroup (16-byte vectors when both rows are 16-byte aligned)
@@ -235,23 +394,11 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
   // the staging buffer now holds the input of window 1 (if it exists), unchanged
   int own = (2 * pair + 1 < W) ? 1 : -1;
   bool dirty = false, moved0 = false, moved1 = false;  // moved: the residual is no longer the input
-#ifdef PH_S2L_TIMERS
-  long long tp[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  long long tp0 = wall_clock64();
-  int nev = 0, nepoch = 0, nswap = 0;
-  if (tid == 0) qc[5] = 0;
-#define PH_S2LQ_MARK(k)                    \
-  {                                        \
-    const long long now_ = wall_clock64(); \
-    tp[k] += now_ - tp0;                   \
-    tp0 = now_;                            \
-  }
-#else
-#define PH_S2LQ_MARK(k)
-#endif
-#ifdef PH_CLOCKS
-  const long long wk0 = wall_clock64();
-#endif
+  // stages: 0 screen, 1 exact (reduce + decide), 2 update, 3 partials and 4 means (split_row_means), 5 trial, 7 swap + entry;
+  // counters: epochs, events, swaps
+  StageClock<kS2LTimers, 8, 3> clk;
+  if (kS2LTimers && tid == 0) qc[S2L_PASSES] = 0;
+  [[maybe_unused]] WgStamp<kClocks> stamp;
 
   bool had_event = false;  // the epoch before this one held a barrier after its control words were read
   for (;;) {
@@ -295,34 +442,12 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
           }
         }
         q = lds_ticket_value(nxt);
-#ifdef PH_S2L_EXTRA_SALU  // sensitivity probe: PH_S2L_EXTRA_SALU x 8 scalar adds (or vector adds with PH_S2L_EXTRA_VALU) per pass
-        {
-          int dummy_s = q;
-#pragma unroll
-          for (int e = 0; e < PH_S2L_EXTRA_SALU; ++e)
-            asm volatile("s_add_u32 %0, %0, 1\n\ts_add_u32 %0, %0, 3\n\ts_add_u32 %0, %0, 5\n\ts_add_u32 %0, %0, 7\n\ts_add_u32 %0, %0, 1\n\ts_add_u32 %0, %0, 3\n\ts_add_u32 %0, %0, 5\n\ts_add_u32 %0, %0, 7" : "+s"(dummy_s) : : "scc");
-          if (dummy_s == 0x7fffff01) qc[7] = dummy_s;
-        }
-#endif
-#ifdef PH_S2L_EXTRA_VALU
-        {
-          int dummy_v = pair_lane();
-#pragma unroll
-          for (int e = 0; e < PH_S2L_EXTRA_VALU; ++e)
-            asm volatile("v_add_u32 %0, %0, %0\n\tv_add_u32 %0, 1, %0\n\tv_add_u32 %0, %0, %0\n\tv_add_u32 %0, 3, %0\n\tv_add_u32 %0, %0, %0\n\tv_add_u32 %0, 5, %0\n\tv_add_u32 %0, %0, %0\n\tv_add_u32 %0, 7, %0" : "+v"(dummy_v));
-          if (dummy_v == 0x7fffff01) qc[7] = dummy_v;
-        }
-#endif
-#ifdef PH_S2L_TIMERS
-        if (pair_lane() == 0) atomicAdd(&qc[5], 1);  // passes executed
-#endif
+        if (kS2LTimers && pair_lane() == 0) atomicAdd(&qc[S2L_PASSES], 1);
       }
     }
     __syncthreads();
-    PH_S2LQ_MARK(0)
-#ifdef PH_S2L_TIMERS
-    nepoch += 1;
-#endif
+    clk.mark(0);
+    clk.count(0);
     prio_short_phase();
     // every ticket below `front` was executed; a flag at or beyond it is not known to be the window's first
     // (the events below run beside the other workgroup's screen, whose folds keep the LDS queue of the CU full: an LDS
@@ -359,9 +484,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
         s2l_copy((w ? moved1 : moved0) ? gres + gw * gstride : x + gw * (int64_t)N, stg, N);
         own = w;
         dirty = false;
-#ifdef PH_S2L_TIMERS
-        nswap += 1;
-#endif
+        clk.count(2);
         __syncthreads();
       }
       had_event = true;
@@ -371,13 +494,9 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
       double tsq = 0.0;
       const bool flat = cand <= kEx;  // means through LDS, sums and update flat over the samples (s2l_flat_trial)
       if (flat) {
-#ifdef PH_S2L_TIMERS
-        PH_S2LQ_MARK(7)  // swap + entry
-        tsq = s2l_flat_trial(stg, cand <= kEx / 2 ? msm : prt, prt, N, cand, tid, kEx, [&](int k) { PH_S2LQ_MARK(k) });
-        PH_S2LQ_MARK(5)  // flat trial loop
-#else
-        tsq = s2l_flat_trial(stg, cand <= kEx / 2 ? msm : prt, prt, N, cand, tid, kEx);
-#endif
+        clk.mark(7);  // swap + entry
+        tsq = s2l_flat_trial(stg, cand <= kEx / 2 ? msm : prt, prt, N, cand, tid, kEx, clk.marker());
+        clk.mark(5);  // flat trial loop
       } else if (ex) {
         for (int j = tid; j < cand; j += kEx) {
           const double m = residue_mean(stg, f, j, false);
@@ -389,10 +508,8 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
         }
       }
       tsq = block_sum_once(tsq, red);  // `red` rests until the next event: barriers in between
-      PH_S2LQ_MARK(1)
-#ifdef PH_S2L_TIMERS
-      nev += 1;
-#endif
+      clk.mark(1);
+      clk.count(1);
       const double tn = uniform_f64(sqrt(tsq) / sqrtN);
       const double imposed = uniform_f64((rn - tn) / dn);
       if (imposed > thresh) {  // strict, Periods.py:281
@@ -417,10 +534,11 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
         else
           moved0 = true;
         double sc_now = sc;
-        if (pair_usable(tsq) && tsq * sc * sc < 9.0e-13 * (double)N) {  // float image below 2^-20 RMS: renew its scale
+        // (pair_image_stale, written out: as a call it costs this kernel 12 bytes of scratch)
+        if (pair_usable(tsq) && tsq * sc * sc < kPairStaleMeanSq * (double)N) {
           __syncthreads();
           const double sc2 = uniform_f64(pair_pick_scale(tsq, N));
-          s2l_pair_rescale(pwf, w, N, (float)(sc2 / sc));
+          pair_rescale(pwf, w, N, (float)(sc2 / sc));
           sc_now = sc2;
         }
         if (tid == bk) {  // a thread that has no part in the update (it runs meanwhile)
@@ -439,23 +557,19 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
         pos1 = cand + 1;
       else
         pos0 = cand + 1;
-      PH_S2LQ_MARK(2)
+      clk.mark(2);
     }
   }
-#ifdef PH_S2L_TIMERS
-  if (pair < 6 && tid == 0)
+  if (kS2LTimers && pair < 6 && tid == 0)
     printf("s2l queue timers (100 MHz ticks) screen %lld exact(reduce+decide) %lld update %lld swap+entry %lld partials %lld means %lld trial %lld  epochs %d events %d swaps %d passes %d accepts %d %d\n",
-           tp[0], tp[1], tp[2], tp[7], tp[3], tp[4], tp[5], nepoch, nev, nswap, qc[5], ct[0], ct[1]);
-#endif
-#ifdef PH_CLOCKS
+           clk.ticks(0), clk.ticks(1), clk.ticks(2), clk.ticks(7), clk.ticks(3), clk.ticks(4), clk.ticks(5), clk.counted(0), clk.counted(1), clk.counted(2), qc[S2L_PASSES], ct[0], ct[1]);
+#ifdef PH_CLOCKS  // (g_ph_stamps exists in that build only)
   if (tid == 0 && pair < kStampCap) {  // start, end (100 MHz), hardware id, accepts: read back by ph_debug_stamps
-    unsigned hwid, xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+    stamp.finish();
     long long* o = g_ph_stamps + 4 * (size_t)pair;
-    o[0] = wk0;
-    o[1] = wall_clock64();
-    o[2] = ((long long)(xcc & 15) << 32) | hwid;
+    o[0] = stamp.wk0;
+    o[1] = stamp.wk1;
+    o[2] = ((long long)stamp.xcc << 32) | stamp.hwid;
     o[3] = ct[0] + ct[1];
   }
 #endif
@@ -469,9 +583,9 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
       if (count > cap) atomicMax(max_count, count);  // rare: the host retries with this capacity
     }
   }
-  if (tid == 0) qc[6] = (int)gridDim.x + atomicAdd(next_pair, 1);  // the host zeroes the counter before the launch
+  if (tid == 0) qc[S2L_NEXT_PAIR] = (int)gridDim.x + atomicAdd(next_pair, 1);  // the host zeroes the counter before the launch
   __syncthreads();
-  pair = __builtin_amdgcn_readfirstlane(qc[6]);
+  pair = __builtin_amdgcn_readfirstlane(qc[S2L_NEXT_PAIR]);
   }  // pairs
 }
 

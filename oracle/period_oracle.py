@@ -452,6 +452,42 @@ def ramanujan_norm_folded_q(x, q: int) -> float:
     return float(np.sum(fold_counts(len(x), q) * o * o))
 
 
+def _mobius(m: int) -> int:
+    res, d = 1, 2
+    while d * d <= m:
+        if m % d == 0:
+            m //= d
+            if m % d == 0:
+                return 0
+            res = -res
+        d += 1
+    return -res if m > 1 else res
+
+
+def ramanujan_norm_projector_q(x, q: int) -> tuple:
+    """The same entry in its projector form, in ``np.longdouble``, for wide ranges (the q x q index matrix above costs
+    seconds per entry beyond q = 2000): out = (q/phi)^2 E_q S_q with E_q = sum_{d | q} mu(q/d) P_d and P_d the mean over
+    the q/d residues of a coset modulo d, norms[q] = sum_j cnt_q[j] out_j^2.
+    -> (norms[q], B_q), both longdouble.  B_q = (q/phi)^4 sum_j cnt_q[j] S_q[j]^2 is the energy in front of the projector:
+    an upper scale of norms[q] (E_q is a projector and cnt_q is constant up to one row: norms[q] <= rows / (rows - 1) B_q,
+    and <= B_q where rows == 1) and the unit its rounding error is measured in.  This form shares its algebra with the HIP kernel; tests/test_ramanujan_census_cpu.py pins it to the
+    correlation form above."""
+    q = int(q)
+    ld = np.longdouble
+    x = np.asarray(x, dtype=ld)
+    s = fold_sums(x, q)
+    cnt = fold_counts(x.size, q).astype(ld)
+    e = np.zeros(q, dtype=ld)
+    for d in range(1, q + 1):
+        if q % d:
+            continue
+        mu = _mobius(q // d)
+        if mu:
+            e += mu * np.tile(s.reshape(q // d, d).sum(0) / ld(q // d), q // d)
+    scale4 = (ld(q) / ld(phi(q))) ** 4
+    return scale4 * np.sum(cnt * e * e), scale4 * np.sum(cnt * s * s)
+
+
 def ramanujan_norms_folded(x, min_length=2, max_length=None) -> np.ndarray:
     """fp64 folded form of the same quantity.  This is what the HIP kernel
     evaluates; it differs from the float32 reference path by ~1e-7 relative."""

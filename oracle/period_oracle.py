@@ -169,9 +169,12 @@ def sweep_maxabs(data, p_lo, p_hi) -> np.ndarray:
 
 def small_to_large(data, thresh=0.1, n_periods=None, trunc=False, orth=False, trace=None):
     """`trace` (a dict, test tooling only) receives under "min_margin" the smallest |imposed - thresh| / thresh over all
-    p (1.0 when no p gives a finite value): how far the closest accept/reject decision is from flipping."""
+    p (1.0 when no p gives a finite value): how far the closest accept/reject decision is from flipping; and under
+    "events" one record per period p, in order: (p, imposed, accepted, periodic_norm(residual), max|residual|), the last
+    two of the residual the decision was taken on (before an accept changes it)."""
     periods, powers, bases = [], [], []
     margin = 1.0
+    events = []
     data_norm = periodic_norm(data)  # :269
     residual = data.copy()
     if n_periods is None:
@@ -180,8 +183,11 @@ def small_to_large(data, thresh=0.1, n_periods=None, trunc=False, orth=False, tr
         base = project(residual, p, trunc, orth)
         trial = residual - base
         imposed = (periodic_norm(residual) - periodic_norm(trial)) / data_norm  # :278-280
-        if trace is not None and imposed == imposed and thresh:
-            margin = min(margin, abs(imposed - thresh) / abs(thresh))
+        if trace is not None:
+            if imposed == imposed and thresh:
+                margin = min(margin, abs(imposed - thresh) / abs(thresh))
+            events.append((p, float(imposed), bool(imposed > thresh), float(periodic_norm(residual)),
+                           float(np.max(np.abs(residual))) if residual.size else 0.0))
         if imposed > thresh:  # strict, :281
             residual = trial
             periods.append(p)
@@ -189,6 +195,7 @@ def small_to_large(data, thresh=0.1, n_periods=None, trunc=False, orth=False, tr
             bases.append(base)
     if trace is not None:
         trace["min_margin"] = float(margin)
+        trace["events"] = events
     return periods, powers, bases
 
 

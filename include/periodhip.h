@@ -462,6 +462,25 @@ int ph_ramanujan_fit(ph_ctx* ctx, const void* x, int dtype, int64_t W, int N, in
                      double* norms, int32_t* periods, int32_t* counts, int32_t* keeps,
                      double* weights, void* residual, int32_t* status);
 
+/* ---- the threshold of ph_ramanujan_fit on given norms, against a choosable level and with a capped list ----------
+ * One launch (k_ram_select_ref, one wavefront per row) on norms (W, q_hi + 1) float64 as ph_ramanujan_norms writes them.
+ *   m_w        = ref[w] when ref is given (W doubles); with ref == NULL what ph_ramanujan_fit uses: |max| of the row
+ *                as numpy.max sees it, so a NaN anywhere makes it NaN
+ *   candidates = the q in 0 .. q_hi with norms[w, q] / m_w > thresh -- that IEEE double division and strict
+ *                comparison: a NaN entry or a NaN / zero-over-zero quotient is never a candidate, and with thresh > 0
+ *                and m_w >= 0 every candidate is strictly positive
+ *   over[w]    = number of candidates
+ *   kept       = all of them when over[w] <= pcap; otherwise q is kept iff fewer than pcap candidates q' have
+ *                norms[q'] > norms[q], or norms[q'] == norms[q] and q' < q: the pcap largest, ties to the smaller period
+ *   counts[w]  = min(over[w], pcap); periods[w, :counts[w]] = the kept periods ascending, zeros behind them
+ * With ref == NULL and over[w] <= pcap the lists are those of ph_ramanujan_fit, bit for bit.  periods (W, pcap),
+ * counts (W) and over (W) are int32; every array follows PH_FLAG_DEVICE.  PH_E_ARG before anything is launched: a NULL
+ * ctx / norms / output, W < 1, q_hi < 1 or beyond the record format of ph_ramanujan_norms, pcap outside [1, 2^20],
+ * !(thresh > 0). */
+int ph_ramanujan_select(ph_ctx* ctx, const double* norms, int64_t W, int q_hi, double thresh,
+                        const double* ref /* W or NULL */, int pcap, unsigned flags,
+                        int32_t* periods, int32_t* counts, int32_t* over);
+
 /* ---- QOPeriods.get_best_period_orthogonal / eq_3 / auto_corr (QOPeriods.py:1122-1232) -----
  * powers (W, max_p) float64: the Muresan-Parks orthogonal period powers `pows` for q < max_p
  * (entry 0 is 0), divided by q when normalize != 0; autocorr (W, N) = auto_corr(x, k) for every

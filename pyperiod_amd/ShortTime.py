@@ -22,6 +22,14 @@ of p samples per period -- and one routed overlap-add that tiles those waveforms
 
     dq = st.decompose_qo(recording, num=4, thresh=0.1)
     dq.track_periods, dq.tracks, dq.other, dq.periodic, dq.residual
+
+``decompose_ramanujan`` is that split by ``RamanujanPeriods``: the Ramanujan norms of every frame (the time-period map
+of the recording), a threshold against the frame, the recording or an absolute level that keeps at most `max_periods`
+periods per frame (``PeriodEngine.ramanujan_select``), ``find_periods_with_weights``' fit of those lists and the same
+routed overlap-add.
+
+    dr = st.decompose_ramanujan(recording, thresh=0.2, reference="recording", max_periods=16)
+    dr.norms, dr.over, dr.frame_status, dr.track_periods, dr.tracks, dr.periodic
 """
 
 from __future__ import annotations
@@ -66,6 +74,28 @@ class ShortTimeTracks(NamedTuple):
     other: np.ndarray
     activity: np.ndarray
     counts: Optional[np.ndarray] = None
+
+
+class ShortTimeRamanujan(NamedTuple):
+    """What ``ShortTime.decompose_ramanujan`` returns: the fields of ``ShortTimeTracks`` (``periods`` / ``powers`` (W, K)
+    are the blocks' periods and the mean square of each block's waveform over its period, zeros behind ``counts``), and
+    ``norms`` (W, q_hi + 1), the Ramanujan norms of every frame -- the time-period map of the recording; ``over`` (W),
+    the candidates of each frame before the cap (``over > counts`` marks a capped frame); ``frame_status`` (W) int8:
+    0 fitted on the device, 1 fitted on the host, 2 nothing selected (a silent frame, all norms under the threshold, a
+    NaN frame under ``reference="frame"``), 3 no fit exists.  Frames of status 2 and 3 contribute nothing."""
+
+    periods: np.ndarray
+    powers: np.ndarray
+    periodic: np.ndarray
+    residual: np.ndarray
+    track_periods: list
+    tracks: np.ndarray
+    other: np.ndarray
+    activity: np.ndarray
+    counts: Optional[np.ndarray] = None
+    norms: Optional[np.ndarray] = None
+    over: Optional[np.ndarray] = None
+    frame_status: Optional[np.ndarray] = None
 
 
 _MAX_ROWS = 64  # rows per frame a 64-bit routing mask can name
@@ -344,6 +374,164 @@ class ShortTime:
         periodic = routed[T + 1]
         return ShortTimeTracks(per_h, pw_h, periodic, x.astype(np.float64) - periodic, wanted, routed[:T], routed[T],
                                self._activity(masks, pw_h, T), counts_h)
+
+    def decompose_ramanujan(self, signal, thresh=0.2, min_length=2, max_length=None, reference="recording",
+                            max_periods=16, tracks=None, max_tracks=8, max_rows=2048):
+        """``RamanujanPeriods.find_periods_with_weights`` followed by ``get_periods`` on every frame, and the per-period
+        waveforms overlap-added onto tracks: -> ShortTimeRamanujan.  Natural basis, no analysis window inside the fit
+        (the ``ShortTime`` window shapes the frames).  `max_length` defaults to ``frame_length // 3``; `tracks` /
+        `max_tracks` / `max_rows` are those of ``decompose_qo``.
+
+        Selection (``PeriodEngine.ramanujan_select``): the candidates of a frame are the periods q with
+        ``norms[q] / level > thresh`` and the `max_periods` (1 .. 64) strongest of them are kept, ties to the smaller
+        period.  `reference` chooses the level:
+          "frame"      the reference's rule: ``|max(norms)|`` of the frame itself, so a near-silent frame selects as many
+                       periods as a loud one, and a frame with a NaN norm selects nothing;
+          "recording"  the largest finite row maximum of the whole recording's norms (silent and NaN frames ignored;
+                       when no frame has a finite positive maximum nothing is selected anywhere);
+          a positive finite float: that value.
+
+        Everything runs on device tensors after the one upload of the signal: ``frames`` -> ``ramanujan_norms`` -> the
+        level (torch, no read-back) -> ``ramanujan_select`` -> ``qo_fit`` on the lists (frames that end PH_ST_CAP are
+        re-run at the next capacity as a gathered sub-batch and scattered back: 512 rows, halved until `max_rows` and the
+        LDS hold them, then doubled, `max_rows` itself being the last step) -> ``qo_get_periods`` and the block powers ->
+        ONE ``overlap_add_periodic`` launch with T + 2 mask rows.  L samples go up; (T + 2) L doubles, the (W, q_hi + 1)
+        norms and the per-frame periods / counts / powers come down.  A frame the device fit does not finish (an
+        ill-conditioned or indefinite dictionary, more rows than `max_rows`) is downloaded, run through the 1-D
+        ``find_periods_with_weights`` with the frame's device list as test function and packed back into the device
+        arrays; such frames are named in one warning.  A frame whose dictionary is singular on the host as well keeps
+        no block.
+
+        Result: the fields of ``ShortTimeTracks`` with ``periods`` / ``powers`` / ``counts`` as in ``decompose_qo``, and
+        ``norms`` (W, q_hi + 1), ``over`` (W) -- candidates before the cap, ``over > counts`` marks a capped frame --
+        and ``frame_status`` (W) int8: 0 fitted on the device, 1 fitted on the host, 2 nothing selected, 3 no fit
+        exists.  Frames of status 2 and 3 contribute nothing to ``periodic``."""
+        import torch
+
+        if isinstance(thresh, bool) or not isinstance(thresh, (int, float, np.integer, np.floating)) or not thresh > 0:
+            raise ValueError(f"thresh={thresh!r}: decompose_ramanujan needs thresh > 0 (period 0 would be selected)")
+        if (isinstance(max_periods, bool) or not isinstance(max_periods, (int, np.integer))
+                or not 1 <= int(max_periods) <= _MAX_ROWS):
+            raise ValueError(f"max_periods={max_periods!r}: decompose_ramanujan needs 1 <= max_periods <= {_MAX_ROWS}")
+        level = None
+        if not (isinstance(reference, str) and reference in ("frame", "recording")):
+            ok = not isinstance(reference, (bool, str)) and isinstance(reference, (int, float, np.integer, np.floating))
+            if not ok or not (reference > 0 and math.isfinite(reference)):
+                raise ValueError(f"reference={reference!r}: must be 'frame', 'recording' or a positive finite number")
+            level = float(reference)
+        max_periods, max_rows, max_tracks, min_length = int(max_periods), int(max_rows), int(max_tracks), int(min_length)
+        if max_rows < 1:
+            raise ValueError("max_rows must be >= 1")
+        if max_tracks < 0:
+            raise ValueError("max_tracks must be >= 0")
+        if min_length < 1:
+            raise ValueError("min_length must be >= 1")
+        wanted = None if tracks is None else self._track_list(tracks)
+        q_hi = self.frame_length // 3 if max_length is None else int(max_length)
+        if q_hi < 1:
+            raise ValueError(f"max_length={q_hi}: decompose_ramanujan needs periods up to at least 1")
+        x, L, W, eng, dev, win, fr = self._device_frames(signal)
+        norms = eng.ramanujan_norms(fr, min_length, q_hi)
+        if reference == "frame":
+            ref = None
+        elif level is not None:
+            ref = torch.full((W,), level, dtype=torch.float64, device=dev)
+        else:
+            rmax = norms.max(dim=1).values  # (a NaN anywhere in a row makes its maximum NaN)
+            rmax = torch.where(torch.isfinite(rmax), rmax, rmax.new_full((), -math.inf)).max()
+            ref = torch.where(rmax > 0, rmax, rmax.new_full((), math.nan)).expand(W).contiguous()
+        per, cnt, over = eng.ramanujan_select(norms, float(thresh), ref, max_periods)
+        keeps, wts, st = self._ram_fit(torch, eng, fr, per, cnt, q_hi, max_rows)
+        cnt_h = cnt.cpu().numpy()
+        blocks, status = self._ram_host_route(torch, fr, (per, keeps, cnt, wts), cnt_h, st, min_length, q_hi)
+        seg, per_h, pw_h, counts_h = self._qo_segments(torch, eng, blocks)
+        if wanted is None:
+            wanted = [(p,) for p in self.rank_periods(per_h, pw_h, counts_h, max_tracks)]
+        T = len(wanted)
+        masks, routed = self._qo_route(torch, eng, seg, blocks, per_h, counts_h, wanted, L, win)
+        periodic = routed[T + 1]
+        return ShortTimeRamanujan(per_h, pw_h, periodic, x.astype(np.float64) - periodic, wanted, routed[:T], routed[T],
+                                  self._activity(masks, pw_h, T), counts_h, norms.cpu().numpy(), over.cpu().numpy(), status)
+
+    def _ram_capacities(self, eng, q_hi, max_rows):
+        """The dictionary-row capacities (kcap) the fit of decompose_ramanujan is given, one after the other: 512 rows,
+        halved until `max_rows` and the plan query accept them, then doubled while both still do -- with `max_rows`
+        itself as the last step when the doubling passes it.  Nothing is yielded when no capacity is feasible."""
+        kcap = 512
+        while kcap > 1 and (kcap > max_rows or not eng.qo_fit_feasible(kcap, q_hi, self.frame_length)):
+            kcap //= 2
+        while kcap <= max_rows and eng.qo_fit_feasible(kcap, q_hi, self.frame_length):
+            yield kcap
+            if kcap == max_rows:
+                return
+            kcap = min(2 * kcap, max_rows)
+
+    def _ram_fit(self, torch, eng, fr, per, cnt, q_hi, max_rows):
+        """``qo_fit`` on the lists per[f, :cnt[f]]; frames that end PH_ST_CAP run again at the next capacity, gathered and
+        scattered back.  -> rows per block and weights on the device, the host status words (PH_ST_CAP everywhere when
+        no capacity is feasible)."""
+        (W, pcap), dev = per.shape, per.device
+        keeps = torch.zeros((W, pcap), dtype=torch.int32, device=dev)
+        wts = torch.zeros((W, 1), dtype=torch.float64, device=dev)
+        st = np.full(W, _ffi.PH_ST_CAP, dtype=np.int32)
+        todo = np.arange(W)
+        for kcap in self._ram_capacities(eng, q_hi, max_rows):
+            whole = todo.size == W
+            idx = None if whole else torch.as_tensor(todo, device=dev)
+            k2, w2, _, s2 = (eng.qo_fit(fr, per, cnt, kcap, q_hi) if whole else
+                             eng.qo_fit(fr[idx], per[idx], cnt[idx], kcap, q_hi))
+            if whole:
+                keeps, wts = k2, w2
+            else:
+                wts = torch.cat([wts, wts.new_zeros((W, kcap - wts.shape[1]))], dim=1)
+                keeps[idx] = k2
+                wts[idx] = w2
+            st[todo] = s2.cpu().numpy()
+            todo = todo[st[todo] == _ffi.PH_ST_CAP]
+            if not todo.size:
+                break
+        return keeps, wts, st
+
+    def _ram_host_route(self, torch, fr, blocks, cnt_h, st, min_length, q_hi):
+        """Frames with a list the device fit did not finish: the 1-D ``find_periods_with_weights`` on the same list,
+        packed into the device arrays; a dictionary that is singular there too keeps no block.  -> the blocks as the
+        extraction takes them and frame_status (W) int8."""
+        from .RamanujanPeriods import RamanujanPeriods
+
+        per, keeps, nb, wts = blocks
+        W, dev = fr.shape[0], fr.device
+        status = np.where(cnt_h <= 0, 2, np.where(st == _ffi.PH_ST_OK, 0, 1)).astype(np.int8)
+        unfinished = np.flatnonzero(status == 1)
+        if unfinished.size:
+            idx = torch.as_tensor(unfinished, device=dev)
+            rows_h, lists_h = fr[idx].cpu().numpy(), per[idx].cpu().numpy()
+            rp = RamanujanPeriods()
+            packed = []
+            for f, row, lst in zip(unfinished, rows_h, lists_h):
+                lst = lst[: cnt_h[f]].astype(np.int64)
+                try:
+                    out, _ = rp.find_periods_with_weights(row, min_length, q_hi, test_function=lambda _norms, lst=lst: lst)
+                except np.linalg.LinAlgError:
+                    status[f] = 3
+                    packed.append(([], [], np.zeros(0)))
+                    continue
+                wt = np.asarray(out["weights"], dtype=np.float64).reshape(-1)
+                packed.append(self._pack_dictionary(wt, out["basis_dictionary"]))
+            kneed = max([wts.shape[1]] + [p[2].size for p in packed])
+            if kneed > wts.shape[1]:
+                wts = torch.cat([wts, wts.new_zeros((W, kneed - wts.shape[1]))], dim=1)
+            hp = np.zeros((unfinished.size, per.shape[1]), np.int32)
+            hk = np.zeros((unfinished.size, per.shape[1]), np.int32)
+            hw = np.zeros((unfinished.size, wts.shape[1]))
+            hn = np.zeros(unfinished.size, np.int32)
+            for j, (ps, ks, ws_) in enumerate(packed):
+                hn[j] = len(ps)
+                hp[j, : len(ps)], hk[j, : len(ps)], hw[j, : ws_.size] = ps, ks, ws_
+            per, keeps, nb = per.clone(), keeps.clone(), nb.clone()
+            per[idx], keeps[idx] = torch.as_tensor(hp, device=dev), torch.as_tensor(hk, device=dev)
+            wts[idx], nb[idx] = torch.as_tensor(hw, device=dev), torch.as_tensor(hn, device=dev)
+            warn(f"decompose_ramanujan: frames {unfinished.tolist()} were not finished by the device fit and ran on the host")
+        return (per.contiguous(), keeps.contiguous(), nb.contiguous(), wts.contiguous()), status
 
     def _qo_fit(self, torch, eng, fr, fit, max_rows):
         """The device fit: frames that end PH_ST_CAP run again at the next capacity; without a feasible capacity every

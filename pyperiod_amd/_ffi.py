@@ -69,6 +69,7 @@ SIGNATURES = {
     "ph_qo_fit": [_vp, _vp, _i, _i64, _i, _pi32, _pi32, _i, _i, _i, _i, _u, _vp, _vp, _vp, _vp],
     "ph_qo_fit_win": [_vp, _vp, _i, _i64, _i, _vp, _pi32, _pi32, _i, _i, _i, _i, _u, _vp, _vp, _vp, _vp],
     "ph_ramanujan_fit": [_vp, _vp, _i, _i64, _i, _i, _i, _d, _i, _i, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ph_ramanujan_select": [_vp, _vp, _i64, _i, _d, _vp, _i, _u, _vp, _vp, _vp],
     "ph_qo_feasible": [_vp, _i, _i, _i, _i, C.POINTER(_i)],
     "ph_qo_plan_info": [_vp, _i, _i, _i, _i, _u, C.POINTER(_i), C.POINTER(_i)],
     "ph_plan_info": [_vp, _i, _i, _i, _pi32, _i, _u, _pi32],

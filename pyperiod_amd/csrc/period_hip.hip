@@ -2361,6 +2361,34 @@ int ph_ramanujan_fit(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int 
   return st.finish();
 }
 
+// ----------------------------------------------------------------------------- capped selection from given norms
+int ph_ramanujan_select(ph_ctx* c, const double* norms, int64_t W, int q_hi, double thresh, const double* ref, int pcap,
+                        unsigned flags, int32_t* periods, int32_t* counts, int32_t* over) {
+  if (!c) return fail(PH_E_ARG, "ctx is NULL");
+  if (!norms) return fail(PH_E_ARG, "norms is NULL");
+  if (!periods || !counts || !over) return fail(PH_E_ARG, "output pointer is NULL");
+  if (W < 1 || W > 0x7fffffffLL / 64) return fail(PH_E_ARG, "W=%lld out of range", (long long)W);
+  if (q_hi < 1) return fail(PH_E_ARG, "need q_hi >= 1 (got %d)", q_hi);
+  if (q_hi >= 30030 || q_hi > 0xffff)
+    return fail(PH_E_ARG, "ph_ramanujan_select: q_hi=%d is beyond the record format of ph_ramanujan_norms", q_hi);
+  if (pcap < 1 || pcap > (1 << 20)) return fail(PH_E_ARG, "pcap=%d must be in [1, 2^20]", pcap);
+  if (!(thresh > 0.0)) return fail(PH_E_ARG, "thresh=%g must be > 0 (index 0 would be selected)", thresh);
+  // W < 2^25, q_hi + 1 <= 30030 and pcap <= 2^20: every byte count below stays under 2^48
+  static_assert(sizeof(size_t) >= 8, "byte counts are 64-bit");
+  PH_HIP(hipSetDevice(c->device));
+  Stage st(c, flags);
+  const void *dnrm, *dref = nullptr;
+  void *dper, *dcnt, *dover;
+  PH_TRY(st.in(norms, (size_t)W * ((size_t)q_hi + 1) * sizeof(double), &dnrm));
+  if (ref) PH_TRY(st.in(ref, (size_t)W * sizeof(double), &dref, B_GWIN));
+  PH_TRY(st.out(B_OUT1, periods, (size_t)W * (size_t)pcap * sizeof(int32_t), &dper));
+  PH_TRY(st.out(B_OUT2, counts, (size_t)W * sizeof(int32_t), &dcnt));
+  PH_TRY(st.out(B_OUT3, over, (size_t)W * sizeof(int32_t), &dover));
+  PH_TRY(launch(c, "k_ram_select_ref", ph::k_ram_select_ref, dim3((unsigned)W), ph::kWave, 0, (const double*)dnrm, q_hi,
+                thresh, (const double*)dref, pcap, (int*)dper, (int*)dcnt, (int*)dover));
+  return st.finish();
+}
+
 // ----------------------------------------------------------------------------- orthogonal period powers
 int ph_orth_powers(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int max_p, int normalize,
                    unsigned flags, double* autocorr, double* eq3, double* powers) {

@@ -2,7 +2,7 @@
 // device: k_qo_fit runs get_subspaces' row bookkeeping, the right-hand side by folds and the matrix-free conjugate
 // gradients of k_qo_find for a list it is handed instead of one it selects greedily; k_qo_fit_win is the same fit under an
 // analysis window (its product goes through a staged sample-length vector); k_ram_select turns Ramanujan norms into that
-// list.  Included by period_hip.hip behind ph_kernels.h (it uses qo_offdiag and qo_gcd of ph_qo.h).  Reference
+// list, k_ram_select_ref does so against a choosable reference level and keeps at most pcap periods.  Included by period_hip.hip behind ph_kernels.h (it uses qo_offdiag and qo_gcd of ph_qo.h).  Reference
 // citations are file:line into /root/reference/pyPeriod/.
 #pragma once
 
@@ -696,6 +696,104 @@ __global__ __launch_bounds__(kWave) void k_ram_select(const double* __restrict__
   }
   for (int k = count + lane; k < pcap; k += kWave) prow[k] = 0;
   if (lane == 0) counts[w] = count;
+}
+
+// A double as a 64-bit key with the order of the doubles (NaN aside): a < b <=> ram_key(a) < ram_key(b), and equal keys
+// <=> equal bits.  Candidates of k_ram_select_ref are never zero, so equal values have equal keys.
+__device__ __forceinline__ unsigned long long ram_key(double v) {
+  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+  return b ^ ((b >> 63) ? ~0ull : 0x8000000000000000ull);
+}
+
+// ======================================================================================
+// k_ram_select against a choosable reference level and with a capped list: one wavefront per window.
+//   m          ref[w] when `ref` is given, otherwise k_ram_select's |max| of the row (a NaN anywhere makes it NaN)
+//   candidates the q in 0 .. q_hi with norms[w, q] / m > thresh -- k_ram_select's IEEE double division and strict
+//              comparison: a NaN entry or quotient is never a candidate, and with thresh > 0 neither is a zero
+//   over[w]    how many candidates there are
+//   kept       all of them when over[w] <= pcap; otherwise q is kept iff fewer than pcap candidates q' have
+//              norms[q'] > norms[q], or norms[q'] == norms[q] and q' < q: the pcap largest, ties to the smaller period
+//   counts[w]  min(over[w], pcap); periods[w, :counts[w]] the kept q ascending, zeros behind them
+// With ref == nullptr and over[w] <= pcap the lists are k_ram_select's bit for bit (the same passes).
+// A row over the cap finds c, the pcap-th largest candidate, by bisection on the 64 bits of ram_key, most significant
+// first -- one strided pass over the row per bit, the row read from global memory / L2 -- and compacts once more:
+// everything > c and the first pcap - #{> c} of the entries == c in ascending q.
+// ======================================================================================
+__global__ __launch_bounds__(kWave) void k_ram_select_ref(const double* __restrict__ norms, int q_hi, double thresh,
+                                                         const double* __restrict__ ref, int pcap,
+                                                         int* __restrict__ periods, int* __restrict__ counts,
+                                                         int* __restrict__ over) {
+  const int64_t w = blockIdx.x;
+  const int lane = threadIdx.x;
+  const double* row = norms + w * (int64_t)(q_hi + 1);
+  double m;
+  if (ref) {
+    m = ref[w];
+  } else {
+    m = -INFINITY;
+    int bad = 0;
+    for (int q = lane; q <= q_hi; q += kWave) {
+      const double v = row[q];
+      bad |= v != v;
+      m = fmax(m, v);
+    }
+    m = wave_max(m);
+    if (__ballot(bad) != 0ull) m = NAN;
+    m = fabs(m);
+  }
+  int* prow = periods + w * (int64_t)pcap;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  int count = 0;
+  for (int q0 = 0; q0 <= q_hi; q0 += kWave) {
+    const int q = q0 + lane;
+    const bool sel = q <= q_hi && row[q <= q_hi ? q : 0] / m > thresh;
+    const unsigned long long mask = __ballot(sel);
+    const int pos = count + __popcll(mask & below);
+    if (sel && pos < pcap) prow[pos] = q;
+    count += __popcll(mask);
+  }
+  if (lane == 0) {
+    over[w] = count;
+    counts[w] = count < pcap ? count : pcap;
+  }
+  if (count <= pcap) {  // (uniform over the wavefront)
+    for (int k = count + lane; k < pcap; k += kWave) prow[k] = 0;
+    return;
+  }
+  // ---- over the cap: c = the largest key that at least pcap candidates reach
+  unsigned long long c = 0ull;
+  for (int bit = 63; bit >= 0; --bit) {
+    const unsigned long long trial = c | (1ull << bit);
+    int n = 0;
+    for (int q0 = 0; q0 <= q_hi; q0 += kWave) {
+      const int q = q0 + lane;
+      const double v = row[q <= q_hi ? q : 0];
+      n += __popcll(__ballot(q <= q_hi && v / m > thresh && ram_key(v) >= trial));
+    }
+    if (n >= pcap) c = trial;
+  }
+  int above = 0;
+  for (int q0 = 0; q0 <= q_hi; q0 += kWave) {
+    const int q = q0 + lane;
+    const double v = row[q <= q_hi ? q : 0];
+    above += __popcll(__ballot(q <= q_hi && v / m > thresh && ram_key(v) > c));
+  }
+  const int ties = pcap - above;  // (>= 1: fewer than pcap candidates lie above c)
+  __syncthreads();                // the first pass wrote prow from other lanes
+  int kept = 0, eq = 0;
+  for (int q0 = 0; q0 <= q_hi; q0 += kWave) {
+    const int q = q0 + lane;
+    const double v = row[q <= q_hi ? q : 0];
+    const bool cand = q <= q_hi && v / m > thresh;
+    const unsigned long long key = ram_key(v);
+    const unsigned long long eqm = __ballot(cand && key == c);
+    const bool sel = cand && (key > c || (key == c && eq + __popcll(eqm & below) < ties));
+    const unsigned long long mask = __ballot(sel);
+    const int pos = kept + __popcll(mask & below);
+    if (sel && pos < pcap) prow[pos] = q;
+    kept += __popcll(mask);
+    eq += __popcll(eqm);
+  }
 }
 
 // ======================================================================================

@@ -568,6 +568,30 @@ class PeriodEngine:
                    mk.addr(status))
         return norms, periods, counts, keeps, weights, resid, status
 
+    def ramanujan_select(self, norms, thresh, ref=None, pcap=64):
+        """The threshold of ramanujan_fit on given norms (W, q_hi + 1) float64, against a choosable level and capped
+        (ph_ramanujan_select, one launch): -> periods (W, pcap) i32, counts (W) i32, over (W) i32.
+        Candidates of row w are the q with norms[w, q] / m > thresh, m = ref[w] or -- `ref` None -- |max| of the row as
+        numpy.max sees it; over[w] counts them.  At most `pcap` are kept: the largest norms, ties to the smaller
+        period; counts[w] = min(over[w], pcap) and periods[w, :counts[w]] lists them ascending, zeros behind.
+        `ref`: None or W float64 levels.  numpy in, numpy out; a float64 tensor on the engine's device (then `ref` is a
+        float64 tensor there too) gives tensors on torch's current stream."""
+        x, code, W, n, fl, mk = self._prep(norms if _is_torch(norms) else np.asarray(norms, dtype=np.float64))
+        if code != _ffi.PH_F64:
+            raise TypeError("norms must be float64")
+        rf = None
+        if ref is not None:
+            rf = _side(mk, x, ref, np.float64, "ref", "norms")
+            if tuple(rf.shape) != (W,):
+                raise ValueError("ref must hold one level per row")
+        pcap = int(pcap)
+        periods = mk.empty((W, max(pcap, 0)), np.int32)
+        counts = mk.empty((W,), np.int32)
+        over = mk.empty((W,), np.int32)
+        self._call(mk, W, self._lib.ph_ramanujan_select, mk.addr(x), W, n - 1, float(thresh), mk.addr(rf), pcap, fl,
+                   mk.addr(periods), mk.addr(counts), mk.addr(over))
+        return periods, counts, over
+
     def orth_powers(self, x, max_p=None, normalize=False, want_autocorr=False, want_eq3=False):
         """Orthogonal period powers (QOPeriods.get_best_period_orthogonal(return_powers=True)).
         -> pows (W, max_p) [, autocorr (W, N)] [, eq3 (W, max_p)]."""

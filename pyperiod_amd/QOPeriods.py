@@ -136,6 +136,31 @@ def _qo_capacities(eng, n, dtype, num, max_length, update_weights, max_rows=None
         kcap *= step
 
 
+def _qo_fit_start(feasible):
+    """The first capacity (kcap) ph_qo_fit / ph_ramanujan_fit are given where nothing caps it: 512 rows, halved while
+    above 64 and not `feasible`.  -> that capacity, or None when it is not feasible either."""
+    kcap = 512
+    while kcap > 64 and not feasible(kcap):
+        kcap //= 2
+    return kcap if feasible(kcap) else None
+
+
+def _ram_capacities(eng, n, max_period, max_rows):
+    """The dictionary-row capacities (kcap) ph_qo_fit is given by ``ShortTime.decompose_ramanujan`` for frames of `n`
+    samples and periods up to `max_period`, one after the other: 512 rows, halved until `max_rows` and the plan query
+    accept them (down to 1, not 64 as in ``_qo_fit_start``: `max_rows` may ask for less), then doubled while both still
+    do -- with `max_rows` itself as the last step when the doubling passes it.  Nothing is yielded when no capacity is
+    feasible."""
+    kcap = 512
+    while kcap > 1 and (kcap > max_rows or not eng.qo_fit_feasible(kcap, max_period, n)):
+        kcap //= 2
+    while kcap <= max_rows and eng.qo_fit_feasible(kcap, max_period, n):
+        yield kcap
+        if kcap == max_rows:
+            return
+        kcap = min(2 * kcap, max_rows)
+
+
 class _LazyBases(dict):
     """The output_bases dict of one row of a batched find_periods.  Its "subspaces" entry -- the stacked
     natural-basis rows of the dictionary blocks, rows x N doubles -- is built from the blocks on first read and
@@ -643,10 +668,8 @@ class QOPeriods(Periods):
             return todo[(st == _ffi.PH_ST_CAP) & (counts[todo] <= per.shape[1])]
 
         if first is None:
-            kcap = 512
-            while kcap > 64 and not feasible(kcap):
-                kcap //= 2
-            if not feasible(kcap):
+            kcap = _qo_fit_start(feasible)
+            if kcap is None:
                 return out
             todo = np.arange(W)
             todo = take(todo, kcap, *eng.qo_fit(x, per, counts, kcap, max_period, window))

@@ -14,7 +14,7 @@ import numpy as np
 from ._factors import get_factors, phi  # noqa: F401
 from .engine import default_engine
 from .Periods import _as_window, rms  # noqa: F401
-from .QOPeriods import QOPeriods, _LazyBases, flatten, ramanujan_sum  # noqa: F401
+from .QOPeriods import QOPeriods, _LazyBases, _qo_fit_start, flatten, ramanujan_sum  # noqa: F401
 
 
 class RamanujanPeriods(QOPeriods):
@@ -90,10 +90,8 @@ class RamanujanPeriods(QOPeriods):
             q_hi = int(max_length) if max_length else N // 3
             eng = default_engine()
             if select is None:
-                kcap = 512
-                while kcap > 64 and not eng.qo_fit_feasible(kcap, q_hi):
-                    kcap //= 2
-                if eng.qo_fit_feasible(kcap, q_hi):
+                kcap = _qo_fit_start(lambda k: eng.qo_fit_feasible(k, q_hi))
+                if kcap is not None:
                     norms, per, counts, keeps, wts, resid, st = eng.ramanujan_fit(x, int(min_length), q_hi, thresh, 64, kcap)
                     fits = self._fit_lists_device(eng, x, per, counts, q_hi, first=(kcap, keeps, wts, resid, st))
                     lists = [per[w, : min(int(counts[w]), 64)].astype(np.int64) for w in range(W)]

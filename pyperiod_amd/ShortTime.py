@@ -294,10 +294,7 @@ class ShortTime:
         method has run, so there the check comes after the method's kernels and before the two overlap-adds."""
         if method not in _METHODS:
             raise ValueError(f"method must be one of {_METHODS}")
-        wanted = None if tracks is None else self._track_list(tracks)
-        max_tracks = int(max_tracks)
-        if max_tracks < 0:
-            raise ValueError("max_tracks must be >= 0")
+        wanted, max_tracks, _, _ = self._track_args(tracks, max_tracks, tracks_first=True)
         if method != "small_to_large" and int(kwargs.get("num", 5)) > _MAX_ROWS:
             raise ValueError(f"num={int(kwargs['num'])} bases per frame: decompose routes at most {_MAX_ROWS}")
         x64, L, W, eng, win, num, per, pw, bases, counts = self._run(signal, method, kwargs)
@@ -354,26 +351,14 @@ class ShortTime:
             raise ValueError("decompose_qo: orthogonal selection is stepped from the host and not offered here")
         if isinstance(num, bool) or not isinstance(num, (int, np.integer)) or not 1 <= int(num) <= _MAX_ROWS:
             raise ValueError(f"num={num!r}: decompose_qo needs 1 <= num <= {_MAX_ROWS} blocks per frame")
-        num, max_rows, max_tracks = int(num), int(max_rows), int(max_tracks)
-        if max_rows < 1:
-            raise ValueError("max_rows must be >= 1")
-        if max_tracks < 0:
-            raise ValueError("max_tracks must be >= 0")
-        wanted = None if tracks is None else self._track_list(tracks)
+        wanted, max_tracks, max_rows, _ = self._track_args(tracks, max_tracks, max_rows)
         max_length = self.frame_length // 3 if max_length is None else int(max_length)
-        fit = (num, thresh, int(min_length), max_length, bool(update_weights))
+        fit = (int(num), thresh, int(min_length), max_length, bool(update_weights))
         x, L, W, eng, dev, win, fr = self._device_frames(signal)
         silent = (fr.to(torch.float64).abs().sum(dim=1) <= 1e-16).cpu().numpy()
         blocks, st = self._qo_fit(torch, eng, fr, fit, max_rows)
         blocks = self._qo_host_route(torch, fr, silent, st, blocks, fit)
-        seg, per_h, pw_h, counts_h = self._qo_segments(torch, eng, blocks)
-        if wanted is None:
-            wanted = [(p,) for p in self.rank_periods(per_h, pw_h, counts_h, max_tracks)]
-        T = len(wanted)
-        masks, routed = self._qo_route(torch, eng, seg, blocks, per_h, counts_h, wanted, L, win)
-        periodic = routed[T + 1]
-        return ShortTimeTracks(per_h, pw_h, periodic, x.astype(np.float64) - periodic, wanted, routed[:T], routed[T],
-                               self._activity(masks, pw_h, T), counts_h)
+        return ShortTimeTracks(*self._block_tracks(torch, eng, blocks, wanted, max_tracks, x, L, win))
 
     def decompose_ramanujan(self, signal, thresh=0.2, min_length=2, max_length=None, reference="recording",
                             max_periods=16, tracks=None, max_tracks=8, max_rows=2048):
@@ -419,14 +404,7 @@ class ShortTime:
             if not ok or not (reference > 0 and math.isfinite(reference)):
                 raise ValueError(f"reference={reference!r}: must be 'frame', 'recording' or a positive finite number")
             level = float(reference)
-        max_periods, max_rows, max_tracks, min_length = int(max_periods), int(max_rows), int(max_tracks), int(min_length)
-        if max_rows < 1:
-            raise ValueError("max_rows must be >= 1")
-        if max_tracks < 0:
-            raise ValueError("max_tracks must be >= 0")
-        if min_length < 1:
-            raise ValueError("min_length must be >= 1")
-        wanted = None if tracks is None else self._track_list(tracks)
+        wanted, max_tracks, max_rows, min_length = self._track_args(tracks, max_tracks, max_rows, min_length)
         q_hi = self.frame_length // 3 if max_length is None else int(max_length)
         if q_hi < 1:
             raise ValueError(f"max_length={q_hi}: decompose_ramanujan needs periods up to at least 1")
@@ -440,56 +418,85 @@ class ShortTime:
             rmax = norms.max(dim=1).values  # (a NaN anywhere in a row makes its maximum NaN)
             rmax = torch.where(torch.isfinite(rmax), rmax, rmax.new_full((), -math.inf)).max()
             ref = torch.where(rmax > 0, rmax, rmax.new_full((), math.nan)).expand(W).contiguous()
-        per, cnt, over = eng.ramanujan_select(norms, float(thresh), ref, max_periods)
+        per, cnt, over = eng.ramanujan_select(norms, float(thresh), ref, int(max_periods))
         keeps, wts, st = self._ram_fit(torch, eng, fr, per, cnt, q_hi, max_rows)
         cnt_h = cnt.cpu().numpy()
         blocks, status = self._ram_host_route(torch, fr, (per, keeps, cnt, wts), cnt_h, st, min_length, q_hi)
+        tail = self._block_tracks(torch, eng, blocks, wanted, max_tracks, x, L, win)
+        return ShortTimeRamanujan(*tail, norms.cpu().numpy(), over.cpu().numpy(), status)
+
+    @staticmethod
+    def _track_args(tracks, max_tracks, max_rows=1, min_length=1, tracks_first=False):
+        """The arguments the decompose methods share, checked once: -> (track list or None, max_tracks, max_rows,
+        min_length), the last three as ints.  Which refusal comes first is part of each method's surface:
+        ``decompose`` reads `tracks` first (`tracks_first`), the block pipelines last."""
+        wanted = ShortTime._track_list(tracks) if tracks_first and tracks is not None else None
+        max_rows, max_tracks, min_length = int(max_rows), int(max_tracks), int(min_length)
+        if max_rows < 1:
+            raise ValueError("max_rows must be >= 1")
+        if max_tracks < 0:
+            raise ValueError("max_tracks must be >= 0")
+        if min_length < 1:
+            raise ValueError("min_length must be >= 1")
+        if not tracks_first and tracks is not None:
+            wanted = ShortTime._track_list(tracks)
+        return wanted, max_tracks, max_rows, min_length
+
+    def _block_tracks(self, torch, eng, blocks, wanted, max_tracks, x, L, win):
+        """The tail of the block pipelines: one period per block, the tracks (ranked when none were named) and the one
+        routed overlap-add.  -> the nine fields of ShortTimeTracks, in order."""
         seg, per_h, pw_h, counts_h = self._qo_segments(torch, eng, blocks)
         if wanted is None:
             wanted = [(p,) for p in self.rank_periods(per_h, pw_h, counts_h, max_tracks)]
         T = len(wanted)
         masks, routed = self._qo_route(torch, eng, seg, blocks, per_h, counts_h, wanted, L, win)
         periodic = routed[T + 1]
-        return ShortTimeRamanujan(per_h, pw_h, periodic, x.astype(np.float64) - periodic, wanted, routed[:T], routed[T],
-                                  self._activity(masks, pw_h, T), counts_h, norms.cpu().numpy(), over.cpu().numpy(), status)
+        return (per_h, pw_h, periodic, x.astype(np.float64) - periodic, wanted, routed[:T], routed[T],
+                self._activity(masks, pw_h, T), counts_h)
 
-    def _ram_capacities(self, eng, q_hi, max_rows):
-        """The dictionary-row capacities (kcap) the fit of decompose_ramanujan is given, one after the other: 512 rows,
-        halved until `max_rows` and the plan query accept them, then doubled while both still do -- with `max_rows`
-        itself as the last step when the doubling passes it.  Nothing is yielded when no capacity is feasible."""
-        kcap = 512
-        while kcap > 1 and (kcap > max_rows or not eng.qo_fit_feasible(kcap, q_hi, self.frame_length)):
-            kcap //= 2
-        while kcap <= max_rows and eng.qo_fit_feasible(kcap, q_hi, self.frame_length):
-            yield kcap
-            if kcap == max_rows:
-                return
-            kcap = min(2 * kcap, max_rows)
-
-    def _ram_fit(self, torch, eng, fr, per, cnt, q_hi, max_rows):
-        """``qo_fit`` on the lists per[f, :cnt[f]]; frames that end PH_ST_CAP run again at the next capacity, gathered and
-        scattered back.  -> rows per block and weights on the device, the host status words (PH_ST_CAP everywhere when
-        no capacity is feasible)."""
-        (W, pcap), dev = per.shape, per.device
-        keeps = torch.zeros((W, pcap), dtype=torch.int32, device=dev)
-        wts = torch.zeros((W, 1), dtype=torch.float64, device=dev)
+    @staticmethod
+    def _rerun_capped(torch, dev, W, capacities, tensors, launch):
+        """The capacity loop of the block pipelines.  `tensors`: the zero-initialised whole-batch results, the weights
+        (W, 1) last; ``launch(idx, kcap)`` runs the frames `idx` (None: all of them, otherwise a device index tensor) at
+        `kcap` dictionary rows and returns their tensors in that order and the device status words.  The first capacity
+        runs the whole batch and its tensors are adopted as they are; every later one runs the frames whose last status
+        was PH_ST_CAP, gathered by `launch` and scattered back here, the weights widened to `kcap` columns.  One status
+        read-back per capacity.  -> the tensors and the host status words (PH_ST_CAP everywhere, and the zero tensors,
+        when `capacities` is empty; a frame still PH_ST_CAP at the end keeps its last attempt)."""
+        tensors = list(tensors)
         st = np.full(W, _ffi.PH_ST_CAP, dtype=np.int32)
         todo = np.arange(W)
-        for kcap in self._ram_capacities(eng, q_hi, max_rows):
-            whole = todo.size == W
-            idx = None if whole else torch.as_tensor(todo, device=dev)
-            k2, w2, _, s2 = (eng.qo_fit(fr, per, cnt, kcap, q_hi) if whole else
-                             eng.qo_fit(fr[idx], per[idx], cnt[idx], kcap, q_hi))
-            if whole:
-                keeps, wts = k2, w2
+        for kcap in capacities:
+            idx = None if todo.size == W else torch.as_tensor(todo, device=dev)
+            *got, s2 = launch(idx, kcap)
+            if idx is None:
+                tensors = got
             else:
-                wts = torch.cat([wts, wts.new_zeros((W, kcap - wts.shape[1]))], dim=1)
-                keeps[idx] = k2
-                wts[idx] = w2
+                wts = tensors[-1]
+                tensors[-1] = torch.cat([wts, wts.new_zeros((W, kcap - wts.shape[1]))], dim=1)
+                for whole, part in zip(tensors, got):
+                    whole[idx] = part
             st[todo] = s2.cpu().numpy()
             todo = todo[st[todo] == _ffi.PH_ST_CAP]
             if not todo.size:
                 break
+        return tensors, st
+
+    def _ram_fit(self, torch, eng, fr, per, cnt, q_hi, max_rows):
+        """``qo_fit`` on the lists per[f, :cnt[f]] at the capacities of ``_ram_capacities`` (``_rerun_capped``).
+        -> rows per block and weights on the device, the host status words."""
+        from .QOPeriods import _ram_capacities
+
+        def launch(idx, kcap):
+            k2, w2, _, s2 = (eng.qo_fit(fr, per, cnt, kcap, q_hi) if idx is None else
+                             eng.qo_fit(fr[idx], per[idx], cnt[idx], kcap, q_hi))
+            return k2, w2, s2
+
+        (W, pcap), dev = per.shape, per.device
+        zeros = (torch.zeros((W, pcap), dtype=torch.int32, device=dev),
+                 torch.zeros((W, 1), dtype=torch.float64, device=dev))
+        (keeps, wts), st = self._rerun_capped(
+            torch, dev, W, _ram_capacities(eng, self.frame_length, q_hi, max_rows), zeros, launch)
         return keeps, wts, st
 
     def _ram_host_route(self, torch, fr, blocks, cnt_h, st, min_length, q_hi):
@@ -499,11 +506,10 @@ class ShortTime:
         from .RamanujanPeriods import RamanujanPeriods
 
         per, keeps, nb, wts = blocks
-        W, dev = fr.shape[0], fr.device
         status = np.where(cnt_h <= 0, 2, np.where(st == _ffi.PH_ST_OK, 0, 1)).astype(np.int8)
         unfinished = np.flatnonzero(status == 1)
         if unfinished.size:
-            idx = torch.as_tensor(unfinished, device=dev)
+            idx = torch.as_tensor(unfinished, device=fr.device)
             rows_h, lists_h = fr[idx].cpu().numpy(), per[idx].cpu().numpy()
             rp = RamanujanPeriods()
             packed = []
@@ -517,51 +523,31 @@ class ShortTime:
                     continue
                 wt = np.asarray(out["weights"], dtype=np.float64).reshape(-1)
                 packed.append(self._pack_dictionary(wt, out["basis_dictionary"]))
-            kneed = max([wts.shape[1]] + [p[2].size for p in packed])
-            if kneed > wts.shape[1]:
-                wts = torch.cat([wts, wts.new_zeros((W, kneed - wts.shape[1]))], dim=1)
-            hp = np.zeros((unfinished.size, per.shape[1]), np.int32)
-            hk = np.zeros((unfinished.size, per.shape[1]), np.int32)
-            hw = np.zeros((unfinished.size, wts.shape[1]))
-            hn = np.zeros(unfinished.size, np.int32)
-            for j, (ps, ks, ws_) in enumerate(packed):
-                hn[j] = len(ps)
-                hp[j, : len(ps)], hk[j, : len(ps)], hw[j, : ws_.size] = ps, ks, ws_
-            per, keeps, nb = per.clone(), keeps.clone(), nb.clone()
-            per[idx], keeps[idx] = torch.as_tensor(hp, device=dev), torch.as_tensor(hk, device=dev)
-            wts[idx], nb[idx] = torch.as_tensor(hw, device=dev), torch.as_tensor(hn, device=dev)
+            # (the lists and counts are ramanujan_select's own tensors: the host results go into copies)
+            blocks = (per.clone(), keeps.clone(), nb.clone(), wts)
+            per, keeps, nb, wts = self._pack_back(torch, blocks, unfinished, packed)
             warn(f"decompose_ramanujan: frames {unfinished.tolist()} were not finished by the device fit and ran on the host")
         return (per.contiguous(), keeps.contiguous(), nb.contiguous(), wts.contiguous()), status
 
     def _qo_fit(self, torch, eng, fr, fit, max_rows):
-        """The device fit: frames that end PH_ST_CAP run again at the next capacity; without a feasible capacity every
+        """The device fit at the capacities of ``_qo_capacities`` (``_rerun_capped``); without a feasible capacity every
         frame goes the way of the unfinished ones.  -> (periods, rows, blocks per frame, weights) on the device and the
         host status words."""
         from .QOPeriods import _qo_capacities
 
         num, thresh, min_length, max_length, uw = fit
         (W, N), dev, trunc = fr.shape, fr.device, self._trunc_to_integer_multiple
-        per = torch.zeros((W, num), dtype=torch.int32, device=dev)
-        keeps = torch.zeros((W, num), dtype=torch.int32, device=dev)
-        nb = torch.zeros((W,), dtype=torch.int32, device=dev)
-        wts = torch.zeros((W, 1), dtype=torch.float64, device=dev)
-        st = np.full(W, _ffi.PH_ST_CAP, dtype=np.int32)
-        todo = np.arange(W)
-        for kcap in _qo_capacities(eng, N, self.dtype, num, max_length, uw, max_rows):
-            whole = todo.size == W
-            idx = None if whole else torch.as_tensor(todo, device=dev)
-            p2, _, k2, c2, w2, _, s2 = eng.qo_find_periods(fr if whole else fr[idx], num, thresh, min_length, max_length,
-                                                           kcap, trunc=trunc, update_weights=uw)
-            if whole:
-                per, keeps, nb, wts = p2, k2, c2[:, 1].contiguous(), w2
-            else:
-                wts = torch.cat([wts, wts.new_zeros((W, kcap - wts.shape[1]))], dim=1)
-                per[idx], keeps[idx], nb[idx] = p2, k2, c2[:, 1]
-                wts[idx] = w2
-            st[todo] = s2.cpu().numpy()
-            todo = todo[st[todo] == _ffi.PH_ST_CAP]
-            if not todo.size:
-                break
+
+        def launch(idx, kcap):
+            p2, _, k2, c2, w2, _, s2 = eng.qo_find_periods(fr if idx is None else fr[idx], num, thresh, min_length,
+                                                           max_length, kcap, trunc=trunc, update_weights=uw)
+            nb2 = c2[:, 1]
+            return p2, k2, nb2.contiguous() if idx is None else nb2, w2, s2
+
+        zeros = [torch.zeros(shape, dtype=torch.int32, device=dev) for shape in ((W, num), (W, num), (W,))]
+        zeros.append(torch.zeros((W, 1), dtype=torch.float64, device=dev))
+        (per, keeps, nb, wts), st = self._rerun_capped(
+            torch, dev, W, _qo_capacities(eng, N, self.dtype, num, max_length, uw, max_rows), zeros, launch)
         if not uw:  # a keeps entry of 0 stands for `period` rows
             keeps = torch.where(keeps == 0, per, keeps)
         return (per, keeps, nb, wts), st
@@ -573,7 +559,7 @@ class ShortTime:
 
         num, thresh, min_length, max_length, uw = fit
         per, keeps, nb, wts = blocks
-        W, dev, trunc = fr.shape[0], fr.device, self._trunc_to_integer_multiple
+        dev, trunc = fr.device, self._trunc_to_integer_multiple
         nb_h = nb.cpu().numpy()
         unfinished = np.flatnonzero(~silent & ((st != _ffi.PH_ST_OK) | (nb_h == 0)))
         if unfinished.size:
@@ -593,28 +579,38 @@ class ShortTime:
             pcap = max([num] + [len(p[0]) for p in packed])
             if pcap > _MAX_ROWS:
                 raise ValueError(f"{pcap} blocks in frame {int(unfinished[0])}: decompose_qo routes at most {_MAX_ROWS}")
-            kneed = max([wts.shape[1]] + [p[2].size for p in packed])
-            if pcap > num:
-                per = torch.cat([per, per.new_zeros((W, pcap - num))], dim=1)
-                keeps = torch.cat([keeps, keeps.new_zeros((W, pcap - num))], dim=1)
-            if kneed > wts.shape[1]:
-                wts = torch.cat([wts, wts.new_zeros((W, kneed - wts.shape[1]))], dim=1)
-            hp = np.zeros((unfinished.size, pcap), np.int32)
-            hk = np.zeros((unfinished.size, pcap), np.int32)
-            hw = np.zeros((unfinished.size, wts.shape[1]))
-            hn = np.zeros(unfinished.size, np.int32)
-            for j, (ps, ks, ws_) in enumerate(packed):
-                hn[j] = len(ps)
-                hp[j, : len(ps)], hk[j, : len(ps)], hw[j, : ws_.size] = ps, ks, ws_
-            idx = torch.as_tensor(unfinished, device=dev)
-            per[idx], keeps[idx] = torch.as_tensor(hp, device=dev), torch.as_tensor(hk, device=dev)
-            wts[idx], nb[idx] = torch.as_tensor(hw, device=dev), torch.as_tensor(hn, device=dev)
+            per, keeps, nb, wts = self._pack_back(torch, (per, keeps, nb, wts), unfinished, packed)
             warn(f"decompose_qo: frames {unfinished.tolist()} were not finished by the device loop and ran on the host")
         if silent.any():
             nb[torch.as_tensor(np.flatnonzero(silent), device=dev)] = 0
         if not uw:  # the fixed-weight loop lists a period once per fit: one block per period for the extraction
             per, keeps, nb, wts = self._merge_repeats(torch, per, keeps, nb, wts, max(max_length, 1))
         per, keeps, nb, wts = per.contiguous(), keeps.contiguous(), nb.contiguous(), wts.contiguous()
+        return per, keeps, nb, wts
+
+    @staticmethod
+    def _pack_back(torch, blocks, unfinished, packed):
+        """The host results of the frames `unfinished` -- one ``_pack_dictionary`` triple each -- written into the device
+        blocks (periods, rows, blocks per frame, weights): the first two widened to the longest list, the weights to the
+        longest weight vector, zeros behind what a frame uses.  The tensors are written in place where they are wide
+        enough.  -> the four tensors."""
+        per, keeps, nb, wts = blocks
+        W, dev, n = per.shape[0], per.device, len(packed)
+        pcap = max([per.shape[1]] + [len(p[0]) for p in packed])
+        kneed = max([wts.shape[1]] + [p[2].size for p in packed])
+        if pcap > per.shape[1]:
+            per = torch.cat([per, per.new_zeros((W, pcap - per.shape[1]))], dim=1)
+            keeps = torch.cat([keeps, keeps.new_zeros((W, pcap - keeps.shape[1]))], dim=1)
+        if kneed > wts.shape[1]:
+            wts = torch.cat([wts, wts.new_zeros((W, kneed - wts.shape[1]))], dim=1)
+        hp, hk = np.zeros((n, pcap), np.int32), np.zeros((n, pcap), np.int32)
+        hw, hn = np.zeros((n, kneed)), np.zeros(n, np.int32)
+        for j, (ps, ks, ws_) in enumerate(packed):
+            hn[j] = len(ps)
+            hp[j, : len(ps)], hk[j, : len(ps)], hw[j, : ws_.size] = ps, ks, ws_
+        idx = torch.as_tensor(unfinished, device=dev)
+        per[idx], keeps[idx] = torch.as_tensor(hp, device=dev), torch.as_tensor(hk, device=dev)
+        wts[idx], nb[idx] = torch.as_tensor(hw, device=dev), torch.as_tensor(hn, device=dev)
         return per, keeps, nb, wts
 
     @staticmethod

@@ -663,17 +663,9 @@ __global__ __launch_bounds__(1024) void k_qo_fit_win(const T* __restrict__ x, in
   if (tid == 0) status_out[w] = 0;
 }
 
-// ======================================================================================
-// The threshold of RamanujanPeriods.find_periods_with_weights (RamanujanPeriods.py:95-99): one wavefront per window.
-// m = |max_q norms[w, q]| over the whole row as numpy.max sees it (a NaN anywhere makes it NaN), then the ascending
-// list of the q with norms[w, q] / m > thresh -- that IEEE double division and strict comparison, so NaN is never
-// selected.  counts[w] = how many there are (also beyond pcap), periods[w, :] the first pcap of them.
-// ======================================================================================
-__global__ __launch_bounds__(kWave) void k_ram_select(const double* __restrict__ norms, int q_hi, double thresh, int pcap,
-                                                     int* __restrict__ periods, int* __restrict__ counts) {
-  const int64_t w = blockIdx.x;
-  const int lane = threadIdx.x;
-  const double* row = norms + w * (int64_t)(q_hi + 1);
+// The two passes k_ram_select and k_ram_select_ref share, one wavefront per row.
+// The level of a row as numpy.max sees it: |max_q row[q]| over q in 0 .. q_hi, NaN when any entry is NaN.
+__device__ __forceinline__ double ram_row_level(const double* __restrict__ row, int q_hi, int lane) {
   double m = -INFINITY;
   int bad = 0;
   for (int q = lane; q <= q_hi; q += kWave) {
@@ -683,8 +675,14 @@ __global__ __launch_bounds__(kWave) void k_ram_select(const double* __restrict__
   }
   m = wave_max(m);
   if (__ballot(bad) != 0ull) m = NAN;
-  m = fabs(m);
-  int* prow = periods + w * (int64_t)pcap;
+  return fabs(m);
+}
+
+// The candidates of a row -- the q in 0 .. q_hi with row[q] / m > thresh -- compacted in ascending q by ballot and
+// popcount: prow[pos] = q for the candidates at positions pos < pcap.  -> how many there are (also beyond pcap), the
+// same number in every lane.
+__device__ __forceinline__ int ram_compact_candidates(const double* __restrict__ row, int q_hi, double m, double thresh,
+                                                      int pcap, int lane, int* __restrict__ prow) {
   int count = 0;
   for (int q0 = 0; q0 <= q_hi; q0 += kWave) {
     const int q = q0 + lane;
@@ -694,6 +692,24 @@ __global__ __launch_bounds__(kWave) void k_ram_select(const double* __restrict__
     if (sel && pos < pcap) prow[pos] = q;
     count += __popcll(mask);
   }
+  return count;
+}
+
+// ======================================================================================
+// The threshold of RamanujanPeriods.find_periods_with_weights (RamanujanPeriods.py:95-99): one wavefront per window.
+// m = |max_q norms[w, q]| over the whole row as numpy.max sees it (a NaN anywhere makes it NaN: ram_row_level), then the
+// ascending list of the q with norms[w, q] / m > thresh -- that IEEE double division and strict comparison, so NaN is
+// never selected (ram_compact_candidates).  counts[w] = how many there are (also beyond pcap), periods[w, :] the first
+// pcap of them.
+// ======================================================================================
+__global__ __launch_bounds__(kWave) void k_ram_select(const double* __restrict__ norms, int q_hi, double thresh, int pcap,
+                                                     int* __restrict__ periods, int* __restrict__ counts) {
+  const int64_t w = blockIdx.x;
+  const int lane = threadIdx.x;
+  const double* row = norms + w * (int64_t)(q_hi + 1);
+  const double m = ram_row_level(row, q_hi, lane);
+  int* prow = periods + w * (int64_t)pcap;
+  const int count = ram_compact_candidates(row, q_hi, m, thresh, pcap, lane, prow);
   for (int k = count + lane; k < pcap; k += kWave) prow[k] = 0;
   if (lane == 0) counts[w] = count;
 }
@@ -714,7 +730,8 @@ __device__ __forceinline__ unsigned long long ram_key(double v) {
 //   kept       all of them when over[w] <= pcap; otherwise q is kept iff fewer than pcap candidates q' have
 //              norms[q'] > norms[q], or norms[q'] == norms[q] and q' < q: the pcap largest, ties to the smaller period
 //   counts[w]  min(over[w], pcap); periods[w, :counts[w]] the kept q ascending, zeros behind them
-// With ref == nullptr and over[w] <= pcap the lists are k_ram_select's bit for bit (the same passes).
+// With ref == nullptr and over[w] <= pcap the lists are k_ram_select's bit for bit: both kernels call ram_row_level and
+// ram_compact_candidates.
 // A row over the cap finds c, the pcap-th largest candidate, by bisection on the 64 bits of ram_key, most significant
 // first -- one strided pass over the row per bit, the row read from global memory / L2 -- and compacts once more:
 // everything > c and the first pcap - #{> c} of the entries == c in ascending q.
@@ -726,32 +743,10 @@ __global__ __launch_bounds__(kWave) void k_ram_select_ref(const double* __restri
   const int64_t w = blockIdx.x;
   const int lane = threadIdx.x;
   const double* row = norms + w * (int64_t)(q_hi + 1);
-  double m;
-  if (ref) {
-    m = ref[w];
-  } else {
-    m = -INFINITY;
-    int bad = 0;
-    for (int q = lane; q <= q_hi; q += kWave) {
-      const double v = row[q];
-      bad |= v != v;
-      m = fmax(m, v);
-    }
-    m = wave_max(m);
-    if (__ballot(bad) != 0ull) m = NAN;
-    m = fabs(m);
-  }
+  const double m = ref ? ref[w] : ram_row_level(row, q_hi, lane);
   int* prow = periods + w * (int64_t)pcap;
   const unsigned long long below = (1ull << lane) - 1ull;
-  int count = 0;
-  for (int q0 = 0; q0 <= q_hi; q0 += kWave) {
-    const int q = q0 + lane;
-    const bool sel = q <= q_hi && row[q <= q_hi ? q : 0] / m > thresh;
-    const unsigned long long mask = __ballot(sel);
-    const int pos = count + __popcll(mask & below);
-    if (sel && pos < pcap) prow[pos] = q;
-    count += __popcll(mask);
-  }
+  const int count = ram_compact_candidates(row, q_hi, m, thresh, pcap, lane, prow);
   if (lane == 0) {
     over[w] = count;
     counts[w] = count < pcap ? count : pcap;

@@ -1,5 +1,5 @@
 // Drives ph_ramanujan_select through the HOST half of the library (hip_stub.cpp stands in for the runtime; kernels do not
-// run, outputs are not looked at).  Built with -fsanitize=address,undefined by tests/test_host_sanitizers_ram_select.py:
+// run, outputs are not looked at).  Built with -fsanitize=address,undefined by tests/test_host_sanitizers.py:
 // argument validation, the staging of the norms and the optional reference levels and of the three int32 outputs must
 // touch no byte out of bounds -- at pcap = 2^20 too, and the size arithmetic with W * (q_hi + 1) * 8 beyond 2^31 --,
 // every refusal comes before a launch, and an accepted call launches k_ram_select_ref once: one wavefront per row, no

@@ -11,7 +11,7 @@ import pytest
 from conftest import rel_err
 from oracle import period_oracle as po
 from pyperiod_amd import QOPeriods, _ffi
-from pyperiod_amd.QOPeriods import _qo_capacities
+from pyperiod_amd.QOPeriods import _qo_capacities, _qo_fit_start, _ram_capacities
 from pyperiod_amd.synth import multi_sinusoid_window
 from test_qo_orth_cpu import group_kw
 from test_qo_window_cpu import windowed_solve
@@ -295,6 +295,10 @@ class PlanStub:
         self.asked.append(kcap)
         return kcap <= self.rows
 
+    def qo_fit_feasible(self, kcap, max_period, n=None, window=False):
+        self.asked.append(kcap)
+        return kcap <= self.rows
+
 
 # (num, max_length, update_weights, max_rows, feasible up to) -> the capacities, worked out by hand: bound = num *
 # max_length, room = bound rounded up to a multiple of 64 and at least 64
@@ -333,3 +337,32 @@ def test_capacity_ladder_asks_only_as_far_as_the_caller_goes():
     eng = PlanStub(2048)
     caps = _qo_capacities(eng, 600, np.float64, 4, 100, True)
     assert next(caps) == 448 and max(eng.asked) == 448  # nothing beyond the start was planned
+
+
+# (max_rows, feasible up to) -> the capacities decompose_ramanujan gives ph_qo_fit, worked out by hand: 512, halved while
+# above 1 and over max_rows or not feasible, then doubled while <= max_rows and feasible, max_rows itself the last step
+INF = 1 << 30
+RAM_LADDERS = [
+    ((2048, INF), [512, 1024, 2048]),
+    ((3000, INF), [512, 1024, 2048, 3000]),  # 4096 > 3000: max_rows itself
+    ((512, INF), [512]),
+    ((50, INF), [32, 50]),  # 512 -> ... -> 32 <= 50; 64 > 50: max_rows itself
+    ((1, INF), [1]),
+    ((2048, 700), [512]),  # 1024 is not feasible
+    ((2048, 100), [64]),  # 512 -> 256 -> 128 -> 64; 128 is not feasible
+    ((2048, 0), []),  # halved down to 1, which is not feasible either
+]
+
+
+@pytest.mark.parametrize("case,want", RAM_LADDERS)
+def test_ramanujan_capacity_ladder(case, want):
+    max_rows, rows = case
+    assert list(_ram_capacities(PlanStub(rows), 600, 200, max_rows)) == want
+
+
+@pytest.mark.parametrize("rows,want", [(INF, 512), (100, 64), (10, None)])
+def test_qo_fit_start(rows, want):
+    """The 512-to-64 start that RamanujanPeriods' batch and QOPeriods._fit_lists_device share; None: infeasible."""
+    eng = PlanStub(rows)
+    assert _qo_fit_start(lambda k: eng.qo_fit_feasible(k, 200)) == want
+    assert min(eng.asked) >= 64  # never halved below the floor

@@ -609,6 +609,32 @@ int ph_overlap_add_periodic(ph_ctx* ctx, const double* seg /* (W, ccap) */, cons
                             int ccap, int64_t T, int N, int hop, int64_t L, const double* win_a, const double* win_s,
                             unsigned flags /* PH_FLAG_DEVICE | PH_FLAG_OLA_NORM */, double* out /* (T, L) */);
 
+/* ph_overlap_add_block / ph_overlap_add_finish: ph_overlap_add and ph_overlap_add_tracks for a recording whose frames come
+ * in blocks, so that the (W, K, N) array never exists as a whole.
+ * ph_overlap_add_block adds the frames f0 .. f0 + Wb - 1 of the recording into acc (T, L) float64, read and written:
+ *   acc[t, n] += sum_{f0 <= f < f0 + Wb} win_s[n - f * hop] * sum_{k < K_f [, bit k of masks[t, f - f0] set]} y[f - f0, k, n - f * hop]
+ * y (Wb, K, N) of dtype, counts (Wb) and masks (T, Wb) are block-local; K_f, win_s and the frames of a sample as in
+ * ph_overlap_add.  masks == NULL: T must be 1, every row k < K_f is added (ph_overlap_add's walk; K may exceed 64).
+ * With masks: ph_overlap_add_tracks's walk, K <= 64.  Only the samples f0 * hop .. min(L, (f0 + Wb - 1) * hop + N) - 1 of
+ * each row of acc are read and written.  One launch (k_overlap_add_block).  The host-pointer form moves all of acc up and
+ * down again; a long recording keeps acc on the device (PH_FLAG_DEVICE).
+ * ph_overlap_add_finish: out[t, n] = acc[t, n], or with PH_FLAG_OLA_NORM acc[t, n] / den[n] where den[n] > 0 and exactly
+ * 0.0 elsewhere; den[n] is that of ph_overlap_add for the W frames of the whole recording, recomputed here.  out may be
+ * acc.  One launch (k_overlap_add_finish).
+ * Contract, which neither call can check: acc is zeroed before the first block; the blocks are applied on one stream in
+ * ascending f0; every frame f < W belongs to exactly one block.  After ph_overlap_add_finish, out is then bit for bit what
+ * ph_overlap_add (masks == NULL) or ph_overlap_add_tracks gives for the whole (W, K, N) array: every sample's terms are
+ * added in the same order, a later block continuing the sum where the block before left it.
+ * Every array follows PH_FLAG_DEVICE.  PH_E_ARG, before any HIP call, for a NULL ctx / y / acc / out, an unknown dtype, a
+ * size < 1, f0 < 0, (f0 + Wb - 1) * hop >= L (a frame that starts behind the signal; for finish (W - 1) * hop >= L),
+ * masks == NULL with T != 1, masks with K > 64, or Wb * K * N * 8 / T * L * 8 / T * Wb * 8 beyond 64 bits. */
+int ph_overlap_add_block(ph_ctx* ctx, const void* y, int dtype, int64_t Wb, int K, int N, int hop, int64_t L, int64_t f0,
+                         const int32_t* counts /* Wb or NULL */, const uint64_t* masks /* (T, Wb) or NULL */, int64_t T,
+                         const double* win_s, unsigned flags, double* acc /* (T, L), read and written */);
+int ph_overlap_add_finish(ph_ctx* ctx, const double* acc, int64_t T, int N, int hop, int64_t L, int64_t W,
+                          const double* win_a, const double* win_s, unsigned flags /* PH_FLAG_DEVICE | PH_FLAG_OLA_NORM */,
+                          double* out /* (T, L) */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,12 @@ and the ``(W, K, N)`` bases never leave the device.
     dec = st.decompose(recording, method="m_best", num=10, max_tracks=8)
     dec.track_periods, dec.tracks, dec.other, dec.activity
 
+Both take ``block_frames=B`` for a recording whose frames and bases do not fit the device at once: the frames are
+analysed B at a time and every block's bases are added into a running sum of the size of the result
+(``PeriodEngine.overlap_add_block``, then one ``overlap_add_finish``) -- the same result, bit for bit.
+
+    res = st.analyze(recording, method="m_best", num=10, block_frames=256)
+
 ``decompose_qo`` is the same split by ``QOPeriods``: ``find_periods`` and ``get_periods`` on every frame -- one waveform
 of p samples per period -- and one routed overlap-add that tiles those waveforms on the fly
 (``PeriodEngine.overlap_add_periodic``), so no ``(W, K, N)`` array exists even on the device.
@@ -180,10 +186,20 @@ class ShortTime:
         win = self._device_window(y)
         return default_engine().overlap_add(y, self.hop, length, counts, win, win, normalize)
 
-    def analyze(self, signal, method="m_best", **kwargs):
+    def analyze(self, signal, method="m_best", block_frames=None, **kwargs):
         """Frame `signal`, run ``Periods.<method>`` (its keyword arguments in **kwargs) over the frames and overlap-add
         the bases: -> ShortTimeResult.  One upload of the signal, one download of the results; status words raise what
-        the ``Periods`` method raises, with the first offending frame named."""
+        the ``Periods`` method raises, with the first offending frame named.
+
+        `block_frames`: None -- all W frames and their ``(W, K, N)`` bases on the device at once -- or an int B >= 1:
+        the signal goes up once, the frames are analysed B at a time and every block's bases are added into one running
+        sum of L doubles (``PeriodEngine.overlap_add_block``), normalised once at the end (``overlap_add_finish``), so
+        the device holds one block's frames and bases, whatever the length of the recording.  The result is field for
+        field, bit for bit that of ``block_frames=None``; so is the exception, which is raised once every block has
+        run."""
+        B = self._block_frames(block_frames)
+        if B is not None:
+            return self._analyze_blocks(signal, method, B, kwargs)
         x64, L, W, eng, win, num, per, pw, bases, counts = self._run(signal, method, kwargs)
         if num == 0:  # the reference's loops do not run: empty per-frame arrays, nothing periodic
             return ShortTimeResult(np.zeros((W, 0), np.uint32), np.zeros((W, 0)), np.zeros(L), x64)
@@ -203,8 +219,14 @@ class ShortTime:
         return np.where(used, per, 0), np.where(used, pw, 0.0), counts
 
     def _device_frames(self, signal):
-        """The start of every pipeline: the signal as a host array, uploaded once, and its frames on the device.
+        """The start of every unblocked pipeline: the signal as a host array, uploaded once, and its frames on the device.
         -> (host signal, L, W, engine, device, device window, frames)."""
+        x, L, W, eng, xd, win, tdt = self._upload(signal)
+        return x, L, W, eng, xd.device, win, eng.frames(xd, self.frame_length, self.hop, W, win, tdt)
+
+    def _upload(self, signal):
+        """The one upload of L samples, no frames yet: -> (host signal, L, W, engine, device signal, device window,
+        frame dtype)."""
         import torch  # lazily, as QOPeriods.solve_quadratic does
 
         x = self._signal(signal)
@@ -217,7 +239,7 @@ class ShortTime:
         xd = torch.as_tensor(x, device=dev)  # the one upload: L samples
         win = None if self.window is None else torch.as_tensor(self.window, device=dev)
         tdt = torch.float64 if self.dtype == np.float64 else torch.float32
-        return x, L, W, eng, dev, win, eng.frames(xd, self.frame_length, self.hop, W, win, tdt)
+        return x, L, W, eng, xd, win, tdt
 
     @staticmethod
     def _activity(masks, powers, T):
@@ -236,9 +258,21 @@ class ShortTime:
         if method not in _METHODS:
             raise ValueError(f"method must be one of {_METHODS}")
         x, L, W, eng, _, win, fr = self._device_frames(signal)
+        num, run = self._method(method, kwargs)
+        if num > 0:
+            per, pw, bases, st, counts = run(eng, fr)
+        x64 = x.astype(np.float64)
+        if num == 0:
+            return x64, L, W, eng, win, 0, None, None, None, None
+        self._raise_status(st.cpu().numpy(), method)
+        return x64, L, W, eng, win, num, per, pw, bases, counts
+
+    def _method(self, method, kwargs):
+        """The engine call behind `method`, its keyword arguments taken out of `kwargs` with the defaults, warnings and
+        TypeError of ``Periods.<method>``: -> (num, run) with run(engine, frames) -> (periods, powers, bases, status,
+        counts) on the device, counts None for every method but small_to_large (whose num is 1: it always runs)."""
         N = self.frame_length
         trunc, orth = self._trunc_to_integer_multiple, self._orthogonalize
-        counts = None
         if method in ("m_best", "m_best_gamma"):
             if orth:
                 warn("`Orthogonalize = True` has no effect in M-best.")
@@ -248,18 +282,17 @@ class ShortTime:
             self._no_more(kwargs, method)
             if max_length is None:
                 max_length = math.floor(N / 3)
-            if num > 0:
-                per, pw, bases, st = eng.m_best(fr, num, max_length, min_length, method == "m_best_gamma", trunc, orth)
-        elif method == "best_correlation":
+            gamma = method == "m_best_gamma"
+            return num, lambda eng, fr: eng.m_best(fr, num, max_length, min_length, gamma, trunc, orth) + (None,)
+        if method == "best_correlation":
             num = int(kwargs.pop("num", 5))
             max_length = kwargs.pop("max_length", None)
             ratio = kwargs.pop("ratio", 0.01)
             self._no_more(kwargs, method)
             if max_length is None:
                 max_length = math.floor(N / 3)
-            if num > 0:
-                per, pw, bases, st = eng.best_correlation(fr, num, max_length, ratio, trunc, orth)
-        elif method == "best_frequency":
+            return num, lambda eng, fr: eng.best_correlation(fr, num, max_length, ratio, trunc, orth) + (None,)
+        if method == "best_frequency":
             num = int(kwargs.pop("num", 5))
             win_size = kwargs.pop("win_size", None)
             self._no_more(kwargs, method)
@@ -267,23 +300,122 @@ class ShortTime:
                 win_size = N
             elif win_size < N:
                 warn("win_size is smaller than the input signal length. It will be truncated and information will be lost.")
-            if num > 0:
-                per, pw, bases, st = eng.best_frequency(fr, win_size, num, trunc, orth)
-        else:
-            thresh = kwargs.pop("thresh", 0.1)
-            n_periods = kwargs.pop("n_periods", None)
-            self._no_more(kwargs, method)
-            if n_periods is None:
-                n_periods = math.floor(N / 2)
-            num = 1
-            counts, per, pw, bases, st = eng.small_to_large(fr, thresh, n_periods, trunc, orth)
-        x64 = x.astype(np.float64)
-        if num == 0:
-            return x64, L, W, eng, win, 0, None, None, None, None
-        self._raise_status(st.cpu().numpy(), method)
-        return x64, L, W, eng, win, num, per, pw, bases, counts
+            return num, lambda eng, fr: eng.best_frequency(fr, win_size, num, trunc, orth) + (None,)
+        thresh = kwargs.pop("thresh", 0.1)
+        n_periods = kwargs.pop("n_periods", None)
+        self._no_more(kwargs, method)
+        if n_periods is None:
+            n_periods = math.floor(N / 2)
 
-    def decompose(self, signal, method="m_best", tracks=None, max_tracks=8, **kwargs):
+        def small_to_large(eng, fr):
+            counts, per, pw, bases, st = eng.small_to_large(fr, thresh, n_periods, trunc, orth)
+            return per, pw, bases, st, counts
+
+        return 1, small_to_large
+
+    @staticmethod
+    def _block_frames(block_frames):
+        """None, or the frames per block as an int >= 1 (ValueError for a bool, a float, 0 or a negative value)."""
+        if block_frames is None:
+            return None
+        if isinstance(block_frames, bool) or not isinstance(block_frames, (int, np.integer)) or block_frames < 1:
+            raise ValueError(f"block_frames={block_frames!r} must be an int >= 1")
+        return int(block_frames)
+
+    def _pass(self, up, run, B, want_periodic, masks_of):
+        """One pass over the recording in blocks of B frames.  Per block: ``frames`` on the slice of the device signal
+        that starts at the block's first sample, the engine method, ``overlap_add_block`` into a (1, L) running sum
+        (`want_periodic`) and, with `masks_of`, into a (T + 1, L) one under the block's masks -- masks_of(f0, periods,
+        counts) -> (T + 1, Wb) uint64 from the block's host results; the block's frames and bases are released before
+        the next block, its periods / powers / counts / status come down and are concatenated (small_to_large: padded
+        with zeros to the widest block).  No ``overlap_add_finish`` and no status check here.
+        -> (periods, powers, counts, status, periodic sum or None, routed sum or None, masks (T + 1, W) or None, the
+        most rows per frame any block had)."""
+        import torch
+
+        _, L, W, eng, xd, win, tdt = up
+        N, hop = self.frame_length, self.hop
+        acc = torch.zeros((1, L), dtype=torch.float64, device=xd.device) if want_periodic else None
+        routed = None
+        pers, pws, cnts, sts, msks, kmax = [], [], [], [], [], 0
+        for f0 in range(0, W, B):
+            fr = eng.frames(xd[f0 * hop :], N, hop, min(B, W - f0), win, tdt)
+            per, pw, bases, st, counts = run(eng, fr)
+            kmax = max(kmax, int(bases.shape[1]))
+            if want_periodic:
+                eng.overlap_add_block(bases, hop, L, f0, acc, counts, None, win)
+            sts.append(st.cpu().numpy())
+            per_h, pw_h, counts_h = self._host_results(per, pw, counts)
+            if masks_of is not None and bases.shape[1] <= _MAX_ROWS:  # (more rows: the caller raises once all blocks ran)
+                masks = masks_of(f0, per_h, counts_h)
+                if routed is None:
+                    routed = torch.zeros((masks.shape[0], L), dtype=torch.float64, device=xd.device)
+                masks_d = torch.as_tensor(masks.view(np.int64), device=xd.device)
+                eng.overlap_add_block(bases, hop, L, f0, routed, counts, masks_d, win)
+                msks.append(masks)
+            pers.append(per_h)
+            pws.append(pw_h)
+            cnts.append(counts_h)
+            del fr, per, pw, bases, st, counts  # the block's frames and bases go before the next block's come
+
+        def rows(parts):  # (W, cap): small_to_large's blocks differ in cap = max(16, largest count)
+            cap = max(p.shape[1] for p in parts)
+            return np.concatenate([np.pad(p, ((0, 0), (0, cap - p.shape[1]))) for p in parts])
+
+        counts = None if cnts[0] is None else np.concatenate(cnts)
+        masks = np.concatenate(msks, axis=1) if msks and kmax <= _MAX_ROWS else None
+        return rows(pers), rows(pws), counts, np.concatenate(sts), acc, routed, masks, kmax
+
+    def _finish(self, up, acc):
+        """``overlap_add_finish`` of a running sum, in place, and the result on the host."""
+        _, _, W, eng, _, win, _ = up
+        return eng.overlap_add_finish(acc, self.frame_length, self.hop, W, win, win, True, out=acc).cpu().numpy()
+
+    def _analyze_blocks(self, signal, method, B, kwargs):
+        if method not in _METHODS:
+            raise ValueError(f"method must be one of {_METHODS}")
+        num, run = self._method(method, kwargs)
+        up = self._upload(signal)
+        x64, L, W = up[0].astype(np.float64), up[1], up[2]
+        if num == 0:
+            return ShortTimeResult(np.zeros((W, 0), np.uint32), np.zeros((W, 0)), np.zeros(L), x64)
+        per, pw, counts, st, acc, _, _, _ = self._pass(up, run, B, True, None)
+        self._raise_status(st, method)
+        periodic = self._finish(up, acc)[0]
+        return ShortTimeResult(per, pw, periodic, x64 - periodic, counts)
+
+    def _decompose_blocks(self, signal, method, wanted, max_tracks, B, kwargs):
+        num, run = self._method(method, kwargs)
+        up = self._upload(signal)
+        x64, L, W = up[0].astype(np.float64), up[1], up[2]
+        if num == 0:
+            wanted = wanted or []
+            return ShortTimeTracks(np.zeros((W, 0), np.uint32), np.zeros((W, 0)), np.zeros(L), x64, wanted,
+                                   np.zeros((len(wanted), L)), np.zeros(L), np.zeros((len(wanted), W)))
+
+        def too_many(kmax):
+            if kmax > _MAX_ROWS:
+                raise ValueError(f"{kmax} bases per frame: decompose routes at most {_MAX_ROWS}")
+
+        if wanted is not None:  # one pass: the tracks are known before the first block
+            per, pw, counts, st, acc, routed, masks, kmax = self._pass(
+                up, run, B, True, lambda f0, p, c: self.track_masks(p, c, wanted))
+            self._raise_status(st, method)
+            too_many(kmax)
+        else:  # the ranking needs every frame: analyse, rank, then run the method again to route
+            per, pw, counts, st, acc, _, _, kmax = self._pass(up, run, B, True, None)
+            self._raise_status(st, method)
+            too_many(kmax)
+            wanted = [(p,) for p in self.rank_periods(per, pw, counts, max_tracks)]
+            masks = self.track_masks(per, counts, wanted)
+            routed = self._pass(up, run, B, False, lambda f0, p, c: masks[:, f0 : f0 + p.shape[0]])[5]
+        T = len(wanted)
+        periodic = self._finish(up, acc)[0]
+        routed = self._finish(up, routed)
+        return ShortTimeTracks(per, pw, periodic, x64 - periodic, wanted, routed[:T], routed[T],
+                               self._activity(masks, pw, T), counts)
+
+    def decompose(self, signal, method="m_best", tracks=None, max_tracks=8, block_frames=None, **kwargs):
         """``analyze``, and the periodic part split by period: -> ShortTimeTracks.  `tracks`: None -- the `max_tracks`
         strongest periods of the recording, one track each (``rank_periods``) -- or a list whose entries are a period or
         an iterable of periods, e.g. ``[12, (17, 34)]``.  The pipeline is that of ``analyze`` (same methods, keyword
@@ -291,12 +423,21 @@ class ShortTime:
         (``track_masks``) go up, and one routed overlap-add (``PeriodEngine.overlap_add_tracks``) folds the bases onto
         T + 1 rows: the tracks and ``other``.  The ``(W, K, N)`` bases never leave the device.  K <= 64 bases per
         frame: `num` > 64 raises ValueError before anything is launched; for small_to_large K is known only once the
-        method has run, so there the check comes after the method's kernels and before the two overlap-adds."""
+        method has run, so there the check comes after the method's kernels and before the two overlap-adds.
+
+        `block_frames`: as in ``analyze`` -- B frames at a time, the bases of a block added into two running sums, (L)
+        and (T + 1, L), under the block's masks; the same result and exceptions, bit for bit.  With `tracks` given the
+        analysis runs once.  With ``tracks=None`` the ranking needs every frame before the first block can be routed,
+        so the analysis runs TWICE: once for the per-frame results and ``periodic``, then, after ``rank_periods``, again
+        block by block to fold the bases onto the tracks."""
         if method not in _METHODS:
             raise ValueError(f"method must be one of {_METHODS}")
+        B = self._block_frames(block_frames)
         wanted, max_tracks, _, _ = self._track_args(tracks, max_tracks, tracks_first=True)
         if method != "small_to_large" and int(kwargs.get("num", 5)) > _MAX_ROWS:
             raise ValueError(f"num={int(kwargs['num'])} bases per frame: decompose routes at most {_MAX_ROWS}")
+        if B is not None:
+            return self._decompose_blocks(signal, method, wanted, max_tracks, B, kwargs)
         x64, L, W, eng, win, num, per, pw, bases, counts = self._run(signal, method, kwargs)
         if num == 0:
             wanted = wanted or []

@@ -2681,4 +2681,63 @@ int ph_overlap_add_periodic(ph_ctx* c, const double* seg, const int32_t* periods
   return st.finish();
 }
 
+int ph_overlap_add_block(ph_ctx* c, const void* y, int dtype, int64_t Wb, int K, int N, int hop, int64_t L, int64_t f0,
+                         const int32_t* counts, const uint64_t* masks, int64_t T, const double* win_s, unsigned flags,
+                         double* acc) {
+  if (!c) return fail(PH_E_ARG, "ctx is NULL");
+  if (!y || !acc) return fail(PH_E_ARG, "y / acc is NULL");
+  if (dtype != PH_F64 && dtype != PH_F32) return fail(PH_E_ARG, "dtype must be PH_F64 or PH_F32");
+  PH_TRY(check_frame_walk("ph_overlap_add_block", Wb, &K, N, hop, L));  // (the sizes, and the block as if f0 were 0)
+  if (f0 < 0) return fail(PH_E_ARG, "ph_overlap_add_block: f0=%lld must be >= 0", (long long)f0);
+  if (f0 > (L - 1) / hop - (Wb - 1))  // (no f0 + Wb, which may overflow)
+    return fail(PH_E_ARG, "ph_overlap_add_block: the block's last frame starts at or behind the end of the signal "
+                "((f0 + Wb - 1) * hop >= L = %lld with f0 = %lld, Wb = %lld)", (long long)L, (long long)f0, (long long)Wb);
+  PH_TRY(check_framed_size("ph_overlap_add_block", Wb, K, N));
+  if (!masks && T != 1) return fail(PH_E_ARG, "ph_overlap_add_block: T=%lld without masks (one track: T = 1)", (long long)T);
+  PH_TRY(check_tracks("ph_overlap_add_block", T));
+  if (masks && K > 64) return fail(PH_E_ARG, "ph_overlap_add_block: K=%d rows per frame do not fit a 64-bit mask", K);
+  PH_TRY(check_tracks_size("ph_overlap_add_block", T, Wb, L));
+  PH_HIP(hipSetDevice(c->device));
+  Stage st(c, flags);
+  OlaSides sd;
+  const void *dy, *dold;
+  void* dacc;
+  PH_TRY(st.in(y, (size_t)Wb * K * N * elem_size(dtype), &dy));
+  PH_TRY(sd.stage(st, flags, Wb, N, counts, masks, T, nullptr, win_s));
+  // acc travels both ways, whole: up into the slot it comes down from
+  PH_TRY(st.in(acc, (size_t)T * L * sizeof(double), &dold, B_OUT0));
+  PH_TRY(st.out(B_OUT0, acc, (size_t)T * L * sizeof(double), &dacc));
+  const int64_t end = (f0 + Wb - 1) * hop + N;  // <= L - 1 + N
+  const dim3 grid(flat_grid(c, T * (std::min(end, L) - f0 * hop)));
+  PH_TRY(dispatch(dtype, [&](auto t) {
+    using E = decltype(t);
+    if (sd.masks)
+      return launch(c, "k_overlap_add_block", ph::k_overlap_add_block<E, true>, grid, ph::kFramesBlock, 0, (const E*)dy, Wb, K,
+                    N, hop, L, f0, sd.counts, sd.masks, T, sd.ws, (double*)dacc);
+    return launch(c, "k_overlap_add_block", ph::k_overlap_add_block<E, false>, grid, ph::kFramesBlock, 0, (const E*)dy, Wb, K,
+                  N, hop, L, f0, sd.counts, sd.masks, T, sd.ws, (double*)dacc);
+  }));
+  return st.finish();
+}
+
+int ph_overlap_add_finish(ph_ctx* c, const double* acc, int64_t T, int N, int hop, int64_t L, int64_t W,
+                          const double* win_a, const double* win_s, unsigned flags, double* out) {
+  if (!c) return fail(PH_E_ARG, "ctx is NULL");
+  if (!acc || !out) return fail(PH_E_ARG, "acc / out is NULL");
+  PH_TRY(check_frame_walk("ph_overlap_add_finish", W, nullptr, N, hop, L));
+  PH_TRY(check_tracks("ph_overlap_add_finish", T));
+  PH_TRY(check_tracks_size("ph_overlap_add_finish", T, W, L));
+  PH_HIP(hipSetDevice(c->device));
+  Stage st(c, flags);
+  OlaSides sd;
+  const void* dacc;
+  void* dout;
+  PH_TRY(st.in(acc, (size_t)T * L * sizeof(double), &dacc));
+  PH_TRY(sd.stage(st, flags, W, N, nullptr, nullptr, 0, win_a, win_s));
+  PH_TRY(st.out(B_OUT0, out, (size_t)T * L * sizeof(double), &dout));
+  PH_TRY(launch(c, "k_overlap_add_finish", ph::k_overlap_add_finish, dim3(flat_grid(c, T * L)), ph::kFramesBlock, 0,
+                (const double*)dacc, T, N, hop, L, W, sd.wa, sd.ws, sd.norm, (double*)dout));
+  return st.finish();
+}
+
 }  // extern "C"

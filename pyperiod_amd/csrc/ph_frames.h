@@ -1,7 +1,9 @@
 // Short-time framing and overlap-add on the device: k_frames cuts a signal of L samples into the (W, N) batch every
 // other entry point takes, k_overlap_add folds a (W, K, N) result back onto the L samples of the signal, and
 // k_overlap_add_tracks folds it onto several tracks of L samples, the rows of each chosen by a mask;
-// k_overlap_add_periodic does the same from one period per row (the segments of k_qo_extract), tiled on the fly.  All are
+// k_overlap_add_periodic does the same from one period per row (the segments of k_qo_extract), tiled on the fly;
+// k_overlap_add_block / k_overlap_add_finish do the work of the first two for a recording that comes in blocks of
+// frames.  All are
 // memory-bound element-wise kernels without LDS; all index arithmetic is int64 (f * hop and f * N pass 2^31 for real
 // recordings).  Included by period_hip.hip behind ph_fit.h.
 #pragma once
@@ -286,6 +288,110 @@ __global__ __launch_bounds__(kFramesBlock) void k_overlap_add_periodic(const dou
       }
     }
     out[item] = ola_result(num, den, norm);
+  }
+}
+
+// ======================================================================================
+// Overlap-add in frame blocks: k_overlap_add_block adds the frames f0 .. f0 + Wb - 1 of a recording into a running sum
+// acc (NT, L) float64, k_overlap_add_finish turns the running sum into the result.  Everything about the block is
+// block-local: y (Wb, K, N) of T, counts (Wb), masks (NT, Wb); only f0 places it in the recording.
+//   Routed = false (NT = 1): acc[0, n] += the terms k_overlap_add adds for the frames of the block, every k < K_f, four
+//     loads in flight, added in ascending k; K may exceed 64.
+//   Routed = true: acc[t, n] += the terms k_overlap_add_tracks adds for them: ola_cut, lowest set bit first, bit 63 a
+//     row like any other.
+// The work items are the NT * (n1 - n0) samples of the block's span, n0 = f0 hop, n1 = min(L, (f0 + Wb - 1) hop + N);
+// a sample outside the span is neither read nor written.  A lane loads num = acc[t, n], walks the frames
+// max(f_lo(n), f0) .. min(f_hi(n), f0 + Wb - 1) in ascending f -- f_lo / f_hi are those of the whole recording; its last
+// frame can only cut f_hi where the block's last frame does already -- with the very expression of the one-launch
+// kernels (num += s * (double)row[...]), and stores num back.  den is not touched here: it depends on n, W, hop and the
+// windows alone, and k_overlap_add_finish recomputes it by the walk of the one-launch kernels over all W frames
+// (ola_window only) and writes out[t, n] = ola_result(acc[t, n], den[n], norm); out may be acc itself, each lane reads
+// its own element before it writes it.
+// Contract (nothing here can check it): acc is zeroed before the first block, the blocks are applied on one stream in
+// ascending f0, and every frame belongs to exactly one block.  A lane of a later block then continues the walk of its
+// sample where the lane of the block before left it: the same additions in the same order as one launch over the whole
+// (W, K, N) array, whose `num = 0.0` is the zeroed acc.  After finish the result is, bit for bit, that of k_overlap_add
+// (Routed = false) or of k_overlap_add_tracks (Routed = true).
+// No LDS, int64 index arithmetic, flat grid-stride loops.  A block moves 2 * 8 * NT * (n1 - n0) bytes of acc on top of
+// the rows it reads.
+// ======================================================================================
+template <typename T, bool Routed>
+__global__ __launch_bounds__(kFramesBlock) void k_overlap_add_block(const T* __restrict__ y, int64_t Wb, int K, int N, int hop,
+                                                                   int64_t L, int64_t f0, const int* __restrict__ counts,
+                                                                   const unsigned long long* __restrict__ masks, int64_t NT,
+                                                                   const double* __restrict__ ws, double* __restrict__ acc) {
+  const int64_t n0 = f0 * hop;
+  const int64_t end = (f0 + Wb - 1) * hop + N;
+  const int64_t span = (end < L ? end : L) - n0;
+  const int64_t total = NT * span;
+  const int64_t stride = (int64_t)gridDim.x * kFramesBlock;
+  for (int64_t item = (int64_t)blockIdx.x * kFramesBlock + threadIdx.x; item < total; item += stride) {
+    const int64_t t = item / span;
+    const int64_t n = n0 + (item - t * span);
+    int64_t f_lo, f_hi;
+    ola_frame_span(n, N, hop, f0 + Wb, f_lo, f_hi);
+    if (f_lo < f0) f_lo = f0;
+    double num = acc[t * L + n], den = 0.0;  // (den: what ola_window wants; dead here)
+    for (int64_t f = f_lo; f <= f_hi; ++f) {
+      const int64_t fb = f - f0;
+      const int i = (int)(n - f * hop);
+      const int kf = counts ? ola_clip(counts[fb], K) : K;
+      const double s = ola_window(i, nullptr, ws, den);
+      const T* row = y + (fb * K) * (int64_t)N + i;
+      if constexpr (Routed) {
+        unsigned long long m = ola_cut(masks[t * Wb + fb], kf);
+        int left = __builtin_popcountll(m);
+        for (; left >= 4; left -= 4) {  // four loads in flight, added in ascending k
+          const int k0 = __builtin_ctzll(m);
+          m &= m - 1ull;
+          const int k1 = __builtin_ctzll(m);
+          m &= m - 1ull;
+          const int k2 = __builtin_ctzll(m);
+          m &= m - 1ull;
+          const int k3 = __builtin_ctzll(m);
+          m &= m - 1ull;
+          const double a0 = (double)row[(int64_t)k0 * N], a1 = (double)row[(int64_t)k1 * N];
+          const double a2 = (double)row[(int64_t)k2 * N], a3 = (double)row[(int64_t)k3 * N];
+          num += s * a0;
+          num += s * a1;
+          num += s * a2;
+          num += s * a3;
+        }
+        for (; left > 0; --left) {
+          const int k = __builtin_ctzll(m);
+          m &= m - 1ull;
+          num += s * (double)row[(int64_t)k * N];
+        }
+      } else {
+        int k = 0;
+        for (; k + 4 <= kf; k += 4) {  // four loads in flight, added in ascending k
+          const double a0 = (double)row[(int64_t)(k + 0) * N], a1 = (double)row[(int64_t)(k + 1) * N];
+          const double a2 = (double)row[(int64_t)(k + 2) * N], a3 = (double)row[(int64_t)(k + 3) * N];
+          num += s * a0;
+          num += s * a1;
+          num += s * a2;
+          num += s * a3;
+        }
+        for (; k < kf; ++k) num += s * (double)row[(int64_t)k * N];
+      }
+    }
+    acc[t * L + n] = num;
+  }
+}
+
+// (acc and out may be one array: no __restrict__ on either)
+__global__ __launch_bounds__(kFramesBlock) void k_overlap_add_finish(const double* acc, int64_t NT, int N, int hop, int64_t L,
+                                                                    int64_t W, const double* __restrict__ wa,
+                                                                    const double* __restrict__ ws, int norm, double* out) {
+  const int64_t total = NT * L;
+  const int64_t stride = (int64_t)gridDim.x * kFramesBlock;
+  for (int64_t item = (int64_t)blockIdx.x * kFramesBlock + threadIdx.x; item < total; item += stride) {
+    const int64_t n = item % L;
+    int64_t f_lo, f_hi;
+    ola_frame_span(n, N, hop, W, f_lo, f_hi);
+    double den = 0.0;
+    for (int64_t f = f_lo; f <= f_hi; ++f) ola_window((int)(n - f * hop), wa, ws, den);
+    out[item] = ola_result(acc[item], den, norm);
   }
 }
 

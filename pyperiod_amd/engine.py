@@ -789,6 +789,67 @@ class PeriodEngine:
                               mk.addr(msk), W, pcap, int(ccap), T, N, hop, L, mk.addr(wa), mk.addr(ws), fl=fl,
                               normalize=normalize)
 
+    def _ola_acc(self, mk, x, acc, name, of):
+        """The running sum of a blocked overlap-add, (L,) or (T, L) float64, as the library writes it in place: a
+        C-contiguous numpy array, or with torch input a contiguous float64 tensor on x's device.  -> (T, L)."""
+        if mk.torch:
+            if not _is_torch(acc) or acc.dtype != mk._t.float64 or acc.device != x.device:
+                raise TypeError(f"{name} must be a float64 tensor on the device of {of}")
+            ok = acc.is_contiguous()
+        else:
+            if not isinstance(acc, np.ndarray) or acc.dtype != np.float64:
+                raise TypeError(f"{name} must be a float64 array")
+            ok = acc.flags.c_contiguous and acc.flags.writeable
+        if acc.ndim not in (1, 2) or not ok:
+            raise ValueError(f"{name} must be contiguous (and writable), of shape (L,) or (T, L)")
+        return (1, int(acc.shape[0])) if acc.ndim == 1 else (int(acc.shape[0]), int(acc.shape[1]))
+
+    def overlap_add_block(self, y, hop, length, first_frame, acc, counts=None, masks=None, win_s=None):
+        """One block of a blocked overlap-add (ph_overlap_add_block, one launch): adds the frames first_frame ..
+        first_frame + Wb - 1 of a recording of `length` samples, y (Wb, N) or (Wb, K, N), into `acc` in place and returns
+        it.  `acc` (length,) or (1, length) float64 without `masks`; with `masks` (T, Wb) -- block-local, as
+        overlap_add_tracks takes them, K <= 64 -- (T, length).  `counts` (Wb) int32, `win_s` (N) float64 or None.  numpy
+        arrays, or torch tensors on the engine's device (on torch's current stream); acc is of y's kind.
+        Zero acc before the first block, apply the blocks in ascending first_frame, every frame in exactly one block:
+        overlap_add_finish then gives, bit for bit, what overlap_add (no masks) or overlap_add_tracks gives for all frames
+        at once.  Only the samples the block's frames cover are read and written."""
+        x, code, W, K, N, hop, L, fl, mk, cnt, _, ws = self._ola_args(y, hop, length, counts, None, win_s)
+        T, La = self._ola_acc(mk, x, acc, "acc", "y")
+        msk = None if masks is None else _masks(mk, x, masks, W, "y")
+        if La != L or T != (1 if msk is None else int(msk.shape[0])):
+            raise ValueError("acc must be (length,) without masks and (T, length) with masks (T, Wb)")
+        self._call(mk, W, self._lib.ph_overlap_add_block, mk.addr(x), code, W, K, N, hop, L, int(first_frame), mk.addr(cnt),
+                   mk.addr(msk), T, mk.addr(ws), fl, mk.addr(acc))
+        return acc
+
+    def overlap_add_finish(self, acc, frame_length, hop, frames, win_a=None, win_s=None, normalize=True, out=None):
+        """The end of a blocked overlap-add (ph_overlap_add_finish, one launch): acc (L,) or (T, L) float64, the running sum
+        of overlap_add_block over all `frames` frames of the recording -> the same shape, acc divided by the overlap-added
+        window product of those frames where that is > 0 and exactly 0.0 elsewhere (`normalize` False: acc as it is).
+        `out`: None (a new array) or an array of acc's kind and shape, acc itself included.  `win_a` / `win_s` as in
+        overlap_add."""
+        N, hop, W = int(frame_length), int(hop), int(frames)
+        if W < 0:
+            raise ValueError("frames must be >= 0")
+        if _is_torch(acc):
+            x, _, _, _, fl, mk = self._prep(acc.reshape(1, -1) if acc.dim() == 1 else acc)
+        else:
+            fl, mk = 0, _Out(acc)
+            x = acc
+        T, L = self._ola_acc(mk, x, acc, "acc", "acc")
+        if out is None:
+            out = mk.empty(tuple(acc.shape), np.float64)
+        elif self._ola_acc(mk, x, out, "out", "acc") != (T, L) or out.ndim != acc.ndim:
+            raise ValueError("out must have the shape of acc")
+        wa = None if win_a is None else self._window(mk, x, win_a, N)
+        ws = None if win_s is None else self._window(mk, x, win_s, N)
+        if W == 0 or L == 0:
+            out[...] = 0.0
+            return out
+        self._call(mk, W, self._lib.ph_overlap_add_finish, mk.addr(acc), T, N, hop, L, W, mk.addr(wa), mk.addr(ws),
+                   fl | (_ffi.PH_FLAG_OLA_NORM if normalize else 0), mk.addr(out))
+        return out
+
     def fold_sums(self, x, p_list, keep):
         """W = A x for natural-basis rows (QOPeriods.py:782): (W, sum(keep)) float64."""
         x, code, W, N, fl, mk = self._prep(x)

@@ -13,7 +13,19 @@ sample grows.
 End to end (host clock around calls that end in a download, `--e2e-reps` repeats after one warm-up, alternating):
   ShortTime.analyze("m_best", num=K) against frames built in numpy, Periods().m_best(batch, num=K) and a numpy
   overlap-add, for the same three hops; the two periodic parts are compared.
-Prints one JSON line per measurement."""
+Prints one JSON line per measurement.
+
+    python tools/short_time_bench.py --blocks [--frames 1024] [--n 4096] [--hop 512] [--num 10] [--block-frames 16,64,256]
+
+The blocked mode, everything in one process:
+  kernels     k_overlap_add_block per block + one k_overlap_add_finish against the one k_overlap_add launch on the same
+              (W, K, N) bases, between the engine's event timers (ph_timer_begin / ph_timer_end around the whole
+              sequence of launches), alternating; the two results are compared bit for bit.  Next to the times stands
+              what is known without a run: per block 2 * 8 * (Wb hop + N) bytes of the running sum moved against
+              8 * Wb K N bytes of bases read.
+  end to end  ShortTime.analyze("m_best", num=K) without blocks and at every `--block-frames`: wall time (host clock, the
+              call ends in a download) and torch.cuda.max_memory_allocated over the call, less what was allocated before
+              it; the results are compared field for field."""
 
 import argparse
 import json
@@ -81,14 +93,103 @@ def host_route(x, n, hop, w_count, win, num):
     return per, pw, out
 
 
+def timed_ms(eng, fn):
+    """Milliseconds between the engine's two event timers around fn() (all of fn's launches, on the engine's stream)."""
+    eng.timer_begin()
+    out = fn()
+    ms = eng.timer_end()
+    return ms, out
+
+
+def blocks_mode(a):
+    import __graft_entry__ as ge
+
+    ge.build()
+    import torch
+
+    from pyperiod_amd import ShortTime, default_engine
+    from pyperiod_amd.synth import multi_sinusoid_window
+
+    eng = default_engine()
+    dev = torch.device("cuda", eng.device)
+    W, N, K, hop = a.frames, a.n, a.num, a.hop
+    L = (W - 1) * hop + N
+    sizes = [int(b) for b in a.block_frames.split(",")]
+    win = np.sqrt(0.5 - 0.5 * np.cos(2 * np.pi * np.arange(N) / N))
+    win_d = torch.as_tensor(win, device=dev)
+    y = torch.randn((W, K, N), dtype=torch.float64, device=dev)
+    stream = torch.cuda.current_stream(dev)
+
+    def one_launch():
+        return eng.overlap_add(y, hop, L, None, win_d, win_d, True)
+
+    def blocked(B):
+        acc = torch.zeros(L, dtype=torch.float64, device=dev)
+        for f0 in range(0, W, B):
+            eng.overlap_add_block(y[f0 : f0 + B], hop, L, f0, acc, None, None, win_d)
+        return eng.overlap_add_finish(acc, N, hop, W, win_d, win_d, out=acc)
+
+    # the engine's timers record on the stream the engine is bound to: bind it to torch's with one call first
+    want = one_launch()
+    for B in sizes:
+        same = bool(torch.equal(blocked(B).view(torch.int64), want.view(torch.int64)))
+        ours, yard = alternate(lambda: timed_ms(eng, lambda: blocked(B))[0], lambda: timed_ms(eng, one_launch)[0], a.reps)
+        so, sy = stats(ours), stats(yard)
+        nb = -(-W // B)
+        acc_bytes = sum(2 * 8 * (min(L, (min(f0 + B, W) - 1) * hop + N) - f0 * hop) for f0 in range(0, W, B))
+        print(json.dumps({"kernels": "k_overlap_add_block x blocks + k_overlap_add_finish", "W": W, "K": K, "N": N, "hop": hop,
+                          "L": L, "block_frames": B, "blocks": nb, "bytes_read": W * K * N * 8, "acc_bytes_moved": acc_bytes,
+                          "acc_over_read": round(acc_bytes / (W * K * N * 8), 4), "ms": so, "one_launch_ms": sy,
+                          "ratio_to_one_launch": round(so["median"] / sy["median"], 3), "bit_equal": same}), flush=True)
+    del y, want
+    stream.synchronize()
+    torch.cuda.empty_cache()
+
+    x = np.concatenate([multi_sinusoid_window(s, N) for s in range(-(-L // N))])[:L]
+    st = ShortTime(N, hop, window=win)
+    assert st.frame_count(L) == W
+
+    def run(B):
+        torch.cuda.synchronize(dev)
+        torch.cuda.reset_peak_memory_stats(dev)
+        base = torch.cuda.memory_allocated(dev)
+        t0 = time.perf_counter()
+        res = st.analyze(x, method="m_best", num=K, block_frames=B)
+        ms = 1e3 * (time.perf_counter() - t0)
+        return res, ms, torch.cuda.max_memory_allocated(dev) - base
+
+    ref = run(None)[0]  # warm-up
+    for B in sizes:
+        run(B)
+    times, peaks, same = {B: [] for B in [None] + sizes}, {}, {}
+    for _ in range(a.e2e_reps):
+        for B in [None] + sizes:
+            res, ms, peak = run(B)
+            times[B].append(ms)
+            peaks[B] = peak
+            same[B] = all(np.array_equal(g, w) for g, w in zip(res[:4], ref[:4]))
+    base_ms = stats(times[None])["median"]
+    for B in [None] + sizes:
+        sb = stats(times[B])
+        print(json.dumps({"end_to_end": "m_best", "num": K, "W": W, "N": N, "hop": hop, "L": L, "block_frames": B,
+                          "analyze_ms": sb, "ratio_to_unblocked": round(sb["median"] / base_ms, 3),
+                          "peak_torch_bytes": peaks[B], "peak_over_unblocked": round(peaks[B] / peaks[None], 4),
+                          "bases_bytes": W * K * N * 8, "equal_to_unblocked": same[B]}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--blocks", action="store_true", help="the blocked mode (analyze with block_frames, the block kernels)")
+    ap.add_argument("--hop", type=int, default=512, help="--blocks only")
+    ap.add_argument("--block-frames", default="16,64,256", help="--blocks only: comma-separated block sizes")
     ap.add_argument("--frames", type=int, default=1024)
     ap.add_argument("--n", type=int, default=4096)
     ap.add_argument("--num", type=int, default=10)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--e2e-reps", type=int, default=5)
     a = ap.parse_args()
+    if a.blocks:
+        return blocks_mode(a)
     import __graft_entry__ as ge
 
     ge.build()

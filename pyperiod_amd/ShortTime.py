@@ -41,6 +41,7 @@ routed overlap-add.
 from __future__ import annotations
 
 import math
+from functools import cached_property
 from typing import NamedTuple, Optional
 from warnings import warn
 
@@ -105,6 +106,20 @@ class ShortTimeRamanujan(NamedTuple):
 
 
 _MAX_ROWS = 64  # rows per frame a 64-bit routing mask can name
+
+
+class _Recording:
+    """A recording on its way through a pipeline (``ShortTime._upload``): uploaded once, framed block by block."""
+
+    def __init__(self, x, W, eng, xd, win, tdt):
+        self.x, self.L, self.W = x, x.shape[0], W  # the host signal (float64 or float32), its samples, its frames
+        self.eng, self.xd, self.win, self.tdt = eng, xd, win, tdt  # engine, device signal and window (or None), frame dtype
+
+    @cached_property
+    def x64(self):
+        """The float64 copy of the signal (residual = x64 - periodic), made when first asked for: L samples on the
+        host, which a pipeline reads once the device has work to do."""
+        return self.x.astype(np.float64)
 
 
 def _first(mask):
@@ -198,14 +213,147 @@ class ShortTime:
         field, bit for bit that of ``block_frames=None``; so is the exception, which is raised once every block has
         run."""
         B = self._block_frames(block_frames)
-        if B is not None:
-            return self._analyze_blocks(signal, method, B, kwargs)
-        x64, L, W, eng, win, num, per, pw, bases, counts = self._run(signal, method, kwargs)
+        self._known(method)
+        return self._pipeline(signal, method, B, kwargs)
+
+    def decompose(self, signal, method="m_best", tracks=None, max_tracks=8, block_frames=None, **kwargs):
+        """``analyze``, and the periodic part split by period: -> ShortTimeTracks.  `tracks`: None -- the `max_tracks`
+        strongest periods of the recording, one track each (``rank_periods``) -- or a list whose entries are a period or
+        an iterable of periods, e.g. ``[12, (17, 34)]``.  The pipeline is that of ``analyze`` (same methods, keyword
+        arguments and exceptions); afterwards only the per-frame periods / powers / counts come down, the routing masks
+        (``track_masks``) go up, and one routed overlap-add (``PeriodEngine.overlap_add_tracks``) folds the bases onto
+        T + 1 rows: the tracks and ``other``.  The ``(W, K, N)`` bases never leave the device.  K <= 64 bases per
+        frame: `num` > 64 raises ValueError before anything is launched; for small_to_large K is known only once the
+        method has run, so there the check comes after the method's kernels and before the two overlap-adds.
+
+        `block_frames`: as in ``analyze`` -- B frames at a time, the bases of a block added into two running sums, (L)
+        and (T + 1, L), under the block's masks; the same result and exceptions, bit for bit.  With `tracks` given the
+        analysis runs once.  With ``tracks=None`` the ranking needs every frame before the first block can be routed,
+        so the analysis runs TWICE: once for the per-frame results and ``periodic``, then, after ``rank_periods``, again
+        block by block to fold the bases onto the tracks."""
+        self._known(method)
+        B = self._block_frames(block_frames)
+        wanted, max_tracks, _, _ = self._track_args(tracks, max_tracks, tracks_first=True)
+        if method != "small_to_large":
+            self._routable(int(kwargs.get("num", 5)), "num=")
+        return self._pipeline(signal, method, B, kwargs, wanted, max_tracks)
+
+    @staticmethod
+    def _known(method):
+        if method not in _METHODS:
+            raise ValueError(f"method must be one of {_METHODS}")
+
+    @staticmethod
+    def _routable(rows, named=""):
+        """decompose's limit on the rows of a frame: refused as ``num=...`` before the launch, as counted after it."""
+        if rows > _MAX_ROWS:
+            raise ValueError(f"{named}{rows} bases per frame: decompose routes at most {_MAX_ROWS}")
+
+    def _pipeline(self, signal, method, B, kwargs, wanted=None, max_tracks=None):
+        """``analyze`` (`max_tracks` None) and ``decompose`` (`wanted`: the named tracks, or None for the `max_tracks`
+        strongest), over blocks of `B` frames; None is one block of all W frames.  The signal goes up once.  Per block:
+        ``frames`` on the slice of the device signal that starts at the block's first sample, the engine method, its
+        periods / powers / counts / status down (``_host_results``), and the block's bases folded.  Then the status
+        check and, for ``decompose``, the limit on the rows per frame.
+
+        What differs is the fold.  The one block of an unblocked call stays alive past those checks and is folded by
+        ``overlap_add_tracks`` and then ``overlap_add``, under masks from its own host results: ranked tracks need no
+        second run.  A block of a blocked call is added into the running sums -- (L) first, then (T + 1, L) under the
+        block's masks -- and released before the next block is made; ``overlap_add_finish`` ends each sum, in place.
+        There, ranked tracks need every frame before the first block can be routed: a second run of the method folds
+        the bases onto the tracks, and nothing else."""
+        import torch
+
+        N, hop, route = self.frame_length, self.hop, max_tracks is not None
+        # (an unblocked call has its signal up and framed before the method's keyword arguments are read, a blocked
+        # call after: which refusal a caller sees first, and after which launches, is part of the surface)
+        rec = self._upload(signal) if B is None else None
+        whole = self._frames(rec, 0, rec.W) if B is None else None
+        num, run = self._method(method, kwargs)
+        rec = rec or self._upload(signal)
+        L, W, eng, win, dev = rec.L, rec.W, rec.eng, rec.win, rec.xd.device
         if num == 0:  # the reference's loops do not run: empty per-frame arrays, nothing periodic
-            return ShortTimeResult(np.zeros((W, 0), np.uint32), np.zeros((W, 0)), np.zeros(L), x64)
-        periodic = eng.overlap_add(bases, self.hop, L, counts, win, win, True).cpu().numpy()
-        per, pw, counts = self._host_results(per, pw, counts)
-        return ShortTimeResult(per, pw, periodic, x64 - periodic, counts)
+            wanted = (wanted or []) if route else None
+            return self._assemble(rec, np.zeros((W, 0), np.uint32), np.zeros((W, 0)), None, np.zeros(L), wanted,
+                                  np.zeros((len(wanted or []) + 1, L)))
+
+        def running_sum(rows):
+            return torch.zeros((rows, L), dtype=torch.float64, device=dev)
+
+        def finish(total):  # the end of a blocked run's sum, in place, and the result on the host
+            return eng.overlap_add_finish(total, N, hop, W, win, win, True, out=total).cpu().numpy()
+
+        def up(masks):  # (T + 1) * Wb words
+            return torch.as_tensor(masks.view(np.int64), device=dev)
+
+        def rows(parts):  # (W, cap): small_to_large's blocks differ in cap = max(16, largest count)
+            if len(parts) == 1:
+                return parts[0]
+            cap = max(p.shape[1] for p in parts)
+            return np.concatenate([np.pad(p, ((0, 0), (0, cap - p.shape[1]))) for p in parts])
+
+        def run_blocks(acc, routed, masks_of):
+            """One run of the method over the recording.  Blocked, every block is added into `acc` (1, L) and, under
+            masks_of(f0, periods, counts) -> (T + 1, Wb) uint64 from its host results, into `routed` (T + 1, L), each
+            where given; unblocked, the block is kept.  -> the recording's host periods, powers and counts, the masks
+            (T + 1, W) or None, the kept (bases, counts) or None."""
+            blocks = [(0, whole)] if B is None else (
+                (f0, self._frames(rec, f0, min(B, W - f0))) for f0 in range(0, W, B))
+            got, sts, msks, kmax, kept = [], [], [], 0, None
+            for f0, fr in blocks:
+                per, pw, bases, st, counts = run(eng, fr)
+                rec.x64  # (the host's copy of L samples, made here the first time: the device is at work on the block)
+                kmax = max(kmax, int(bases.shape[1]))
+                if acc is not None:
+                    eng.overlap_add_block(bases, hop, L, f0, acc, counts, None, win)
+                sts.append(st.cpu().numpy())
+                got.append(self._host_results(per, pw, counts))
+                if masks_of is not None and bases.shape[1] <= _MAX_ROWS:  # (more rows: refused below, after every block)
+                    msks.append(masks_of(f0, got[-1][0], got[-1][2]))
+                    eng.overlap_add_block(bases, hop, L, f0, routed, counts, up(msks[-1]), win)
+                if B is None:
+                    kept = bases, counts
+                del fr, per, pw, bases, st, counts  # the block's frames and bases go before the next block's come
+            self._raise_status(np.concatenate(sts), method)
+            if route:
+                self._routable(kmax)
+            pers, pws, cnts = zip(*got)
+            return (rows(pers), rows(pws), None if cnts[0] is None else np.concatenate(cnts),
+                    np.concatenate(msks, axis=1) if msks else None, kept)
+
+        acc = routed = by_block = None
+        if B is not None:
+            acc = running_sum(1)
+            if wanted is not None:  # named tracks: every block is routed as it comes
+                routed, by_block = running_sum(len(wanted) + 1), lambda f0, p, c: self.track_masks(p, c, wanted)
+        per, pw, counts, masks, kept = run_blocks(acc, routed, by_block)
+        if route and masks is None:  # every other decompose: routed once the whole recording's results are down
+            wanted = self._ranked(per, pw, counts, wanted, max_tracks)
+            masks = self.track_masks(per, counts, wanted)
+            if B is None:
+                routed = eng.overlap_add_tracks(kept[0], up(masks), hop, L, kept[1], win, win, True)
+            else:
+                routed = running_sum(len(wanted) + 1)
+                run_blocks(None, routed, lambda f0, p, c: masks[:, f0 : f0 + p.shape[0]])
+        if B is None:
+            periodic = eng.overlap_add(kept[0], hop, L, kept[1], win, win, True).cpu().numpy()
+            routed = routed.cpu().numpy() if route else None
+        else:
+            periodic, routed = finish(acc)[0], finish(routed) if route else None
+        return self._assemble(rec, per, pw, counts, periodic, wanted, routed, masks)
+
+    def _assemble(self, rec, per, pw, counts, periodic, wanted=None, routed=None, masks=None):
+        """The result of every pipeline from its host arrays: ShortTimeResult, or with `wanted` (T tracks) ShortTimeTracks
+        from `routed`, whose rows T and up are ``other`` and whatever else the pipeline routed, and its `masks`."""
+        if wanted is None:
+            return ShortTimeResult(per, pw, periodic, rec.x64 - periodic, counts)
+        T = len(wanted)
+        return ShortTimeTracks(per, pw, periodic, rec.x64 - periodic, wanted, routed[:T], routed[T],
+                               self._activity(masks, pw, T), counts)
+
+    def _ranked(self, per, pw, counts, wanted, max_tracks):
+        """The named tracks, or with none named one track for each of the `max_tracks` strongest periods."""
+        return [(p,) for p in self.rank_periods(per, pw, counts, max_tracks)] if wanted is None else wanted
 
     @staticmethod
     def _host_results(per, pw, counts):
@@ -218,28 +366,23 @@ class ShortTime:
         used = np.arange(per.shape[1])[None, :] < counts[:, None]
         return np.where(used, per, 0), np.where(used, pw, 0.0), counts
 
-    def _device_frames(self, signal):
-        """The start of every unblocked pipeline: the signal as a host array, uploaded once, and its frames on the device.
-        -> (host signal, L, W, engine, device, device window, frames)."""
-        x, L, W, eng, xd, win, tdt = self._upload(signal)
-        return x, L, W, eng, xd.device, win, eng.frames(xd, self.frame_length, self.hop, W, win, tdt)
-
     def _upload(self, signal):
-        """The one upload of L samples, no frames yet: -> (host signal, L, W, engine, device signal, device window,
-        frame dtype)."""
+        """The one upload of L samples, no frames yet: -> _Recording."""
         import torch  # lazily, as QOPeriods.solve_quadratic does
 
         x = self._signal(signal)
         if _is_torch(x):
             x = x.detach().cpu().numpy()
-        L = x.shape[0]
-        W = self.frame_count(L)
+        W = self.frame_count(x.shape[0])
         eng = default_engine()
         dev = torch.device("cuda", eng.device)
-        xd = torch.as_tensor(x, device=dev)  # the one upload: L samples
-        win = None if self.window is None else torch.as_tensor(self.window, device=dev)
-        tdt = torch.float64 if self.dtype == np.float64 else torch.float32
-        return x, L, W, eng, xd, win, tdt
+        return _Recording(x, W, eng, torch.as_tensor(x, device=dev),  # the one upload: L samples
+                          None if self.window is None else torch.as_tensor(self.window, device=dev),
+                          torch.float64 if self.dtype == np.float64 else torch.float32)
+
+    def _frames(self, rec, f0, count):
+        """The frames f0 .. f0 + count - 1 of an uploaded recording, on the device."""
+        return rec.eng.frames(rec.xd[f0 * self.hop :], self.frame_length, self.hop, count, rec.win, rec.tdt)
 
     @staticmethod
     def _activity(masks, powers, T):
@@ -250,22 +393,6 @@ class ShortTime:
             bit = (masks[:T] >> np.uint64(k)) & np.uint64(1)
             activity += np.where(bit != 0, powers[None, :, k], 0.0)
         return activity
-
-    def _run(self, signal, method, kwargs):
-        """The pipeline analyze and decompose share: one upload of the signal, frames, the engine method, the status
-        check.  -> (float64 signal, L, W, engine, device window, num, periods, powers, bases, counts) with the last four
-        on the device (None when num == 0: nothing ran)."""
-        if method not in _METHODS:
-            raise ValueError(f"method must be one of {_METHODS}")
-        x, L, W, eng, _, win, fr = self._device_frames(signal)
-        num, run = self._method(method, kwargs)
-        if num > 0:
-            per, pw, bases, st, counts = run(eng, fr)
-        x64 = x.astype(np.float64)
-        if num == 0:
-            return x64, L, W, eng, win, 0, None, None, None, None
-        self._raise_status(st.cpu().numpy(), method)
-        return x64, L, W, eng, win, num, per, pw, bases, counts
 
     def _method(self, method, kwargs):
         """The engine call behind `method`, its keyword arguments taken out of `kwargs` with the defaults, warnings and
@@ -322,144 +449,6 @@ class ShortTime:
             raise ValueError(f"block_frames={block_frames!r} must be an int >= 1")
         return int(block_frames)
 
-    def _pass(self, up, run, B, want_periodic, masks_of):
-        """One pass over the recording in blocks of B frames.  Per block: ``frames`` on the slice of the device signal
-        that starts at the block's first sample, the engine method, ``overlap_add_block`` into a (1, L) running sum
-        (`want_periodic`) and, with `masks_of`, into a (T + 1, L) one under the block's masks -- masks_of(f0, periods,
-        counts) -> (T + 1, Wb) uint64 from the block's host results; the block's frames and bases are released before
-        the next block, its periods / powers / counts / status come down and are concatenated (small_to_large: padded
-        with zeros to the widest block).  No ``overlap_add_finish`` and no status check here.
-        -> (periods, powers, counts, status, periodic sum or None, routed sum or None, masks (T + 1, W) or None, the
-        most rows per frame any block had)."""
-        import torch
-
-        _, L, W, eng, xd, win, tdt = up
-        N, hop = self.frame_length, self.hop
-        acc = torch.zeros((1, L), dtype=torch.float64, device=xd.device) if want_periodic else None
-        routed = None
-        pers, pws, cnts, sts, msks, kmax = [], [], [], [], [], 0
-        for f0 in range(0, W, B):
-            fr = eng.frames(xd[f0 * hop :], N, hop, min(B, W - f0), win, tdt)
-            per, pw, bases, st, counts = run(eng, fr)
-            kmax = max(kmax, int(bases.shape[1]))
-            if want_periodic:
-                eng.overlap_add_block(bases, hop, L, f0, acc, counts, None, win)
-            sts.append(st.cpu().numpy())
-            per_h, pw_h, counts_h = self._host_results(per, pw, counts)
-            if masks_of is not None and bases.shape[1] <= _MAX_ROWS:  # (more rows: the caller raises once all blocks ran)
-                masks = masks_of(f0, per_h, counts_h)
-                if routed is None:
-                    routed = torch.zeros((masks.shape[0], L), dtype=torch.float64, device=xd.device)
-                masks_d = torch.as_tensor(masks.view(np.int64), device=xd.device)
-                eng.overlap_add_block(bases, hop, L, f0, routed, counts, masks_d, win)
-                msks.append(masks)
-            pers.append(per_h)
-            pws.append(pw_h)
-            cnts.append(counts_h)
-            del fr, per, pw, bases, st, counts  # the block's frames and bases go before the next block's come
-
-        def rows(parts):  # (W, cap): small_to_large's blocks differ in cap = max(16, largest count)
-            cap = max(p.shape[1] for p in parts)
-            return np.concatenate([np.pad(p, ((0, 0), (0, cap - p.shape[1]))) for p in parts])
-
-        counts = None if cnts[0] is None else np.concatenate(cnts)
-        masks = np.concatenate(msks, axis=1) if msks and kmax <= _MAX_ROWS else None
-        return rows(pers), rows(pws), counts, np.concatenate(sts), acc, routed, masks, kmax
-
-    def _finish(self, up, acc):
-        """``overlap_add_finish`` of a running sum, in place, and the result on the host."""
-        _, _, W, eng, _, win, _ = up
-        return eng.overlap_add_finish(acc, self.frame_length, self.hop, W, win, win, True, out=acc).cpu().numpy()
-
-    def _analyze_blocks(self, signal, method, B, kwargs):
-        if method not in _METHODS:
-            raise ValueError(f"method must be one of {_METHODS}")
-        num, run = self._method(method, kwargs)
-        up = self._upload(signal)
-        x64, L, W = up[0].astype(np.float64), up[1], up[2]
-        if num == 0:
-            return ShortTimeResult(np.zeros((W, 0), np.uint32), np.zeros((W, 0)), np.zeros(L), x64)
-        per, pw, counts, st, acc, _, _, _ = self._pass(up, run, B, True, None)
-        self._raise_status(st, method)
-        periodic = self._finish(up, acc)[0]
-        return ShortTimeResult(per, pw, periodic, x64 - periodic, counts)
-
-    def _decompose_blocks(self, signal, method, wanted, max_tracks, B, kwargs):
-        num, run = self._method(method, kwargs)
-        up = self._upload(signal)
-        x64, L, W = up[0].astype(np.float64), up[1], up[2]
-        if num == 0:
-            wanted = wanted or []
-            return ShortTimeTracks(np.zeros((W, 0), np.uint32), np.zeros((W, 0)), np.zeros(L), x64, wanted,
-                                   np.zeros((len(wanted), L)), np.zeros(L), np.zeros((len(wanted), W)))
-
-        def too_many(kmax):
-            if kmax > _MAX_ROWS:
-                raise ValueError(f"{kmax} bases per frame: decompose routes at most {_MAX_ROWS}")
-
-        if wanted is not None:  # one pass: the tracks are known before the first block
-            per, pw, counts, st, acc, routed, masks, kmax = self._pass(
-                up, run, B, True, lambda f0, p, c: self.track_masks(p, c, wanted))
-            self._raise_status(st, method)
-            too_many(kmax)
-        else:  # the ranking needs every frame: analyse, rank, then run the method again to route
-            per, pw, counts, st, acc, _, _, kmax = self._pass(up, run, B, True, None)
-            self._raise_status(st, method)
-            too_many(kmax)
-            wanted = [(p,) for p in self.rank_periods(per, pw, counts, max_tracks)]
-            masks = self.track_masks(per, counts, wanted)
-            routed = self._pass(up, run, B, False, lambda f0, p, c: masks[:, f0 : f0 + p.shape[0]])[5]
-        T = len(wanted)
-        periodic = self._finish(up, acc)[0]
-        routed = self._finish(up, routed)
-        return ShortTimeTracks(per, pw, periodic, x64 - periodic, wanted, routed[:T], routed[T],
-                               self._activity(masks, pw, T), counts)
-
-    def decompose(self, signal, method="m_best", tracks=None, max_tracks=8, block_frames=None, **kwargs):
-        """``analyze``, and the periodic part split by period: -> ShortTimeTracks.  `tracks`: None -- the `max_tracks`
-        strongest periods of the recording, one track each (``rank_periods``) -- or a list whose entries are a period or
-        an iterable of periods, e.g. ``[12, (17, 34)]``.  The pipeline is that of ``analyze`` (same methods, keyword
-        arguments and exceptions); afterwards only the per-frame periods / powers / counts come down, the routing masks
-        (``track_masks``) go up, and one routed overlap-add (``PeriodEngine.overlap_add_tracks``) folds the bases onto
-        T + 1 rows: the tracks and ``other``.  The ``(W, K, N)`` bases never leave the device.  K <= 64 bases per
-        frame: `num` > 64 raises ValueError before anything is launched; for small_to_large K is known only once the
-        method has run, so there the check comes after the method's kernels and before the two overlap-adds.
-
-        `block_frames`: as in ``analyze`` -- B frames at a time, the bases of a block added into two running sums, (L)
-        and (T + 1, L), under the block's masks; the same result and exceptions, bit for bit.  With `tracks` given the
-        analysis runs once.  With ``tracks=None`` the ranking needs every frame before the first block can be routed,
-        so the analysis runs TWICE: once for the per-frame results and ``periodic``, then, after ``rank_periods``, again
-        block by block to fold the bases onto the tracks."""
-        if method not in _METHODS:
-            raise ValueError(f"method must be one of {_METHODS}")
-        B = self._block_frames(block_frames)
-        wanted, max_tracks, _, _ = self._track_args(tracks, max_tracks, tracks_first=True)
-        if method != "small_to_large" and int(kwargs.get("num", 5)) > _MAX_ROWS:
-            raise ValueError(f"num={int(kwargs['num'])} bases per frame: decompose routes at most {_MAX_ROWS}")
-        if B is not None:
-            return self._decompose_blocks(signal, method, wanted, max_tracks, B, kwargs)
-        x64, L, W, eng, win, num, per, pw, bases, counts = self._run(signal, method, kwargs)
-        if num == 0:
-            wanted = wanted or []
-            return ShortTimeTracks(np.zeros((W, 0), np.uint32), np.zeros((W, 0)), np.zeros(L), x64, wanted,
-                                   np.zeros((len(wanted), L)), np.zeros(L), np.zeros((len(wanted), W)))
-        if bases.shape[1] > _MAX_ROWS:
-            raise ValueError(f"{bases.shape[1]} bases per frame: decompose routes at most {_MAX_ROWS}")
-        import torch
-
-        counts_d = counts
-        per, pw, counts = self._host_results(per, pw, counts)  # the small per-frame arrays down
-        if wanted is None:
-            wanted = [(p,) for p in self.rank_periods(per, pw, counts, max_tracks)]
-        masks = self.track_masks(per, counts, wanted)
-        T = len(wanted)
-        masks_d = torch.as_tensor(masks.view(np.int64), device=bases.device)  # (T + 1) * W words up
-        routed = eng.overlap_add_tracks(bases, masks_d, self.hop, L, counts_d, win, win, True)
-        periodic = eng.overlap_add(bases, self.hop, L, counts_d, win, win, True).cpu().numpy()
-        routed = routed.cpu().numpy()
-        return ShortTimeTracks(per, pw, periodic, x64 - periodic, wanted, routed[:T], routed[T],
-                               self._activity(masks, pw, T), counts)
-
     def decompose_qo(self, signal, num, thresh, min_length=2, max_length=None, update_weights=True, tracks=None,
                      max_tracks=8, max_rows=2048):
         """``QOPeriods.find_periods`` followed by ``get_periods`` on every frame, and the per-period waveforms
@@ -495,11 +484,12 @@ class ShortTime:
         wanted, max_tracks, max_rows, _ = self._track_args(tracks, max_tracks, max_rows)
         max_length = self.frame_length // 3 if max_length is None else int(max_length)
         fit = (int(num), thresh, int(min_length), max_length, bool(update_weights))
-        x, L, W, eng, dev, win, fr = self._device_frames(signal)
+        rec = self._upload(signal)
+        fr = self._frames(rec, 0, rec.W)
         silent = (fr.to(torch.float64).abs().sum(dim=1) <= 1e-16).cpu().numpy()
-        blocks, st = self._qo_fit(torch, eng, fr, fit, max_rows)
+        blocks, st = self._qo_fit(torch, rec.eng, fr, fit, max_rows)
         blocks = self._qo_host_route(torch, fr, silent, st, blocks, fit)
-        return ShortTimeTracks(*self._block_tracks(torch, eng, blocks, wanted, max_tracks, x, L, win))
+        return self._block_tracks(torch, rec, blocks, wanted, max_tracks)
 
     def decompose_ramanujan(self, signal, thresh=0.2, min_length=2, max_length=None, reference="recording",
                             max_periods=16, tracks=None, max_tracks=8, max_rows=2048):
@@ -549,7 +539,8 @@ class ShortTime:
         q_hi = self.frame_length // 3 if max_length is None else int(max_length)
         if q_hi < 1:
             raise ValueError(f"max_length={q_hi}: decompose_ramanujan needs periods up to at least 1")
-        x, L, W, eng, dev, win, fr = self._device_frames(signal)
+        rec = self._upload(signal)
+        W, eng, dev, fr = rec.W, rec.eng, rec.xd.device, self._frames(rec, 0, rec.W)
         norms = eng.ramanujan_norms(fr, min_length, q_hi)
         if reference == "frame":
             ref = None
@@ -563,7 +554,7 @@ class ShortTime:
         keeps, wts, st = self._ram_fit(torch, eng, fr, per, cnt, q_hi, max_rows)
         cnt_h = cnt.cpu().numpy()
         blocks, status = self._ram_host_route(torch, fr, (per, keeps, cnt, wts), cnt_h, st, min_length, q_hi)
-        tail = self._block_tracks(torch, eng, blocks, wanted, max_tracks, x, L, win)
+        tail = self._block_tracks(torch, rec, blocks, wanted, max_tracks)
         return ShortTimeRamanujan(*tail, norms.cpu().numpy(), over.cpu().numpy(), status)
 
     @staticmethod
@@ -583,17 +574,13 @@ class ShortTime:
             wanted = ShortTime._track_list(tracks)
         return wanted, max_tracks, max_rows, min_length
 
-    def _block_tracks(self, torch, eng, blocks, wanted, max_tracks, x, L, win):
+    def _block_tracks(self, torch, rec, blocks, wanted, max_tracks):
         """The tail of the block pipelines: one period per block, the tracks (ranked when none were named) and the one
-        routed overlap-add.  -> the nine fields of ShortTimeTracks, in order."""
-        seg, per_h, pw_h, counts_h = self._qo_segments(torch, eng, blocks)
-        if wanted is None:
-            wanted = [(p,) for p in self.rank_periods(per_h, pw_h, counts_h, max_tracks)]
-        T = len(wanted)
-        masks, routed = self._qo_route(torch, eng, seg, blocks, per_h, counts_h, wanted, L, win)
-        periodic = routed[T + 1]
-        return (per_h, pw_h, periodic, x.astype(np.float64) - periodic, wanted, routed[:T], routed[T],
-                self._activity(masks, pw_h, T), counts_h)
+        routed overlap-add, whose last row is ``periodic``.  -> ShortTimeTracks."""
+        seg, per_h, pw_h, counts_h = self._qo_segments(torch, rec.eng, blocks)
+        wanted = self._ranked(per_h, pw_h, counts_h, wanted, max_tracks)
+        masks, routed = self._qo_route(torch, rec.eng, seg, blocks, per_h, counts_h, wanted, rec.L, rec.win)
+        return self._assemble(rec, per_h, pw_h, counts_h, routed[len(wanted) + 1], wanted, routed, masks)
 
     @staticmethod
     def _rerun_capped(torch, dev, W, capacities, tensors, launch):

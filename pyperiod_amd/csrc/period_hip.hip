@@ -2711,11 +2711,11 @@ int ph_overlap_add_block(ph_ctx* c, const void* y, int dtype, int64_t Wb, int K,
   const dim3 grid(flat_grid(c, T * (std::min(end, L) - f0 * hop)));
   PH_TRY(dispatch(dtype, [&](auto t) {
     using E = decltype(t);
-    if (sd.masks)
-      return launch(c, "k_overlap_add_block", ph::k_overlap_add_block<E, true>, grid, ph::kFramesBlock, 0, (const E*)dy, Wb, K,
-                    N, hop, L, f0, sd.counts, sd.masks, T, sd.ws, (double*)dacc);
-    return launch(c, "k_overlap_add_block", ph::k_overlap_add_block<E, false>, grid, ph::kFramesBlock, 0, (const E*)dy, Wb, K,
-                  N, hop, L, f0, sd.counts, sd.masks, T, sd.ws, (double*)dacc);
+    auto block = [&](auto routed) {
+      return launch(c, "k_overlap_add_block", ph::k_overlap_add_block<E, decltype(routed)::value>, grid, ph::kFramesBlock, 0,
+                    (const E*)dy, Wb, K, N, hop, L, f0, sd.counts, sd.masks, T, sd.ws, (double*)dacc);
+    };
+    return sd.masks ? block(std::true_type{}) : block(std::false_type{});
   }));
   return st.finish();
 }

@@ -127,6 +127,49 @@ __device__ __forceinline__ unsigned long long ola_cut(unsigned long long m, int 
 __device__ __forceinline__ double ola_result(double num, double den, int norm) {
   return norm ? (den > 0.0 ? num / den : 0.0) : num;
 }
+// The two row walks over row[k * N], the sample of one frame's rows.  The one-launch kernels and the blocked kernel add
+// their terms with these, so a block continues a sample's sum with the very expression of the one-launch kernels:
+// num += s * (double)row[...], four loads in flight, added in ascending k.
+// the rows k < kf
+template <typename T>
+__device__ __forceinline__ void ola_add_rows(const T* __restrict__ row, int N, int kf, double s, double& num) {
+  int k = 0;
+  for (; k + 4 <= kf; k += 4) {
+    const double a0 = (double)row[(int64_t)(k + 0) * N], a1 = (double)row[(int64_t)(k + 1) * N];
+    const double a2 = (double)row[(int64_t)(k + 2) * N], a3 = (double)row[(int64_t)(k + 3) * N];
+    num += s * a0;
+    num += s * a1;
+    num += s * a2;
+    num += s * a3;
+  }
+  for (; k < kf; ++k) num += s * (double)row[(int64_t)k * N];
+}
+// the rows a mask word names, already cut to the rows in use (ola_cut): lowest set bit first
+template <typename T>
+__device__ __forceinline__ void ola_add_masked(const T* __restrict__ row, int N, unsigned long long m, double s, double& num) {
+  int left = __builtin_popcountll(m);
+  for (; left >= 4; left -= 4) {
+    const int k0 = __builtin_ctzll(m);
+    m &= m - 1ull;
+    const int k1 = __builtin_ctzll(m);
+    m &= m - 1ull;
+    const int k2 = __builtin_ctzll(m);
+    m &= m - 1ull;
+    const int k3 = __builtin_ctzll(m);
+    m &= m - 1ull;
+    const double a0 = (double)row[(int64_t)k0 * N], a1 = (double)row[(int64_t)k1 * N];
+    const double a2 = (double)row[(int64_t)k2 * N], a3 = (double)row[(int64_t)k3 * N];
+    num += s * a0;
+    num += s * a1;
+    num += s * a2;
+    num += s * a3;
+  }
+  for (; left > 0; --left) {
+    const int k = __builtin_ctzll(m);
+    m &= m - 1ull;
+    num += s * (double)row[(int64_t)k * N];
+  }
+}
 
 // ======================================================================================
 // Overlap-add in the gather form: y (W, K, N) of T -> out (L) float64.
@@ -155,16 +198,7 @@ __global__ __launch_bounds__(kFramesBlock) void k_overlap_add(const T* __restric
       const int kf = counts ? ola_clip(counts[f], K) : K;
       const double s = ola_window(i, wa, ws, den);
       const T* row = y + (f * K) * (int64_t)N + i;
-      int k = 0;
-      for (; k + 4 <= kf; k += 4) {  // four loads in flight, added in ascending k
-        const double a0 = (double)row[(int64_t)(k + 0) * N], a1 = (double)row[(int64_t)(k + 1) * N];
-        const double a2 = (double)row[(int64_t)(k + 2) * N], a3 = (double)row[(int64_t)(k + 3) * N];
-        num += s * a0;
-        num += s * a1;
-        num += s * a2;
-        num += s * a3;
-      }
-      for (; k < kf; ++k) num += s * (double)row[(int64_t)k * N];
+      ola_add_rows(row, N, kf, s, num);
     }
     out[n] = ola_result(num, den, norm);
   }
@@ -178,9 +212,9 @@ __global__ __launch_bounds__(kFramesBlock) void k_overlap_add(const T* __restric
 // mask instead of a (W, K) label array: with labels a lane would compare all K labels of a frame for the ~K / NT rows it
 // loads; with a mask it is one 8-byte load per frame -- the same address for every lane of a wavefront unless the
 // wavefront straddles two frames' worth of n or two tracks -- and then a walk over the set bits.  Bits at or above K_f
-// are cut off (ola_cut), the walk takes the lowest set bit with ctz and clears it with m & (m - 1), so bit 63 is a row
-// like any other.  Masks may overlap (the row is added to every track that names it); rows behind K_f or in no mask are
-// never read.
+// are cut off (ola_cut), the walk (ola_add_masked) takes the lowest set bit with ctz and clears it with m & (m - 1), so
+// bit 63 is a row like any other.  Masks may overlap (the row is added to every track that names it); rows behind K_f
+// or in no mask are never read.
 // One lane owns one (t, n) and walks frames in ascending f, rows in ascending k, accumulating in float64: one fixed
 // order, no atomics, the same bits on every run.  Items are flat over NT * L, so the lanes of a wavefront may lie in two
 // tracks (L not a multiple of 64): every lane derives its own (t, n) and loads its own mask word.  Grid-stride loop.
@@ -205,30 +239,8 @@ __global__ __launch_bounds__(kFramesBlock) void k_overlap_add_tracks(const T* __
       const int i = (int)(n - f * hop);
       const int kf = counts ? ola_clip(counts[f], K) : K;
       const double s = ola_window(i, wa, ws, den);
-      unsigned long long m = ola_cut(mrow[f], kf);
       const T* row = y + (f * K) * (int64_t)N + i;
-      int left = __builtin_popcountll(m);
-      for (; left >= 4; left -= 4) {  // four loads in flight, added in ascending k
-        const int k0 = __builtin_ctzll(m);
-        m &= m - 1ull;
-        const int k1 = __builtin_ctzll(m);
-        m &= m - 1ull;
-        const int k2 = __builtin_ctzll(m);
-        m &= m - 1ull;
-        const int k3 = __builtin_ctzll(m);
-        m &= m - 1ull;
-        const double a0 = (double)row[(int64_t)k0 * N], a1 = (double)row[(int64_t)k1 * N];
-        const double a2 = (double)row[(int64_t)k2 * N], a3 = (double)row[(int64_t)k3 * N];
-        num += s * a0;
-        num += s * a1;
-        num += s * a2;
-        num += s * a3;
-      }
-      for (; left > 0; --left) {
-        const int k = __builtin_ctzll(m);
-        m &= m - 1ull;
-        num += s * (double)row[(int64_t)k * N];
-      }
+      ola_add_masked(row, N, ola_cut(mrow[f], kf), s, num);
     }
     out[item] = ola_result(num, den, norm);
   }
@@ -295,18 +307,17 @@ __global__ __launch_bounds__(kFramesBlock) void k_overlap_add_periodic(const dou
 // Overlap-add in frame blocks: k_overlap_add_block adds the frames f0 .. f0 + Wb - 1 of a recording into a running sum
 // acc (NT, L) float64, k_overlap_add_finish turns the running sum into the result.  Everything about the block is
 // block-local: y (Wb, K, N) of T, counts (Wb), masks (NT, Wb); only f0 places it in the recording.
-//   Routed = false (NT = 1): acc[0, n] += the terms k_overlap_add adds for the frames of the block, every k < K_f, four
-//     loads in flight, added in ascending k; K may exceed 64.
-//   Routed = true: acc[t, n] += the terms k_overlap_add_tracks adds for them: ola_cut, lowest set bit first, bit 63 a
-//     row like any other.
+//   Routed = false (NT = 1): acc[0, n] += the terms k_overlap_add adds for the frames of the block (ola_add_rows); K
+//     may exceed 64.
+//   Routed = true: acc[t, n] += the terms k_overlap_add_tracks adds for them (ola_cut, ola_add_masked).
 // The work items are the NT * (n1 - n0) samples of the block's span, n0 = f0 hop, n1 = min(L, (f0 + Wb - 1) hop + N);
 // a sample outside the span is neither read nor written.  A lane loads num = acc[t, n], walks the frames
 // max(f_lo(n), f0) .. min(f_hi(n), f0 + Wb - 1) in ascending f -- f_lo / f_hi are those of the whole recording; its last
-// frame can only cut f_hi where the block's last frame does already -- with the very expression of the one-launch
-// kernels (num += s * (double)row[...]), and stores num back.  den is not touched here: it depends on n, W, hop and the
-// windows alone, and k_overlap_add_finish recomputes it by the walk of the one-launch kernels over all W frames
-// (ola_window only) and writes out[t, n] = ola_result(acc[t, n], den[n], norm); out may be acc itself, each lane reads
-// its own element before it writes it.
+// frame can only cut f_hi where the block's last frame does already -- with the row walk of the one-launch kernels, and
+// stores num back.  den is not touched here: it depends on n, W, hop and the windows alone, and k_overlap_add_finish
+// recomputes it by the walk of the one-launch kernels over all W frames (ola_window only) and writes
+// out[t, n] = ola_result(acc[t, n], den[n], norm); out may be acc itself, each lane reads its own element before it
+// writes it.
 // Contract (nothing here can check it): acc is zeroed before the first block, the blocks are applied on one stream in
 // ascending f0, and every frame belongs to exactly one block.  A lane of a later block then continues the walk of its
 // sample where the lane of the block before left it: the same additions in the same order as one launch over the whole
@@ -338,42 +349,10 @@ __global__ __launch_bounds__(kFramesBlock) void k_overlap_add_block(const T* __r
       const int kf = counts ? ola_clip(counts[fb], K) : K;
       const double s = ola_window(i, nullptr, ws, den);
       const T* row = y + (fb * K) * (int64_t)N + i;
-      if constexpr (Routed) {
-        unsigned long long m = ola_cut(masks[t * Wb + fb], kf);
-        int left = __builtin_popcountll(m);
-        for (; left >= 4; left -= 4) {  // four loads in flight, added in ascending k
-          const int k0 = __builtin_ctzll(m);
-          m &= m - 1ull;
-          const int k1 = __builtin_ctzll(m);
-          m &= m - 1ull;
-          const int k2 = __builtin_ctzll(m);
-          m &= m - 1ull;
-          const int k3 = __builtin_ctzll(m);
-          m &= m - 1ull;
-          const double a0 = (double)row[(int64_t)k0 * N], a1 = (double)row[(int64_t)k1 * N];
-          const double a2 = (double)row[(int64_t)k2 * N], a3 = (double)row[(int64_t)k3 * N];
-          num += s * a0;
-          num += s * a1;
-          num += s * a2;
-          num += s * a3;
-        }
-        for (; left > 0; --left) {
-          const int k = __builtin_ctzll(m);
-          m &= m - 1ull;
-          num += s * (double)row[(int64_t)k * N];
-        }
-      } else {
-        int k = 0;
-        for (; k + 4 <= kf; k += 4) {  // four loads in flight, added in ascending k
-          const double a0 = (double)row[(int64_t)(k + 0) * N], a1 = (double)row[(int64_t)(k + 1) * N];
-          const double a2 = (double)row[(int64_t)(k + 2) * N], a3 = (double)row[(int64_t)(k + 3) * N];
-          num += s * a0;
-          num += s * a1;
-          num += s * a2;
-          num += s * a3;
-        }
-        for (; k < kf; ++k) num += s * (double)row[(int64_t)k * N];
-      }
+      if constexpr (Routed)
+        ola_add_masked(row, N, ola_cut(masks[t * Wb + fb], kf), s, num);
+      else
+        ola_add_rows(row, N, kf, s, num);
     }
     acc[t * L + n] = num;
   }

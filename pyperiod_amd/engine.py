@@ -727,9 +727,11 @@ class PeriodEngine:
         ws = None if win_s is None else self._window(mk, x, win_s, N)
         return cnt, wa, ws
 
-    def _ola_call(self, mk, shape, W, L, fn, *args, fl, normalize):
-        """The float64 result of an overlap-add: one call of `fn` (flags and result last), or zeros when W or L is 0."""
-        out = mk.empty(shape, np.float64)
+    def _ola_call(self, mk, shape, W, L, fn, *args, fl, normalize, out=None):
+        """The float64 result of an overlap-add, a new array or `out`: one call of `fn` (flags and result last), or zeros
+        when W or L is 0."""
+        if out is None:
+            out = mk.empty(shape, np.float64)
         if W == 0 or L == 0:
             out[...] = 0.0
             return out
@@ -837,18 +839,11 @@ class PeriodEngine:
             fl, mk = 0, _Out(acc)
             x = acc
         T, L = self._ola_acc(mk, x, acc, "acc", "acc")
-        if out is None:
-            out = mk.empty(tuple(acc.shape), np.float64)
-        elif self._ola_acc(mk, x, out, "out", "acc") != (T, L) or out.ndim != acc.ndim:
+        if out is not None and (self._ola_acc(mk, x, out, "out", "acc") != (T, L) or out.ndim != acc.ndim):
             raise ValueError("out must have the shape of acc")
-        wa = None if win_a is None else self._window(mk, x, win_a, N)
-        ws = None if win_s is None else self._window(mk, x, win_s, N)
-        if W == 0 or L == 0:
-            out[...] = 0.0
-            return out
-        self._call(mk, W, self._lib.ph_overlap_add_finish, mk.addr(acc), T, N, hop, L, W, mk.addr(wa), mk.addr(ws),
-                   fl | (_ffi.PH_FLAG_OLA_NORM if normalize else 0), mk.addr(out))
-        return out
+        _, wa, ws = self._ola_sides(mk, x, W, N, None, win_a, win_s, "acc")
+        return self._ola_call(mk, tuple(acc.shape), W, L, self._lib.ph_overlap_add_finish, mk.addr(acc), T, N, hop, L, W,
+                              mk.addr(wa), mk.addr(ws), fl=fl, normalize=normalize, out=out)
 
     def fold_sums(self, x, p_list, keep):
         """W = A x for natural-basis rows (QOPeriods.py:782): (W, sum(keep)) float64."""

@@ -10,7 +10,8 @@ block of one frame at hop = 1 makes a thousand launches per partition); the bind
 partitions of every shape.
 
 End to end: ``analyze`` / ``decompose`` with ``block_frames`` against the same call without, field for field and bit for
-bit, the exception of a bad frame in a late block, and the peak device memory of a blocked run."""
+bit, the kernels either call launches, the exception of a bad frame in a late block, and the peak device memory of a
+blocked run."""
 
 import warnings
 
@@ -487,6 +488,28 @@ def test_decompose_in_blocks_is_decompose(eng, method, kwargs):
         _, names = _launches(eng, lambda: st.analyze(x, method=method, block_frames=B, **kwargs))
         assert names.count("k_frames") == nb and names.count(first) == nb
         assert names.count("k_overlap_add_block") == nb and names.count("k_overlap_add_finish") == 1
+
+
+@pytest.mark.parametrize("method,kwargs", [("m_best", {"num": 3}), ("small_to_large", {"thresh": 0.1})])
+def test_unblocked_calls_launch_one_block_and_no_block_kernel(eng, method, kwargs):
+    """Without ``block_frames``: one k_frames, one run of the method, the one-launch overlap-adds (decompose: the routed
+    one first) and neither block kernel -- with ranked tracks too, which need no second run of the method."""
+    st, x = _short_time(), _recording(method)
+    blocked = {"k_overlap_add_block", "k_overlap_add_finish"}
+    _, names = _launches(eng, lambda: st.analyze(x, method=method, **kwargs))
+    assert len(names) < 256
+    assert names[0] == "k_frames" and names.count("k_frames") == 1
+    assert names[-1] == "k_overlap_add" and names.count("k_overlap_add") == 1
+    assert "k_overlap_add_tracks" not in names and not blocked & set(names)
+    # a kernel of the method that one run of it launches once
+    first = next(n for n in names[1:] if names.count(n) == 1 and not n.startswith("k_overlap_add"))
+    for kw in ({"tracks": [12, (17, 34), 5]}, {"max_tracks": 4}):
+        _, got = _launches(eng, lambda: st.decompose(x, method=method, **kw, **kwargs))
+        assert len(got) < 256
+        assert got[0] == "k_frames" and got.count("k_frames") == 1 and got.count(first) == 1, kw
+        assert got[-2:] == ["k_overlap_add_tracks", "k_overlap_add"], kw
+        assert got.count("k_overlap_add_tracks") == 1 and got.count("k_overlap_add") == 1 and not blocked & set(got), kw
+        assert got[1:-2] == names[1:-1], kw  # the method's kernels once, as analyze launches them: not twice
 
 
 def test_bad_frame_in_a_late_block_raises_what_the_unblocked_call_raises(eng):

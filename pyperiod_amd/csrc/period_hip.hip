@@ -81,6 +81,8 @@ struct ph_ctx {
   bool pair_chain = true;  // PH_PAIR_CHAIN=0: the window-pair kernels take the periods below 64 one pass each
   bool pair_cover = true;  // PH_PAIR_COVER=0: plain m_best screens every period instead of the top half (pair_screen_lo)
   bool pair_duo = true;    // PH_PAIR_DUO=0: the window-pair m_best screen folds every period in a pass of its own
+  bool pair_fold_once = true;  // PH_PAIR_FOLD_ONCE=0: k_mbest_step1_pair stages, thins and evaluates every window-sweep as before the fold-once path
+  bool pair_fold_report = false;  // PH_PAIR_FOLD_REPORT=1 (tests): n_sweeps carries the window's fold-once count above bit 16
   DevBuf twid;  // cos/sin(2 pi k / L), k < L, of the last best_frequency win_size
   int twid_len = -1;
   DevBuf bs_tab;  // Bluestein tables of the last (win_size, min(N, win_size)): M twiddles, chirp, FFT of the wrapped chirp
@@ -1150,6 +1152,8 @@ int ph_create(int device, ph_ctx** out) {
   if (const char* e = std::getenv("PH_PAIR_CHAIN")) c->pair_chain = std::atoi(e) != 0;
   if (const char* e = std::getenv("PH_PAIR_COVER")) c->pair_cover = std::atoi(e) != 0;
   if (const char* e = std::getenv("PH_PAIR_DUO")) c->pair_duo = std::atoi(e) != 0;
+  if (const char* e = std::getenv("PH_PAIR_FOLD_ONCE")) c->pair_fold_once = std::atoi(e) != 0;
+  if (const char* e = std::getenv("PH_PAIR_FOLD_REPORT")) c->pair_fold_report = std::atoi(e) != 0;
   if (const char* e = std::getenv("PH_STEP1_BLOCK")) {
     const int v = std::atoi(e);
     if (v >= 64 && v <= 1024 && v % 64 == 0) c->step1_block = v;
@@ -1583,7 +1587,7 @@ int ph_m_best(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int num, in
     PH_TRY(launch(c, "k_mbest_step1", ph::k_mbest_step1_pair, dim3((unsigned)((W + 1) / 2)), s1.block, s1.lds,
                   (const double*)dx, (int)W, N, num, min_length, max_length, p_scr, gamma, tb.fac_off, tb.fac_q, geom, ws.geomf,
                   ws.radq, plan, n_pass, ws.gwin, max_iters, (uint32_t*)dper, (double*)dpow, (double*)drows, row_stride, dnorm,
-                  (int*)dstat, (int*)dsweeps));
+                  (int*)dstat, (int*)dsweeps, c->pair_fold_once ? ph::pair_thin_band(N) : -1.0, c->pair_fold_report ? 1 : 0));
   } else {
     PH_TRY(dispatch(dtype, !gwin1, [&](auto t, auto lw) {
       using T = decltype(t);

@@ -284,7 +284,7 @@ enum {
   MP_LISTED = 0,      // survivors listed
   MP_FILLED = 2,      // rows filled (`i` of Periods.py:494)
   MP_REPEATS = 4,     // `iters` of Periods.py:494
-  MP_STATUS = 6,
+  MP_STATUS = 6,      // status in the low byte; above it the window-sweeps that took the fold-once path
   MP_SWEEPS = 8,      // sweeps done
   MP_RUNNING = 10,    // still running
   MP_EXACT_ALL = 12,  // every period goes through the exact evaluation
@@ -309,7 +309,10 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
     const int* __restrict__ fac_off, const int* __restrict__ fac_q, const PGeom* __restrict__ geom, const PGeomF* __restrict__ geomf, const double* __restrict__ radq, const PassPlan* __restrict__ plan, int n_pass,
     double* __restrict__ gres, int max_iters, uint32_t* __restrict__ periods_out, double* __restrict__ norms_out,
     double* __restrict__ rows_out, int row_stride, double* __restrict__ dnorm_out, int* __restrict__ status_out,
-    int* __restrict__ sweeps_out) {
+    int* __restrict__ sweeps_out, double thin_band, int fold_report) {
+  // thin_band: pair_thin_band(N) from the host (computed here it is a loop invariant in vector registers, spilled around the
+  // screen), or a negative number: no fold-once path (PH_PAIR_FOLD_ONCE=0)
+  const bool fold_once = __double2hiint(thin_band) >= 0;  // (the sign bit, on the scalar unit)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   Carve cv(smem);
   f2* pw = cv.take<f2>(N + kPad);
@@ -364,7 +367,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
       if (exists) dnorm_out[gw] = periodic_norm_from_sq_n(rsq, sqrtN, 0);
     }
   }
-  StageClock<kPairTimers, 5, 2> clk;  // stages: screen, scan, load, exact, update; counters: candidates, exact_all
+  StageClock<kPairTimers, 6, 3> clk;  // stages: screen, scan, load, thin, exact, update; counters: candidates, exact_all, folded
   WgStamp<kClocks> stamp;
   for (;;) {
     __syncthreads();
@@ -505,18 +508,73 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
       uint32_t* sk = skip + w * SK;
       const int* lst = list + w * kPairListCap;
       __syncthreads();
+      bool folded = false;  // this window-sweep took the fold-once path
       if (iters + 1 > max_iters) {
         status = 2;
       } else {
         const double* src = iters == 0 ? x + gw * (int64_t)N : gres + gw * gstride;
         iters += 1;
+        // ---- fold-once path (ph_pair.h, pair_thin_band): the list is one top period m > kPairSmallP and divisors of it.
+        // The residual is folded once, at m, straight from the workspace (the input before the first subtraction): the
+        // column sums S_m go to the idle staging buffer and give the cooperative value of m -- thread <-> residue and
+        // order of pair_exact_part --, the value of every listed divisor and the means of the update.  A divisor within
+        // the band of m (a window that is d-periodic), or any other list, takes the phases below from the staging load on.
+        int fold_m = 0;
+        double fold_ss = 0.0;
+        if (fold_once && !exact_all) {
+          const int k0 = lane, k1 = kWave + lane;
+          const int q0 = k0 < ncand ? lst[k0] : 0, q1 = k1 < ncand ? lst[k1] : 0;
+          const unsigned long long t0 = __ballot(q0 >= p_scr), t1 = __ballot(q1 >= p_scr);
+          if (__popcll(t0) + __popcll(t1) == 1) {
+            const int m = t0 ? __builtin_amdgcn_readlane(q0, __builtin_amdgcn_readfirstlane(__ffsll((long long)t0) - 1))
+                             : __builtin_amdgcn_readlane(q1, __builtin_amdgcn_readfirstlane(__ffsll((long long)t1) - 1));
+            // every other entry must divide m (a skipped top period lists its divisors too): m = k d with k the rounded
+            // float quotient, exact for m < 2^22
+            const float fm = (float)m;
+            const int c0 = (int)(fm * __builtin_amdgcn_rcpf((float)max(q0, 1)) + 0.5f), c1 = (int)(fm * __builtin_amdgcn_rcpf((float)max(q1, 1)) + 0.5f);
+            const bool odd = (k0 < ncand && c0 * q0 != m) || (k1 < ncand && c1 * q1 != m);
+            if (m > kPairSmallP && __ballot(odd) == 0ull) fold_m = m;
+          }
+        }
+        if (fold_m != 0) {
+          const PGeom gm = geom[fold_m];
+          double part = 0.0;
+          if (tid == 0) wbestp[0] = 0;  // the tie flag of the thinning below
+          for (int j = tid; j < fold_m; j += blockDim.x) {
+            const bool full = j < gm.nfull;
+            const double s = pair_column_sum_global(src, j, fold_m, full ? gm.rows : gm.rows - 1);
+            part = fma(s * s, full ? gm.w_full : gm.w_short, part);
+            stg[j] = s;
+          }
+          fold_ss = block_sum(part, red);
+          clk.mark(2);
+          if (ncand > 1) {
+            // a wavefront per listed divisor: its value from S_m (pair_thin_part) against the threshold; one that reaches it
+            // raises the flag (wbestp is idle on this path; cleared in front of the barriers of the block sum above)
+            // the band in the units of the values: MP_UNIT without its scale, a power of two
+            const int se = __builtin_amdgcn_frexp_exp(dst2[MP_SCALE + w]) - 1;
+            const double band = thin_band * ldexp(dst2[MP_UNIT + w], -2 * se);
+            // (1e-9 through a scalar register pair at its use: as a loop invariant in vector registers it is spilled around
+            // the screen)
+            double tie = 1e-9;
+            asm volatile("" : "+s"(tie));
+            const double thr = fold_ss - fabs(fold_ss) * tie - band;
+            for (int k = wv; k < ncand; k += nw) {
+              const int d = __builtin_amdgcn_readfirstlane(lst[k]);
+              if (d == fold_m) continue;
+              const double t = wave_sum(pair_thin_part(stg, fold_m, d, geom[d], lane));
+              if (lane == 0 && !(t < thr)) wbestp[0] = 1;
+            }
+            __syncthreads();
+            // (a window that falls back rewrites the staging buffer at once; wbestp only behind further barriers)
+            if (__builtin_amdgcn_readfirstlane(wbestp[0]) != 0) fold_m = 0;
+          }
+          clk.mark(3);
+        }
+        if (fold_m == 0) {
         load_window(src, stg, N);
         __syncthreads();
         clk.mark(2);
-        if (kPairTimers) {  // (spelled out: an unused look at exact_all changes the branches the compiler builds from it)
-          clk.count(0, ncand);
-          clk.count(1, exact_all ? 1 : 0);
-        }
         if (p_scr > p_lo && !exact_all && ncand > 1) {
           // cover rule: the list holds the surviving screened periods AND their divisors, which no screen value has
           // thinned out.  A wavefront per candidate evaluates them in fp64; only those within 1e-9 (relative) of the
@@ -547,6 +605,14 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
           __syncthreads();
           ncand = __builtin_amdgcn_readfirstlane(ctl[MP_LISTED + w]);
         }
+        clk.mark(3);
+        }  // staging load and thinning of a window-sweep that does not fold once
+        folded = fold_m != 0;
+        if (kPairTimers) {  // (spelled out: an unused look at exact_all changes the branches the compiler builds from it)
+          clk.count(0, exact_all ? P : nlisted);  // (candidates in front of the thinning)
+          clk.count(1, exact_all ? 1 : 0);
+          clk.count(2, fold_m != 0 ? 1 : 0);
+        }
         double best_ss = 0.0;
         int bestp = 0;
         // (the norm with sqrt(N) from a scalar register)
@@ -559,7 +625,11 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
           }
         };
         double best = 0.0;
-        if (ncand <= kPairCoop) {
+        if (fold_m != 0) {
+          consider(fold_ss, fold_m);
+          best = bestp != 0 ? periodic_norm_from_sq_n(best_ss, sqrtN, gamma ? bestp : 0) : 0.0;
+          if (!(best > 0.0)) bestp = 0;
+        } else if (ncand <= kPairCoop) {
           // few survivors (the normal case): the whole workgroup folds one candidate at a time, a wavefront per
           // 64 residues; partial sums are combined in wave order, so every thread holds the same value
           for (int k = 0; k < ncand; ++k) {
@@ -594,7 +664,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
           red_argmax(wbest, wbestp, nw, best, bestp);
           __syncthreads();
         }
-        clk.mark(3);
+        clk.mark(4);
         if (bestp == 0) {  // reference: max_base is None -> TypeError at Periods.py:520/537
           status = 1;
         } else {
@@ -616,7 +686,39 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
           double acc = 0.0;
           const PGeom gb = geom[__builtin_amdgcn_readfirstlane(bestp)];  // (a scalar load; Fold(N, p) divides in every thread)
           const Fold f(bestp, gb.rows, gb.nfull);
-          if (bestp <= kPairSmallP) {
+          if (fold_m != 0) {
+            // the means from the column sums in the staging buffer (S / cnt: residue_mean's expression); every thread
+            // subtracts them from its own columns, read again from the source and written to the workspace -- in place
+            // after the first sweep, a thread touches only its own columns
+            for (int j = tid; j < bestp; j += blockDim.x) {
+              const int cnt = f.count(j);
+              const double m = stg[j] / (double)cnt;
+              if (action == 1)
+                brow[j] = m;
+              else if (action == 2)
+                brow[j] += m;
+              if (more) {
+                // (four rows are read before the first is written: source and workspace may be the same memory, and a
+                // load behind a store would wait for it)
+                for (int r0 = 0; r0 < cnt; r0 += 4) {
+                  const unsigned at = (unsigned)(r0 * bestp + j);
+                  double v[4];
+#pragma unroll
+                  for (int u = 0; u < 4; ++u) v[u] = src[r0 + u < cnt ? at + (unsigned)(u * bestp) : at];
+#pragma unroll
+                  for (int u = 0; u < 4; ++u) {
+                    if (r0 + u < cnt) {
+                      const unsigned n = at + (unsigned)(u * bestp);
+                      const double t = v[u] - m;
+                      dst[n] = t;
+                      pwf[2 * n + w] = (float)(t * sc);
+                      acc = fma(t, t, acc);
+                    }
+                  }
+                }
+              }
+            }
+          } else if (bestp <= kPairSmallP) {
             // a short period: its few residues have hundreds of rows each -- means through LDS, the subtraction is spread
             // over the workgroup
             // (the usual winner of m_best_gamma); split_row_means deals the rows of a residue to several threads
@@ -682,11 +784,11 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
       if (tid == 0) {
         ctl[MP_FILLED + w] = filled;
         ctl[MP_REPEATS + w] = repeats;
-        ctl[MP_STATUS + w] = status;
+        ctl[MP_STATUS + w] = status | (((ctl[MP_STATUS + w] >> 8) + (folded ? 1 : 0)) << 8);
         ctl[MP_SWEEPS + w] = iters;
         ctl[MP_RUNNING + w] = (status == 0 && filled < num) ? 1 : 0;
       }
-      clk.mark(4);
+      clk.mark(5);
     }
     }  // phases 2 and 3
   }
@@ -696,8 +798,9 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
            100.0 * (double)(stamp.ck1 - stamp.ck0) / (double)(stamp.wk1 - stamp.wk0), stamp.hwid, stamp.xcc);
   }
   if (kPairTimers && blockIdx.x < PH_PAIR_TIMERS_WGS && tid == 0)
-    printf("pair timers (100 MHz ticks) screen %lld scan %lld load %lld exact %lld update %lld  candidates %d exact_all %d sweeps %d %d\n",
-           clk.ticks(0), clk.ticks(1), clk.ticks(2), clk.ticks(3), clk.ticks(4), clk.counted(0), clk.counted(1), ctl[MP_SWEEPS], ctl[MP_SWEEPS + 1]);
+    printf("pair timers (100 MHz ticks) screen %lld scan %lld load %lld thin %lld exact %lld update %lld  candidates %d exact_all %d folded %d sweeps %d %d\n",
+           clk.ticks(0), clk.ticks(1), clk.ticks(2), clk.ticks(3), clk.ticks(4), clk.ticks(5), clk.counted(0), clk.counted(1), clk.counted(2), ctl[MP_SWEEPS],
+           ctl[MP_SWEEPS + 1]);
   __syncthreads();
   // rows the algorithm never filled keep period 0: step 2 writes them as zeros (np.zeros((num, N)), Periods.py:490)
   for (int w = 0; w < 2; ++w) {
@@ -708,8 +811,9 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
       norms_out[gw * num + k] = norms[w * num + k];
     }
     if (tid == 0) {
-      status_out[gw] = ctl[MP_STATUS + w];
-      if (sweeps_out) sweeps_out[gw] = ctl[MP_SWEEPS + w];
+      status_out[gw] = ctl[MP_STATUS + w] & 255;
+      // fold_report (PH_PAIR_FOLD_REPORT=1, tests): the fold-once count of the window above bit 16 of its sweep count
+      if (sweeps_out) sweeps_out[gw] = ctl[MP_SWEEPS + w] | (fold_report ? (ctl[MP_STATUS + w] >> 8) << 16 : 0);
     }
   }
 }

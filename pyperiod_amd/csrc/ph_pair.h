@@ -836,8 +836,91 @@ __host__ __device__ __forceinline__ double pair_radius(int rows, int q) {
 // e_d <= (2 N + N/64 + 16) 2^-53 < (2 N + 32) 2^-52, the factor 2 covering the second-order terms.  The slack is
 // ABSOLUTE, in units of ssq: after a period has been removed E_d and E_m are both rounding noise of order 1e-33 ssq in
 // either order, which no bound relative to E_m would cover.  Never less than 2^-40.
-__device__ __forceinline__ double pair_cover_slack(int N) {
+__host__ __device__ __forceinline__ double pair_cover_slack(int N) {
   return fmax(9.094947017729282e-13, (2.0 * (double)N + 32.0) * 2.220446049250313e-16);
+}
+
+// Fold-once path of k_mbest_step1_pair: the residual is folded ONCE at the surviving top period m (column sums S_m in
+// row order), and a listed divisor d | m is valued from those sums, T_d = sum_j (sum_{k = j (mod d)} S_m[k])^2 / cnt_d[j],
+// instead of by a fold of its own over the window (v_d, the value of the staged thinning in k_mbest_step1_pair).  Both
+// are fp64 evaluations of the same E_d, and they differ only in the ORDER in which a residue's R_d samples are added: v_d
+// adds them row by row, T_d adds the rows of each of the m / d columns of m first, then those column sums, for d < 64
+// finished by shuffles.  The bound e_d behind pair_cover_slack holds for any order: its first-order term is
+// gamma_{n-1} A_j with n <= R_d the number of terms of the residue, whatever the tree (the sum over the residues likewise:
+// d / 64 + 10 terms at most in either form).  So |T_d - E_d| and |v_d - E_d| are at most e_d ssq <= slack ssq, and
+// |T_d - v_d| <= 2 slack ssq.  The same holds for m itself:
+// the cooperative value E^_m (whole workgroup) and the thinning's wavefront value v_m differ by at most 2 slack ssq.
+// The path is taken only when every listed divisor has
+//   T_d < E^_m - |E^_m| 1e-9 - band ssq,   band = 5 slack.
+// Then v_d <= T_d + 2 slack ssq < v_m + 4 slack ssq - (|v_m| - 2 slack ssq) 1e-9 - 5 slack ssq < v_m - |v_m| 1e-9 (the
+// spare (1 - 2e-9) slack ssq >= 9e-13 ssq is far above the rounding of these few operations, ~1e-16 E): the staged
+// thinning keeps m alone, and the staged phases then decide on the cooperative value of m alone -- the value this path has.
+// Units as for pair_cover_slack: the sum of squares of the (scaled) residual, MP_UNIT of the kernel.
+// (the kernel gets the number from the host)
+__host__ __device__ __forceinline__ double pair_thin_band(int N) { return 5.0 * pair_cover_slack(N); }
+
+// Row-order sum of column j of period m over `n` >= 1 rows of a window in GLOBAL memory (the first row is read
+// unconditionally: the pair kernel runs only with max_length < N, pair_eligible, so every column of a candidate period
+// has at least one row and a full one at least two): ((x[j] + x[m + j]) + x[2 m + j]) + ...,
+// the additions of column_sum in the same order, so the same bits.  Groups of four loads behind the first (a top period
+// has 3 ... 6 rows) on 32-bit offsets from the wave-uniform base: the kernel sits at its register cap.
+__device__ __forceinline__ double pair_column_sum_global(const double* __restrict__ src, int j, int m, int n) {
+  unsigned at = (unsigned)j;
+  double s = src[at];
+  at += (unsigned)m;
+  // (a row past the end re-reads the group's first sample and is not added: no tail loop of dependent round trips, and
+  // no "+ 0.0" that would turn a sum of -0.0 into +0.0)
+  for (int r = 1; r < n; r += 4) {
+    const bool k1 = r + 1 < n, k2 = r + 2 < n, k3 = r + 3 < n;
+    const double a = src[at], b = src[k1 ? at + (unsigned)m : at], c = src[k2 ? at + 2u * (unsigned)m : at],
+                 d = src[k3 ? at + 3u * (unsigned)m : at];
+    s += a;
+    s = k1 ? s + b : s;
+    s = k2 ? s + c : s;
+    s = k3 ? s + d : s;
+    at += 4u * (unsigned)m;
+  }
+  return s;
+}
+
+// T_d of the fold-once path for one wavefront: S = the column sums of period m in LDS, d | m, g = geometry of d in the
+// window (the counts cnt_d[j]).  d >= 64: lane j, j + 64, ... adds its m / d sums.  d < 64: G = 64 / d lanes share a
+// residue (lane l adds S[l], S[l + G d], ...), and the G partial sums are added by shuffles.  Per-lane partials; the
+// caller sums them over the wavefront.
+__device__ __forceinline__ double pair_thin_part(const double* __restrict__ S, int m, int d, const PGeom& g, int lane) {
+  double part = 0.0;
+  if (d >= kWave) {
+    // four residues per trip, their reads in flight together (a residue has only m / d sums, a chain of that many LDS
+    // round trips each); a residue past the end re-reads the trip's first one and is left out
+    const int n = m / d;
+    for (int j0 = lane; j0 < d; j0 += 4 * kWave) {
+      double s[4];
+      const double* at = S + j0;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) s[u] = at[j0 + u * kWave < d ? u * kWave : 0];
+      for (int r = 1; r < n; ++r) {
+        at += d;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) s[u] += at[j0 + u * kWave < d ? u * kWave : 0];
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int j = j0 + u * kWave;
+        if (j < d) part = fma(s[u] * s[u], j < g.nfull ? g.w_full : g.w_short, part);
+      }
+    }
+  } else {
+    const int G = kWave / d, L = G * d;
+    const int q = m / L, rem = m - q * L;
+    double tot = lane < L ? column_sum(S, lane, L, q + (lane < rem ? 1 : 0)) : 0.0;
+    const double own = tot;
+    for (int k = 1; k < G; ++k) {
+      const double o = __shfl(own, (lane + k * d) & (kWave - 1), kWave);  // (lanes below d read lanes below L)
+      tot += o;
+    }
+    part = lane < d ? tot * tot * (lane < g.nfull ? g.w_full : g.w_short) : 0.0;
+  }
+  return part;
 }
 
 // ---------------------------------------------------------------- shared by the window-pair kernels

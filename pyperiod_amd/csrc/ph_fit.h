@@ -1,9 +1,11 @@
 // Fit of a GIVEN period list (QOPeriods.compute_reconstruction, RamanujanPeriods.find_periods_with_weights) on the
-// device: k_qo_fit runs get_subspaces' row bookkeeping, the right-hand side by folds and the matrix-free conjugate
-// gradients of k_qo_find for a list it is handed instead of one it selects greedily; k_qo_fit_win is the same fit under an
-// analysis window (its product goes through a staged sample-length vector); k_ram_select turns Ramanujan norms into that
-// list, k_ram_select_ref does so against a choosable reference level and keeps at most pcap periods.  Included by period_hip.hip behind ph_kernels.h (it uses qo_offdiag and qo_gcd of ph_qo.h).  Reference
-// citations are file:line into /root/reference/pyPeriod/.
+// device.  k_qo_fit runs get_subspaces' row bookkeeping, the right-hand side by folds and the solver of k_qo_find
+// (qo_cg around qo_gram_apply, ph_qo.h) for a list it is handed instead of one it selects greedily.  k_qo_fit_win is
+// the same fit under an analysis window: the same carve, prologue, bookkeeping, solver and epilogue around a product
+// that goes through a staged sample-length vector.  k_ram_select turns Ramanujan norms into that list; k_ram_select_ref
+// does so against a choosable reference level and keeps at most pcap periods.  Then the orthogonal selection step
+// (k_qo_orth_select) and QOPeriods.get_periods (k_qo_extract).
+// Included by period_hip.hip behind ph_kernels.h.  Reference citations are file:line into /root/reference/pyPeriod/.
 #pragma once
 
 #include "ph_kernels.h"
@@ -11,9 +13,9 @@
 namespace ph {
 
 constexpr int kFitMaxPeriod = 1 << 20;  // qo_offdiag's index arithmetic holds for periods below 2^20
-constexpr int kFitCtl = 4;              // control words: status, blocks, rows
+constexpr int kFitCtl = 4;              // control words: status, rows, -, k_qo_fit_win's zero-diagonal flag
 
-// Dynamic LDS of k_qo_fit, the one statement of its layout (the kernel carves in this order; the host plans with it).
+// Dynamic LDS of k_qo_fit, the one statement of its layout (qo_fit_carve carves in this order; the host plans with it).
 // Bookkeeping, then the solver's seven vectors + the sample counts, one slot per dictionary row and one per block.  The
 // divisor bitset over 1 .. max_period is only alive during the row bookkeeping and overlays the vectors, so the size
 // depends on kcap alone unless the bitset is the larger of the two.  The window never enters LDS.
@@ -41,78 +43,102 @@ __device__ __forceinline__ double row16_sum(double v) {
   return v;
 }
 
-// ======================================================================================
-// QOPeriods.compute_reconstruction / get_subspaces + solve_quadratic for a given period list (QOPeriods.py:807-852,
-// :779-796, :1054-1116), natural basis, no analysis window.  One workgroup per window; all solver arithmetic in fp64.
-//   rows of block b = Euler-phi mass the divisors of p_b add to the running divisor set (get_subspaces :830-840)
-//   right-hand side A x by folds of the window, read from HBM / L2 (the window is read twice: here and for the residual)
-//   A A^T w = A x by the Jacobi-preconditioned single-reduction conjugate gradients of k_qo_find, started from zero:
-//     same matrix-free product (qo_offdiag, lanes-per-row split, DPP combine), tolerances and iteration bound.
-//     The solver is a copy of k_qo_find's, not shared code: k_qo_find's code object stays what it was.
-//   weights in row order, residual x - A^T w
-// status: 0 ok; 1 empty list; 3 more entries than pcap or kQoMaxBlocks, or more rows than kcap; 2 a period outside
-// 1 .. max_period, a block without rows (repeated period / all divisors present: the reference's Pp(.., keep=0) hands
-// back all p rows and its matrix is singular) or with more rows than samples (zero diagonal), a dictionary with more
-// rows than samples altogether (rank deficient: conjugate gradients would still converge on it), non-positive curvature, a
-// non-finite residual of the solve, or no convergence within 4 K + 100 iterations.  Windows that are not ok get zero
-// weights; their residual is not written.  Every loop is bounded; nothing waits on anything outside the workgroup.
-// ======================================================================================
-template <typename T>
-__global__ __launch_bounds__(1024) void k_qo_fit(const T* __restrict__ x, int N, const int* __restrict__ periods,
-                                                 const int* __restrict__ n_periods, int pcap, int per_stride,
-                                                 int max_period, const int* __restrict__ phi,
-                                                 const int* __restrict__ div_off, const int* __restrict__ div_q, int kcap,
-                                                 int* __restrict__ keeps_out, double* __restrict__ weights_out,
-                                                 T* __restrict__ resid_out, int* __restrict__ status_out) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+// ---- What k_qo_fit and k_qo_fit_win share besides the solver: the carve, the prologue, the row bookkeeping, the
+//      epilogue.  (k_qo_fit_win leaves blg, bsteps, ptab and trm unused.)
+struct QoFitLds {
+  double* red;
+  double* red3;    // wave partials of the solver's fused reduction (two parities)
+  int* bper;       // period of dictionary block b
+  int* bkeep;      // rows kept for it
+  int* boff;       // first row of block b
+  int* ioff;       // first work item of block b (k_qo_fit: of the product; k_qo_fit_win: of the fold)
+  int* blg;        // log2 of the lanes that share a row of block b in the product
+  int* bsteps;     // steps one row of block b walks in the product
+  int* ptab;       // (a, b): {p_b / gcd(p_a, p_b), p_a mod p_b}
+  int* ctl;
+  uint32_t* seen;  // the divisor bitset (bookkeeping only); the solver's vectors take its place
+  QoCgVectors v;   // solver layout; rv starts as the right-hand side (QOPeriods.py:782), dv = 1 / diagonal
+  int* trm;        // samples of the row's residue
+};
+__device__ __forceinline__ QoFitLds qo_fit_carve(unsigned char* smem, int kcap) {
   Carve cv(smem);
-  double* red = cv.take<double>(kRedDoubles);
-  double* red3 = cv.take<double>(6 * kMaxWaves);  // wave partials of the solver's fused reduction (two parities)
-  int* bper = cv.take<int>(kQoMaxBlocks + 1);     // period of dictionary block b
-  int* bkeep = cv.take<int>(kQoMaxBlocks + 1);    // rows kept for it
-  int* boff = cv.take<int>(kQoMaxBlocks + 1);     // first row of block b
-  int* ioff = cv.take<int>(kQoMaxBlocks + 1);     // first work item of block b
-  int* blg = cv.take<int>(kQoMaxBlocks);          // log2 of the lanes that share a row of block b in the product
-  int* bsteps = cv.take<int>(kQoMaxBlocks);       // steps one row of block b walks in the product
-  int* ptab = cv.take<int>(2 * kQoPairTab * kQoPairTab);  // (a, b): {p_b / gcd(p_a, p_b), p_a mod p_b}
-  int* ctl = cv.take<int>(kFitCtl);
-  // the divisor bitset (bookkeeping only) and the solver's vectors share what follows
-  uint32_t* seen = reinterpret_cast<uint32_t*>(cv.base + cv.off);
+  QoFitLds L;
+  L.red = cv.take<double>(kRedDoubles);
+  L.red3 = cv.take<double>(6 * kMaxWaves);
+  L.bper = cv.take<int>(kQoMaxBlocks + 1);
+  L.bkeep = cv.take<int>(kQoMaxBlocks + 1);
+  L.boff = cv.take<int>(kQoMaxBlocks + 1);
+  L.ioff = cv.take<int>(kQoMaxBlocks + 1);
+  L.blg = cv.take<int>(kQoMaxBlocks);
+  L.bsteps = cv.take<int>(kQoMaxBlocks);
+  L.ptab = cv.take<int>(2 * kQoPairTab * kQoPairTab);
+  L.ctl = cv.take<int>(kFitCtl);
+  L.seen = reinterpret_cast<uint32_t*>(cv.base + cv.off);
   const int kv = kcap + kQoMaxBlocks;
-  double* xv = cv.take<double>(kv);   // weights, solver layout: block b's k_b entries at boff[b] + b, then one zero
-  double* rv = cv.take<double>(kv);   // residual of the normal equations (starts as A x, QOPeriods.py:782)
-  double* pv = cv.take<double>(kv);   // search direction
-  double* qv = cv.take<double>(kv);   // A A^T pv
-  double* zv = cv.take<double>(kv);   // preconditioned residual
-  double* wv_ = cv.take<double>(kv);  // A A^T zv
-  double* dv = cv.take<double>(kv);   // 1 / diagonal = 1 / samples of the row's residue (Jacobi preconditioner)
-  int* trm = cv.take<int>(kv);        // samples of the row's residue
+  L.v.xv = cv.take<double>(kv);
+  L.v.rv = cv.take<double>(kv);
+  L.v.pv = cv.take<double>(kv);
+  L.v.qv = cv.take<double>(kv);
+  L.v.zv = cv.take<double>(kv);
+  L.v.wv_ = cv.take<double>(kv);
+  L.v.dv = cv.take<double>(kv);
+  L.trm = cv.take<int>(kv);
+  return L;
+}
 
+// The calling workgroup's window: its slices of the arguments.
+template <typename T>
+struct QoFitWindow {
+  const T* data;
+  const int* list;  // its period list
+  int n_list;
+  int* keeps_row;
+  double* wout;
+  T* resid;
+  int* status;
+};
+
+// Prologue: the window's slices, zero keeps and weights.  -> status 0, 1 (empty list) or 3 (more entries than pcap or
+// kQoMaxBlocks), uniform over the workgroup.
+template <typename T>
+__device__ __forceinline__ int qo_fit_begin(QoFitWindow<T>& W, const T* __restrict__ x, int N,
+                                            const int* __restrict__ periods, const int* __restrict__ n_periods, int pcap,
+                                            int per_stride, int kcap, int* __restrict__ keeps_out,
+                                            double* __restrict__ weights_out, T* __restrict__ resid_out,
+                                            int* __restrict__ status_out) {
   const int64_t w = blockIdx.x;
   const int tid = threadIdx.x;
-  const int lane = tid & (kWave - 1);
-  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int nw = blockDim.x >> 6;
-  const T* data = x + w * (int64_t)N;
-  const int* list = periods + (per_stride ? w * (int64_t)per_stride : 0);
-  const int n_list = n_periods[per_stride ? w : 0];
-  int* keeps_row = keeps_out + w * (int64_t)pcap;
-  double* wout = weights_out + w * (int64_t)kcap;
-
-  for (int k = tid; k < pcap; k += blockDim.x) keeps_row[k] = 0;
-  for (int r = tid; r < kcap; r += blockDim.x) wout[r] = 0.0;
+  W.data = x + w * (int64_t)N;
+  W.list = periods + (per_stride ? w * (int64_t)per_stride : 0);
+  W.n_list = n_periods[per_stride ? w : 0];
+  W.keeps_row = keeps_out + w * (int64_t)pcap;
+  W.wout = weights_out + w * (int64_t)kcap;
+  W.resid = resid_out + w * (int64_t)N;
+  W.status = status_out + w;
+  for (int k = tid; k < pcap; k += blockDim.x) W.keeps_row[k] = 0;
+  for (int r = tid; r < kcap; r += blockDim.x) W.wout[r] = 0.0;
   int status = 0;
-  if (n_list <= 0) status = 1;
-  if (n_list > pcap || n_list > kQoMaxBlocks) status = 3;
-  if (status != 0) {  // (uniform over the workgroup)
-    if (tid == 0) status_out[w] = status;
-    return;
-  }
+  if (W.n_list <= 0) status = 1;
+  if (W.n_list > pcap || W.n_list > kQoMaxBlocks) status = 3;
+  return status;
+}
+
+// Rows each period contributes (get_subspaces, QOPeriods.py:830-840): one wavefront, the lanes over the divisors.
+// Fills bper, bkeep, boff and the window's keeps; ioff becomes the prefix of block_items(p, keep) (k_qo_fit_win's fold
+// work items; k_qo_fit's lane split writes ioff afterwards).  -> status 0, 2 or 3 (see k_qo_fit), uniform; K = rows.
+// The bitset is dead on return: the vectors may take its place.
+template <typename Items>
+__device__ __forceinline__ int qo_fit_rows(const QoFitLds& L, const int* __restrict__ list, int n_list, int N,
+                                           int max_period, const int* __restrict__ phi, const int* __restrict__ div_off,
+                                           const int* __restrict__ div_q, int kcap, int* __restrict__ keeps_row, int& K,
+                                           Items&& block_items) {
+  const int tid = threadIdx.x, lane = tid & (kWave - 1);
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  uint32_t* const seen = L.seen;
   for (int k = tid; k < (max_period + 32) / 32; k += blockDim.x) seen[k] = 0u;
   __syncthreads();
-  // ---- rows each period contributes (QOPeriods.py:830-840): one wavefront, the lanes over the divisors
   if (wv == 0) {
-    int st = 0, rows = 0;
+    int st = 0, rows = 0, items = 0;
     for (int b = 0; b < n_list; ++b) {
       const int p = list[b];
       if (p < 1 || p > max_period) {  // (uniform)
@@ -133,32 +159,105 @@ __global__ __launch_bounds__(1024) void k_qo_fit(const T* __restrict__ x, int N,
       }
       ram_wave_sync();
       if (lane == 0) {
-        bper[b] = p;
-        bkeep[b] = keep;
-        boff[b] = rows;
+        L.bper[b] = p;
+        L.bkeep[b] = keep;
+        L.boff[b] = rows;
+        L.ioff[b] = items;
         keeps_row[b] = keep;
       }
       if (keep == 0 || keep > N) st = 2;
       rows += keep;  // (<= 64 * 2^20: no overflow)
+      items += block_items(p, keep);
     }
-    if (st == 0 && rows > N) st = 2;  // more rows than samples: rank(A A^T) <= N, singular whatever the blocks are
+    if (st == 0 && rows > N) st = 2;  // more rows than samples: rank of the matrix <= N, singular whatever the blocks are
     if (st == 0 && rows > kcap) st = 3;
     if (lane == 0) {
-      boff[n_list] = rows;
-      ctl[0] = st;
-      ctl[1] = rows;
+      L.boff[n_list] = rows;
+      L.ioff[n_list] = items;
+      L.ctl[0] = st;
+      L.ctl[1] = rows;
+      L.ctl[3] = 0;
     }
   }
   __syncthreads();
-  status = ctl[0];
-  if (status != 0) {
-    if (tid == 0) status_out[w] = status;
+  const int status = L.ctl[0];
+  K = L.ctl[1];
+  __syncthreads();
+  return status;
+}
+
+// Epilogue (after the solve; holds the barrier that ends it): a failed solve is status 2 with the zero weights of the
+// prologue and no residual; otherwise the weights in row order, the reconstruction A^T w (QOPeriods.py:795, never
+// windowed) in row order and the residual x - A^T w in the dtype of x.
+template <typename T>
+__device__ __forceinline__ void qo_fit_finish(const QoFitLds& L, const QoFitWindow<T>& W, int N, int K, bool failed) {
+  const int tid = threadIdx.x, nblk = W.n_list;
+  const double* const xv = L.v.xv;
+  __syncthreads();
+  if (failed) {
+    if (tid == 0) *W.status = 2;
     return;
   }
-  const int nblk = n_list;
-  const int K = ctl[1];
+  for (int r = tid; r < K; r += blockDim.x) {
+    int a = 0;
+    while (a + 1 < nblk && L.boff[a + 1] <= r) ++a;
+    W.wout[r] = xv[r + a];
+  }
+  for (int n = tid; n < N; n += blockDim.x) {
+    double rec = 0.0;
+    for (int b = 0; b < nblk; ++b) {
+      const int i = n % L.bper[b];
+      if (i < L.bkeep[b]) rec += xv[L.boff[b] + b + i];
+    }
+    W.resid[n] = (T)((double)W.data[n] - rec);
+  }
+  if (tid == 0) *W.status = 0;
+}
+
+// ======================================================================================
+// QOPeriods.compute_reconstruction / get_subspaces + solve_quadratic for a given period list (QOPeriods.py:807-852,
+// :779-796, :1054-1116), natural basis, no analysis window.  One workgroup per window; all solver arithmetic in fp64.
+//   rows of block b = Euler-phi mass the divisors of p_b add to the running divisor set (get_subspaces :830-840)
+//   right-hand side A x by folds of the window, read from HBM / L2 (the window is read twice: here and for the residual)
+//   A A^T w = A x by the solver k_qo_find uses (ph_qo.h: qo_cg around qo_gram_apply with qo_lane_split's work split),
+//     started from zero
+//   weights in row order, residual x - A^T w
+// status: 0 ok; 1 empty list; 3 more entries than pcap or kQoMaxBlocks, or more rows than kcap; 2 a period outside
+// 1 .. max_period, a block without rows (repeated period / all divisors present: the reference's Pp(.., keep=0) hands
+// back all p rows and its matrix is singular) or with more rows than samples (zero diagonal), a dictionary with more
+// rows than samples altogether (rank deficient: conjugate gradients would still converge on it), non-positive curvature, a
+// non-finite residual of the solve, or no convergence within 4 K + 100 iterations (the host path solves those as the
+// reference does).  Windows that are not ok get zero weights; their residual is not written.  Every loop is bounded;
+// nothing waits on anything outside the workgroup.
+// ======================================================================================
+template <typename T>
+__global__ __launch_bounds__(1024) void k_qo_fit(const T* __restrict__ x, int N, const int* __restrict__ periods,
+                                                 const int* __restrict__ n_periods, int pcap, int per_stride,
+                                                 int max_period, const int* __restrict__ phi,
+                                                 const int* __restrict__ div_off, const int* __restrict__ div_q, int kcap,
+                                                 int* __restrict__ keeps_out, double* __restrict__ weights_out,
+                                                 T* __restrict__ resid_out, int* __restrict__ status_out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const QoFitLds L = qo_fit_carve(smem, kcap);
+  int *const bper = L.bper, *const bkeep = L.bkeep, *const boff = L.boff, *const ptab = L.ptab, *const trm = L.trm;
+  double* const rv = L.v.rv;
+  const int tid = threadIdx.x;
+  const int lane = tid & (kWave - 1);
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int nw = blockDim.x >> 6;
+  QoFitWindow<T> W;
+  int K = 0;
+  int status = qo_fit_begin(W, x, N, periods, n_periods, pcap, per_stride, kcap, keeps_out, weights_out, resid_out, status_out);
+  if (status == 0)
+    status = qo_fit_rows(L, W.list, W.n_list, N, max_period, phi, div_off, div_q, kcap, W.keeps_row, K,
+                         [](int, int) { return 0; });
+  if (status != 0) {  // (uniform over the workgroup)
+    if (tid == 0) *W.status = status;
+    return;
+  }
+  const T* data = W.data;
+  const int nblk = W.n_list;
   const int KS = K + nblk;  // slots
-  __syncthreads();          // the bitset is dead: the vectors take its place
   // pair constants of every block against every block (the diagonal is unused)
   if (nblk <= kQoPairTab) {
     for (int e = tid; e < nblk * nblk; e += blockDim.x) {
@@ -176,13 +275,13 @@ __global__ __launch_bounds__(1024) void k_qo_fit(const T* __restrict__ x, int N,
     const bool pad = i >= bkeep[a];  // the zero behind block a
     const int terms = pad ? 1 : (N - 1 - i) / bper[a] + 1;
     trm[sl] = terms;
-    dv[sl] = pad ? 0.0 : 1.0 / (double)terms;
-    xv[sl] = 0.0;
+    L.v.dv[sl] = pad ? 0.0 : 1.0 / (double)terms;
+    L.v.xv[sl] = 0.0;
     rv[sl] = 0.0;
-    zv[sl] = 0.0;  // (the product never writes the pad slots)
-    wv_[sl] = 0.0;
-    qv[sl] = 0.0;
-    pv[sl] = 0.0;
+    L.v.zv[sl] = 0.0;  // (the product never writes the pad slots)
+    L.v.wv_[sl] = 0.0;
+    L.v.qv[sl] = 0.0;
+    L.v.pv[sl] = 0.0;
   }
   __syncthreads();
   // ---- right-hand side A x (QOPeriods.py:782): folds of the window.  One wavefront per residue; blocks whose residues
@@ -208,162 +307,19 @@ __global__ __launch_bounds__(1024) void k_qo_fit(const T* __restrict__ x, int N,
       }
     }
   }
-  // Work split of the product, as in k_qo_find: a row of block a costs sum_b min(cycle_ab, samples) steps; block a gets
-  // L_a = 1, 2, ..., 16 lanes per row, the lanes of a row are neighbours and combine with DPP.
-  for (int a = tid; a < nblk; a += blockDim.x) {
-    const int pa = bper[a], terms = (N - 1) / pa + 1;
-    int st = 0;
-    for (int b = 0; b < nblk; ++b) {
-      if (b == a) continue;
-      const int cyc = bper[b] / qo_gcd(pa, bper[b]);
-      st += cyc < terms ? cyc : terms;
-    }
-    bsteps[a] = st;
-  }
+  // work split of the product, the steps across the threads
+  for (int a = tid; a < nblk; a += blockDim.x) L.bsteps[a] = qo_row_steps(bper, nblk, a, N);
   __syncthreads();
-  if (tid == 0) {
-    int items = 0;
-    for (int a = 0; a < nblk; ++a) {
-      blg[a] = bper[a] < 64 ? 4 : 0;
-      items += ((bkeep[a] << blg[a]) + 15) & ~15;
-    }
-    for (int round = 0; round < 4 * kQoMaxBlocks; ++round) {  // (every round adds one to some blg[a] <= 4)
-      int worst = -1, wst = 24;
-      for (int a = 0; a < nblk; ++a)
-        if (blg[a] < 4 && (bsteps[a] >> blg[a]) > wst) {
-          wst = bsteps[a] >> blg[a];
-          worst = a;
-        }
-      if (worst < 0) break;
-      const int grown = items - (((bkeep[worst] << blg[worst]) + 15) & ~15) + (((bkeep[worst] << (blg[worst] + 1)) + 15) & ~15);
-      if (grown > (int)blockDim.x) break;
-      items = grown;
-      blg[worst] += 1;
-    }
-    int off = 0;
-    for (int a = 0; a < nblk; ++a) {
-      ioff[a] = off;
-      off += ((bkeep[a] << blg[a]) + 15) & ~15;  // groups never straddle a 16-lane DPP row
-    }
-    ioff[nblk] = off;
-  }
+  if (tid == 0) qo_lane_split(bper, bkeep, L.bsteps, nblk, L.blg, L.ioff);
   __syncthreads();
-  // ---- A A^T w = A x (see k_qo_find for the derivation of the product and of the single-reduction recurrence)
-  double dg = 0.0, dd = 0.0, dr = 0.0;
-  auto gram_apply = [&](const double* __restrict__ vv, double* __restrict__ out) {
-    const int nitems = ioff[nblk];
-    for (int v = tid; v < nitems; v += blockDim.x) {
-      int a = 0;
-      while (a + 1 < nblk && ioff[a + 1] <= v) ++a;
-      const int lg = blg[a], L = 1 << lg;
-      const int e = v - ioff[a];
-      const int i = e >> lg, gl = e & (L - 1);
-      const int ka = bkeep[a];
-      double acc = 0.0;
-      int terms = 1;
-      const int sl = boff[a] + a + (i < ka ? i : 0);
-      if (i < ka) {  // (the padding items of the last row group only take part in the DPP steps)
-        const int pa = bper[a];
-        terms = trm[sl];
-        for (int b = 0; b < nblk; ++b) {
-          if (b == a) continue;
-          const int pb = bper[b];
-          int cycle, step;
-          if (nblk <= kQoPairTab) {
-            cycle = ptab[2 * (a * kQoPairTab + b)];
-            step = ptab[2 * (a * kQoPairTab + b) + 1];
-          } else {
-            cycle = pb / qo_gcd(pa, pb);
-            step = pa % pb;
-          }
-          acc += qo_offdiag(vv + boff[b] + b, bkeep[b], pb, cycle, step, i, terms, gl, L);
-        }
-      }
-      if (lg >= 4) acc += dpp_f64<kDppRor8>(acc);
-      if (lg >= 3) acc += dpp_f64<kDppHalfMirror>(acc);
-      if (lg >= 2) acc += dpp_f64<kDppXor2>(acc);
-      if (lg >= 1) acc += dpp_f64<kDppXor1>(acc);
-      if (gl == 0 && i < ka) {
-        const double z = vv[sl], wrow = fma((double)terms, z, acc);
-        out[sl] = wrow;
-        const double t = rv[sl];
-        dg = fma(t, z, dg);
-        dd = fma(wrow, z, dd);
-        dr = fma(t, t, dr);
-      }
-    }
-  };
-  bool failed = false;
-  int iter = 0;
-  {
-    double bb = 0.0;
-    for (int r = tid; r < KS; r += blockDim.x) {  // start from zero: the residual is the right-hand side
-      const double t = rv[r];
-      zv[r] = t * dv[r];
-      bb = fma(t, t, bb);
-    }
-    bb = block_sum(bb, red);  // (its barriers also publish zv)
-    const double tol = sizeof(T) == 4 ? 1e-9 : 1e-13;
-    const double tol2 = tol * tol * bb;
-    const int itmax = 4 * K + 100;
-    double gamma_old = 0.0, alpha = 0.0, rr = 1.0 / 0.0;
-    for (;; ++iter) {
-      dg = dd = dr = 0.0;
-      gram_apply(zv, wv_);
-      double* part = red3 + (iter & 1) * 3 * kMaxWaves;
-      const double sg = wave_sum(dg), sd = wave_sum(dd), sr = wave_sum(dr);
-      if (lane == 0) {
-        part[wv] = sg;
-        part[kMaxWaves + wv] = sd;
-        part[2 * kMaxWaves + wv] = sr;
-      }
-      __syncthreads();
-      const double g = uniform_f64(red_combine(part, nw)), d = uniform_f64(red_combine(part + kMaxWaves, nw));
-      rr = uniform_f64(red_combine(part + 2 * kMaxWaves, nw));
-      if (rr <= tol2 || iter >= itmax) break;
-      const double beta = iter == 0 ? 0.0 : g / gamma_old;
-      const double denom = iter == 0 ? d : d - beta * g / alpha;
-      if (!(denom > 0.0) || !(g > 0.0)) {  // not positive definite: numpy.linalg.solve would raise or return garbage
-        failed = true;
-        break;
-      }
-      alpha = g / denom;
-      gamma_old = g;
-      for (int r = tid; r < KS; r += blockDim.x) {
-        const double pn = fma(beta, iter == 0 ? 0.0 : pv[r], zv[r]);
-        const double qn = fma(beta, iter == 0 ? 0.0 : qv[r], wv_[r]);
-        pv[r] = pn;
-        qv[r] = qn;
-        xv[r] = fma(alpha, pn, xv[r]);
-        const double t = fma(-alpha, qn, rv[r]);
-        rv[r] = t;
-        zv[r] = t * dv[r];
-      }
-      __syncthreads();
-    }
-    if (!(rr <= tol2)) failed = true;  // not finite, or the bound was hit: the host path solves as the reference does
-  }
-  if (kFitTimers && w < 64 && tid == 0) printf("qo_fit window %d: blocks %d rows %d cg iterations %d %s\n", (int)w, nblk, K, iter, failed ? "FAILED" : "ok");
-  __syncthreads();
-  if (failed) {
-    if (tid == 0) status_out[w] = 2;
-    return;
-  }
-  for (int r = tid; r < K; r += blockDim.x) {
-    int a = 0;
-    while (a + 1 < nblk && boff[a + 1] <= r) ++a;
-    wout[r] = xv[r + a];
-  }
-  // ---- reconstruction A^T w (QOPeriods.py:795) in row order, residual in the dtype of x
-  for (int n = tid; n < N; n += blockDim.x) {
-    double rec = 0.0;
-    for (int b = 0; b < nblk; ++b) {
-      const int i = n % bper[b];
-      if (i < bkeep[b]) rec += xv[boff[b] + b + i];
-    }
-    resid_out[w * (int64_t)N + n] = (T)((double)data[n] - rec);
-  }
-  if (tid == 0) status_out[w] = 0;
+  // ---- A A^T w = A x from zero
+  const QoDict dict{bper, bkeep, boff, L.ioff, L.blg, ptab, trm, nblk};
+  const QoCgResult cg = qo_cg<T, false>(L.v, KS, K, L.red, L.red3,
+                                        [&](const double* __restrict__ vv, double* __restrict__ out, double& dg, double& dd,
+                                            double& dr) { qo_gram_apply(dict, vv, out, rv, true, dg, dd, dr); });
+  const bool failed = cg.curvature || !cg.converged;  // (not converged: not finite, or the bound was hit)
+  if (kFitTimers && blockIdx.x < 64 && tid == 0) printf("qo_fit window %d: blocks %d rows %d cg iterations %d %s\n", (int)blockIdx.x, nblk, K, cg.iter, failed ? "FAILED" : "ok");
+  qo_fit_finish(L, W, N, K, failed);
 }
 
 // ======================================================================================
@@ -406,116 +362,39 @@ __global__ __launch_bounds__(1024) void k_qo_fit_win(const T* __restrict__ x, in
                                                      int* __restrict__ keeps_out, double* __restrict__ weights_out,
                                                      T* __restrict__ resid_out, int* __restrict__ status_out) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  Carve cv(smem);
-  double* red = cv.take<double>(kRedDoubles);
-  double* red3 = cv.take<double>(6 * kMaxWaves);  // wave partials of the solver's fused reduction (two parities)
-  int* bper = cv.take<int>(kQoMaxBlocks + 1);     // period of dictionary block b
-  int* bkeep = cv.take<int>(kQoMaxBlocks + 1);    // rows kept for it
-  int* boff = cv.take<int>(kQoMaxBlocks + 1);     // first row of block b
-  int* ioff = cv.take<int>(kQoMaxBlocks + 1);     // first fold work item of block b
-  cv.take<int>(kQoMaxBlocks);                     // (k_qo_fit's lane split and pair table: not used here)
-  cv.take<int>(kQoMaxBlocks);
-  cv.take<int>(2 * kQoPairTab * kQoPairTab);
-  int* ctl = cv.take<int>(kFitCtl);
-  // the divisor bitset (bookkeeping only) and the solver's vectors share what follows
-  uint32_t* seen = reinterpret_cast<uint32_t*>(cv.base + cv.off);
-  const int kv = kcap + kQoMaxBlocks;
-  double* xv = cv.take<double>(kv);   // weights, solver layout: block b's k_b entries at boff[b] + b, then one zero
-  double* rv = cv.take<double>(kv);   // residual of the normal equations (starts as A (win . x))
-  double* pv = cv.take<double>(kv);   // search direction
-  double* qv = cv.take<double>(kv);   // A diag(win) A^T pv
-  double* zv = cv.take<double>(kv);   // preconditioned residual
-  double* wv_ = cv.take<double>(kv);  // A diag(win) A^T zv
-  double* dv = cv.take<double>(kv);   // 1 / diagonal = 1 / fold of the window (Jacobi preconditioner)
-
-  const int64_t w = blockIdx.x;
+  const QoFitLds L = qo_fit_carve(smem, kcap);
+  int *const bper = L.bper, *const bkeep = L.bkeep, *const boff = L.boff, *const ioff = L.ioff, *const ctl = L.ctl;
+  double *const rv = L.v.rv, *const dv = L.v.dv;
   const int tid = threadIdx.x;
   const int lane = tid & (kWave - 1);
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nw = blockDim.x >> 6;
-  const T* data = x + w * (int64_t)N;
-  const int* list = periods + (per_stride ? w * (int64_t)per_stride : 0);
-  const int n_list = n_periods[per_stride ? w : 0];
-  int* keeps_row = keeps_out + w * (int64_t)pcap;
-  double* wout = weights_out + w * (int64_t)kcap;
   double* u;
   if constexpr (ULDS) {
     u = reinterpret_cast<double*>(smem + qo_fit_win_u_offset(kcap, max_period));
   } else {
-    u = ws + w * (int64_t)N;
+    u = ws + blockIdx.x * (int64_t)N;
   }
-
-  for (int k = tid; k < pcap; k += blockDim.x) keeps_row[k] = 0;
-  for (int r = tid; r < kcap; r += blockDim.x) wout[r] = 0.0;
-  int status = 0;
-  if (n_list <= 0) status = 1;
-  if (n_list > pcap || n_list > kQoMaxBlocks) status = 3;
+  QoFitWindow<T> W;
+  int K = 0;
+  int status = qo_fit_begin(W, x, N, periods, n_periods, pcap, per_stride, kcap, keeps_out, weights_out, resid_out, status_out);
+  if (status == 0)  // a block's fold work items: one for a period below 64, else one per 64 kept rows
+    status = qo_fit_rows(L, W.list, W.n_list, N, max_period, phi, div_off, div_q, kcap, W.keeps_row, K,
+                         [](int p, int keep) { return p < kWave ? 1 : (keep + kWave - 1) / kWave; });
   if (status != 0) {  // (uniform over the workgroup)
-    if (tid == 0) status_out[w] = status;
+    if (tid == 0) *W.status = status;
     return;
   }
-  for (int k = tid; k < (max_period + 32) / 32; k += blockDim.x) seen[k] = 0u;
-  __syncthreads();
-  // ---- rows each period contributes (QOPeriods.py:830-840): one wavefront, the lanes over the divisors
-  if (wv == 0) {
-    int st = 0, rows = 0, items = 0;
-    for (int b = 0; b < n_list; ++b) {
-      const int p = list[b];
-      if (p < 1 || p > max_period) {  // (uniform)
-        st = 2;
-        break;
-      }
-      const int d0 = div_off[p], d1 = div_off[p + 1];
-      double mass = 0.0;
-      for (int k = d0 + lane; k < d1; k += kWave) {
-        const int r = div_q[k];
-        if (!((seen[r >> 5] >> (r & 31)) & 1u)) mass += (double)phi[r];
-      }
-      const int keep = (int)wave_sum(mass);  // (exact: the mass of all divisors of p is p)
-      ram_wave_sync();
-      for (int k = d0 + lane; k < d1; k += kWave) {
-        const int r = div_q[k];
-        atomicOr(&seen[r >> 5], 1u << (r & 31));
-      }
-      ram_wave_sync();
-      if (lane == 0) {
-        bper[b] = p;
-        bkeep[b] = keep;
-        boff[b] = rows;
-        ioff[b] = items;
-        keeps_row[b] = keep;
-      }
-      if (keep == 0 || keep > N) st = 2;
-      rows += keep;  // (<= 64 * 2^20: no overflow)
-      items += p < kWave ? 1 : (keep + kWave - 1) / kWave;
-    }
-    if (st == 0 && rows > N) st = 2;  // more rows than samples: rank(A diag(win) A^T) <= N, singular
-    if (st == 0 && rows > kcap) st = 3;
-    if (lane == 0) {
-      boff[n_list] = rows;
-      ioff[n_list] = items;
-      ctl[0] = st;
-      ctl[1] = rows;
-      ctl[3] = 0;
-    }
-  }
-  __syncthreads();
-  status = ctl[0];
-  if (status != 0) {
-    if (tid == 0) status_out[w] = status;
-    return;
-  }
-  const int nblk = n_list;
-  const int K = ctl[1];
+  const T* data = W.data;
+  const int nblk = W.n_list;
   const int KS = K + nblk;  // slots
-  __syncthreads();          // the bitset is dead: the vectors take its place
   for (int sl = tid; sl < KS; sl += blockDim.x) {
-    xv[sl] = 0.0;
+    L.v.xv[sl] = 0.0;
     rv[sl] = 0.0;
-    zv[sl] = 0.0;  // (the fold never writes the pad slots)
-    wv_[sl] = 0.0;
-    qv[sl] = 0.0;
-    pv[sl] = 0.0;
+    L.v.zv[sl] = 0.0;  // (the fold never writes the pad slots)
+    L.v.wv_[sl] = 0.0;
+    L.v.qv[sl] = 0.0;
+    L.v.pv[sl] = 0.0;
     dv[sl] = 0.0;
   }
   // A u: consume(slot, sum_r u[i + r p_a]) for every row; the caller's barrier has published u
@@ -550,7 +429,7 @@ __global__ __launch_bounds__(1024) void k_qo_fit_win(const T* __restrict__ x, in
   });
   __syncthreads();
   if (ctl[3] != 0) {
-    if (tid == 0) status_out[w] = 2;
+    if (tid == 0) *W.status = 2;
     return;
   }
   // ---- right-hand side A (win . x) (QOPeriods.py:781-782)
@@ -558,109 +437,42 @@ __global__ __launch_bounds__(1024) void k_qo_fit_win(const T* __restrict__ x, in
   __syncthreads();
   fold_u([&](int sl, double s) { rv[sl] = s; });
   __syncthreads();
-  // ---- A diag(win) A^T w = A (win . x): k_qo_fit's single-reduction recurrence around the staged product
-  double dg = 0.0, dd = 0.0, dr = 0.0;
-  auto gram_apply = [&](const double* __restrict__ vv, double* __restrict__ out) {
-    for (int base = 0; base < N; base += 4 * (int)blockDim.x) {
-      double acc[4] = {0.0, 0.0, 0.0, 0.0};
-      for (int b = 0; b < nblk; ++b) {
-        const int p = bper[b], keep = bkeep[b], step = (int)blockDim.x % p;
-        const double* vb = vv + boff[b] + b;
-        int r = (base + tid) % p;
+  // ---- A diag(win) A^T w = A (win . x) from zero: the shared recurrence around the staged product
+  const QoCgResult cg = qo_cg<T, false>(
+      L.v, KS, K, L.red, L.red3,
+      [&](const double* __restrict__ vv, double* __restrict__ out, double& dg, double& dd, double& dr) {
+        for (int base = 0; base < N; base += 4 * (int)blockDim.x) {
+          double acc[4] = {0.0, 0.0, 0.0, 0.0};
+          for (int b = 0; b < nblk; ++b) {
+            const int p = bper[b], keep = bkeep[b], step = (int)blockDim.x % p;
+            const double* vb = vv + boff[b] + b;
+            int r = (base + tid) % p;
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          if (r < keep) acc[c] += vb[r];
-          r += step;
-          r -= r >= p ? p : 0;
+            for (int c = 0; c < 4; ++c) {
+              if (r < keep) acc[c] += vb[r];
+              r += step;
+              r -= r >= p ? p : 0;
+            }
+          }
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            const int n = base + tid + c * (int)blockDim.x;
+            if (n < N) u[n] = win[n] * acc[c];
+          }
         }
-      }
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const int n = base + tid + c * (int)blockDim.x;
-        if (n < N) u[n] = win[n] * acc[c];
-      }
-    }
-    __syncthreads();
-    fold_u([&](int sl, double wrow) {
-      const double z = vv[sl];
-      out[sl] = wrow;
-      const double t = rv[sl];
-      dg = fma(t, z, dg);
-      dd = fma(wrow, z, dd);
-      dr = fma(t, t, dr);
-    });
-  };
-  bool failed = false;
-  int iter = 0;
-  {
-    double bb = 0.0;
-    for (int r = tid; r < KS; r += blockDim.x) {  // start from zero: the residual is the right-hand side
-      const double t = rv[r];
-      zv[r] = t * dv[r];
-      bb = fma(t, t, bb);
-    }
-    bb = block_sum(bb, red);  // (its barriers also publish zv)
-    const double tol = sizeof(T) == 4 ? 1e-9 : 1e-13;
-    const double tol2 = tol * tol * bb;
-    const int itmax = 4 * K + 100;
-    double gamma_old = 0.0, alpha = 0.0, rr = 1.0 / 0.0;
-    for (;; ++iter) {
-      dg = dd = dr = 0.0;
-      gram_apply(zv, wv_);
-      double* part = red3 + (iter & 1) * 3 * kMaxWaves;
-      const double sg = wave_sum(dg), sd = wave_sum(dd), sr = wave_sum(dr);
-      if (lane == 0) {
-        part[wv] = sg;
-        part[kMaxWaves + wv] = sd;
-        part[2 * kMaxWaves + wv] = sr;
-      }
-      __syncthreads();
-      const double g = uniform_f64(red_combine(part, nw)), d = uniform_f64(red_combine(part + kMaxWaves, nw));
-      rr = uniform_f64(red_combine(part + 2 * kMaxWaves, nw));
-      if (rr <= tol2 || iter >= itmax) break;
-      const double beta = iter == 0 ? 0.0 : g / gamma_old;
-      const double denom = iter == 0 ? d : d - beta * g / alpha;
-      if (!(denom > 0.0) || !(g > 0.0)) {  // not positive definite: conjugate gradients do not apply, the host solves
-        failed = true;
-        break;
-      }
-      alpha = g / denom;
-      gamma_old = g;
-      for (int r = tid; r < KS; r += blockDim.x) {
-        const double pn = fma(beta, iter == 0 ? 0.0 : pv[r], zv[r]);
-        const double qn = fma(beta, iter == 0 ? 0.0 : qv[r], wv_[r]);
-        pv[r] = pn;
-        qv[r] = qn;
-        xv[r] = fma(alpha, pn, xv[r]);
-        const double t = fma(-alpha, qn, rv[r]);
-        rv[r] = t;
-        zv[r] = t * dv[r];
-      }
-      __syncthreads();
-    }
-    if (!(rr <= tol2)) failed = true;  // not finite, or the bound was hit: the host path solves as the reference does
-  }
-  if (kFitTimers && w < 64 && tid == 0) printf("qo_fit_win window %d: blocks %d rows %d cg iterations %d %s\n", (int)w, nblk, K, iter, failed ? "FAILED" : "ok");
-  __syncthreads();
-  if (failed) {
-    if (tid == 0) status_out[w] = 2;
-    return;
-  }
-  for (int r = tid; r < K; r += blockDim.x) {
-    int a = 0;
-    while (a + 1 < nblk && boff[a + 1] <= r) ++a;
-    wout[r] = xv[r + a];
-  }
-  // ---- reconstruction A^T w (QOPeriods.py:795), unwindowed, in row order; residual in the dtype of x
-  for (int n = tid; n < N; n += blockDim.x) {
-    double rec = 0.0;
-    for (int b = 0; b < nblk; ++b) {
-      const int i = n % bper[b];
-      if (i < bkeep[b]) rec += xv[boff[b] + b + i];
-    }
-    resid_out[w * (int64_t)N + n] = (T)((double)data[n] - rec);
-  }
-  if (tid == 0) status_out[w] = 0;
+        __syncthreads();
+        fold_u([&](int sl, double wrow) {
+          const double z = vv[sl];
+          out[sl] = wrow;
+          const double t = rv[sl];
+          dg = fma(t, z, dg);
+          dd = fma(wrow, z, dd);
+          dr = fma(t, t, dr);
+        });
+      });
+  const bool failed = cg.curvature || !cg.converged;  // (not converged: not finite, or the bound was hit)
+  if (kFitTimers && blockIdx.x < 64 && tid == 0) printf("qo_fit_win window %d: blocks %d rows %d cg iterations %d %s\n", (int)blockIdx.x, nblk, K, cg.iter, failed ? "FAILED" : "ok");
+  qo_fit_finish(L, W, N, K, failed);
 }
 
 // The two passes k_ram_select and k_ram_select_ref share, one wavefront per row.

@@ -134,7 +134,221 @@ __device__ __forceinline__ double qo_offdiag(const double* __restrict__ vb, int 
       slo += v;
     idx = qo_wrap(idx + sstep, pb);
   }
-  return (double)chi * shi + (double)(chi - 1) * slo;
+  // (the fused form spelled out: left to the compiler's contraction, which of the two products is rounded on its own
+  // depends on the code around the call, and the callers would not agree to the last bit)
+  return fma((double)chi, shi, (double)(chi - 1) * slo);
+}
+
+// ======================================================================================
+// The solver of the normal equations A A^T w = A x, stated once.  k_qo_find, k_qo_fit (ph_fit.h) and k_qo_fit_win call
+// it: the first two around the matrix-free product below, k_qo_fit_win around its staged product.
+// A dictionary as the product sees it.  Solver layout of a vector: block b's k_b entries start at slot boff[b] + b and
+// are followed by one zero (qo_offdiag clamps indices past the kept rows onto it).
+// ======================================================================================
+struct QoDict {
+  const int* bper;   // period of dictionary block b
+  const int* bkeep;  // rows kept for it
+  const int* boff;   // first row of block b
+  const int* ioff;   // first work item of block b
+  const int* blg;    // log2 of the lanes that share a row of block b
+  const int* ptab;   // (a, b): {p_b / gcd(p_a, p_b), p_a mod p_b}, filled for dictionaries of up to kQoPairTab blocks
+  const int* trm;    // per slot: samples of the row's residue
+  int nblk;
+};
+
+// Work split of the product: a row of block a costs sum_b min(cycle_ab, samples) steps -- the rows of short periods are
+// the long ones.  -> the steps of one row of block a.
+__device__ __forceinline__ int qo_row_steps(const int* bper, int nblk, int a, int N) {
+  const int pa = bper[a], terms = (N - 1) / pa + 1;
+  int st = 0;
+  for (int b = 0; b < nblk; ++b) {
+    if (b == a) continue;
+    const int cyc = bper[b] / qo_gcd(pa, bper[b]);
+    st += cyc < terms ? cyc : terms;
+  }
+  return st;
+}
+
+// Block a gets L_a = 1, 2, ..., 16 lanes per row (blg = log2 L_a) so that no lane walks more than ~1/1024 of all steps;
+// the lanes of a row are neighbours and combine with DPP.  Greedy: give the block with the longest walk twice the lanes
+// while all items still fit one round of the workgroup (blocks of periods below 64 always get 16 lanes: their rows have
+// up to N / 2 samples).  One thread; `steps` from qo_row_steps.
+__device__ __forceinline__ void qo_lane_split(const int* bper, const int* bkeep, const int* steps, int nblk, int* blg,
+                                              int* ioff) {
+  int items = 0;
+  for (int a = 0; a < nblk; ++a) {
+    blg[a] = bper[a] < 64 ? 4 : 0;
+    items += ((bkeep[a] << blg[a]) + 15) & ~15;
+  }
+  for (int round = 0; round < 4 * kQoMaxBlocks; ++round) {  // (every round adds one to some blg[a] <= 4)
+    int worst = -1, wst = 24;
+    for (int a = 0; a < nblk; ++a)
+      if (blg[a] < 4 && (steps[a] >> blg[a]) > wst) {
+        wst = steps[a] >> blg[a];
+        worst = a;
+      }
+    if (worst < 0) break;
+    const int grown = items - (((bkeep[worst] << blg[worst]) + 15) & ~15) + (((bkeep[worst] << (blg[worst] + 1)) + 15) & ~15);
+    if (grown > (int)blockDim.x) break;
+    items = grown;
+    blg[worst] += 1;
+  }
+  int off = 0;
+  for (int a = 0; a < nblk; ++a) {
+    ioff[a] = off;
+    off += ((bkeep[a] << blg[a]) + 15) & ~15;  // groups never straddle a 16-lane DPP row
+  }
+  ioff[nblk] = off;
+}
+
+// out = A A^T vv.  The Gram matrix (integer co-occurrence counts, QOPeriods.py:781) is never formed: its rows are
+// regenerated from the CRT structure inside the product (qo_offdiag), so the solve touches LDS only.  With `dots`, the
+// lane that finishes a row also accumulates that row's terms of gamma = (r, z), delta = (w, z) and |r|^2 (vv is z
+// then, `rv` the residual), so the three sums need no pass of their own.
+__device__ __forceinline__ void qo_gram_apply(const QoDict& D, const double* __restrict__ vv, double* __restrict__ out,
+                                              const double* rv, bool dots, double& dg, double& dd, double& dr) {
+  const int tid = threadIdx.x, nblk = D.nblk;
+  const int nitems = D.ioff[nblk];
+  for (int v = tid; v < nitems; v += blockDim.x) {
+    int a = 0;
+    while (a + 1 < nblk && D.ioff[a + 1] <= v) ++a;
+    const int lg = D.blg[a], L = 1 << lg;
+    const int e = v - D.ioff[a];
+    const int i = e >> lg, gl = e & (L - 1);
+    const int ka = D.bkeep[a];
+    double acc = 0.0;
+    int terms = 1;
+    const int sl = D.boff[a] + a + (i < ka ? i : 0);
+    if (i < ka) {  // (the padding items of the last row group only take part in the DPP steps)
+      const int pa = D.bper[a];
+      terms = D.trm[sl];
+      for (int b = 0; b < nblk; ++b) {
+        if (b == a) continue;
+        const int pb = D.bper[b];
+        int cycle, step;
+        if (nblk <= kQoPairTab) {
+          cycle = D.ptab[2 * (a * kQoPairTab + b)];
+          step = D.ptab[2 * (a * kQoPairTab + b) + 1];
+        } else {
+          cycle = pb / qo_gcd(pa, pb);
+          step = pa % pb;
+        }
+        acc += qo_offdiag(vv + D.boff[b] + b, D.bkeep[b], pb, cycle, step, i, terms, gl, L);
+      }
+    }
+    if (lg >= 4) acc += dpp_f64<kDppRor8>(acc);
+    if (lg >= 3) acc += dpp_f64<kDppHalfMirror>(acc);
+    if (lg >= 2) acc += dpp_f64<kDppXor2>(acc);
+    if (lg >= 1) acc += dpp_f64<kDppXor1>(acc);
+    if (gl == 0 && i < ka) {
+      const double z = vv[sl], wrow = fma((double)terms, z, acc);
+      out[sl] = wrow;
+      if (dots) {
+        const double t = rv[sl];
+        dg = fma(t, z, dg);
+        dd = fma(wrow, z, dd);
+        dr = fma(t, t, dr);
+      }
+    }
+  }
+}
+
+// The seven vectors of a solve, kv doubles each in the solver layout.
+struct QoCgVectors {
+  double* xv;   // weights
+  double* rv;   // residual of the normal equations (on entry: the right-hand side)
+  double* pv;   // search direction
+  double* qv;   // G pv (WARM, on entry: G xv)
+  double* zv;   // preconditioned residual
+  double* wv_;  // G zv
+  double* dv;   // 1 / diagonal (Jacobi preconditioner)
+};
+struct QoCgResult {
+  int iter;        // iterations taken (updates of the weights)
+  double rr;       // |r|^2 at the exit
+  bool curvature;  // not positive definite: numpy.linalg.solve would raise or return garbage
+  bool converged;  // rr <= (tol |A x|)^2; false also when rr is not finite
+};
+
+// Jacobi-preconditioned conjugate gradients in the single-reduction form (Chronopoulos / Gear): z = D^-1 r, w = G z, and
+// gamma = (r, z), delta = (w, z), |r|^2 come out of ONE workgroup reduction per iteration; p and q = G p follow by
+// recurrence.  product(vv, out, dg, dd, dr) writes out = G vv and adds the calling thread's terms of the three sums (vv
+// is z then); it may hold barriers of its own, and the rows it does not write (the pad slots) must be zero in qv and
+// wv_.  WARM: xv holds earlier weights and qv = G xv, the residual starts as rv - qv; otherwise xv = 0.
+// ||r|| <= tol ||A x||: with the condition numbers seen (kappa ~ 3000) the weights are then good to 3e-10 (fp64
+// windows, tol 1e-13, bar 1e-8) and 3e-6 (float windows, whose residual is stored as float; tol 1e-9, bar 1e-4).  The
+// diagonal blocks are diagonal; with that as preconditioner the spectrum is a cluster at 1 plus a few small
+// eigenvalues from the mean / common-divisor directions the blocks share: 20-70 iterations to 1e-13, 4 K + 100 at most.
+// The caller classifies what comes back (k_qo_find tells a finite rr at the bound from a singular dictionary).
+template <typename T, bool WARM, typename Product>
+__device__ __forceinline__ QoCgResult qo_cg(const QoCgVectors& V, int KS, int K, double* red, double* red3,
+                                            Product&& product) {
+  const int tid = threadIdx.x, lane = tid & (kWave - 1), nw = blockDim.x >> 6;
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  double* const xv = V.xv;
+  double* const rv = V.rv;
+  double* const pv = V.pv;
+  double* const qv = V.qv;
+  double* const zv = V.zv;
+  double* const wv_ = V.wv_;
+  const double* const dv = V.dv;
+  double bb = 0.0;
+  for (int r = tid; r < KS; r += blockDim.x) {
+    const double bval = rv[r];
+    double t = bval;
+    if constexpr (WARM) {
+      t = bval - qv[r];
+      rv[r] = t;
+    }
+    zv[r] = t * dv[r];
+    bb = fma(bval, bval, bb);
+  }
+  bb = block_sum(bb, red);  // (its barriers also publish zv)
+  const double tol = sizeof(T) == 4 ? 1e-9 : 1e-13;
+  const double tol2 = tol * tol * bb;
+  const int itmax = 4 * K + 100;
+  double gamma_old = 0.0, alpha = 0.0, rr = 1.0 / 0.0;
+  bool curvature = false;
+  int iter = 0;
+  for (;; ++iter) {
+    double dg = 0.0, dd = 0.0, dr = 0.0;
+    product(zv, wv_, dg, dd, dr);
+    // one reduction for the three sums; the partials of odd and even iterations use different slots, so the only
+    // barriers of an iteration are the one here and the one behind the vector updates
+    double* part = red3 + (iter & 1) * 3 * kMaxWaves;
+    const double sg = wave_sum(dg), sd = wave_sum(dd), sr = wave_sum(dr);
+    if (lane == 0) {
+      part[wv] = sg;
+      part[kMaxWaves + wv] = sd;
+      part[2 * kMaxWaves + wv] = sr;
+    }
+    __syncthreads();
+    // (all reads in flight before the first addition: the loop over the run-time wave count was 3 x 16 dependent LDS
+    // round trips per iteration)
+    const double g = uniform_f64(red_combine(part, nw)), d = uniform_f64(red_combine(part + kMaxWaves, nw));
+    rr = uniform_f64(red_combine(part + 2 * kMaxWaves, nw));
+    if (rr <= tol2 || iter >= itmax) break;
+    const double beta = iter == 0 ? 0.0 : g / gamma_old;
+    const double denom = iter == 0 ? d : d - beta * g / alpha;
+    if (!(denom > 0.0) || !(g > 0.0)) {
+      curvature = true;
+      break;
+    }
+    alpha = g / denom;
+    gamma_old = g;
+    for (int r = tid; r < KS; r += blockDim.x) {
+      const double pn = fma(beta, iter == 0 ? 0.0 : pv[r], zv[r]);
+      const double qn = fma(beta, iter == 0 ? 0.0 : qv[r], wv_[r]);
+      pv[r] = pn;
+      qv[r] = qn;
+      xv[r] = fma(alpha, pn, xv[r]);
+      const double t = fma(-alpha, qn, rv[r]);
+      rv[r] = t;
+      zv[r] = t * dv[r];
+    }
+    __syncthreads();
+  }
+  return {iter, rr, curvature, rr <= tol2};
 }
 
 // TRUNC (trunc_to_integer_multiple): only the selection changes -- the gamma norm of the trunc projection
@@ -315,173 +529,34 @@ __global__ __launch_bounds__(1024) PH_QO_OCC void k_qo_find(const T* __restrict_
       qv[sl] = 0.0;
       if (pad || r >= row0) xv[sl] = 0.0;  // the rows of earlier steps start from their last weights
     }
-    // Work split of the product: a row of block a costs sum_b min(cycle_ab, samples) steps -- the rows of short
-    // periods are the long ones.  Block a gets L_a = 1, 2, ..., 16 lanes per row so that no lane walks more than
-    // ~1/1024 of all steps; the lanes of a row are neighbours and combine with DPP.
+    // work split of the product (qo_row_steps, qo_lane_split)
     if (tid == 0) {
-      long long total = 0;
       int steps[kQoMaxBlocks];
-      for (int a = 0; a < nblk; ++a) {
-        const int pa = bper[a], terms = (N - 1) / pa + 1;
-        int st = 0;
-        for (int b = 0; b < nblk; ++b) {
-          if (b == a) continue;
-          const int cyc = bper[b] / qo_gcd(pa, bper[b]);
-          st += cyc < terms ? cyc : terms;
-        }
-        steps[a] = st;
-        total += (long long)st * bkeep[a];
-      }
-      // greedy: give the block with the longest walk twice the lanes while all items still fit one round of the
-      // workgroup (blocks of periods below 64 always get 16 lanes: their rows have up to N / 2 samples)
-      int items = 0;
-      for (int a = 0; a < nblk; ++a) {
-        blg[a] = bper[a] < 64 ? 4 : 0;
-        items += ((bkeep[a] << blg[a]) + 15) & ~15;
-      }
-      (void)total;
-      for (;;) {
-        int worst = -1, wst = 24;
-        for (int a = 0; a < nblk; ++a)
-          if (blg[a] < 4 && (steps[a] >> blg[a]) > wst) {
-            wst = steps[a] >> blg[a];
-            worst = a;
-          }
-        if (worst < 0) break;
-        const int grown = items - (((bkeep[worst] << blg[worst]) + 15) & ~15) + (((bkeep[worst] << (blg[worst] + 1)) + 15) & ~15);
-        if (grown > (int)blockDim.x) break;
-        items = grown;
-        blg[worst] += 1;
-      }
-      int off = 0;
-      for (int a = 0; a < nblk; ++a) {
-        ioff[a] = off;
-        off += ((bkeep[a] << blg[a]) + 15) & ~15;  // groups never straddle a 16-lane DPP row
-      }
-      ioff[nblk] = off;
+      for (int a = 0; a < nblk; ++a) steps[a] = qo_row_steps(bper, nblk, a, N);
+      qo_lane_split(bper, bkeep, steps, nblk, blg, ioff);
     }
     __syncthreads();
-    // ---- A A^T w = A x by preconditioned conjugate gradients.  The Gram matrix (integer co-occurrence counts,
-    //      QOPeriods.py:781) is never formed: its rows are regenerated from the CRT structure inside the product
-    //      (qo_offdiag), so the solve touches LDS only -- a dense factorisation of the K x K matrix (K up to ~900,
-    //      5 MB) streamed it through HBM K / 32 times.  The diagonal blocks are diagonal (samples per residue); with
-    //      that as preconditioner the spectrum is a cluster at 1 plus a few small eigenvalues from the mean /
-    //      common-divisor directions the blocks share: 20-70 iterations to 1e-13.
-    // With `dots`, the lane that finishes a row also accumulates that row's terms of gamma = (r, z), delta = (w, z)
-    // and |r|^2 (vv is z then), so the three sums need no pass of their own.
-    double dg = 0.0, dd = 0.0, dr = 0.0;
-    auto gram_apply = [&](const double* __restrict__ vv, double* __restrict__ out, bool dots) {
-      const int nitems = ioff[nblk];
-      for (int v = tid; v < nitems; v += blockDim.x) {
-        int a = 0;
-        while (a + 1 < nblk && ioff[a + 1] <= v) ++a;
-        const int lg = blg[a], L = 1 << lg;
-        const int e = v - ioff[a];
-        const int i = e >> lg, gl = e & (L - 1);
-        const int ka = bkeep[a];
-        double acc = 0.0;
-        int terms = 1;
-        const int sl = boff[a] + a + (i < ka ? i : 0);
-        if (i < ka) {  // (the padding items of the last row group only take part in the DPP steps)
-          const int pa = bper[a];
-          terms = trm[sl];
-          for (int b = 0; b < nblk; ++b) {
-            if (b == a) continue;
-            const int pb = bper[b];
-            int cycle, step;
-            if (nblk <= kQoPairTab) {
-              cycle = ptab[2 * (a * kQoPairTab + b)];
-              step = ptab[2 * (a * kQoPairTab + b) + 1];
-            } else {
-              cycle = pb / qo_gcd(pa, pb);
-              step = pa % pb;
-            }
-            acc += qo_offdiag(vv + boff[b] + b, bkeep[b], pb, cycle, step, i, terms, gl, L);
-          }
-        }
-        if (lg >= 4) acc += dpp_f64<kDppRor8>(acc);
-        if (lg >= 3) acc += dpp_f64<kDppHalfMirror>(acc);
-        if (lg >= 2) acc += dpp_f64<kDppXor2>(acc);
-        if (lg >= 1) acc += dpp_f64<kDppXor1>(acc);
-        if (gl == 0 && i < ka) {
-          const double z = vv[sl], wrow = fma((double)terms, z, acc);
-          out[sl] = wrow;
-          if (dots) {
-            const double t = rv[sl];
-            dg = fma(t, z, dg);
-            dd = fma(wrow, z, dd);
-            dr = fma(t, t, dr);
-          }
-        }
-      }
-    };
-    // Single-reduction form (Chronopoulos / Gear): z = D^-1 r, w = G z, and gamma = (r, z), delta = (w, z), |r|^2
-    // come out of ONE workgroup reduction per iteration; p and q = G p follow by recurrence.
+    // ---- A A^T w = A x by preconditioned conjugate gradients (qo_cg around qo_gram_apply), in LDS only -- a dense
+    //      factorisation of the K x K matrix (K up to ~900, 5 MB) streamed it through HBM K / 32 times.  The rows of
+    //      earlier steps start from their last weights, so the residual starts as A x - G xv.
+    const QoDict dict{bper, bkeep, boff, ioff, blg, ptab, trm, nblk};
     bool singular = false;
     {
-      gram_apply(xv, qv, false);
+      double none = 0.0;
+      qo_gram_apply(dict, xv, qv, rv, false, none, none, none);
       __syncthreads();
-      double bb = 0.0;
-      for (int r = tid; r < KS; r += blockDim.x) {
-        const double bval = rv[r], t = bval - qv[r];
-        rv[r] = t;
-        zv[r] = t * dv[r];
-        bb = fma(bval, bval, bb);
-      }
-      bb = block_sum(bb, red);  // (its barriers also publish zv)
-      // ||r|| <= tol ||A x||: with the condition numbers seen (kappa ~ 3000) the weights are then good to 3e-10 (fp64
-      // windows, bar 1e-8) and 3e-6 (float windows, whose residual is stored as float; bar 1e-4)
-      const double tol = sizeof(T) == 4 ? 1e-9 : 1e-13;
-      const double tol2 = tol * tol * bb;
-      const int itmax = 4 * K + 100;
-      double gamma_old = 0.0, alpha = 0.0, rr = 1.0 / 0.0;
-      int iter = 0;
-      for (;; ++iter) {
-        dg = dd = dr = 0.0;
-        gram_apply(zv, wv_, true);
-        // one reduction for the three sums; the partials of odd and even iterations use different slots, so the
-        // only barriers of an iteration are the one here and the one behind the vector updates
-        double* part = red3 + (iter & 1) * 3 * kMaxWaves;
-        const double sg = wave_sum(dg), sd = wave_sum(dd), sr = wave_sum(dr);
-        if (lane == 0) {
-          part[wv] = sg;
-          part[kMaxWaves + wv] = sd;
-          part[2 * kMaxWaves + wv] = sr;
-        }
-        __syncthreads();
-        // (all reads in flight before the first addition: the loop over the run-time wave count was 3 x 16 dependent
-        // LDS round trips per iteration)
-        const double g = uniform_f64(red_combine(part, nw)), d = uniform_f64(red_combine(part + kMaxWaves, nw));
-        rr = uniform_f64(red_combine(part + 2 * kMaxWaves, nw));
-        if (rr <= tol2 || iter >= itmax) break;
-        const double beta = iter == 0 ? 0.0 : g / gamma_old;
-        const double denom = iter == 0 ? d : d - beta * g / alpha;
-        if (!(denom > 0.0) || !(g > 0.0)) {  // not positive definite: numpy.linalg.solve would raise or return garbage
-          singular = true;
-          break;
-        }
-        alpha = g / denom;
-        gamma_old = g;
-        for (int r = tid; r < KS; r += blockDim.x) {
-          const double pn = fma(beta, iter == 0 ? 0.0 : pv[r], zv[r]);
-          const double qn = fma(beta, iter == 0 ? 0.0 : qv[r], wv_[r]);
-          pv[r] = pn;
-          qv[r] = qn;
-          xv[r] = fma(alpha, pn, xv[r]);
-          const double t = fma(-alpha, qn, rv[r]);
-          rv[r] = t;
-          zv[r] = t * dv[r];
-        }
-        __syncthreads();
-      }
-      if (!(rr <= tol2)) {
-        // no convergence: a residual that is not finite means a singular dictionary; a finite one after itmax
+      const QoCgResult cg = qo_cg<T, true>(QoCgVectors{xv, rv, pv, qv, zv, wv_, dv}, KS, K, red, red3,
+                                           [&](const double* __restrict__ vv, double* __restrict__ out, double& dg,
+                                               double& dd, double& dr) { qo_gram_apply(dict, vv, out, rv, true, dg, dd, dr); });
+      singular = cg.curvature;
+      if (!cg.converged) {
+        // no convergence: a residual that is not finite means a singular dictionary; a finite one after the bound of
         // positive-curvature steps is an ill-conditioned but regular one, which numpy.linalg.solve still solves --
         // PH_ST_ITER_CAP hands the window to the host loop
         singular = true;
-        if (rr < 1.0 / 0.0 && status == 0) status = 2;
+        if (cg.rr < 1.0 / 0.0 && status == 0) status = 2;
       }
-      clk.count(0, iter);
+      clk.count(0, cg.iter);
     }
     clk.mark(2);
     __syncthreads();

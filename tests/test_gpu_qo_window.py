@@ -179,6 +179,30 @@ def test_capacity_and_singular_window(engines):
             eng.qo_fit(xs, lst, kcap=64, window=np.ones(n - 1))
 
 
+def test_indefinite_window_ends_on_the_curvature_test(engines):
+    """A window with a negative sample whose folds are all positive (diagonal 1, 3, 3, 3) but whose matrix is indefinite
+    (eigenvalues -1.17, 2.62, 3, 5.55): the diagonal test passes and the solve meets non-positive curvature.  x is
+    chosen so that the first preconditioned residual z = (1, 0, -1, -1) has z^T G z = -1: the solver's curvature test
+    ends the window in its first iteration on either placement, fp64 and fp32 (every number here is exact in fp32 but
+    x[2] = -4/3, which moves z^T G z by 1e-7).  The reference's LU solve has no such limit (cond 4.7): the class hands
+    the row to the 1-D call and returns its answer, held to the windowed solve of the oracle's rows at the 1e-8 bar."""
+    from pyperiod_amd import QOPeriods, _ffi
+
+    win = np.array([2.0, 1.0, -3.0, 1.0, 2.0, 1.0])
+    x = np.array([[-1.5, -3.0, -4.0 / 3.0, 0.0, 0.0, 3.0]])
+    rows, _ = po.qo_get_subspaces([2, 3], 6)
+    g = rows @ np.diag(win) @ rows.T
+    z = (rows @ (win * x[0])) / np.diag(g)
+    assert np.all(np.diag(g) > 0) and np.linalg.eigvalsh(g)[0] < -1 and abs(z @ g @ z + 1.0) < 1e-12
+    for eng in engines:
+        for xs in (x, x.astype(np.float32)):
+            keeps, wts, _, st = eng.qo_fit(xs, [2, 3], kcap=64, window=win)
+            assert st[0] == _ffi.PH_ST_ITER_CAP and list(keeps[0]) == [2, 2] and not wts.any()
+    recon, bases = QOPeriods().compute_reconstruction(x, [2, 3], type="solve", window=win)[0]
+    _, want_w, want_r = _solve(x[0], win, [2, 3])
+    assert rel_err(bases["weights"], want_w) <= TOL and rel_err(x[0] - recon, want_r) <= TOL
+
+
 def test_device_tensors_give_the_same_bits(engines):
     import torch
 

@@ -260,6 +260,67 @@ def test_qo_fit_explicit_lists(eng):
         eng.ramanujan_fit(x, 2, 80, 0.0)
 
 
+def test_qo_fit_pair_table_and_inline_gcd(eng):
+    """4b. k_qo_fit's product with 16 blocks (pair constants from the LDS table, kQoPairTab) and with 17 (computed
+    inline): the shared product of k_qo_find, whose own 16 / 17-block test is in test_gpu_qo_edges.py.  N = 500 is a
+    multiple of no period; cond(A A^T) is about 3e3, so the bar is the 1e-8 of the tests above."""
+    from pyperiod_amd import _ffi
+
+    n, lst = 500, [2, 3, 4, 5, 7, 8, 9, 11, 13, 16, 17, 19, 23, 25, 27, 29, 31]
+    x = multi_sinusoid_batch(5, 2, n)
+    for blocks in (16, 17):
+        keeps, wts, resid, st = eng.qo_fit(x, lst[:blocks], kcap=256)
+        for w in range(2):
+            a, dims, w_o, recon = _oracle_fit(x[w], lst[:blocks])
+            assert np.linalg.cond(a @ a.T) <= COND_CUT
+            assert st[w] == _ffi.PH_ST_OK and list(keeps[w]) == list(dims.values()), (blocks, w)
+            ew, er = rel_err(wts[w, : w_o.size], w_o), rel_err(resid[w], x[w] - recon)
+            print(f"{blocks} blocks, window {w}: weights {ew:.2e} residual {er:.2e}")
+            assert ew < 1e-8 and er < 1e-8 and not wts[w, w_o.size :].any(), (blocks, w, ew, er)
+
+
+@pytest.mark.parametrize("n, lanes", [(2048, 4), (4096, 8)])
+def test_qo_fit_lane_split_four_and_eight(eng, n, lanes):
+    """4b. The lanes-per-row split of the product at 4 and at 8 lanes per row (the fixtures reach 1, 2 and 16): a row
+    of block 64 walks min(105, terms) + min(175, terms) steps against blocks 210 and 350, terms = n / 64 samples, and
+    the split doubles its lanes while steps / lanes > 24 -- 64 steps give 4 lanes at n = 2048, 128 steps give 8 at
+    n = 4096, the smallest windows at which this dictionary gets there.  cond(A A^T) is 519 / 256: the 1e-8 bar."""
+    from pyperiod_amd import _ffi
+
+    lst = [210, 350, 64]
+    steps = sum(min(p // np.gcd(p, 64), (n - 1) // 64 + 1) for p in lst[:2])
+    assert steps // (lanes // 2) > 24 >= steps // lanes  # (the rule of qo_lane_split; all items fit the 1024 threads)
+    x = multi_sinusoid_batch(9, 2, n)
+    keeps, wts, resid, st = eng.qo_fit(x, lst, kcap=552)
+    for w in range(2):
+        a, dims, w_o, recon = _oracle_fit(x[w], lst)
+        assert np.linalg.cond(a @ a.T) <= COND_CUT
+        assert st[w] == _ffi.PH_ST_OK and list(keeps[w]) == list(dims.values()) == [210, 280, 62]
+        ew, er = rel_err(wts[w], w_o), rel_err(resid[w], x[w] - recon)
+        print(f"n {n}, window {w}: weights {ew:.2e} residual {er:.2e}")
+        assert ew < 1e-8 and er < 1e-8, (n, w, ew, er)
+
+
+def test_qo_fit_non_finite_sample(eng):
+    """4c. A NaN sample makes the right-hand side, hence the solver's sums, NaN: no comparison of the solver accepts one,
+    so the window is handed back with PH_ST_ITER_CAP and zero weights; its neighbour in the batch is untouched.
+    Without a window (k_qo_fit) and under one (k_qo_fit_win: the folds of the window itself stay finite)."""
+    from pyperiod_amd import _ffi
+
+    n = 240
+    x = multi_sinusoid_batch(0, 2, n)
+    clean = eng.qo_fit(x, [7, 12], kcap=64)
+    xb = x.copy()
+    xb[0, 100] = np.nan
+    for window in (None, np.ones(n)):
+        keeps, wts, resid, st = eng.qo_fit(xb, [7, 12], kcap=64, window=window)
+        assert list(st) == [_ffi.PH_ST_ITER_CAP, _ffi.PH_ST_OK] and list(keeps[0]) == [7, 11] and not wts[0].any()
+        if window is None:
+            assert np.array_equal(wts[1], clean[1][1]) and np.array_equal(resid[1], clean[2][1])
+        else:  # (the same arithmetic in another order: the bar of test_gpu_qo_window.py)
+            assert rel_err(wts[1], clean[1][1]) < 1e-12 and rel_err(resid[1], clean[2][1]) < 1e-12
+
+
 def test_compute_reconstruction_batch(eng):
     """5. QOPeriods.compute_reconstruction on a batch against get_subspaces + solve_quadratic of the oracle."""
     from pyperiod_amd import QOPeriods

@@ -677,7 +677,7 @@ int plan_m_best(const ph_ctx* c, int dtype, int N, int num, int min_length, int 
   if (pair) {
     s1.variant = PH_PLAN_PAIR;
     s1.lds = pair_lds_bytes(N, num, P);
-    s1.block = 1024;
+    s1.block = ph::kPairWaves * ph::kWave;  // the kernel is compiled for this block and no other
     s1.small_means = 0;  // the pair kernel keeps its own short-period means (kPairSmallP)
   } else {
     s1.lds = lds1;
@@ -731,7 +731,7 @@ int plan_best_correlation(const ph_ctx* c, int dtype, int N, int max_length, uns
   const bool pair = c->bc_pair && dtype == PH_F64 && !general && k.window == PH_PLAN_LDS && max_length <= N &&
                     max_length - 1 >= 2 && lds_pair <= (size_t)c->lds_limit;
   k.variant = pair ? PH_PLAN_PAIR : PH_PLAN_ONE;
-  k.block = pair ? 1024 : c->sweep_block;
+  k.block = pair ? ph::kPairWaves * ph::kWave : c->sweep_block;  // (the pair kernel is compiled for this block and no other)
   if (pair) k.lds = lds_pair;
   return PH_OK;
 }
@@ -1648,7 +1648,9 @@ int ph_small_to_large(ph_ctx* c, const void* x, int dtype, int64_t W, int N, dou
     const int64_t npairs = (W + 1) / 2;
     const int per_cu = (int)std::max<size_t>(1, std::min<size_t>((size_t)c->lds_limit / k.lds, 2048 / (size_t)k.block));
     const unsigned grid_pairs = (unsigned)std::min<int64_t>(npairs, (int64_t)c->num_cu * per_cu);
-    PH_TRY(launch(c, "k_small_to_large", ph::k_small_to_large_pair, dim3(grid_pairs), k.block, k.lds, (const double*)dx,
+    // the instantiation follows the block: the fixed-count one is never launched with another block size
+    const auto kern = k.block == ph::kPairWaves * ph::kWave ? ph::k_small_to_large_pair<ph::kPairWaves> : ph::k_small_to_large_pair<0>;
+    PH_TRY(launch(c, "k_small_to_large", kern, dim3(grid_pairs), k.block, k.lds, (const double*)dx,
                   (int)W, N, thresh, n_periods, ws.geomf, ws.kapf, ws.gwin, cap, (int*)dcnt, (int*)dper, (double*)dpow,
                   (double*)dbases, (int*)dstat, dmax, dmax + 1));
   } else {

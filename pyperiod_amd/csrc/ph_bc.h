@@ -217,7 +217,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
   const int tid = threadIdx.x;
   const int lane = tid & (kWave - 1);
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int nw = blockDim.x >> 6;
+  constexpr int NW = kPairWaves, nw = NW;  // always 64 kPairWaves threads (plan_best_correlation): see k_mbest_step1_pair
   const size_t gstride = win_stride((size_t)N);
   float* pwf = reinterpret_cast<float*>(pw);
   const double sqrtN = uniform_f64(sqrt((double)N));
@@ -241,7 +241,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
       a2 = fma(v, v, a2);
       a1 += fabs(v);
     }
-    block_sum2(a2, a1, red);
+    block_sum2<NW>(a2, a1, red);
     const double sc = uniform_f64(pair_pick_scale(a2, N));
     for (int n = tid; n < N; n += blockDim.x) pwf[2 * n + w] = (float)(stg[n] * sc);
     if (tid == 0) {
@@ -289,12 +289,8 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
           red[kMaxWaves + wv] = lo1;
         }
         __syncthreads();
-        lo0 = red[0];
-        lo1 = red[kMaxWaves];
-        for (int i = 1; i < nw; ++i) {
-          lo0 = fmax(lo0, red[i]);
-          lo1 = fmax(lo1, red[kMaxWaves + i]);
-        }
+        lo0 = red_combine<true, NW>(red, nw);  // (fmax in slot order: the value of the loop this replaces)
+        lo1 = red_combine<true, NW>(red + kMaxWaves, nw);
         for (int idx = tid; idx < P; idx += blockDim.x) {
           const f2 v = vals[idx];
           const double rr = (double)(pair_rows_upper(fn, p_lo + idx) + 2);
@@ -343,7 +339,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
           wbestp[wv] = bestp;
         }
         __syncthreads();
-        red_argmax(wbest, wbestp, nw, best, bestp);
+        red_argmax<NW>(wbest, wbestp, nw, best, bestp);
         __syncthreads();
         if (bestp == 0) {
           status = 1;  // reference: project(data, None) raises
@@ -365,7 +361,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
               a1 += fabs(v);
             }
           }
-          block_sum2(a2, a1, red);
+          block_sum2<NW>(a2, a1, red);
           const double this_norm = sqrt(a2) / sqrtN;
           const double gain = (old_norm - this_norm) / og;
           zero_row = !(gain > ratio);  // :343

@@ -26,6 +26,7 @@ constexpr int kWave = 64;
 constexpr int kBlock = 256;      // 4 wavefronts: thread-per-residue / sequential kernels
 constexpr int kBlockWide = 512;  // 8 wavefronts: sweep kernels (4 workgroups x 32 KiB windows per CU -> 32 waves/CU)
 constexpr int kMaxWaves = 16;
+constexpr int kPairWaves = 16;   // wavefronts of a window-pair workgroup (two of them fill the 32 wave slots of a CU)
 
 constexpr unsigned kTrunc = 1u;
 constexpr unsigned kOrth = 2u;
@@ -114,59 +115,93 @@ __device__ __forceinline__ double uniform_f64(double v) {
   return __hiloint2double(hi, lo);
 }
 
+// A constant through a scalar register pair at its use.  A floating-point constant that a loop body compares against
+// is a loop invariant to the compiler, which materialises it in vector registers in front of the loop; in a kernel at
+// its register cap that pair is spilled around the whole loop and comes back from scratch -- through L2 -- at the use.
+__device__ __forceinline__ double const_at_use(double c) {
+  asm volatile("" : "+s"(c));
+  return c;
+}
+__device__ __forceinline__ int const_at_use(int c) {
+  asm volatile("" : "+s"(c));
+  return c;
+}
+
 // red[0] + red[1] + ... + red[nw - 1] in that order, with all kMaxWaves reads in flight before the first addition
 // (a loop over the run-time wave count was compiled into nw dependent LDS round trips: ~1 us at 16 wavefronts).
 // Slots >= nw are read but not used; the result is the value of the plain loop, bit for bit.
-template <bool MAXOP = false>
+// NW: the wavefront count of the workgroup as a compile-time fact (every workgroup reduction below takes it the same
+// way).  NW == 0: the count is read from blockDim.x, as above.  NW > 0: the kernel is only ever launched with 64 NW
+// threads -- exactly NW slots are read and none is tested.  (The tests `i < nw` become fifteen 64-bit lane masks that
+// the compiler keeps across a kernel's main loop; in the window-pair kernels, which sit at their scalar-register
+// budget, the masks lived in lanes of spill registers and came back by v_readlane in front of two v_cndmask per slot:
+// 120-190 vector instructions around the 16 additions of one sum.)  The order of the operations is the same.
+template <int NW>
+__device__ __forceinline__ int wave_count() {
+  static_assert(NW >= 0 && NW <= kMaxWaves, "a workgroup has at most kMaxWaves wavefronts");
+  return NW > 0 ? NW : (int)((blockDim.x + kWave - 1) / kWave);
+}
+// threads of the workgroup, as a loop stride
+template <int NW>
+__device__ __forceinline__ unsigned block_threads() {
+  return NW > 0 ? (unsigned)(NW * kWave) : blockDim.x;
+}
+
+template <bool MAXOP = false, int NW = 0>
 __device__ __forceinline__ double red_combine(const double* red, int nw) {
-  double v[kMaxWaves];
+  constexpr int kSlots = NW > 0 ? NW : kMaxWaves;
+  double v[kSlots];
 #pragma unroll
-  for (int i = 0; i < kMaxWaves; ++i) v[i] = red[i];
+  for (int i = 0; i < kSlots; ++i) v[i] = red[i];
   double t = MAXOP ? v[0] : 0.0 + v[0];
 #pragma unroll
-  for (int i = 1; i < kMaxWaves; ++i)
-    if (i < nw) t = MAXOP ? fmax(t, v[i]) : t + v[i];
+  for (int i = 1; i < kSlots; ++i)
+    if (NW > 0 || i < nw) t = MAXOP ? fmax(t, v[i]) : t + v[i];
   return t;
 }
 
 // Sum over the workgroup; every thread gets the result.  `red` holds >= 2*kMaxWaves doubles.
 // Partials are combined in wave order, so the result is identical in all threads.
+template <int NW = 0>
 __device__ __forceinline__ double block_sum(double v, double* red) {
   const int tid = threadIdx.x;
-  const int nw = (blockDim.x + kWave - 1) / kWave;
+  const int nw = wave_count<NW>();
   v = wave_sum(v);
   if ((tid & (kWave - 1)) == 0) red[tid >> 6] = v;
   __syncthreads();
-  const double t = red_combine(red, nw);
+  const double t = red_combine<false, NW>(red, nw);
   __syncthreads();
   return uniform_f64(t);
 }
 
 // block_sum without the trailing barrier: `red` must not be written again before the workgroup's next barrier
+template <int NW = 0>
 __device__ __forceinline__ double block_sum_once(double v, double* red) {
   const int tid = threadIdx.x;
-  const int nw = (blockDim.x + kWave - 1) / kWave;
+  const int nw = wave_count<NW>();
   v = wave_sum(v);
   if ((tid & (kWave - 1)) == 0) red[tid >> 6] = v;
   __syncthreads();
-  return uniform_f64(red_combine(red, nw));
+  return uniform_f64(red_combine<false, NW>(red, nw));
 }
 
 // Workgroup argmax from the wave winners (value, period): largest value, lowest period among equals, period 0 = none.
 // All reads in flight before the comparisons, results in scalar registers (identical in every lane).
+template <int NW = 0>
 __device__ __forceinline__ void red_argmax(const double* wbest, const int* wbestp, int nw, double& best, int& bestp) {
-  double v[kMaxWaves];
-  int p[kMaxWaves];
+  constexpr int kSlots = NW > 0 ? NW : kMaxWaves;
+  double v[kSlots];
+  int p[kSlots];
 #pragma unroll
-  for (int i = 0; i < kMaxWaves; ++i) {
+  for (int i = 0; i < kSlots; ++i) {
     v[i] = wbest[i];
     p[i] = wbestp[i];
   }
   double b = 0.0;
   int bp = 0;
 #pragma unroll
-  for (int i = 0; i < kMaxWaves; ++i)
-    if (i < nw && p[i] != 0 && (v[i] > b || (v[i] == b && p[i] < bp))) {
+  for (int i = 0; i < kSlots; ++i)
+    if ((NW > 0 || i < nw) && p[i] != 0 && (v[i] > b || (v[i] == b && p[i] < bp))) {
       b = v[i];
       bp = p[i];
     }
@@ -175,9 +210,10 @@ __device__ __forceinline__ void red_argmax(const double* wbest, const int* wbest
 }
 
 // sums of two values over the workgroup with one pair of barriers (every thread gets both)
+template <int NW = 0>
 __device__ __forceinline__ void block_sum2(double& a, double& b, double* red) {
   const int tid = threadIdx.x;
-  const int nw = (blockDim.x + kWave - 1) / kWave;
+  const int nw = wave_count<NW>();
   a = wave_sum(a);
   b = wave_sum(b);
   if ((tid & (kWave - 1)) == 0) {
@@ -185,20 +221,21 @@ __device__ __forceinline__ void block_sum2(double& a, double& b, double* red) {
     red[kMaxWaves + (tid >> 6)] = b;
   }
   __syncthreads();
-  const double ta = red_combine(red, nw), tb = red_combine(red + kMaxWaves, nw);
+  const double ta = red_combine<false, NW>(red, nw), tb = red_combine<false, NW>(red + kMaxWaves, nw);
   __syncthreads();
   a = uniform_f64(ta);
   b = uniform_f64(tb);
 }
 
 // Maximum over the workgroup (every thread gets it; NaN inputs are ignored by fmax, -inf if there is none).
+template <int NW = 0>
 __device__ __forceinline__ double block_max(double v, double* red) {
   const int tid = threadIdx.x;
-  const int nw = (blockDim.x + kWave - 1) / kWave;
+  const int nw = wave_count<NW>();
   v = wave_max(v);
   if ((tid & (kWave - 1)) == 0) red[tid >> 6] = v;
   __syncthreads();
-  const double t = red_combine<true>(red, nw);
+  const double t = red_combine<true, NW>(red, nw);
   __syncthreads();
   return uniform_f64(t);
 }
@@ -347,14 +384,14 @@ __device__ __forceinline__ void project_lds(const T* __restrict__ src, T* __rest
 }
 
 // sum_n v[n]^2 over the workgroup (every thread gets it).
-template <typename T>
+template <int NW = 0, typename T>
 __device__ __forceinline__ double block_sumsq(const T* __restrict__ v, int N, double* red) {
   double acc = 0.0;
-  for (int n = threadIdx.x; n < N; n += blockDim.x) {
+  for (int n = threadIdx.x; n < N; n += block_threads<NW>()) {
     const double t = (double)v[n];
     acc += t * t;
   }
-  return block_sum(acc, red);
+  return block_sum<NW>(acc, red);
 }
 
 // periodic_norm (Periods.py:221-241) from a sum of squares: (sqrt(ss)/sqrt(N)) [/sqrt(p)].

@@ -333,7 +333,10 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
 
   const int tid = threadIdx.x;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int nw = blockDim.x >> 6;
+  // The host launches this kernel with 64 kPairWaves threads and nothing else (plan_m_best): the wavefront count is a
+  // constant and the workgroup reductions test no slot (ph_device.h, red_combine).  blockDim.x stays the stride of the
+  // thread loops: as the constant 1024 it raised the spills (scratch 60 -> 72 bytes per lane) for 45 instructions.
+  constexpr int NW = kPairWaves, nw = NW;
   const size_t gstride = win_stride((size_t)N);
   float* pwf = reinterpret_cast<float*>(pw);
   const double sqrtN = uniform_f64(sqrt((double)N));
@@ -356,7 +359,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
       for (int n = tid; n < N; n += blockDim.x) stg[n] = 0.0;
     }
     __syncthreads();
-    const double rsq = block_sumsq(stg, N, red);
+    const double rsq = block_sumsq<NW>(stg, N, red);
     const double sc = uniform_f64(pair_pick_scale(rsq, N));
     for (int n = tid; n < N; n += blockDim.x) pwf[2 * n + w] = (float)(stg[n] * sc);
     if (tid == 0) {
@@ -429,7 +432,8 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
         const int idx_own = i0 + tid;
         Entry own = {f2_zero(), 0.0, 1.0, true, true};
         if (idx_own < P) own = entry(idx_own);
-        double lo0 = -1.0 / 0.0, lo1 = -1.0 / 0.0;
+        const double ninf = const_at_use(-1.0 / 0.0);  // (as a vector-register invariant it was spilled around the screen)
+        double lo0 = ninf, lo1 = ninf;
         for (int idx = idx_own; idx < P; idx += blockDim.x) {
           const Entry e = idx == idx_own ? own : entry(idx);
           double a = (double)e.v.x - e.rad * unit0, b = (double)e.v.y - e.rad * unit1;
@@ -447,10 +451,10 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
           red[kMaxWaves + wv] = lo1;
         }
         __syncthreads();
-        lo0 = uniform_f64(red_combine<true>(red, nw));
-        lo1 = uniform_f64(red_combine<true>(red + kMaxWaves, nw));
+        lo0 = uniform_f64(red_combine<true, NW>(red, nw));
+        lo1 = uniform_f64(red_combine<true, NW>(red + kMaxWaves, nw));
         // every screened period skipped: nothing bounds the winner from below, every period goes through the exact phase
-        const bool none0 = cover && scr0 && !(lo0 > -1.0 / 0.0), none1 = cover && scr1 && !(lo1 > -1.0 / 0.0);
+        const bool none0 = cover && scr0 && !(lo0 > ninf), none1 = cover && scr1 && !(lo1 > ninf);
         if (tid == 0 && none0) ctl[MP_LISTED] = kPairListCap + 1;
         if (tid == 0 && none1) ctl[MP_LISTED + 1] = kPairListCap + 1;
         // periods that tie with the winner in the ROUNDED norm survive too
@@ -546,7 +550,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
             part = fma(s * s, full ? gm.w_full : gm.w_short, part);
             stg[j] = s;
           }
-          fold_ss = block_sum(part, red);
+          fold_ss = block_sum<NW>(part, red);
           clk.mark(2);
           if (ncand > 1) {
             // a wavefront per listed divisor: its value from S_m (pair_thin_part) against the threshold; one that reaches it
@@ -595,11 +599,15 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
             const double top = wave_max(fmax(v0, v1));
             const bool keep0 = k0 < ncand && v0 >= top - fabs(top) * 1e-9, keep1 = k1 < ncand && v1 >= top - fabs(top) * 1e-9;
             const unsigned long long m0 = __ballot(keep0), m1 = __ballot(keep1);
-            const unsigned long long below = (1ull << lane) - 1ull;
             const int n0 = __popcll(m0);
             int* out = list + w * kPairListCap;
-            if (keep0) out[__popcll(m0 & below)] = q0;
-            if (keep1) out[n0 + __popcll(m1 & below)] = q1;
+            // (set bits below the lane with v_mbcnt: the mask (1 << lane) - 1 was built in front of the exact phase
+            // of every round and spilled, 16 bytes per lane)
+            const auto below = [](unsigned long long m) {
+              return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+            };
+            if (keep0) out[below(m0)] = q0;
+            if (keep1) out[n0 + below(m1)] = q1;
             if (lane == 0) ctl[MP_LISTED + w] = n0 + __popcll(m1);
           }
           __syncthreads();
@@ -642,7 +650,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
             } else {
               part = pair_exact_part(stg, p, g, tid, blockDim.x);
             }
-            consider(block_sum(part, red), p);
+            consider(block_sum<NW>(part, red), p);
           }
           best = bestp != 0 ? periodic_norm_from_sq_n(best_ss, sqrtN, gamma ? bestp : 0) : 0.0;
           if (!(best > 0.0)) bestp = 0;  // the reference needs p_norm > 0 (Periods.py:497,512)
@@ -661,7 +669,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
             wbestp[wv] = bestp;
           }
           __syncthreads();
-          red_argmax(wbest, wbestp, nw, best, bestp);
+          red_argmax<NW>(wbest, wbestp, nw, best, bestp);
           __syncthreads();
         }
         clk.mark(4);
@@ -762,10 +770,13 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
             }
           }
           if (more) {
-            const double rsq = block_sum(acc, red);
+            const double rsq = block_sum<NW>(acc, red);
             const double unit = rsq * sc * sc;
-            const bool ok = pair_usable(rsq);
-            if (pair_image_stale(rsq, sc, N)) {
+            // (pair_usable and pair_image_stale written out, their constants through scalar registers at this use: as
+            // loop invariants in vector registers 1.79e308 and 9e-13 N were spilled around the round loop, and both
+            // came back from scratch right behind the block sum of every window-sweep)
+            const bool ok = rsq > 0.0 && rsq < const_at_use(1.79e308);
+            if (ok && unit < const_at_use(kPairStaleMeanSq) * (double)const_at_use(N)) {
               const double sc2 = uniform_f64(pair_pick_scale(rsq, N));
               __syncthreads();
               pair_rescale(pwf, w, N, (float)(sc2 / sc), tid);

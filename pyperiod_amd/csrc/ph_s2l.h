@@ -310,6 +310,10 @@ __device__ __forceinline__ void s2l_copy(const double* __restrict__ src, double*
   }
 }
 
+// NW: the wavefronts of the workgroup as a compile-time fact (ph_device.h, red_combine).  The host launches
+// k_small_to_large_pair<kPairWaves> with 64 kPairWaves threads and k_small_to_large_pair<0> with any other block
+// (PH_S2L_BLOCK), and picks the one from the block where it launches.
+template <int NW>
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_small_to_large_pair(
     const double* __restrict__ x, int W, int N, double thresh, int n_periods, const PGeomF* __restrict__ geomf,
     const float* __restrict__ kapf, double* __restrict__ gres, int cap, int* __restrict__ counts,
@@ -331,10 +335,11 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
 
   const int tid = threadIdx.x;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int nw = blockDim.x >> 6;
+  const int nthr = block_threads<NW>();
+  const int nw = NW > 0 ? NW : nthr >> 6;
   constexpr int kEx = kBlockWide;  // threads of the exact phases: the mapping of k_small_to_large (bit-identical sums)
   const bool ex = tid < kEx;
-  const int bk = (int)blockDim.x > kEx ? kEx : 0;  // bookkeeping thread of the accept path
+  const int bk = nthr > kEx ? kEx : 0;  // bookkeeping thread of the accept path
   const size_t gstride = win_stride((size_t)N);
   float* pwf = reinterpret_cast<float*>(pw);
   const double sqrtN = uniform_f64(sqrt((double)N));
@@ -360,7 +365,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     thf[2 * w + 1] = t1;
   };
 
-  for (int i = tid; i < kPad; i += blockDim.x) pw[N + i] = f2_zero();
+  for (int i = tid; i < kPad; i += nthr) pw[N + i] = f2_zero();
   // Persistent workgroups: the grid fills the chip once and every workgroup draws pairs from a device counter until
   // the batch is done (a fresh workgroup per pair left ~5 % of the slots empty between an exit and the next dispatch).
   const int64_t npairs = ((int64_t)W + 1) / 2;
@@ -378,9 +383,9 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
         const double v = stg[n];
         acc = fma(v, v, acc);
       }
-    const double rsq = block_sum(acc, red);
+    const double rsq = block_sum<NW>(acc, red);
     const double sc = uniform_f64(pair_pick_scale(rsq, N));
-    for (int n = tid; n < N; n += blockDim.x) pwf[2 * n + w] = exists ? (float)(stg[n] * sc) : 0.0f;
+    for (int n = tid; n < N; n += nthr) pwf[2 * n + w] = exists ? (float)(stg[n] * sc) : 0.0f;
     if (tid == 0) {
       const double dnorm = sqrt(rsq) / sqrtN;  // data_norm, Periods.py:269
       st[w] = rsq;
@@ -507,7 +512,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
           }
         }
       }
-      tsq = block_sum_once(tsq, red);  // `red` rests until the next event: barriers in between
+      tsq = block_sum_once<NW>(tsq, red);  // `red` rests until the next event: barriers in between
       clk.mark(1);
       clk.count(1);
       const double tn = uniform_f64(sqrt(tsq) / sqrtN);

@@ -478,11 +478,19 @@ int pick_chunks(ph_ctx* c, int64_t W, int items, int min_items_per_chunk) {
 }
 
 using ph::carve_bytes;
+using ph::CarveCount;
 using ph::kBlock;
 using ph::kBlockWide;
 using ph::kPad;
 using ph::kMaxWaves;
 using ph::kRedDoubles;
+
+// LDS bytes of a kernel whose carve depends on the element type: `carve(T())` runs the kernel's x_carve<T> on a
+// CarveCount.
+template <class F>
+size_t lds_of(int dtype, F carve) {
+  return dtype == PH_F64 ? carve(double()).bytes : carve(float()).bytes;
+}
 
 // LDS layout of k_qo_find: bookkeeping, the pair table, the weights, and the six work vectors + sample counts of the
 // conjugate-gradient solve (one slot per dictionary row and one per block).  The residual window stays in LDS when
@@ -490,23 +498,26 @@ using ph::kRedDoubles;
 // workgroup for N = 16384 fp32 with kcap = 1024, two workgroups per CU -- and sit behind it otherwise.  Windows
 // that do not fit (long fp64 windows) move to the HBM workspace and the sweeps read them through L2.
 // *placement_out = PH_QO_LDS_OVERLAY, PH_QO_LDS_BEHIND or PH_QO_HBM.
-int qo_lds_layout(ph_ctx* c, size_t sz, int N, int max_length, int kcap, size_t* lds_out, int* placement_out) {
-  const size_t kv = (size_t)kcap + ph::kQoMaxBlocks;
-  const size_t fixed = carve_bytes(kRedDoubles, 8) + carve_bytes(kMaxWaves, 8) + carve_bytes(kMaxWaves, 4) +
-                       2 * carve_bytes(ph::kQoMaxBlocks, 4) + carve_bytes(ph::kQoMaxBlocks + 1, 4) +
-                       carve_bytes(ph::kQoMaxBlocks, 8) + carve_bytes((max_length + 32) / 32, 4) +
-                       carve_bytes(2 * ph::kQoPairTab * ph::kQoPairTab, 4) + carve_bytes(ph::kQoMaxBlocks, 4) +
-                       carve_bytes(ph::kQoMaxBlocks + 1, 4) + carve_bytes(6 * kMaxWaves, 8) + carve_bytes(kv, 8);
-  const size_t solver = 6 * carve_bytes(kv, 8) + carve_bytes(kv, 4);
-  const size_t win = carve_bytes(N + kPad, sz);
-  const size_t limit = (size_t)c->lds_limit;
-  if (fixed + solver > limit)
-    return fail(PH_E_ARG, "ph_qo_find_periods: kcap=%d needs %zu B of LDS for the solver (limit %d B)", kcap,
-                fixed + solver, c->lds_limit);
-  const bool overlay = win >= solver;
-  const size_t with_window = fixed + (overlay ? win : win + solver);
+int qo_lds_layout(ph_ctx* c, int dtype, int N, int max_length, int kcap, size_t* lds_out, int* placement_out) {
+  struct Count {
+    size_t bytes, window, solver;  // the layout, its window piece, its work vectors
+  };
+  const auto count = [&](bool lw, bool overlay) {
+    const auto of = [&](auto t) {
+      const auto L = ph::qo_find_carve<decltype(t)>(CarveCount(), N, max_length, kcap, lw, overlay);
+      return Count{L.bytes, L.window, L.solver};
+    };
+    return dtype == PH_F64 ? of(double()) : of(float());
+  };
+  const size_t bare = count(false, false).bytes, limit = (size_t)c->lds_limit;
+  if (bare > limit)
+    return fail(PH_E_ARG, "ph_qo_find_periods: kcap=%d needs %zu B of LDS for the solver (limit %d B)", kcap, bare,
+                c->lds_limit);
+  const Count behind = count(true, false);
+  const bool overlay = behind.window >= behind.solver;  // the vectors fit over the window
+  const size_t with_window = overlay ? count(true, true).bytes : behind.bytes;
   const bool lds_window = !c->qo_hbm_window && with_window <= limit;
-  *lds_out = lds_window ? with_window : fixed + solver;
+  *lds_out = lds_window ? with_window : bare;
   *placement_out = !lds_window ? PH_QO_HBM : overlay ? PH_QO_LDS_OVERLAY : PH_QO_LDS_BEHIND;
   return PH_OK;
 }
@@ -515,11 +526,12 @@ int qo_lds_layout(ph_ctx* c, size_t sz, int N, int max_length, int kcap, size_t*
 // divisor bitset lives in the HBM workspace and the block's weights in the output row, so the LDS need does not depend
 // on max_length or kcap, and every N and max_length is feasible.  A window in LDS counts as PH_QO_LDS_BEHIND (there
 // are no work vectors to overlay it).
-void qo_greedy_layout(const ph_ctx* c, size_t sz, int N, size_t* lds_out, int* placement_out) {
-  const size_t fixed = carve_bytes(kRedDoubles, 8) + carve_bytes(kMaxWaves, 8) + carve_bytes(kMaxWaves, 4);
-  const size_t with_window = fixed + carve_bytes(N + kPad, sz);
-  const bool lds_window = !c->qo_hbm_window && with_window <= (size_t)c->lds_limit;
-  *lds_out = lds_window ? with_window : fixed;
+void qo_greedy_layout(const ph_ctx* c, int dtype, int N, size_t* lds_out, int* placement_out) {
+  const auto lds = [&](bool lw) {
+    return lds_of(dtype, [&](auto t) { return ph::qo_greedy_carve<decltype(t)>(CarveCount(), N, lw); });
+  };
+  const bool lds_window = !c->qo_hbm_window && lds(true) <= (size_t)c->lds_limit;
+  *lds_out = lds(lds_window);
   *placement_out = lds_window ? PH_QO_LDS_BEHIND : PH_QO_HBM;
 }
 
@@ -534,21 +546,14 @@ int qo_plan(ph_ctx* c, int dtype, int N, int* max_length_io, int kcap, unsigned 
   if (!keep_weights && (kcap < 1 || kcap > 2048)) return fail(PH_E_ARG, "kcap=%d must be in [1, 2048]", kcap);
   if (keep_weights && (kcap < 1 || kcap > ph::kQoGreedyMaxRows))
     return fail(PH_E_ARG, "kcap=%d must be in [1, %d] with PH_FLAG_KEEP_WEIGHTS", kcap, ph::kQoGreedyMaxRows);
-  const size_t sz = elem_size(dtype);
   if (keep_weights) {
-    qo_greedy_layout(c, sz, N, lds_out, placement_out);
+    qo_greedy_layout(c, dtype, N, lds_out, placement_out);
     return PH_OK;
   }
-  return qo_lds_layout(c, sz, N, *max_length_io, kcap, lds_out, placement_out);
+  return qo_lds_layout(c, dtype, N, *max_length_io, kcap, lds_out, placement_out);
 }
 
-// LDS of k_mbest_step1_pair: the pair window, one fp64 staging buffer, bookkeeping of two windows.
-size_t pair_lds_bytes(int N, int num, int P) {
-  return 2 * carve_bytes(N + kPad, 8) + carve_bytes(kRedDoubles, 8) + carve_bytes(kMaxWaves, 8) +
-         carve_bytes(kMaxWaves, 4) + carve_bytes(2 * num, 8) + carve_bytes(2 * num, 4) +
-         carve_bytes(2 * ((P + 31) / 32), 4) + carve_bytes(2 * ph::kPairListCap, 4) + carve_bytes(16, 4) +
-         carve_bytes(4, 8) + carve_bytes(ph::kPairSmallP, 8) + carve_bytes(ph::kPairSplitW, 8);
-}
+size_t pair_lds_bytes(int N, int num, int P) { return ph::step1_pair_carve(CarveCount(), N, num, P).bytes; }
 
 // The window-pair screen serves fp64 windows, plain projection, candidate periods below N, when the pair window
 // and the staging buffer fit the LDS; everything else runs k_mbest_step1.
@@ -586,21 +591,15 @@ struct Plan {
   KernelPlan k[2];
 };
 
-// Second window-sized buffer (materialised projections): in LDS when both fit, otherwise in an HBM workspace.
-// `lds` comes in with the second buffer included and loses it when it moves.
-int plan_second_buffer(const ph_ctx* c, size_t* lds, bool needed, size_t buf_bytes) {
-  if (!needed) return PH_PLAN_NONE;
-  if (!c->hbm_window && *lds <= (size_t)c->lds_limit) return PH_PLAN_LDS;
-  *lds -= ((buf_bytes + 15) & ~size_t(15));
-  return PH_PLAN_HBM;
-}
-
-// Window buffer: LDS when it fits (after the second buffer has been placed), otherwise an HBM workspace that the
-// kernels' <T, false> instantiations fold through L2.  `lds` comes in with the window buffer included.
-int plan_window(const ph_ctx* c, size_t* lds, size_t win_len, size_t sz) {
-  if (!c->hbm_window && *lds <= (size_t)c->lds_limit) return PH_PLAN_LDS;
-  *lds -= carve_bytes(win_len, sz);
-  return PH_PLAN_HBM;
+// Placement of the window buffer and of the second window-sized buffer (materialised projections) of one kernel.
+// `lds(window_in_lds, second_in_lds)` counts the kernel's carve.  Everything in LDS when it fits; otherwise the second
+// buffer moves to an HBM workspace, and then the window (the kernels' <T, false> instantiations fold it through L2).
+template <class F>
+void plan_buffers(const ph_ctx* c, KernelPlan* k, bool second_needed, F lds) {
+  const auto fits = [&](bool lw, bool second) { return !c->hbm_window && lds(lw, second) <= (size_t)c->lds_limit; };
+  k->second = !second_needed ? PH_PLAN_NONE : fits(true, true) ? PH_PLAN_LDS : PH_PLAN_HBM;
+  k->window = fits(true, k->second == PH_PLAN_LDS) ? PH_PLAN_LDS : PH_PLAN_HBM;
+  k->lds = lds(k->window == PH_PLAN_LDS, k->second == PH_PLAN_LDS);
 }
 
 // The HBM workspace (slot, `bytes`) of a buffer the plan put there; nullptr when it stays in LDS or is not needed.
@@ -614,26 +613,27 @@ int place(ph_ctx* c, int where, int slot, size_t bytes, void** p) {
 
 // k_project_batch: window + projection scratch (min(p_max, N), N with PH_FLAG_ORTH).
 int plan_project(const ph_ctx* c, int dtype, int N, int pmax, unsigned flags, Plan* pl, int* scratch_len) {
-  const size_t sz = elem_size(dtype);
   KernelPlan& k = pl->k[0];
   *scratch_len = (flags & PH_FLAG_ORTH) ? N : std::min(pmax, N);
-  k.lds = carve_bytes(N, sz) + carve_bytes(*scratch_len, sz);
-  k.second = plan_second_buffer(c, &k.lds, true, (size_t)*scratch_len * sz);
-  k.window = plan_window(c, &k.lds, N, sz);
+  plan_buffers(c, &k, true, [&](bool lw, bool second) {
+    return lds_of(dtype,
+                  [&](auto t) { return ph::project_carve<decltype(t)>(CarveCount(), N, *scratch_len, lw, second); });
+  });
   k.block = kBlock;
   return check_lds(c, k.lds, N, "ph_project_batch");
 }
 
 // k_sweep: the norm modes with trunc / orth materialise the projection in a second buffer.
 int plan_sweep(const ph_ctx* c, int dtype, int N, int mode, unsigned flags, Plan* pl) {
-  const size_t sz = elem_size(dtype);
   KernelPlan& k = pl->k[0];
   const bool general = (flags & (PH_FLAG_TRUNC | PH_FLAG_ORTH)) && mode != PH_SWEEP_MAXABS;
-  k.lds = carve_bytes(N + kPad, sz) + (general ? carve_bytes(N, sz) : 0) + carve_bytes(kRedDoubles, 8) + carve_bytes(4, 4);
+  const auto lds = [&](bool lw, bool second) {
+    return dtype == PH_F64 ? ph::sweep_lds_bytes<double>(N, lw, general && second)
+                           : ph::sweep_lds_bytes<float>(N, lw, general && second);
+  };
   // long windows (at most two workgroups per CU): 16 wavefronts per workgroup
-  k.block = (3 * k.lds > (size_t)c->lds_limit && c->sweep_block == ph::kBlockWide) ? 1024 : c->sweep_block;
-  k.second = plan_second_buffer(c, &k.lds, general, (size_t)N * sz);
-  k.window = plan_window(c, &k.lds, N + kPad, sz);
+  k.block = (3 * lds(true, true) > (size_t)c->lds_limit && c->sweep_block == ph::kBlockWide) ? 1024 : c->sweep_block;
+  plan_buffers(c, &k, general, lds);
   return check_lds(c, k.lds, N, "ph_sweep");
 }
 
@@ -641,35 +641,32 @@ int plan_sweep(const ph_ctx* c, int dtype, int N, int mode, unsigned flags, Plan
 // proper divisors any candidate period has (PGeom / divisor slots of step 2).
 int plan_m_best(const ph_ctx* c, int dtype, int N, int num, int min_length, int max_length, int max_fac, unsigned flags,
                 Plan* pl) {
-  const size_t sz = elem_size(dtype);
   const bool general = flags & (PH_FLAG_TRUNC | PH_FLAG_ORTH);
   const int P = max_length - min_length + 1;
   KernelPlan& s1 = pl->k[0];
   KernelPlan& s2 = pl->k[1];
   pl->n_kernels = 2;
-  size_t lds1 = carve_bytes(N + kPad, sz) + (general ? carve_bytes(N, sz) : 0) + carve_bytes(kRedDoubles, 8) +
-                carve_bytes(kMaxWaves, 8) + carve_bytes(kMaxWaves, 4) + carve_bytes(num, 8) +
-                carve_bytes(num, 4) + carve_bytes((P + 31) / 32, 4);
-  size_t lds2 = carve_bytes(N + kPad, sz) + carve_bytes(N, sz) + carve_bytes(kRedDoubles, 8) +
-                carve_bytes(num, 8) + carve_bytes(num, 4) + carve_bytes(max_fac, 8) + carve_bytes(max_fac, 4) +
-                carve_bytes(kMaxWaves, sizeof(ph::PGeom)) + 3 * carve_bytes(num, 4) + carve_bytes(std::max(max_fac, 64), 4);
+  const auto lds1 = [&](bool lw, bool second, bool small_means) {
+    return dtype == PH_F64 ? ph::step1_lds_bytes<double>(N, num, P, lw, general && second, small_means)
+                           : ph::step1_lds_bytes<float>(N, num, P, lw, general && second, small_means);
+  };
+  const auto lds2 = [&](bool lw, bool second) {
+    return lds_of(dtype,
+                  [&](auto t) { return ph::step2_carve<decltype(t)>(CarveCount(), N, num, max_fac, lw, second); });
+  };
   // LDS for the means of a short winning period (split_row_means): only when the window stays in LDS beside it
-  const size_t lds_small = carve_bytes(ph::kPairSmallP, sz) + carve_bytes(ph::kPairSplitW, sz);
-  s1.small_means = (!general && !c->hbm_window && lds1 + lds_small <= (size_t)c->lds_limit) ? 1 : 0;
-  if (s1.small_means) lds1 += lds_small;
-  s1.second = plan_second_buffer(c, &lds1, general, (size_t)N * sz);
+  s1.small_means = (!general && !c->hbm_window && lds1(true, false, true) <= (size_t)c->lds_limit) ? 1 : 0;
+  plan_buffers(c, &s1, general, [&](bool lw, bool second) { return lds1(lw, second, s1.small_means); });
   // step 2 materialises a projection only when a row is split (rare) or in the trunc/orth modes:
   // in plain mode that buffer always lives in the HBM workspace, which lets four workgroups of
   // eight wavefronts share a CU instead of two of four
   if (general) {
-    s2.second = plan_second_buffer(c, &lds2, true, (size_t)N * sz);
+    plan_buffers(c, &s2, true, lds2);
   } else {
-    lds2 -= carve_bytes(N, sz);
+    plan_buffers(c, &s2, false, lds2);
     s2.second = PH_PLAN_HBM;
   }
-  s1.window = plan_window(c, &lds1, N + kPad, sz);
-  s2.window = plan_window(c, &lds2, N + kPad, sz);
-  PH_TRY(check_lds(c, std::max(lds1, lds2), N, "ph_m_best"));
+  PH_TRY(check_lds(c, std::max(s1.lds, s2.lds), N, "ph_m_best"));
   // Window-pair screen (k_mbest_step1_pair): fp64 windows, plain projection, candidate periods below N, and room for
   // the pair window plus one fp64 staging buffer in LDS.
   const bool pair = pair_eligible(c, dtype, N, num, min_length, max_length, flags) && s1.window == PH_PLAN_LDS &&
@@ -680,27 +677,24 @@ int plan_m_best(const ph_ctx* c, int dtype, int N, int num, int min_length, int 
     s1.block = ph::kPairWaves * ph::kWave;  // the kernel is compiled for this block and no other
     s1.small_means = 0;  // the pair kernel keeps its own short-period means (kPairSmallP)
   } else {
-    s1.lds = lds1;
     // 16 wavefronts per window: two workgroups per CU at N = 4096 (-2.4 % against four of 8 waves),
     // and long windows, which leave room for one or two workgroups per CU, still fill the SIMDs
     // (N = 8192: -15 %, N = 16384: -23 %)
     // (short windows, N < 3072, keep 8: four workgroups per CU there)
     s1.block = c->step1_block ? c->step1_block : (c->sweep_block == ph::kBlockWide && N >= 3072) ? 1024 : c->sweep_block;
   }
-  s2.lds = lds2;
   s2.block = general ? kBlock : c->sweep_block;
   return PH_OK;
 }
 
 // small_to_large: k_small_to_large or the persistent window-pair screen k_small_to_large_pair.
 int plan_small_to_large(const ph_ctx* c, int dtype, int N, int n_periods, unsigned flags, Plan* pl) {
-  const size_t sz = elem_size(dtype);
   const bool general = flags & (PH_FLAG_TRUNC | PH_FLAG_ORTH);
   KernelPlan& k = pl->k[0];
-  k.lds = carve_bytes(N + kPad, sz) + (general ? carve_bytes(N, sz) : carve_bytes(kBlockWide, sz)) +
-          carve_bytes(kRedDoubles, 8) + carve_bytes(ph::kS2LBatch, 8) + carve_bytes(4, 4);
-  k.second = plan_second_buffer(c, &k.lds, general, (size_t)N * sz);
-  k.window = plan_window(c, &k.lds, N + kPad, sz);
+  plan_buffers(c, &k, general, [&](bool lw, bool second) {
+    return lds_of(dtype,
+                  [&](auto t) { return ph::s2l_carve<decltype(t)>(CarveCount(), N, general, lw, general && second); });
+  });
   PH_TRY(check_lds(c, k.lds, N, "ph_small_to_large"));
   // Window-pair screen (ph_s2l.h): fp64 windows, plain projection, candidate periods below N.  LDS: the pair window and
   // one fp64 staging buffer, two 16-wave workgroups per CU; the fp64 residuals live in an HBM workspace.
@@ -715,19 +709,14 @@ int plan_small_to_large(const ph_ctx* c, int dtype, int N, int n_periods, unsign
 
 // best_correlation: k_best_correlation or the window-pair screen k_best_correlation_pair.
 int plan_best_correlation(const ph_ctx* c, int dtype, int N, int max_length, unsigned flags, Plan* pl) {
-  const size_t sz = elem_size(dtype);
   const bool general = flags & (PH_FLAG_TRUNC | PH_FLAG_ORTH);
   KernelPlan& k = pl->k[0];
-  k.lds = carve_bytes(N + kPad, sz) + (general ? carve_bytes(N, sz) : 0) + carve_bytes(kRedDoubles, 8) +
-          carve_bytes(kMaxWaves, 8) + carve_bytes(kMaxWaves, 4) + carve_bytes(ph::kCandCap, 4) +
-          carve_bytes(ph::kCandCap, 8) + carve_bytes(1, sizeof(ph::CandCtl));
-  k.second = plan_second_buffer(c, &k.lds, general, (size_t)N * sz);
-  k.window = plan_window(c, &k.lds, N + kPad, sz);
+  plan_buffers(c, &k, general, [&](bool lw, bool second) {
+    return lds_of(dtype, [&](auto t) { return ph::bc_carve<decltype(t)>(CarveCount(), N, lw, general && second); });
+  });
   PH_TRY(check_lds(c, k.lds, N, "ph_best_correlation"));
   // Window-pair screen (k_best_correlation_pair): fp64 windows, plain projection, pair window + staging buffer in LDS
-  const size_t lds_pair = 2 * carve_bytes(N + kPad, 8) + carve_bytes(kRedDoubles, 8) + carve_bytes(kMaxWaves, 8) +
-                          carve_bytes(kMaxWaves, 4) + carve_bytes(2 * ph::kPairListCap, 4) + carve_bytes(8, 4) +
-                          carve_bytes(10, 8);
+  const size_t lds_pair = ph::bc_pair_carve(CarveCount(), N).bytes;
   const bool pair = c->bc_pair && dtype == PH_F64 && !general && k.window == PH_PLAN_LDS && max_length <= N &&
                     max_length - 1 >= 2 && lds_pair <= (size_t)c->lds_limit;
   k.variant = pair ? PH_PLAN_PAIR : PH_PLAN_ONE;
@@ -743,22 +732,22 @@ struct BfShape {
 };
 
 int plan_best_frequency(const ph_ctx* c, int dtype, int N, int L, Plan* pl, BfShape* g) {
-  const size_t sz = elem_size(dtype);
   KernelPlan& s = pl->k[0];
   KernelPlan& u = pl->k[1];
   pl->n_kernels = 2;
-  size_t lds = 2 * carve_bytes(N, sz) + carve_bytes(kRedDoubles, 8);  // update kernel
-  u.second = plan_second_buffer(c, &lds, true, (size_t)N * sz);
   // windows longer than the LDS: both kernels work on the residual where it lives (HBM workspace)
-  u.window = (!c->hbm_window && lds <= (size_t)c->lds_limit) ? PH_PLAN_LDS : PH_PLAN_HBM;
-  if (u.window == PH_PLAN_HBM) lds -= carve_bytes(N, sz);
-  PH_TRY(check_lds(c, lds, N, "ph_best_frequency"));
-  u.lds = lds;
+  plan_buffers(c, &u, true, [&](bool lw, bool second) {
+    return lds_of(dtype, [&](auto t) { return ph::bf_update_carve<decltype(t)>(CarveCount(), N, lw, second); });
+  });
+  PH_TRY(check_lds(c, u.lds, N, "ph_best_frequency"));
   u.block = kBlockWide;
-  g->lds_spec = (u.window == PH_PLAN_LDS ? carve_bytes(N, sz) : 0) + carve_bytes(kMaxWaves, 8) + carve_bytes(kMaxWaves, 4);
+  const auto lds_spectrum = [&](size_t stage_len, size_t n) {
+    return lds_of(dtype, [&](auto t) { return ph::bf_spectrum_carve<decltype(t)>(CarveCount(), stage_len, n); });
+  };
+  g->lds_spec = lds_spectrum(u.window == PH_PLAN_LDS ? N : 0, 0);
   PH_TRY(check_lds(c, g->lds_spec, N, "ph_best_frequency"));
   // power-of-two win_size whose complex work array fits the LDS: in-LDS FFT, one record per window
-  g->lds_fft = 2 * carve_bytes(L, 8) + carve_bytes(kMaxWaves, 8) + carve_bytes(kMaxWaves, 4);
+  g->lds_fft = lds_spectrum(0, L);
   const bool use_fft = (L & (L - 1)) == 0 && L >= 4 && g->lds_fft <= (size_t)c->lds_limit && !std::getenv("PH_BF_DIRECT");
   g->logL = 0;
   while ((1 << g->logL) < L) ++g->logL;
@@ -767,7 +756,7 @@ int plan_best_frequency(const ph_ctx* c, int dtype, int N, int L, Plan* pl, BfSh
   g->logM = 0;
   while ((1LL << g->logM) < (long long)g->M0 + L / 2 + 1) ++g->logM;
   g->M = 1 << g->logM;
-  g->lds_chirp = 2 * carve_bytes(g->M, 8) + carve_bytes(kMaxWaves, 8) + carve_bytes(kMaxWaves, 4);
+  g->lds_chirp = lds_spectrum(0, g->M);
   const bool use_chirp =
       !use_fft && L >= 4 && g->logM <= 20 && g->lds_chirp <= (size_t)c->lds_limit && !std::getenv("PH_BF_DIRECT");
   g->nchunk = (use_fft || use_chirp) ? 1 : (L / 2 + 1 + ph::kBfBlock - 1) / ph::kBfBlock;
@@ -786,7 +775,10 @@ int plan_best_frequency(const ph_ctx* c, int dtype, int N, int L, Plan* pl, BfSh
 int plan_ramanujan(const ph_ctx* c, int dtype, int N, int q_hi, Plan* pl) {
   const size_t sz = elem_size(dtype);
   KernelPlan& k = pl->k[0];
-  const size_t strip = carve_bytes((size_t)q_hi, 8) + carve_bytes((size_t)std::max(1, q_hi / 2), 8);
+  const auto lds = [&](int nw, int pad, bool lw) {
+    return lds_of(dtype, [&](auto t) { return ph::ram_carve<decltype(t)>(CarveCount(), N, q_hi, nw, pad, lw); });
+  };
+  const size_t strip = lds(1, 0, false);  // strips A and B of one wavefront
   const size_t win_bytes = carve_bytes(N + kPad, sz);
   auto waves_for = [&](size_t room) { return (int)std::min<size_t>(ph::kRamMaxWaves, room / strip); };
   const size_t limit = (size_t)c->lds_limit;
@@ -816,8 +808,7 @@ int plan_ramanujan(const ph_ctx* c, int dtype, int N, int q_hi, Plan* pl) {
   if (nw < 1)
     return fail(PH_E_ARG, "ph_ramanujan_norms: q_hi=%d needs %zu B of LDS per wavefront, device limit is %d B", q_hi, strip,
                 c->lds_limit);
-  k.lds = (hbm ? 0 : pad ? win_bytes : carve_bytes(N, sz)) + carve_bytes((size_t)nw * q_hi, 8) +
-          carve_bytes((size_t)nw * std::max(1, q_hi / 2), 8);
+  k.lds = lds(nw, pad, !hbm);
   PH_TRY(check_lds(c, k.lds, N, "ph_ramanujan_norms"));
   if (q_hi >= 30030 || q_hi > 0xffff) return fail(PH_E_ARG, "ph_ramanujan_norms: q_hi=%d is beyond the record format", q_hi);
   k.window = hbm ? PH_PLAN_HBM : PH_PLAN_LDS;
@@ -831,9 +822,11 @@ int plan_ramanujan(const ph_ctx* c, int dtype, int N, int q_hi, Plan* pl) {
 // from HBM / L2 and the two work arrays live in an HBM workspace.
 void plan_orth_powers(const ph_ctx* c, int dtype, int N, int max_p, Plan* pl) {
   KernelPlan& k = pl->k[0];
-  k.lds = carve_bytes(N, elem_size(dtype)) + carve_bytes(N, 8) + carve_bytes(max_p, 8);
-  const bool lds_window = !c->hbm_window && k.lds <= (size_t)c->lds_limit;
-  if (!lds_window) k.lds = 0;
+  const auto lds = [&](bool lw) {
+    return lds_of(dtype, [&](auto t) { return ph::orth_carve<decltype(t)>(CarveCount(), N, max_p, lw, false); });
+  };
+  const bool lds_window = !c->hbm_window && lds(true) <= (size_t)c->lds_limit;
+  k.lds = lds(lds_window);
   k.window = k.second = lds_window ? PH_PLAN_LDS : PH_PLAN_HBM;
   k.block = kBlockWide;
 }
@@ -843,9 +836,11 @@ void plan_orth_powers(const ph_ctx* c, int dtype, int N, int max_p, Plan* pl) {
 int plan_qo_orth_select(const ph_ctx* c, int dtype, int N, int max_p, Plan* pl) {
   if (max_p < 2) return fail(PH_E_ARG, "ph_qo_orth_select: max_p=%d must be >= 2", max_p);
   KernelPlan& k = pl->k[0];
-  const size_t sz = elem_size(dtype);
-  const bool lds_window = !c->hbm_window && ph::qo_orth_select_lds_bytes(N, sz, max_p, true) <= (size_t)c->lds_limit;
-  k.lds = ph::qo_orth_select_lds_bytes(N, sz, max_p, lds_window);
+  const auto lds = [&](bool lw) {
+    return lds_of(dtype, [&](auto t) { return ph::orth_carve<decltype(t)>(CarveCount(), N, max_p, lw, true); });
+  };
+  const bool lds_window = !c->hbm_window && lds(true) <= (size_t)c->lds_limit;
+  k.lds = lds(lds_window);
   k.window = k.second = lds_window ? PH_PLAN_LDS : PH_PLAN_HBM;
   k.block = kBlockWide;
   return PH_OK;
@@ -891,8 +886,9 @@ int prepare_mobius(ph_ctx* c, int max_p, const int** d_off, const int** d_d, con
 // k_fold_sums: longer windows are folded from HBM / L2.
 void plan_fold_sums(const ph_ctx* c, int dtype, int N, Plan* pl) {
   KernelPlan& k = pl->k[0];
-  const bool lds_window = !c->hbm_window && carve_bytes(N, elem_size(dtype)) <= (size_t)c->lds_limit;
-  k.lds = lds_window ? carve_bytes(N, elem_size(dtype)) : 0;
+  const size_t staged = lds_of(dtype, [&](auto t) { return ph::stage_carve<decltype(t)>(CarveCount(), N); });
+  const bool lds_window = !c->hbm_window && staged <= (size_t)c->lds_limit;
+  k.lds = lds_window ? staged : 0;
   k.window = lds_window ? PH_PLAN_LDS : PH_PLAN_HBM;
   k.block = kBlock;
 }
@@ -2057,7 +2053,7 @@ int ph_tile_sum(ph_ctx* c, const double* wts, int64_t W, int N, const int32_t* p
   const int *d_p, *d_keep, *d_off;
   int stride;
   PH_TRY(qo_tables(c, p_list, keep, n_p, &d_p, &d_keep, &d_off, &stride));
-  const size_t lds = carve_bytes(stride, 8);
+  const size_t lds = ph::stage_carve<double>(CarveCount(), stride).bytes;
   PH_TRY(check_lds(c, lds, N, "ph_tile_sum"));
   Stage st(c, flags);
   const void* dw;
@@ -2220,7 +2216,7 @@ int ph_qo_feasible(ph_ctx* c, int dtype, int N, int max_length, int kcap, int* o
   if (max_length < 0) max_length = N / 3;
   size_t lds;
   int placement;
-  if (qo_lds_layout(c, elem_size(dtype), N, max_length, kcap, &lds, &placement) == PH_OK) *ok = 1;
+  if (qo_lds_layout(c, dtype, N, max_length, kcap, &lds, &placement) == PH_OK) *ok = 1;
   return PH_OK;
 }
 

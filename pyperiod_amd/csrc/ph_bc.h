@@ -17,6 +17,33 @@ struct CandCtl {
   int nsurv;
 };
 
+template <typename T>
+struct BcLds {
+  T* work;
+  T* buf;
+  double* red;
+  double* wbest;
+  int* wbestp;
+  int* cand_q;
+  double* cand_hi;
+  CandCtl* ctl;
+  size_t bytes;
+};
+template <typename T, class C>
+__host__ __device__ __forceinline__ BcLds<T> bc_carve(C cv, int N, bool lw, bool buf_lds) {
+  BcLds<T> L;
+  L.work = lw ? cv.template take<T>(N + kPad) : nullptr;
+  L.buf = buf_lds ? cv.template take<T>(N) : nullptr;
+  L.red = cv.template take<double>(kRedDoubles);
+  L.wbest = cv.template take<double>(kMaxWaves);
+  L.wbestp = cv.template take<int>(kMaxWaves);
+  L.cand_q = cv.template take<int>(kCandCap);
+  L.cand_hi = cv.template take<double>(kCandCap);
+  L.ctl = cv.template take<CandCtl>(1);
+  L.bytes = cv.off;
+  return L;
+}
+
 template <typename T, bool LW>
 __global__ __launch_bounds__(kBlockWide) __attribute__((amdgpu_waves_per_eu(PH_STEP1_WAVES, 8))) void k_best_correlation(const T* __restrict__ x, int N, int num,
                                                              int max_length, double ratio, unsigned flags,
@@ -28,16 +55,13 @@ __global__ __launch_bounds__(kBlockWide) __attribute__((amdgpu_waves_per_eu(PH_S
                                                              T* __restrict__ bases_out,
                                                              int* __restrict__ status_out) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  Carve cv(smem);
-  T* work = window_buf<T, LW>(cv, gwin, N + kPad);
   const bool general = flags & (kTrunc | kOrth);
-  T* buf = !general ? nullptr : gbuf ? gbuf + (int64_t)blockIdx.x * N : cv.take<T>(N);
-  double* red = cv.take<double>(kRedDoubles);
-  double* wbest = cv.take<double>(kMaxWaves);
-  int* wbestp = cv.take<int>(kMaxWaves);
-  int* cand_q = cv.take<int>(kCandCap);
-  double* cand_hi = cv.take<double>(kCandCap);
-  CandCtl* ctl = cv.take<CandCtl>(1);
+  const BcLds<T> L = bc_carve<T>(Carve(smem), N, LW, general && !gbuf);
+  T* work = window_buf<T, LW>(L.work, gwin, N + kPad);
+  T* buf = !general ? nullptr : second_buf(L.buf, gbuf, N);
+  double *red = L.red, *wbest = L.wbest, *cand_hi = L.cand_hi;
+  int *wbestp = L.wbestp, *cand_q = L.cand_q;
+  CandCtl* ctl = L.ctl;
 
   const int64_t w = blockIdx.x;
   const int tid = threadIdx.x;
@@ -198,21 +222,42 @@ enum {
   BP_DOUBLES = 10
 };
 
+struct BcPairLds {
+  f2* pw;
+  double* stg;
+  double* red;
+  double* wbest;
+  int* wbestp;
+  int* list;
+  int* ctl;
+  double* st;
+  size_t bytes;
+};
+template <class C>
+__host__ __device__ __forceinline__ BcPairLds bc_pair_carve(C cv, int N) {
+  BcPairLds L;
+  L.pw = cv.template take<f2>(N + kPad);
+  L.stg = cv.template take<double>(N + kPad);
+  L.red = cv.template take<double>(kRedDoubles);
+  L.wbest = cv.template take<double>(kMaxWaves);
+  L.wbestp = cv.template take<int>(kMaxWaves);
+  L.list = cv.template take<int>(2 * kPairListCap);
+  L.ctl = cv.template take<int>(BP_WORDS);
+  L.st = cv.template take<double>(BP_DOUBLES);
+  L.bytes = cv.off;
+  return L;
+}
+
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_WAVES, 8))) void k_best_correlation_pair(
     const double* __restrict__ x, int W, int N, int num, int max_length, double ratio, const PGeom* __restrict__ geom,
     const PGeomF* __restrict__ geomf, const PassPlan* __restrict__ plan, int n_pass, double* __restrict__ gres,
     uint32_t* __restrict__ periods_out, double* __restrict__ norms_out, double* __restrict__ bases_out,
     int* __restrict__ status_out) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  Carve cv(smem);
-  f2* pw = cv.take<f2>(N + kPad);
-  double* stg = cv.take<double>(N + kPad);
-  double* red = cv.take<double>(kRedDoubles);
-  double* wbest = cv.take<double>(kMaxWaves);
-  int* wbestp = cv.take<int>(kMaxWaves);
-  int* list = cv.take<int>(2 * kPairListCap);
-  int* ctl = cv.take<int>(BP_WORDS);
-  double* st = cv.take<double>(BP_DOUBLES);
+  const BcPairLds L = bc_pair_carve(Carve(smem), N);
+  f2* pw = L.pw;
+  double *stg = L.stg, *red = L.red, *wbest = L.wbest, *st = L.st;
+  int *wbestp = L.wbestp, *list = L.list, *ctl = L.ctl;
 
   const int tid = threadIdx.x;
   const int lane = tid & (kWave - 1);

@@ -33,18 +33,41 @@ __device__ __forceinline__ double bf_mag2(double re, double im, int e) {
   return r * r + i * i;
 }
 
+// LDS of the three spectrum kernels: the staged window (k_bf_spectrum, when it is in LDS) or the complex work array of
+// n points (k_bf_fft: n = L, k_bf_chirp: n = M), then the slots of the peak reduction.
+template <typename T>
+struct BfSpectrumLds {
+  T* stage;
+  double* re;
+  double* im;
+  double* wbest;
+  int* wbestp;
+  size_t bytes;
+};
+template <typename T, class C>
+__host__ __device__ __forceinline__ BfSpectrumLds<T> bf_spectrum_carve(C cv, size_t stage_len, size_t n) {
+  BfSpectrumLds<T> L;
+  L.stage = stage_len ? cv.template take<T>(stage_len) : nullptr;
+  L.re = n ? cv.template take<double>(n) : nullptr;
+  L.im = n ? cv.template take<double>(n) : nullptr;
+  L.wbest = cv.template take<double>(kMaxWaves);
+  L.wbestp = cv.template take<int>(kMaxWaves);
+  L.bytes = cv.off;
+  return L;
+}
+
 template <typename T, bool LW>
 __global__ __launch_bounds__(kBfBlock) void k_bf_spectrum(const T* __restrict__ res, int N, int L,
                                                           const double2* __restrict__ tw,
                                                           const int* __restrict__ status,
                                                           double* __restrict__ part_m2, int* __restrict__ part_k) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  Carve cv(smem);
+  const BfSpectrumLds<T> lds = bf_spectrum_carve<T>(Carve(smem), LW ? N : 0, 0);
   const int64_t w = blockIdx.y;
   const T* xs = res + w * (int64_t)N;  // LW == false: every thread walks the residual in HBM / L2 (broadcast reads)
-  T* stage = LW ? cv.take<T>(N) : nullptr;
-  double* wbest = cv.take<double>(kMaxWaves);
-  int* wbestp = cv.take<int>(kMaxWaves);
+  T* stage = lds.stage;
+  double* wbest = lds.wbest;
+  int* wbestp = lds.wbestp;
   const int chunk = blockIdx.x, nchunk = gridDim.x;
   if (status[w] != 0) return;  // the reference has raised for this window already
   const int tid = threadIdx.x, lane = tid & (kWave - 1);
@@ -164,11 +187,9 @@ __global__ __launch_bounds__(kBlockWide) void k_bf_fft(const T* __restrict__ res
                                                        const int* __restrict__ status,
                                                        double* __restrict__ part_m2, int* __restrict__ part_k) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  Carve cv(smem);
-  double* re = cv.take<double>(L);
-  double* im = cv.take<double>(L);
-  double* wbest = cv.take<double>(kMaxWaves);
-  int* wbestp = cv.take<int>(kMaxWaves);
+  const BfSpectrumLds<T> lds = bf_spectrum_carve<T>(Carve(smem), 0, L);
+  double *re = lds.re, *im = lds.im, *wbest = lds.wbest;
+  int* wbestp = lds.wbestp;
   const int64_t w = blockIdx.x;
   if (status[w] != 0) return;  // the reference has raised for this window already
   const int M0 = N < L ? N : L;  // rfft(data, L) truncates or zero-pads to L samples
@@ -199,11 +220,9 @@ __global__ __launch_bounds__(kBlockWide) void k_bf_chirp(const T* __restrict__ r
                                                          const int* __restrict__ status,
                                                          double* __restrict__ part_m2, int* __restrict__ part_k) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  Carve cv(smem);
-  double* re = cv.take<double>(M);
-  double* im = cv.take<double>(M);
-  double* wbest = cv.take<double>(kMaxWaves);
-  int* wbestp = cv.take<int>(kMaxWaves);
+  const BfSpectrumLds<T> lds = bf_spectrum_carve<T>(Carve(smem), 0, M);
+  double *re = lds.re, *im = lds.im, *wbest = lds.wbest;
+  int* wbestp = lds.wbestp;
   const int64_t w = blockIdx.x;
   if (status[w] != 0) return;
   const int M0 = N < L ? N : L;
@@ -250,6 +269,23 @@ __global__ __launch_bounds__(kBlockWide) void k_bf_chirp(const T* __restrict__ r
   bf_store_peak(re, im, L >> 1, e, wbest, wbestp, w, part_m2, part_k);
 }
 
+template <typename T>
+struct BfUpdateLds {
+  T* work;
+  T* buf;
+  double* red;
+  size_t bytes;
+};
+template <typename T, class C>
+__host__ __device__ __forceinline__ BfUpdateLds<T> bf_update_carve(C cv, int N, bool lw, bool buf_lds) {
+  BfUpdateLds<T> L;
+  L.work = lw ? cv.template take<T>(N) : nullptr;
+  L.buf = buf_lds ? cv.template take<T>(N) : nullptr;
+  L.red = cv.template take<double>(kRedDoubles);
+  L.bytes = cv.off;
+  return L;
+}
+
 template <typename T, bool LW>
 __global__ __launch_bounds__(kBlockWide) void k_bf_update(T* __restrict__ res, int N, int L, int num, int it,
                                                           unsigned flags, Tables tb, T* __restrict__ gbuf, int nchunk,
@@ -259,12 +295,12 @@ __global__ __launch_bounds__(kBlockWide) void k_bf_update(T* __restrict__ res, i
                                                           double* __restrict__ powers_out, T* __restrict__ bases_out,
                                                           int* __restrict__ status) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  Carve cv(smem);
+  const BfUpdateLds<T> lds = bf_update_carve<T>(Carve(smem), N, LW, !gbuf);
   const int64_t w = blockIdx.x;
   // LW == false: the residual is projected where it lives (the HBM workspace `res`)
-  T* work = LW ? cv.take<T>(N) : res + w * (int64_t)N;
-  T* buf = gbuf ? gbuf + (int64_t)blockIdx.x * N : cv.take<T>(N);
-  double* red = cv.take<double>(kRedDoubles);
+  T* work = LW ? lds.work : res + w * (int64_t)N;
+  T* buf = second_buf(lds.buf, gbuf, N);
+  double* red = lds.red;
   const int tid = threadIdx.x;
   T* brow = bases_out + (w * num + it) * (int64_t)N;
   bool dead = status[w] != 0;

@@ -1103,6 +1103,11 @@ __device__ __forceinline__ void load_window(const T* __restrict__ g, T* __restri
 }
 
 // Dynamic LDS carve-up; every piece starts 16-byte aligned (guide: Guideline 17).
+// A kernel states its layout once, as a function x_carve(C cv, shape...) that takes the pieces in order, fills a plain
+// struct of pointers and records bytes = the end of the layout.  The kernel runs it with Carve(smem); the host sizes
+// the launch by running the same function with CarveCount() and reading .bytes.  A piece that lies over others is taken
+// from a copy of the carver (at(): a copy moved to an offset), and bytes is the larger of the ends.  (k_sweep and
+// k_mbest_step1 take their pieces in the kernel body and the host counts a mirror of them: see there.)
 struct Carve {
   unsigned char* base;
   size_t off;
@@ -1113,21 +1118,44 @@ struct Carve {
     off += (n * sizeof(U) + 15) & ~size_t(15);
     return p;
   }
+  __device__ Carve at(size_t o) const {
+    Carve c(base);
+    c.off = o;
+    return c;
+  }
 };
 
 __host__ __device__ inline size_t carve_bytes(size_t n, size_t elem) { return (n * elem + 15) & ~size_t(15); }
 
-// The window buffer of workgroup blockIdx.x: LDS normally; for windows longer than the LDS
-// (LW == false) a slice of the HBM workspace `gwin` (stride win_stride(len) elements).
+// Carve without memory: every take returns nullptr and advances `off` as Carve does.
+struct CarveCount {
+  size_t off = 0;
+  template <typename U>
+  __host__ __device__ U* take(size_t n) {
+    off += carve_bytes(n, sizeof(U));
+    return nullptr;
+  }
+  __host__ __device__ CarveCount at(size_t o) const { return CarveCount{o}; }
+};
+
+// The window buffer of workgroup blockIdx.x: LDS normally (the piece `lds` of the kernel's carve); for windows longer
+// than the LDS (LW == false) a slice of the HBM workspace `gwin` (stride win_stride(len) elements).
 __host__ __device__ inline size_t win_stride(size_t len) { return (len + 3) & ~size_t(3); }
 
 template <typename T, bool LW>
-__device__ __forceinline__ T* window_buf(Carve& cv, T* gwin, size_t len) {
+__device__ __forceinline__ T* window_buf(T* lds, T* gwin, size_t len) {
   if constexpr (LW) {
-    return cv.take<T>(len);
+    return lds;
   } else {
     return gwin + (size_t)blockIdx.x * win_stride(len);
   }
+}
+
+// The second window-sized buffer (materialised projections) of workgroup blockIdx.x: its slice of the HBM workspace
+// `gbuf` when the host put it there, otherwise the piece `lds` of the kernel's carve.
+template <typename T>
+__device__ __forceinline__ T* second_buf(T* lds, T* gbuf, size_t len) {
+  return gbuf ? gbuf + (int64_t)blockIdx.x * len : lds;
 }
 
 constexpr int kRedDoubles = 2 * kMaxWaves;

@@ -15,22 +15,6 @@ namespace ph {
 constexpr int kFitMaxPeriod = 1 << 20;  // qo_offdiag's index arithmetic holds for periods below 2^20
 constexpr int kFitCtl = 4;              // control words: status, rows, -, k_qo_fit_win's zero-diagonal flag
 
-// Dynamic LDS of k_qo_fit, the one statement of its layout (qo_fit_carve carves in this order; the host plans with it).
-// Bookkeeping, then the solver's seven vectors + the sample counts, one slot per dictionary row and one per block.  The
-// divisor bitset over 1 .. max_period is only alive during the row bookkeeping and overlays the vectors, so the size
-// depends on kcap alone unless the bitset is the larger of the two.  The window never enters LDS.
-__host__ __device__ inline size_t qo_fit_fixed_bytes() {
-  return carve_bytes(kRedDoubles, 8) + carve_bytes(6 * kMaxWaves, 8) + 4 * carve_bytes(kQoMaxBlocks + 1, 4) +
-         2 * carve_bytes(kQoMaxBlocks, 4) + carve_bytes(2 * kQoPairTab * kQoPairTab, 4) + carve_bytes(kFitCtl, 4);
-}
-__host__ __device__ inline size_t qo_fit_vector_bytes(int kcap) {
-  const size_t kv = (size_t)kcap + kQoMaxBlocks;
-  return 7 * carve_bytes(kv, 8) + carve_bytes(kv, 4);
-}
-__host__ __device__ inline size_t qo_fit_lds_bytes(int kcap, int max_period) {
-  const size_t vec = qo_fit_vector_bytes(kcap), seen = carve_bytes((size_t)(max_period + 32) / 32, 4);
-  return qo_fit_fixed_bytes() + (vec > seen ? vec : seen);
-}
 // Threads per workgroup: small dictionaries take small workgroups, so that several share a CU.
 __host__ __device__ inline int qo_fit_block(int kcap) { return kcap > 512 ? 1024 : kcap > 128 ? 512 : 256; }
 
@@ -59,31 +43,45 @@ struct QoFitLds {
   uint32_t* seen;  // the divisor bitset (bookkeeping only); the solver's vectors take its place
   QoCgVectors v;   // solver layout; rv starts as the right-hand side (QOPeriods.py:782), dv = 1 / diagonal
   int* trm;        // samples of the row's residue
+  double* u;       // k_qo_fit_win: the staging vector of u_len doubles when it lives in LDS
+  size_t bytes;
 };
-__device__ __forceinline__ QoFitLds qo_fit_carve(unsigned char* smem, int kcap) {
-  Carve cv(smem);
+// Dynamic LDS of k_qo_fit and k_qo_fit_win, the one statement of its layout (the kernels carve with it, the host counts
+// with it).  Bookkeeping, then the solver's seven vectors + the sample counts, one slot per dictionary row and one per
+// block.  The divisor bitset over 1 .. max_period is only alive during the row bookkeeping and lies over the vectors,
+// so the size depends on kcap alone unless the bitset is the larger of the two.  The window never enters LDS;
+// k_qo_fit_win's u sits behind the larger of the two when the host places it in LDS (u_len = N, otherwise 0).
+template <class C>
+__host__ __device__ __forceinline__ QoFitLds qo_fit_carve(C cv, int kcap, int max_period, size_t u_len = 0) {
   QoFitLds L;
-  L.red = cv.take<double>(kRedDoubles);
-  L.red3 = cv.take<double>(6 * kMaxWaves);
-  L.bper = cv.take<int>(kQoMaxBlocks + 1);
-  L.bkeep = cv.take<int>(kQoMaxBlocks + 1);
-  L.boff = cv.take<int>(kQoMaxBlocks + 1);
-  L.ioff = cv.take<int>(kQoMaxBlocks + 1);
-  L.blg = cv.take<int>(kQoMaxBlocks);
-  L.bsteps = cv.take<int>(kQoMaxBlocks);
-  L.ptab = cv.take<int>(2 * kQoPairTab * kQoPairTab);
-  L.ctl = cv.take<int>(kFitCtl);
-  L.seen = reinterpret_cast<uint32_t*>(cv.base + cv.off);
+  L.red = cv.template take<double>(kRedDoubles);
+  L.red3 = cv.template take<double>(6 * kMaxWaves);
+  L.bper = cv.template take<int>(kQoMaxBlocks + 1);
+  L.bkeep = cv.template take<int>(kQoMaxBlocks + 1);
+  L.boff = cv.template take<int>(kQoMaxBlocks + 1);
+  L.ioff = cv.template take<int>(kQoMaxBlocks + 1);
+  L.blg = cv.template take<int>(kQoMaxBlocks);
+  L.bsteps = cv.template take<int>(kQoMaxBlocks);
+  L.ptab = cv.template take<int>(2 * kQoPairTab * kQoPairTab);
+  L.ctl = cv.template take<int>(kFitCtl);
+  C sn = cv.at(cv.off);
+  L.seen = sn.template take<uint32_t>((size_t)(max_period + 32) / 32);
   const int kv = kcap + kQoMaxBlocks;
-  L.v.xv = cv.take<double>(kv);
-  L.v.rv = cv.take<double>(kv);
-  L.v.pv = cv.take<double>(kv);
-  L.v.qv = cv.take<double>(kv);
-  L.v.zv = cv.take<double>(kv);
-  L.v.wv_ = cv.take<double>(kv);
-  L.v.dv = cv.take<double>(kv);
-  L.trm = cv.take<int>(kv);
+  L.v.xv = cv.template take<double>(kv);
+  L.v.rv = cv.template take<double>(kv);
+  L.v.pv = cv.template take<double>(kv);
+  L.v.qv = cv.template take<double>(kv);
+  L.v.zv = cv.template take<double>(kv);
+  L.v.wv_ = cv.template take<double>(kv);
+  L.v.dv = cv.template take<double>(kv);
+  L.trm = cv.template take<int>(kv);
+  C uc = cv.at(cv.off > sn.off ? cv.off : sn.off);
+  L.u = u_len ? uc.template take<double>(u_len) : nullptr;
+  L.bytes = uc.off;
   return L;
+}
+__host__ __device__ inline size_t qo_fit_lds_bytes(int kcap, int max_period) {
+  return qo_fit_carve(CarveCount(), kcap, max_period).bytes;
 }
 
 // The calling workgroup's window: its slices of the arguments.
@@ -238,7 +236,7 @@ __global__ __launch_bounds__(1024) void k_qo_fit(const T* __restrict__ x, int N,
                                                  int* __restrict__ keeps_out, double* __restrict__ weights_out,
                                                  T* __restrict__ resid_out, int* __restrict__ status_out) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const QoFitLds L = qo_fit_carve(smem, kcap);
+  const QoFitLds L = qo_fit_carve(Carve(smem), kcap, max_period);
   int *const bper = L.bper, *const bkeep = L.bkeep, *const boff = L.boff, *const ptab = L.ptab, *const trm = L.trm;
   double* const rv = L.v.rv;
   const int tid = threadIdx.x;
@@ -330,9 +328,8 @@ __global__ __launch_bounds__(1024) void k_qo_fit(const T* __restrict__ x, int N,
 // LDS when that still fits the workgroup's limit and otherwise in an HBM workspace of N doubles per workgroup; win is
 // shared by the whole grid and is always read from HBM / L2.
 // ======================================================================================
-__host__ __device__ inline size_t qo_fit_win_u_offset(int kcap, int max_period) { return qo_fit_lds_bytes(kcap, max_period); }
 __host__ __device__ inline size_t qo_fit_win_lds_bytes(int N, int kcap, int max_period, bool u_in_lds) {
-  return qo_fit_win_u_offset(kcap, max_period) + (u_in_lds ? carve_bytes((size_t)N, 8) : 0);
+  return qo_fit_carve(CarveCount(), kcap, max_period, u_in_lds ? N : 0).bytes;
 }
 // Threads per workgroup: the staging pass is one element of u per thread and step, so long windows take wide workgroups.
 __host__ __device__ inline int qo_fit_win_block(int kcap, int N) {
@@ -362,7 +359,7 @@ __global__ __launch_bounds__(1024) void k_qo_fit_win(const T* __restrict__ x, in
                                                      int* __restrict__ keeps_out, double* __restrict__ weights_out,
                                                      T* __restrict__ resid_out, int* __restrict__ status_out) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const QoFitLds L = qo_fit_carve(smem, kcap);
+  const QoFitLds L = qo_fit_carve(Carve(smem), kcap, max_period, ULDS ? N : 0);
   int *const bper = L.bper, *const bkeep = L.bkeep, *const boff = L.boff, *const ioff = L.ioff, *const ctl = L.ctl;
   double *const rv = L.v.rv, *const dv = L.v.dv;
   const int tid = threadIdx.x;
@@ -371,7 +368,7 @@ __global__ __launch_bounds__(1024) void k_qo_fit_win(const T* __restrict__ x, in
   const int nw = blockDim.x >> 6;
   double* u;
   if constexpr (ULDS) {
-    u = reinterpret_cast<double*>(smem + qo_fit_win_u_offset(kcap, max_period));
+    u = L.u;
   } else {
     u = ws + blockIdx.x * (int64_t)N;
   }
@@ -617,13 +614,9 @@ __global__ __launch_bounds__(kWave) void k_ram_select_ref(const double* __restri
 //            once the powers are final), then base -= project(base, p / f) for the sub-periods of the orth tables in
 //            their order, then ||base|| / sqrt(N) / sqrt(p)
 // All arithmetic is in double whatever T is; the window is only read.  LW: window, work arrays and reductions in LDS
-// (qo_orth_select_lds_bytes: k_orth_powers' layout + the reduction slots); otherwise the window is read from HBM / L2
+// (orth_carve: k_orth_powers' layout + the reduction slots); otherwise the window is read from HBM / L2
 // and the work arrays are N + max_p doubles per workgroup of the workspace `gws`.
 // ======================================================================================
-__host__ __device__ inline size_t qo_orth_select_lds_bytes(int N, size_t elem, int max_p, bool lds_window) {
-  const size_t red = carve_bytes(kRedDoubles, 8) + carve_bytes(kMaxWaves, 8) + carve_bytes(kMaxWaves, 4);
-  return (lds_window ? carve_bytes(N, elem) + carve_bytes(N, 8) + carve_bytes(max_p, 8) : 0) + red;
-}
 
 // Row-order sum of residue j over n rows of a window of T, in double: column_sum's order for either element type.
 template <typename T>
@@ -672,23 +665,21 @@ __global__ __launch_bounds__(kBlockWide) void k_qo_orth_select(const T* __restri
   const int64_t w = blockIdx.x;
   const int tid = threadIdx.x;
   const int nw = (blockDim.x + kWave - 1) / kWave;
-  Carve cv(smem);
+  const OrthLds<T> L = orth_carve<T>(Carve(smem), N, max_p, LW, true);
   const T* xs = x + w * (int64_t)N;
   double *r, *m;
   if constexpr (LW) {
-    T* stage = cv.take<T>(N);
-    r = cv.take<double>(N);
-    m = cv.take<double>(max_p);
-    load_window(xs, stage, N);
+    r = L.r;
+    m = L.m;
+    load_window(xs, L.stage, N);
     __syncthreads();
-    xs = stage;
+    xs = L.stage;
   } else {
     r = gws + w * ((int64_t)N + max_p);
     m = r + N;
   }
-  double* red = cv.take<double>(kRedDoubles);
-  double* wbest = cv.take<double>(kMaxWaves);
-  int* wbestp = cv.take<int>(kMaxWaves);
+  double *red = L.red, *wbest = L.wbest;
+  int* wbestp = L.wbestp;
 
   // ---- powers; each thread keeps the first maximum of its own q (ascending), keyed q + 1 (0 = none)
   double bv = -1.0;
@@ -768,13 +759,46 @@ __host__ __device__ inline int qo_extract_dcap(int ccap, int max_period) {
   const int d = ccap / 2 < max_period ? ccap / 2 : max_period;
   return d < 1 ? 1 : d;
 }
-__host__ __device__ inline size_t qo_extract_fixed_bytes() { return carve_bytes(kExtCtl, 4); }
+struct QoExtractWork {
+  double* cin;  // the concatenated input segments
+  double* acc;  // the output accumulators
+  double* uv;   // u_a^d of the current (d, a)
+  double* sv;   // sum_a u_a^d, then v
+  int* dl;      // the d shared by at least two periods, ascending
+  size_t bytes;
+};
+template <class C>
+__host__ __device__ __forceinline__ QoExtractWork qo_extract_work_carve(C wk, int ccap, int max_period) {
+  const int dcap = qo_extract_dcap(ccap, max_period);
+  const size_t wk0 = wk.off;
+  QoExtractWork L;
+  L.cin = wk.template take<double>(ccap);
+  L.acc = wk.template take<double>(ccap);
+  L.uv = wk.template take<double>(dcap);
+  L.sv = wk.template take<double>(dcap);
+  L.dl = wk.template take<int>(dcap);
+  L.bytes = wk.off - wk0;
+  return L;
+}
 __host__ __device__ inline size_t qo_extract_work_bytes(int ccap, int max_period) {
-  const size_t d = (size_t)qo_extract_dcap(ccap, max_period);
-  return 2 * carve_bytes((size_t)ccap, 8) + 2 * carve_bytes(d, 8) + carve_bytes(d, 4);
+  return qo_extract_work_carve(CarveCount(), ccap, max_period).bytes;
+}
+// LDS of k_qo_extract: the control words, then the working storage when it lives there
+struct QoExtractLds {
+  int* ctl;
+  QoExtractWork work;
+  size_t bytes;
+};
+template <class C>
+__host__ __device__ __forceinline__ QoExtractLds qo_extract_carve(C cv, int ccap, int max_period, bool work_in_lds) {
+  QoExtractLds L;
+  L.ctl = cv.template take<int>(kExtCtl);
+  L.work = work_in_lds ? qo_extract_work_carve(cv, ccap, max_period) : QoExtractWork{};
+  L.bytes = cv.off + L.work.bytes;
+  return L;
 }
 __host__ __device__ inline size_t qo_extract_lds_bytes(int ccap, int max_period, bool work_in_lds) {
-  return qo_extract_fixed_bytes() + (work_in_lds ? qo_extract_work_bytes(ccap, max_period) : 0);
+  return qo_extract_carve(CarveCount(), ccap, max_period, work_in_lds).bytes;
 }
 
 template <bool WL>
@@ -791,16 +815,15 @@ __global__ __launch_bounds__(kBlock) void k_qo_extract(const int* __restrict__ p
   const int lane = tid & (kWave - 1);
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nthr = blockDim.x;
-  Carve cv(smem);
-  int* ctl = cv.take<int>(kExtCtl);
-  const int dcap = qo_extract_dcap(ccap, max_period);
-  Carve wk(WL ? smem + qo_extract_fixed_bytes()
-              : reinterpret_cast<unsigned char*>(gws) + w * (int64_t)qo_extract_work_bytes(ccap, max_period));
-  double* cin = wk.take<double>(ccap);  // the concatenated input segments
-  double* acc = wk.take<double>(ccap);  // the output accumulators
-  double* uv = wk.take<double>(dcap);   // u_a^d of the current (d, a)
-  double* sv = wk.take<double>(dcap);   // sum_a u_a^d, then v
-  int* dl = wk.take<int>(dcap);         // the d shared by at least two periods, ascending
+  const QoExtractLds L = qo_extract_carve(Carve(smem), ccap, max_period, WL);
+  int* ctl = L.ctl;
+  // WL == false: the working storage is this workgroup's slice of the HBM workspace, carved the same way
+  const QoExtractWork wk = WL ? L.work
+                              : qo_extract_work_carve(Carve(reinterpret_cast<unsigned char*>(gws) +
+                                                            w * (int64_t)qo_extract_work_bytes(ccap, max_period)),
+                                                      ccap, max_period);
+  double *cin = wk.cin, *acc = wk.acc, *uv = wk.uv, *sv = wk.sv;
+  int* dl = wk.dl;
   int* soff = gidx + w * 2 * ((int64_t)pcap + 1);  // first element of segment a
   int* woff = soff + pcap + 1;                     // first weight of block a
   const int* per = periods + w * (int64_t)pcap;

@@ -65,6 +65,26 @@ __device__ __forceinline__ int mbest_book(int& row, int bestp, double best, int 
   return action;
 }
 
+// LDS bytes of k_mbest_step1 for the host.  The kernel spells its takes out itself (see there) and this is their count,
+// kept in step by hand: a piece added to one is added to the other.
+template <typename T>
+__host__ __device__ inline size_t step1_lds_bytes(int N, int num, int P, bool lw, bool buf_lds, bool small_means) {
+  CarveCount cv;
+  if (lw) cv.take<T>(N + kPad);         // work
+  if (buf_lds) cv.take<T>(N);           // buf
+  cv.take<double>(kRedDoubles);         // red
+  cv.take<double>(kMaxWaves);           // wbest
+  cv.take<int>(kMaxWaves);              // wbestp
+  cv.take<double>(num);                 // norms
+  cv.take<uint32_t>(num);               // periods
+  cv.take<uint32_t>((P + 31) / 32);     // skip
+  if (small_means) {
+    cv.take<T>(kPairSmallP);            // msm
+    cv.take<T>(kPairSplitW);            // prt
+  }
+  return cv.off;
+}
+
 template <typename T, bool LW>
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_WAVES, 8))) void k_mbest_step1(const T* __restrict__ x, int N, int num, int p_lo,
                                                         int p_hi, int gamma, unsigned flags, Tables tb,
@@ -77,8 +97,10 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
                                                         int* __restrict__ status_out,
                                                         int* __restrict__ sweeps_out, int small_means) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  // The takes are spelled out here, not run through a carve function as in the other kernels: with one, this kernel
+  // measured 1 % (long windows) to 5 % (trunc) slower (profiles/lds_layout).  The host counts them in step1_lds_bytes.
   Carve cv(smem);
-  T* work = window_buf<T, LW>(cv, gwin, N + kPad);
+  T* work = window_buf<T, LW>(LW ? cv.take<T>(N + kPad) : nullptr, gwin, N + kPad);
   const bool general = flags & (kTrunc | kOrth);
   T* buf = !general ? nullptr : gbuf ? gbuf + (int64_t)blockIdx.x * N : cv.take<T>(N);
   double* red = cv.take<double>(kRedDoubles);
@@ -304,6 +326,43 @@ __device__ __forceinline__ double pair_exact_part(const double* __restrict__ xs,
   return part;
 }
 
+// LDS of k_mbest_step1_pair: the pair window, one fp64 staging buffer, bookkeeping of two windows.
+struct Step1PairLds {
+  f2* pw;
+  double* stg;
+  double* red;
+  double* wbest;
+  int* wbestp;
+  double* norms;
+  uint32_t* periods;
+  uint32_t* skip;
+  int* list;
+  int* ctl;
+  double* dst2;
+  double* msm;  // means of a short winning period
+  double* prt;  // partial sums of split_row_means
+  size_t bytes;
+};
+template <class C>
+__host__ __device__ __forceinline__ Step1PairLds step1_pair_carve(C cv, int N, int num, int P) {
+  Step1PairLds L;
+  L.pw = cv.template take<f2>(N + kPad);
+  L.stg = cv.template take<double>(N + kPad);
+  L.red = cv.template take<double>(kRedDoubles);
+  L.wbest = cv.template take<double>(kMaxWaves);
+  L.wbestp = cv.template take<int>(kMaxWaves);
+  L.norms = cv.template take<double>(2 * num);
+  L.periods = cv.template take<uint32_t>(2 * num);
+  L.skip = cv.template take<uint32_t>(2 * ((P + 31) / 32));
+  L.list = cv.template take<int>(2 * kPairListCap);
+  L.ctl = cv.template take<int>(MP_WORDS);
+  L.dst2 = cv.template take<double>(MP_DOUBLES);
+  L.msm = cv.template take<double>(kPairSmallP);
+  L.prt = cv.template take<double>(kPairSplitW);
+  L.bytes = cv.off;
+  return L;
+}
+
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_WAVES, 8))) void k_mbest_step1_pair(
     const double* __restrict__ x, int W, int N, int num, int p_lo, int p_hi, int p_scr, int gamma,
     const int* __restrict__ fac_off, const int* __restrict__ fac_q, const PGeom* __restrict__ geom, const PGeomF* __restrict__ geomf, const double* __restrict__ radq, const PassPlan* __restrict__ plan, int n_pass,
@@ -314,22 +373,13 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
   // screen), or a negative number: no fold-once path (PH_PAIR_FOLD_ONCE=0)
   const bool fold_once = __double2hiint(thin_band) >= 0;  // (the sign bit, on the scalar unit)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  Carve cv(smem);
-  f2* pw = cv.take<f2>(N + kPad);
-  double* stg = cv.take<double>(N + kPad);
-  double* red = cv.take<double>(kRedDoubles);
-  double* wbest = cv.take<double>(kMaxWaves);
-  int* wbestp = cv.take<int>(kMaxWaves);
-  double* norms = cv.take<double>(2 * num);
-  uint32_t* periods = cv.take<uint32_t>(2 * num);
   const int P = p_hi - p_lo + 1;
   const int SK = (P + 31) / 32;
-  uint32_t* skip = cv.take<uint32_t>(2 * SK);
-  int* list = cv.take<int>(2 * kPairListCap);
-  int* ctl = cv.take<int>(MP_WORDS);
-  double* dst2 = cv.take<double>(MP_DOUBLES);
-  double* msm = cv.take<double>(kPairSmallP);  // means of a short winning period
-  double* prt = cv.take<double>(kPairSplitW);  // partial sums of split_row_means
+  const Step1PairLds L = step1_pair_carve(Carve(smem), N, num, P);
+  f2* pw = L.pw;
+  double *stg = L.stg, *red = L.red, *wbest = L.wbest, *norms = L.norms, *dst2 = L.dst2, *msm = L.msm, *prt = L.prt;
+  int *wbestp = L.wbestp, *list = L.list, *ctl = L.ctl;
+  uint32_t *periods = L.periods, *skip = L.skip;
 
   const int tid = threadIdx.x;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -874,6 +924,42 @@ __device__ __forceinline__ void expand_row(const T* __restrict__ src, int p, T* 
   }
 }
 
+template <typename T>
+struct Step2Lds {
+  T* rowbuf;
+  T* buf;
+  double* red;
+  double* norms;
+  uint32_t* periods;
+  double* fvals;
+  int* ffac;
+  PGeom* fgeom;    // per wavefront: geometry of the fold of a periodic row
+  int* fa;         // divisor list of row k's period: tb.fac_q[fa[k] .. fb[k])
+  int* fb;
+  int* slot;       // compact row of logical row k: rows + slot[k] * row_stride
+  int* ffac_next;  // divisor list of the staged row
+  size_t bytes;
+};
+// max_fac = most proper divisors any candidate period has (PGeom / divisor slots of step 2)
+template <typename T, class C>
+__host__ __device__ __forceinline__ Step2Lds<T> step2_carve(C cv, int N, int num, int max_fac, bool lw, bool buf_lds) {
+  Step2Lds<T> L;
+  L.rowbuf = lw ? cv.template take<T>(N + kPad) : nullptr;
+  L.buf = buf_lds ? cv.template take<T>(N) : nullptr;
+  L.red = cv.template take<double>(kRedDoubles);
+  L.norms = cv.template take<double>(num);
+  L.periods = cv.template take<uint32_t>(num);
+  L.fvals = cv.template take<double>(max_fac > 0 ? max_fac : 1);
+  L.ffac = cv.template take<int>(max_fac > 0 ? max_fac : 1);
+  L.fgeom = cv.template take<PGeom>(kMaxWaves);
+  L.fa = cv.template take<int>(num);
+  L.fb = cv.template take<int>(num);
+  L.slot = cv.template take<int>(num);
+  L.ffac_next = cv.template take<int>(max_fac > 64 ? max_fac : 64);
+  L.bytes = cv.off;
+  return L;
+}
+
 template <typename T, bool LW>
 __global__ __launch_bounds__(kBlockWide) __attribute__((amdgpu_waves_per_eu(PH_STEP1_WAVES, 8))) void k_mbest_step2(int N, int num, int gamma, int stale_p, unsigned flags,
                                                         Tables tb, const PGeom* __restrict__ geom, int max_fac,
@@ -884,19 +970,13 @@ __global__ __launch_bounds__(kBlockWide) __attribute__((amdgpu_waves_per_eu(PH_S
                                                         const int* __restrict__ status, T* __restrict__ rows_io,
                                                         int row_stride) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  Carve cv(smem);
-  T* rowbuf = window_buf<T, LW>(cv, gwin, N + kPad);
-  T* buf = gbuf ? gbuf + (int64_t)blockIdx.x * N : cv.take<T>(N);
-  double* red = cv.take<double>(kRedDoubles);
-  double* norms = cv.take<double>(num);
-  uint32_t* periods = cv.take<uint32_t>(num);
-  double* fvals = cv.take<double>(max_fac > 0 ? max_fac : 1);
-  int* ffac = cv.take<int>(max_fac > 0 ? max_fac : 1);
-  PGeom* fgeom = cv.take<PGeom>(kMaxWaves);  // per wavefront: geometry of the fold of a periodic row
-  int* fa = cv.take<int>(num);               // divisor list of row k's period: tb.fac_q[fa[k] .. fb[k])
-  int* fb = cv.take<int>(num);
-  int* slot = cv.take<int>(num);             // compact row of logical row k: rows + slot[k] * row_stride
-  int* ffac_next = cv.take<int>(max_fac > 64 ? max_fac : 64);  // divisor list of the staged row
+  const Step2Lds<T> L = step2_carve<T>(Carve(smem), N, num, max_fac, LW, !gbuf);
+  T* rowbuf = window_buf<T, LW>(L.rowbuf, gwin, N + kPad);
+  T* buf = second_buf(L.buf, gbuf, N);
+  double *red = L.red, *norms = L.norms, *fvals = L.fvals;
+  uint32_t* periods = L.periods;
+  PGeom* fgeom = L.fgeom;
+  int *ffac = L.ffac, *fa = L.fa, *fb = L.fb, *slot = L.slot, *ffac_next = L.ffac_next;
 
   const int64_t w = blockIdx.x;
   const int tid = threadIdx.x;

@@ -8,6 +8,20 @@ namespace ph {
 // ======================================================================================
 // QOPeriods building blocks (QOPeriods.py:779-795): W = A x and A^T w for natural-basis A.
 // ======================================================================================
+// LDS of k_fold_sums (the staged window) and of k_tile_sum (one window's weights): a single array.
+template <typename U>
+struct StageLds {
+  U* stage;
+  size_t bytes;
+};
+template <typename U, class C>
+__host__ __device__ __forceinline__ StageLds<U> stage_carve(C cv, size_t n) {
+  StageLds<U> L;
+  L.stage = cv.template take<U>(n);
+  L.bytes = cv.off;
+  return L;
+}
+
 template <typename T, bool LW>
 __global__ __launch_bounds__(kBlock) void k_fold_sums(const T* __restrict__ x, int N,
                                                       const int* __restrict__ p_list,
@@ -18,8 +32,7 @@ __global__ __launch_bounds__(kBlock) void k_fold_sums(const T* __restrict__ x, i
   const int64_t w = blockIdx.x;
   const T* xs = x + w * (int64_t)N;  // LW == false: a window longer than the LDS is folded straight from HBM / L2
   if constexpr (LW) {
-    Carve cv(smem);
-    T* stage = cv.take<T>(N);
+    T* stage = stage_carve<T>(Carve(smem), N).stage;
     load_window(xs, stage, N);
     __syncthreads();
     xs = stage;
@@ -40,7 +53,7 @@ __global__ __launch_bounds__(kBlock) void k_tile_sum(const double* __restrict__ 
                                                      const int* __restrict__ row_off, int n_p, int stride,
                                                      T* __restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  double* ws = reinterpret_cast<double*>(smem);
+  double* ws = stage_carve<double>(Carve(smem), stride).stage;
   const int64_t w = blockIdx.x;
   for (int i = threadIdx.x; i < stride; i += blockDim.x) ws[i] = wts[w * (int64_t)stride + i];
   __syncthreads();
@@ -354,6 +367,66 @@ __device__ __forceinline__ QoCgResult qo_cg(const QoCgVectors& V, int KS, int K,
 // TRUNC (trunc_to_integer_multiple): only the selection changes -- the gamma norm of the trunc projection
 // (wave_sweep_trunc); the solve ignores trunc like the reference's _update_weights.  The plain instantiations compile
 // to the code they had before the parameter existed (everything TRUNC touches is `if constexpr`).
+// LDS of k_qo_find: the residual window (when it lives in LDS), bookkeeping, the pair table, the weights, and the six
+// work vectors + sample counts of the conjugate-gradient solve (one slot per dictionary row and one per block: block
+// b's k_b entries start at slot boff[b] + b and are followed by one zero, qo_offdiag clamps indices past the kept rows
+// onto it).  The work vectors only live during a solve, when the residual window is dead (it is rebuilt from the data
+// and the reconstruction afterwards): with `overlay` they lie over the window buffer, which leaves room for a second
+// workgroup on the CU; otherwise they sit behind the weights.
+template <typename T>
+struct QoFindLds {
+  T* work;
+  double* red;
+  double* wbest;
+  int* wbestp;
+  int* bper;       // period of dictionary block b
+  int* bkeep;      // rows kept for it
+  int* boff;       // first row of block b
+  double* bnorm;
+  uint32_t* seen;  // running divisor set R (QOPeriods.py:832-835)
+  int* ptab;       // (a, b): {p_b / gcd(p_a, p_b), p_a mod p_b}
+  double* red3;    // wave partials of the solver's fused reduction (two parities)
+  int* blg;        // log2 of the lanes that share a row of block b in the product
+  int* ioff;       // first work item of block b
+  QoCgVectors v;   // xv persists: earlier rows start from their last values; dv = 1 / samples of the row's residue
+  int* trm;        // samples of the row's residue
+  size_t window;   // bytes of the window piece (0: it lives in HBM) and of the work vectors: the host's overlay rule
+  size_t solver;
+  size_t bytes;
+};
+template <typename T, class C>
+__host__ __device__ __forceinline__ QoFindLds<T> qo_find_carve(C cv, int N, int p_hi, int kcap, bool lw, bool overlay) {
+  QoFindLds<T> L;
+  L.work = lw ? cv.template take<T>(N + kPad) : nullptr;
+  L.window = cv.off;
+  L.red = cv.template take<double>(kRedDoubles);
+  L.wbest = cv.template take<double>(kMaxWaves);
+  L.wbestp = cv.template take<int>(kMaxWaves);
+  L.bper = cv.template take<int>(kQoMaxBlocks);
+  L.bkeep = cv.template take<int>(kQoMaxBlocks);
+  L.boff = cv.template take<int>(kQoMaxBlocks + 1);
+  L.bnorm = cv.template take<double>(kQoMaxBlocks);
+  L.seen = cv.template take<uint32_t>((p_hi + 32) / 32);
+  L.ptab = cv.template take<int>(2 * kQoPairTab * kQoPairTab);
+  L.red3 = cv.template take<double>(6 * kMaxWaves);
+  L.blg = cv.template take<int>(kQoMaxBlocks);
+  L.ioff = cv.template take<int>(kQoMaxBlocks + 1);
+  const int kv = kcap + kQoMaxBlocks;
+  L.v.xv = cv.template take<double>(kv);
+  C sv = cv.at(overlay ? 0 : cv.off);
+  const size_t sv0 = sv.off;
+  L.v.rv = sv.template take<double>(kv);
+  L.v.pv = sv.template take<double>(kv);
+  L.v.qv = sv.template take<double>(kv);
+  L.v.zv = sv.template take<double>(kv);
+  L.v.wv_ = sv.template take<double>(kv);
+  L.v.dv = sv.template take<double>(kv);
+  L.trm = sv.template take<int>(kv);
+  L.solver = sv.off - sv0;
+  L.bytes = cv.off > sv.off ? cv.off : sv.off;
+  return L;
+}
+
 template <typename T, bool LW, bool TRUNC = false>
 __global__ __launch_bounds__(1024) PH_QO_OCC void k_qo_find(const T* __restrict__ x, int N, int num, double thresh,
                                                         int p_lo, int p_hi, const PGeom* __restrict__ geom,
@@ -365,36 +438,15 @@ __global__ __launch_bounds__(1024) PH_QO_OCC void k_qo_find(const T* __restrict_
                                                         int* __restrict__ counts_out, double* __restrict__ weights_out,
                                                         T* __restrict__ resid_out, int* __restrict__ status_out) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  Carve cv(smem);
+  const QoFindLds<T> L = qo_find_carve<T>(Carve(smem), N, p_hi, kcap, LW, LW && overlay);
   // the residual: LDS, or (LW == false: windows that leave no room for the solver's vectors) the HBM workspace
-  T* work = window_buf<T, LW>(cv, gwin, N + kPad);
-  double* red = cv.take<double>(kRedDoubles);
-  double* wbest = cv.take<double>(kMaxWaves);
-  int* wbestp = cv.take<int>(kMaxWaves);
-  int* bper = cv.take<int>(kQoMaxBlocks);       // period of dictionary block b
-  int* bkeep = cv.take<int>(kQoMaxBlocks);      // rows kept for it
-  int* boff = cv.take<int>(kQoMaxBlocks + 1);   // first row of block b
-  double* bnorm = cv.take<double>(kQoMaxBlocks);
-  uint32_t* seen = cv.take<uint32_t>((p_hi + 32) / 32);  // running divisor set R (QOPeriods.py:832-835)
-  int* ptab = cv.take<int>(2 * kQoPairTab * kQoPairTab);  // (a, b): {p_b / gcd(p_a, p_b), p_a mod p_b}
-  double* red3 = cv.take<double>(6 * kMaxWaves);  // wave partials of the solver's fused reduction (two parities)
-  int* blg = cv.take<int>(kQoMaxBlocks);        // log2 of the lanes that share a row of block b in the product
-  int* ioff = cv.take<int>(kQoMaxBlocks + 1);   // first work item of block b
-  // Conjugate gradients on A A^T w = A x.  Solver layout of a vector: block b's k_b entries start at slot
-  // boff[b] + b and are followed by one zero (qo_offdiag clamps indices past the kept rows onto it).
-  const int kv = kcap + kQoMaxBlocks;
-  double* xv = cv.take<double>(kv);  // weights; persistent: the rows of earlier steps start from their last values
-  // The other vectors only live during a solve, when the residual window is dead (it is rebuilt from the data and the
-  // reconstruction afterwards): they overlay the window buffer when that is large enough, which leaves room for a
-  // second workgroup on the CU.
-  Carve sv((LW && overlay) ? reinterpret_cast<unsigned char*>(work) : cv.base + cv.off);
-  double* rv = sv.take<double>(kv);   // residual of the normal equations (starts as A x, QOPeriods.py:782)
-  double* pv = sv.take<double>(kv);   // search direction
-  double* qv = sv.take<double>(kv);   // A A^T pv
-  double* zv = sv.take<double>(kv);   // preconditioned residual
-  double* wv_ = sv.take<double>(kv);  // A A^T zv
-  double* dv = sv.take<double>(kv);   // 1 / diagonal = 1 / samples of the row's residue (Jacobi preconditioner)
-  int* trm = sv.take<int>(kv);        // samples of the row's residue
+  T* work = window_buf<T, LW>(L.work, gwin, N + kPad);
+  double *red = L.red, *wbest = L.wbest, *bnorm = L.bnorm, *red3 = L.red3;
+  int *wbestp = L.wbestp, *bper = L.bper, *bkeep = L.bkeep, *boff = L.boff, *ptab = L.ptab, *blg = L.blg;
+  int* ioff = L.ioff;
+  uint32_t* seen = L.seen;
+  double *xv = L.v.xv, *rv = L.v.rv, *pv = L.v.pv, *qv = L.v.qv, *zv = L.v.zv, *wv_ = L.v.wv_, *dv = L.v.dv;
+  int* trm = L.trm;
 
   const int64_t w = blockIdx.x;
   const int tid = threadIdx.x;
@@ -677,6 +729,25 @@ __device__ __forceinline__ bool window_class_bad(double num, double den) {
   return den == 0.0 || !(fabs(den) <= 1.7976931348623157e308) || !(fabs(num) <= 1.7976931348623157e308);
 }
 
+template <typename T>
+struct QoGreedyLds {
+  T* work;
+  double* red;
+  double* wbest;
+  int* wbestp;
+  size_t bytes;
+};
+template <typename T, class C>
+__host__ __device__ __forceinline__ QoGreedyLds<T> qo_greedy_carve(C cv, int N, bool lw) {
+  QoGreedyLds<T> L;
+  L.work = lw ? cv.template take<T>(N + kPad) : nullptr;
+  L.red = cv.template take<double>(kRedDoubles);
+  L.wbest = cv.template take<double>(kMaxWaves);
+  L.wbestp = cv.template take<int>(kMaxWaves);
+  L.bytes = cv.off;
+  return L;
+}
+
 template <typename T, bool LW, bool TRUNC, bool WIN = false>
 __global__ __launch_bounds__(1024) void k_qo_greedy(const T* __restrict__ x, int N, int num, double thresh, int p_lo,
                                                     int p_hi, const PGeom* __restrict__ geom,
@@ -688,11 +759,10 @@ __global__ __launch_bounds__(1024) void k_qo_greedy(const T* __restrict__ x, int
                                                     double* __restrict__ weights_out, T* __restrict__ resid_out,
                                                     int* __restrict__ status_out, const double* __restrict__ win) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  Carve cv(smem);
-  T* work = window_buf<T, LW>(cv, gwin, N + kPad);  // the running residual
-  double* red = cv.take<double>(kRedDoubles);
-  double* wbest = cv.take<double>(kMaxWaves);
-  int* wbestp = cv.take<int>(kMaxWaves);
+  const QoGreedyLds<T> L = qo_greedy_carve<T>(Carve(smem), N, LW);
+  T* work = window_buf<T, LW>(L.work, gwin, N + kPad);  // the running residual
+  double *red = L.red, *wbest = L.wbest;
+  int* wbestp = L.wbestp;
   // Nothing else lives in LDS, so no N or max_length is too large: the divisors of the periods found so far are a
   // bitset in the HBM workspace, the weights of the block being fitted go straight to the output row.
 
@@ -928,6 +998,31 @@ __device__ __forceinline__ void orth_powers_row(const T* xs, double* r, double* 
   }
 }
 
+// LDS of k_orth_powers and k_qo_orth_select (ph_fit.h): window, autocorrelation and clipped eq. 3 values when they live
+// in LDS (`lw`), then k_qo_orth_select's reduction slots (`select`).
+template <typename T>
+struct OrthLds {
+  T* stage;
+  double* r;
+  double* m;
+  double* red;
+  double* wbest;
+  int* wbestp;
+  size_t bytes;
+};
+template <typename T, class C>
+__host__ __device__ __forceinline__ OrthLds<T> orth_carve(C cv, int N, int max_p, bool lw, bool select) {
+  OrthLds<T> L;
+  L.stage = lw ? cv.template take<T>(N) : nullptr;
+  L.r = lw ? cv.template take<double>(N) : nullptr;
+  L.m = lw ? cv.template take<double>(max_p) : nullptr;
+  L.red = select ? cv.template take<double>(kRedDoubles) : nullptr;
+  L.wbest = select ? cv.template take<double>(kMaxWaves) : nullptr;
+  L.wbestp = select ? cv.template take<int>(kMaxWaves) : nullptr;
+  L.bytes = cv.off;
+  return L;
+}
+
 template <typename T, bool LW>
 __global__ __launch_bounds__(kBlockWide) void k_orth_powers(const T* __restrict__ x, int N, int max_p, int normalize,
                                                             const int* __restrict__ mob_off,
@@ -943,13 +1038,12 @@ __global__ __launch_bounds__(kBlockWide) void k_orth_powers(const T* __restrict_
   const T* xs = x + w * (int64_t)N;
   double *r, *m;
   if constexpr (LW) {
-    Carve cv(smem);
-    T* stage = cv.take<T>(N);
-    r = cv.take<double>(N);
-    m = cv.take<double>(max_p);
-    load_window(xs, stage, N);
+    const OrthLds<T> L = orth_carve<T>(Carve(smem), N, max_p, true, false);
+    r = L.r;
+    m = L.m;
+    load_window(xs, L.stage, N);
     __syncthreads();
-    xs = stage;
+    xs = L.stage;
   } else {
     r = gws + w * ((int64_t)N + max_p);
     m = r + N;

@@ -367,22 +367,42 @@ __device__ __forceinline__ double ram_emit(double* __restrict__ s, const RamJob&
   return wave_sum(cs * acc.all + acc.full) * (J.scale2 * J.scale2);  // out = (q / phi)^2 E_q S, norms = sum cnt out^2
 }
 
+// LDS of k_ramanujan: the window, then per wavefront strip A (q_hi doubles, the root fold) and strip B (q_hi / 2, one
+// child).  pad == 0 (the host drops the zeroed pad when that makes room for one more wavefront; roots >= 64 only): the
+// reads of a fold past the end of the window land in the strips -- they belong to lanes whose sums are discarded.
+template <typename T>
+struct RamLds {
+  T* xs;
+  double* sA;  // nw strips of lenA
+  double* sB;  // nw strips of lenB
+  int lenA, lenB;
+  size_t bytes;
+};
+template <typename T, class C>
+__host__ __device__ __forceinline__ RamLds<T> ram_carve(C cv, int N, int q_hi, int nw, int pad, bool lw) {
+  RamLds<T> L;
+  L.xs = lw ? cv.template take<T>(N + pad) : nullptr;
+  L.lenA = q_hi;
+  L.lenB = q_hi / 2 > 0 ? q_hi / 2 : 1;
+  L.sA = cv.template take<double>((size_t)nw * L.lenA);
+  L.sB = cv.template take<double>((size_t)nw * L.lenB);
+  L.bytes = cv.off;
+  return L;
+}
+
 template <typename T, bool LW>
 __global__ __launch_bounds__(kRamMaxWaves * 64) void k_ramanujan(const T* __restrict__ x, int N, int q_hi,
                                                                 const RamJob* __restrict__ roots, int n_root,
                                                                 const RamJob* __restrict__ children, T* gwin, int pad,
                                                                 double* __restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  Carve cv(smem);
-  // pad == 0 (the host drops the zeroed pad when that makes room for one more wavefront; roots >= 64 only): the reads
-  // of a fold past the end of the window land in the strips -- they belong to lanes whose sums are discarded
-  T* xs = window_buf<T, LW>(cv, gwin, N + pad);
   const int nw = blockDim.x >> 6;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & (kWave - 1);
-  const int lenA = q_hi, lenB = q_hi / 2 > 0 ? q_hi / 2 : 1;
-  double* sA = cv.take<double>((size_t)nw * lenA) + (size_t)wv * lenA;  // this wave's root fold S_Q
-  double* sB = cv.take<double>((size_t)nw * lenB) + (size_t)wv * lenB;  // scratch for one child
+  const RamLds<T> L = ram_carve<T>(Carve(smem), N, q_hi, nw, pad, LW);
+  T* xs = window_buf<T, LW>(L.xs, gwin, N + pad);
+  double* sA = L.sA + (size_t)wv * L.lenA;  // this wave's root fold S_Q
+  double* sB = L.sB + (size_t)wv * L.lenB;  // scratch for one child
 
   const int64_t w = blockIdx.x;
   const WgStamp<kClocks> t0;

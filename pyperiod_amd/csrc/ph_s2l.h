@@ -118,6 +118,29 @@ __device__ __forceinline__ void s2l_flat_update(T* __restrict__ work, const T* _
 // on the config-4 shard) and 16 / 24 / 48.
 constexpr int kS2LBatch = 32;
 
+template <typename T>
+struct S2LLds {
+  T* work;
+  T* buf;
+  double* red;
+  double* psq;
+  int* cand_slot;
+  T* msm;  // means of a candidate period <= kBlockWide (s2l_flat_* below); plain projection only
+  size_t bytes;
+};
+template <typename T, class C>
+__host__ __device__ __forceinline__ S2LLds<T> s2l_carve(C cv, int N, bool general, bool lw, bool buf_lds) {
+  S2LLds<T> L;
+  L.work = lw ? cv.template take<T>(N + kPad) : nullptr;
+  L.buf = buf_lds ? cv.template take<T>(N) : nullptr;
+  L.red = cv.template take<double>(kRedDoubles);
+  L.psq = cv.template take<double>(kS2LBatch);
+  L.cand_slot = cv.template take<int>(4);
+  L.msm = general ? nullptr : cv.template take<T>(kBlockWide);
+  L.bytes = cv.off;
+  return L;
+}
+
 template <typename T, bool LW>
 __global__ __launch_bounds__(kBlockWide) __attribute__((amdgpu_waves_per_eu(PH_STEP1_WAVES, 8))) void k_small_to_large(const T* __restrict__ x, int N, double thresh,
                                                            int n_periods, unsigned flags, Tables tb,
@@ -128,14 +151,13 @@ __global__ __launch_bounds__(kBlockWide) __attribute__((amdgpu_waves_per_eu(PH_S
                                                            T* __restrict__ bases_out, int* __restrict__ status_out,
                                                            int* __restrict__ max_count) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  Carve cv(smem);
-  T* work = window_buf<T, LW>(cv, gwin, N + kPad);
   const bool general = flags & (kTrunc | kOrth);
-  T* buf = !general ? nullptr : gbuf ? gbuf + (int64_t)blockIdx.x * N : cv.take<T>(N);
-  double* red = cv.take<double>(kRedDoubles);
-  double* psq = cv.take<double>(kS2LBatch);
-  int* cand_slot = cv.take<int>(4);
-  T* msm = general ? nullptr : cv.take<T>(kBlockWide);  // means of a candidate period <= kBlockWide (s2l_flat_* below)
+  const S2LLds<T> L = s2l_carve<T>(Carve(smem), N, general, LW, general && !gbuf);
+  T* work = window_buf<T, LW>(L.work, gwin, N + kPad);
+  T* buf = !general ? nullptr : second_buf(L.buf, gbuf, N);
+  double *red = L.red, *psq = L.psq;
+  int* cand_slot = L.cand_slot;
+  T* msm = L.msm;
 
   const int64_t w = blockIdx.x;
   const int tid = threadIdx.x;
@@ -279,11 +301,37 @@ constexpr int kS2LInf = 0x7fffffff;
 
 enum { S2L_TICK = 0, S2L_LIMIT, S2L_STOP0, S2L_STOP1, S2L_SKIP, S2L_PASSES /* executed: timer builds */, S2L_NEXT_PAIR, S2L_QWORDS = 8 };
 
-// LDS of one workgroup (host and device agree through this one function)
-__host__ __device__ inline size_t s2l_pair_lds_bytes(int N) {
-  return carve_bytes(N + kPad, 8) + carve_bytes(N, 8) + carve_bytes(kRedDoubles, 8) + carve_bytes(kBlockWide / 2, 8) + carve_bytes(kBlockWide, 8) + carve_bytes(8, 8) +
-         carve_bytes(4, 4) + carve_bytes(4, 4) + carve_bytes(S2L_QWORDS, 4);
+// LDS of one workgroup of k_small_to_large_pair
+struct S2LPairLds {
+  f2* pw;
+  double* stg;
+  double* red;
+  double* msm;  // means of a candidate period dealt to several threads (<= kBlockWide / 2)
+  double* prt;  // ... its partial sums; the means of a period in (kBlockWide / 2, kBlockWide]
+  // per window w: st[w] ||residual||^2, st[2+w] periodic_norm(residual), st[4+w] periodic_norm(data), st[6+w] scale of
+  // the float image; thf[2w], thf[2w+1]: T0, T1 of the flag test; ct[w] periods accepted
+  double* st;
+  float* thf;
+  int* ct;
+  int* qc;
+  size_t bytes;
+};
+template <class C>
+__host__ __device__ __forceinline__ S2LPairLds s2l_pair_carve(C cv, int N) {
+  S2LPairLds L;
+  L.pw = cv.template take<f2>(N + kPad);
+  L.stg = cv.template take<double>(N);
+  L.red = cv.template take<double>(kRedDoubles);
+  L.msm = cv.template take<double>(kBlockWide / 2);
+  L.prt = cv.template take<double>(kBlockWide);
+  L.st = cv.template take<double>(8);
+  L.thf = cv.template take<float>(4);
+  L.ct = cv.template take<int>(4);
+  L.qc = cv.template take<int>(S2L_QWORDS);
+  L.bytes = cv.off;
+  return L;
 }
+__host__ __device__ __forceinline__ size_t s2l_pair_lds_bytes(int N) { return s2l_pair_carve(CarveCount(), N).bytes; }
 
 // kappa_q of the flag test: float radius of the screen + the fp64 terms of k_small_to_large's bound
 __host__ __device__ inline double s2l_kappa(int N, int rows, int q) {
@@ -320,18 +368,11 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     int* __restrict__ periods_out, double* __restrict__ powers_out, double* __restrict__ bases_out,
     int* __restrict__ status_out, int* __restrict__ max_count, int* __restrict__ next_pair) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  Carve cv(smem);
-  f2* pw = cv.take<f2>(N + kPad);
-  double* stg = cv.take<double>(N);
-  double* red = cv.take<double>(kRedDoubles);
-  double* msm = cv.take<double>(kBlockWide / 2);  // means of a candidate period dealt to several threads (<= kBlockWide / 2)
-  double* prt = cv.take<double>(kBlockWide);  // ... its partial sums; the means of a period in (kBlockWide / 2, kBlockWide]
-  // per window w: st[w] ||residual||^2, st[2+w] periodic_norm(residual), st[4+w] periodic_norm(data), st[6+w] scale of
-  // the float image; thf[2w], thf[2w+1]: T0, T1 of the flag test; ct[w] periods accepted
-  double* st = cv.take<double>(8);
-  float* thf = cv.take<float>(4);
-  int* ct = cv.take<int>(4);
-  int* qc = cv.take<int>(S2L_QWORDS);
+  const S2LPairLds L = s2l_pair_carve(Carve(smem), N);
+  f2* pw = L.pw;
+  double *stg = L.stg, *red = L.red, *msm = L.msm, *prt = L.prt, *st = L.st;
+  float* thf = L.thf;
+  int *ct = L.ct, *qc = L.qc;
 
   const int tid = threadIdx.x;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);

@@ -24,6 +24,7 @@ DRIVERS = {
     "host_driver_tracks": "host sanitizer driver tracks ok",
     "host_driver_periodic": "host sanitizer driver periodic ok",
     "host_driver_ram_select": "host sanitizer driver ram_select ok",
+    "host_driver_plans": "host sanitizer driver plans ok",
 }
 
 

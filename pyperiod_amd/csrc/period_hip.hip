@@ -1580,10 +1580,34 @@ int ph_m_best(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int num, in
   if (pair) {
     PairWs ws;
     PH_TRY(pair_workspace(c, W, N, &ws));
-    PH_TRY(launch(c, "k_mbest_step1", ph::k_mbest_step1_pair, dim3((unsigned)((W + 1) / 2)), s1.block, s1.lds,
-                  (const double*)dx, (int)W, N, num, min_length, max_length, p_scr, gamma, tb.fac_off, tb.fac_q, geom, ws.geomf,
-                  ws.radq, plan, n_pass, ws.gwin, max_iters, (uint32_t*)dper, (double*)dpow, (double*)drows, row_stride, dnorm,
-                  (int*)dstat, (int*)dsweeps, c->pair_fold_once ? ph::pair_thin_band(N) : -1.0, c->pair_fold_report ? 1 : 0));
+    ph::Step1PairArgs a;
+    a.x = (const double*)dx;
+    a.W = (int)W;
+    a.N = N;
+    a.num = num;
+    a.p_lo = min_length;
+    a.p_hi = max_length;
+    a.p_scr = p_scr;
+    a.gamma = gamma;
+    a.n_pass = n_pass;
+    a.fac_off = tb.fac_off;
+    a.fac_q = tb.fac_q;
+    a.geom = geom;
+    a.geomf = ws.geomf;
+    a.radq = ws.radq;
+    a.plan = plan;
+    a.gres = ws.gwin;
+    a.periods_out = (uint32_t*)dper;
+    a.norms_out = (double*)dpow;
+    a.rows_out = (double*)drows;
+    a.dnorm_out = dnorm;
+    a.status_out = (int*)dstat;
+    a.sweeps_out = (int*)dsweeps;
+    a.thin_band = c->pair_fold_once ? ph::pair_thin_band(N) : -1.0;
+    a.max_iters = max_iters;
+    a.row_stride = row_stride;
+    a.fold_report = c->pair_fold_report ? 1 : 0;
+    PH_TRY(launch(c, "k_mbest_step1", ph::k_mbest_step1_pair, dim3((unsigned)((W + 1) / 2)), s1.block, s1.lds, a));
   } else {
     PH_TRY(dispatch(dtype, !gwin1, [&](auto t, auto lw) {
       using T = decltype(t);

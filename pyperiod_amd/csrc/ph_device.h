@@ -240,6 +240,27 @@ __device__ __forceinline__ double block_max(double v, double* red) {
   return uniform_f64(t);
 }
 
+// ---------------------------------------------------------------- tables in constant memory
+// A host table (geometry, pass plan, radii, divisor lists) behind a pointer that the kernel fetched from memory itself:
+// read through the constant address space, so that an entry at a wave-uniform index is a scalar load wherever it is
+// read.  (The compiler takes a pointer it cannot trace back to a `const __restrict__` kernel argument for memory that
+// the kernel's own stores may have changed, and reads it through the vector memory pipe.)  table[i] is a copy of entry i.
+template <typename T>
+struct ConstTable {
+  static_assert(sizeof(T) % 4 == 0, "entries are read word by word");
+  const __attribute__((address_space(4))) uint32_t* w;
+  __device__ __forceinline__ explicit ConstTable(const T* p) : w((const __attribute__((address_space(4))) uint32_t*)p) {}
+  __device__ __forceinline__ T operator[](int i) const {
+    constexpr int K = sizeof(T) / 4;
+    struct Words {
+      uint32_t v[K];
+    } r;
+#pragma unroll
+    for (int k = 0; k < K; ++k) r.v[k] = w[(int64_t)i * K + k];
+    return __builtin_bit_cast(T, r);
+  }
+};
+
 // ---------------------------------------------------------------- geometry of one fold
 struct Fold {
   int p;      // period
@@ -1084,21 +1105,21 @@ __device__ __forceinline__ double block_sweep_value(const T* __restrict__ xs, T*
 }
 
 // Copy one window HBM -> LDS (coalesced, 16-byte vectors when the row is 16-byte aligned).
-template <typename T>
+template <int NW = 0, typename T>
 __device__ __forceinline__ void zero_pad(T* __restrict__ xs, int N) {
-  for (int i = threadIdx.x; i < kPad; i += blockDim.x) xs[N + i] = T(0);
+  for (int i = threadIdx.x; i < kPad; i += block_threads<NW>()) xs[N + i] = T(0);
 }
 
-template <typename T>
+template <int NW = 0, typename T>
 __device__ __forceinline__ void load_window(const T* __restrict__ g, T* __restrict__ xs, int N) {
   constexpr int V = 16 / sizeof(T);
   if ((reinterpret_cast<uintptr_t>(g) & 15) == 0 && (N % V) == 0) {
     using vec_t = typename std::conditional<sizeof(T) == 8, double2, float4>::type;
     const vec_t* gv = reinterpret_cast<const vec_t*>(g);
     vec_t* xv = reinterpret_cast<vec_t*>(xs);
-    for (int i = threadIdx.x; i < N / V; i += blockDim.x) xv[i] = gv[i];
+    for (int i = threadIdx.x; i < N / V; i += block_threads<NW>()) xv[i] = gv[i];
   } else {
-    for (int i = threadIdx.x; i < N; i += blockDim.x) xs[i] = g[i];
+    for (int i = threadIdx.x; i < N; i += block_threads<NW>()) xs[i] = g[i];
   }
 }
 

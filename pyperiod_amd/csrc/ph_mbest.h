@@ -37,6 +37,7 @@ __device__ __forceinline__ bool mbest_prefers(double ss, int p, double best_ss, 
 }
 
 // Bookkeeping of a sweep's winner (Periods.py:518-535), identical in every thread; thread 0 writes the LDS tables.
+// `best` is read by thread 0 alone: k_mbest_step1_pair hands over the norm in wavefront 0 only on its fold-once path.
 // `row` is the row that holds bestp already, or -1.  Returns the action -- 0 = subtract only, 1 = store new row,
 // 2 = accumulate into existing row -- and leaves the row it applies to in `row`.  Ten repeats are accumulated; the
 // next one sets the period's skip bit instead.
@@ -315,6 +316,29 @@ enum {
 };
 enum { MP_UNIT = 0, MP_SCALE = 2, MP_DOUBLES = 4 };  // sum of squares of the scaled residual (unit of the radius); its scale
 
+// block_sum<NW> with the combine done once: every wavefront adding the same NW partial sums is NW loads and NW additions in
+// each of them for one value.  Wavefront 0 adds them -- the same additions in the same order -- between the two barriers
+// block_sum has anyway, and the others read the total behind the second.  The total lies in red[kMaxWaves], a slot no block
+// sum writes its partial values to; it is written again only behind the first barrier of a later call, which no wavefront
+// reaches before it has the value.  What a caller must keep (as block_sum_once has its own condition, ph_device.h): red holds
+// more than kMaxWaves doubles (kRedDoubles = 2 kMaxWaves), and a barrier lies between the read of the total here and anything
+// else that writes the upper half of red -- block_sum2, the survivor scan's second maximum.  In k_mbest_step1_pair every such
+// write is a phase and at least one barrier away.
+template <int NW>
+__device__ __forceinline__ double block_sum_lead(double v, double* red, int wv, int lane) {
+  static_assert(kRedDoubles > kMaxWaves, "the total lies behind the partial sums");
+  double* total = red + kMaxWaves;
+  v = wave_sum(v);
+  if (lane == 0) red[wv] = v;
+  __syncthreads();
+  if (wv == 0) {
+    const double t = red_combine<false, NW>(red, NW);
+    if (lane == 0) *total = t;
+  }
+  __syncthreads();
+  return uniform_f64(*total);
+}
+
 // sum_j S_p[j]^2 / cnt_p[j] of the fp64 window `xs` (LDS), residues j = first, first + stride, ... (p >= 64 path)
 __device__ __forceinline__ double pair_exact_part(const double* __restrict__ xs, int p, const PGeom& g, int first, int stride) {
   double part = 0.0;
@@ -346,6 +370,10 @@ struct Step1PairLds {
 template <class C>
 __host__ __device__ __forceinline__ Step1PairLds step1_pair_carve(C cv, int N, int num, int P) {
   Step1PairLds L;
+  // (the control words first: their addresses -- the pass queue's among them, which every pass of the screen takes a
+  // ticket from -- are constants of the instruction, not values derived from the shape and kept in registers)
+  L.ctl = cv.template take<int>(MP_WORDS);
+  L.dst2 = cv.template take<double>(MP_DOUBLES);
   L.pw = cv.template take<f2>(N + kPad);
   L.stg = cv.template take<double>(N + kPad);
   L.red = cv.template take<double>(kRedDoubles);
@@ -355,70 +383,130 @@ __host__ __device__ __forceinline__ Step1PairLds step1_pair_carve(C cv, int N, i
   L.periods = cv.template take<uint32_t>(2 * num);
   L.skip = cv.template take<uint32_t>(2 * ((P + 31) / 32));
   L.list = cv.template take<int>(2 * kPairListCap);
-  L.ctl = cv.template take<int>(MP_WORDS);
-  L.dst2 = cv.template take<double>(MP_DOUBLES);
   L.msm = cv.template take<double>(kPairSmallP);
   L.prt = cv.template take<double>(kPairSplitW);
   L.bytes = cv.off;
   return L;
 }
 
-__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_WAVES, 8))) void k_mbest_step1_pair(
-    const double* __restrict__ x, int W, int N, int num, int p_lo, int p_hi, int p_scr, int gamma,
-    const int* __restrict__ fac_off, const int* __restrict__ fac_q, const PGeom* __restrict__ geom, const PGeomF* __restrict__ geomf, const double* __restrict__ radq, const PassPlan* __restrict__ plan, int n_pass,
-    double* __restrict__ gres, int max_iters, uint32_t* __restrict__ periods_out, double* __restrict__ norms_out,
-    double* __restrict__ rows_out, int row_stride, double* __restrict__ dnorm_out, int* __restrict__ status_out,
-    int* __restrict__ sweeps_out, double thin_band, int fold_report) {
+// The arguments of k_mbest_step1_pair: one block passed by value, i.e. the kernarg segment itself.  The kernel sits at
+// its scalar-register budget, and 26 arguments loaded in the entry block were parked in lanes of vector registers
+// (v_writelane) and brought back by v_readlane at every use, four of them in front of every pass of the screen.  Only
+// what a pass needs stays in scalar registers across the screen -- N, p_lo, plan, geomf, n_pass --; everything else is
+// fetched from the block by a scalar load at the head of the phase that uses it (pair_args_at_use), which costs no
+// vector instruction.
+struct Step1PairArgs {
+  const double* x;
+  int W, N, num, p_lo, p_hi, p_scr, gamma;
+  int n_pass;
+  const int* fac_off;
+  const int* fac_q;
+  const PGeom* geom;
+  const PGeomF* geomf;
+  const double* radq;
+  const PassPlan* plan;
+  double* gres;
+  uint32_t* periods_out;
+  double* norms_out;
+  double* rows_out;
+  double* dnorm_out;
+  int* status_out;
+  int* sweeps_out;
   // thin_band: pair_thin_band(N) from the host (computed here it is a loop invariant in vector registers, spilled around the
   // screen), or a negative number: no fold-once path (PH_PAIR_FOLD_ONCE=0)
-  const bool fold_once = __double2hiint(thin_band) >= 0;  // (the sign bit, on the scalar unit)
+  double thin_band;
+  int max_iters, row_stride, fold_report;
+};
+typedef const __attribute__((address_space(4))) Step1PairArgs* step1_pair_args_ptr;
+
+// The block for the phase that begins here: its address through a scalar register pair, the way const_at_use passes a
+// constant, so that the loads of the fields stay behind this point (loads from the kernarg segment are invariant and
+// would otherwise all move to the kernel's entry block).
+__device__ __forceinline__ step1_pair_args_ptr pair_args_at_use() {
+  step1_pair_args_ptr p = (step1_pair_args_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(p));
+  return p;
+}
+// the kernel's LDS layout from the block (scalar arithmetic; a phase computes the pieces it uses)
+__device__ __forceinline__ Step1PairLds pair_lds_at_use(step1_pair_args_ptr A, unsigned char* smem) {
+  return step1_pair_carve(Carve(smem), A->N, A->num, A->p_hi - A->p_lo + 1);
+}
+// a pointer fetched that way, known to point to global memory (a pointer loaded from memory is a flat one to the compiler)
+template <typename T>
+__device__ __forceinline__ T* pair_arg_global(T* p) {
+  return (T*)(__attribute__((address_space(1))) T*)p;
+}
+// ... and a table the kernel only reads (ConstTable, ph_device.h)
+template <typename T>
+__device__ __forceinline__ ConstTable<T> pair_arg_table(const T* p) {
+  return ConstTable<T>(p);
+}
+
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_WAVES, 8))) void k_mbest_step1_pair(const Step1PairArgs) {
+  // (the block is read through the segment pointer only: named and read as a parameter, it was copied to scratch)
+  const step1_pair_args_ptr a = (step1_pair_args_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+  // What the screen works with, in scalar registers for the whole kernel: the scr_ names.  Only the round loop's head, the
+  // screen and the debug prints use them.  Every phase behind the screen declares its own N, p_lo, stg, ctl, wv, ... from
+  // the block (below): a phase that read a scr_ value instead would make the compiler keep what it derives from it across
+  // the passes again -- in lanes.
+  const int scr_N = a->N, scr_p_lo = a->p_lo, scr_n_pass = a->n_pass;
+  const ConstTable<PGeomF> scr_geomf = pair_arg_table(a->geomf);
+  const ConstTable<PassPlan> scr_plan = pair_arg_table(a->plan);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int P = p_hi - p_lo + 1;
-  const int SK = (P + 31) / 32;
-  const Step1PairLds L = step1_pair_carve(Carve(smem), N, num, P);
-  f2* pw = L.pw;
-  double *stg = L.stg, *red = L.red, *wbest = L.wbest, *norms = L.norms, *dst2 = L.dst2, *msm = L.msm, *prt = L.prt;
-  int *wbestp = L.wbestp, *list = L.list, *ctl = L.ctl;
-  uint32_t *periods = L.periods, *skip = L.skip;
+  const Step1PairLds scr_L = pair_lds_at_use(a, smem);
+  f2* scr_pw = scr_L.pw;
+  double* scr_stg = scr_L.stg;
+  int* scr_ctl = scr_L.ctl;
 
   const int tid = threadIdx.x;
-  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int scr_wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   // The host launches this kernel with 64 kPairWaves threads and nothing else (plan_m_best): the wavefront count is a
-  // constant and the workgroup reductions test no slot (ph_device.h, red_combine).  blockDim.x stays the stride of the
-  // thread loops: as the constant 1024 it raised the spills (scratch 60 -> 72 bytes per lane) for 45 instructions.
+  // constant and the workgroup reductions test no slot (ph_device.h, red_combine), and so is the stride of the thread
+  // loops (read from the dispatch packet it was a load through the vector memory pipe at every use, its address in a
+  // vector register pair for the whole kernel).
   constexpr int NW = kPairWaves, nw = NW;
-  const size_t gstride = win_stride((size_t)N);
-  float* pwf = reinterpret_cast<float*>(pw);
-  const double sqrtN = uniform_f64(sqrt((double)N));
+  constexpr int kThreads = NW * kWave;
+  const double sqrtN = uniform_f64(sqrt((double)scr_N));
 
-  for (int k = tid; k < 2 * num; k += blockDim.x) {
+  {  // the windows' images and the bookkeeping of both (in front of the round loop: the screen's own values serve)
+  const int N = scr_N, p_lo = scr_p_lo;
+  const Step1PairLds& L = scr_L;
+  f2* pw = scr_pw;
+  double* stg = scr_stg;
+  int* ctl = scr_ctl;
+  const int SK = (a->p_hi - p_lo + 1 + 31) / 32;
+  double *red = L.red, *norms = L.norms, *dst2 = L.dst2;
+  uint32_t *periods = L.periods, *skip = L.skip;
+  float* pwf = reinterpret_cast<float*>(pw);
+  for (int k = tid; k < 2 * a->num; k += kThreads) {
     norms[k] = 0.0;
     periods[k] = 0u;
   }
-  for (int k = tid; k < 2 * SK; k += blockDim.x) skip[k] = 0u;
+  for (int k = tid; k < 2 * SK; k += kThreads) skip[k] = 0u;
   if (tid < MP_WORDS) ctl[tid] = tid == MP_QUEUE ? nw : 0;
-  zero_pad(stg, N);
-  for (int i = tid; i < kPad; i += blockDim.x) pw[N + i] = f2_zero();
+  zero_pad<NW>(stg, N);
+  for (int i = tid; i < kPad; i += kThreads) pw[N + i] = f2_zero();
   for (int w = 0; w < 2; ++w) {
     const int64_t gw = 2 * (int64_t)blockIdx.x + w;
-    const bool exists = gw < W;
+    const bool exists = gw < a->W;
     __syncthreads();
     if (exists) {
-      load_window(x + gw * (int64_t)N, stg, N);
+      load_window<NW>(pair_arg_global(a->x) + gw * (int64_t)N, stg, N);
     } else {
-      for (int n = tid; n < N; n += blockDim.x) stg[n] = 0.0;
+      for (int n = tid; n < N; n += kThreads) stg[n] = 0.0;
     }
     __syncthreads();
     const double rsq = block_sumsq<NW>(stg, N, red);
     const double sc = uniform_f64(pair_pick_scale(rsq, N));
-    for (int n = tid; n < N; n += blockDim.x) pwf[2 * n + w] = (float)(stg[n] * sc);
+    for (int n = tid; n < N; n += kThreads) pwf[2 * n + w] = (float)(stg[n] * sc);
     if (tid == 0) {
       dst2[MP_UNIT + w] = rsq * sc * sc * (1.0 + 1e-9);
       dst2[MP_SCALE + w] = sc;
       ctl[MP_RUNNING + w] = exists ? 1 : 0;
       ctl[MP_EXACT_ALL + w] = pair_usable(rsq) ? 0 : 1;
-      if (exists) dnorm_out[gw] = periodic_norm_from_sq_n(rsq, sqrtN, 0);
+      if (exists) pair_arg_global(a->dnorm_out)[gw] = periodic_norm_from_sq_n(rsq, sqrtN, 0);
     }
+  }
   }
   StageClock<kPairTimers, 6, 3> clk;  // stages: screen, scan, load, thin, exact, update; counters: candidates, exact_all, folded
   WgStamp<kClocks> stamp;
@@ -426,29 +514,43 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
     __syncthreads();
     // (values that are identical in all lanes go to scalar registers as they are read: as vector registers they were
     // spilled around the screen, and every reload is a scratch access through L2 on the critical path of the exact phases)
-    const bool act0 = __builtin_amdgcn_readfirstlane(ctl[MP_RUNNING]) != 0, act1 = __builtin_amdgcn_readfirstlane(ctl[MP_RUNNING + 1]) != 0;
+    const bool act0 = __builtin_amdgcn_readfirstlane(scr_ctl[MP_RUNNING]) != 0, act1 = __builtin_amdgcn_readfirstlane(scr_ctl[MP_RUNNING + 1]) != 0;
     if (!act0 && !act1) break;
-    prio_by_progress(__builtin_amdgcn_readfirstlane(max(ctl[MP_SWEEPS], ctl[MP_SWEEPS + 1])));  // sweeps done: keeps the two workgroups of a CU in step (ph_device.h)
-    if (wv == 0 && pair_lane() == 0) ctl[MP_LISTED] = ctl[MP_LISTED + 1] = 0;  // (read as `ncand` before the last barrier of the previous round)
+    prio_by_progress(__builtin_amdgcn_readfirstlane(max(scr_ctl[MP_SWEEPS], scr_ctl[MP_SWEEPS + 1])));  // sweeps done: keeps the two workgroups of a CU in step (ph_device.h)
+    if (scr_wv == 0 && pair_lane() == 0) scr_ctl[MP_LISTED] = scr_ctl[MP_LISTED + 1] = 0;  // (read as `ncand` before the last barrier of the previous round)
     // ---- 1. screen of both windows (Periods.py:501-515 in float); values into the idle staging buffer
-    f2* vals = reinterpret_cast<f2*>(stg);
+    f2* vals = reinterpret_cast<f2*>(scr_stg);
     pair_sweep_plan<false, true>(
-        pw, N, geomf, plan, wv, n_pass, nw, [&](float z, int q) { pair_store1(vals, z, q, p_lo); },
-        [&](float z, int q_a, int q_b) { pair_store2(vals, z, q_a, q_b, p_lo); },
-        PH_PAIR_QUEUE ? &ctl[MP_QUEUE] : nullptr);
+        scr_pw, scr_N, scr_geomf, scr_plan, scr_wv, scr_n_pass, nw, [&](float z, int q) { pair_store1(vals, z, q, scr_p_lo); },
+        [&](float z, int q_a, int q_b) { pair_store2(vals, z, q_a, q_b, scr_p_lo); },
+        PH_PAIR_QUEUE ? &scr_ctl[MP_QUEUE] : nullptr);
     __syncthreads();
     clk.mark(0);
     prio_short_phase();
     {  // phases 2 and 3 of this round
     // The thread and lane indices are RECOMPUTED here (wave number in a scalar register + v_mbcnt): kept live across the
     // screen they were spilled, and the exact phases reloaded them from scratch -- through L2 -- fifteen times per round.
+    // (the wave number through its scalar register, as const_at_use: what the phases derive from it -- LDS addresses of a
+    // thread's slots -- is then made here, by the scalar unit, and not kept in lanes across the screen)
+    const int wv = const_at_use(scr_wv);
     const int tid = (wv << 6) + pair_lane();
     const int lane = tid & (kWave - 1);
-    if (tid == 0) ctl[MP_QUEUE] = nw;  // the pass queue of the next screen (barriers in between)
+    if (tid == 0) scr_ctl[MP_QUEUE] = nw;  // the pass queue of the next screen (barriers in between)
     // ---- 2. survivors of both windows: two passes over the screened values
     {
-      const bool scr0 = act0 && !__builtin_amdgcn_readfirstlane(ctl[MP_EXACT_ALL]), scr1 = act1 && !__builtin_amdgcn_readfirstlane(ctl[MP_EXACT_ALL + 1]);
+      const bool scr0 = act0 && !__builtin_amdgcn_readfirstlane(scr_ctl[MP_EXACT_ALL]), scr1 = act1 && !__builtin_amdgcn_readfirstlane(scr_ctl[MP_EXACT_ALL + 1]);
       if (scr0 || scr1) {
+        // (everything the scan works with is fetched or derived here, behind the screen: nothing of it is live across the passes)
+        const step1_pair_args_ptr A = pair_args_at_use();
+        const int N = A->N, p_lo = A->p_lo, P = A->p_hi - p_lo + 1, SK = (P + 31) / 32, p_scr = A->p_scr, gamma = A->gamma;
+        const Step1PairLds L = pair_lds_at_use(A, smem);
+        double *stg = L.stg, *red = L.red, *dst2 = L.dst2;
+        int *list = L.list, *ctl = L.ctl;
+        const uint32_t* skip = L.skip;
+        const f2* vals = reinterpret_cast<const f2*>(stg);
+        const ConstTable<double> radq = pair_arg_table(A->radq);
+        const ConstTable<int> fac_off = pair_arg_table(A->fac_off);
+        const ConstTable<int> fac_q = pair_arg_table(A->fac_q);
         const double unit0 = uniform_f64(dst2[MP_UNIT]), unit1 = uniform_f64(dst2[MP_UNIT + 1]);
         // cover rule: the screened periods bound their divisors below p_scr.  `seen` (a bit per such divisor and
         // window, so that a divisor of two covering periods is listed once) lies in front of the first screened
@@ -457,11 +559,11 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
         const bool cover = i0 > 0;
         const int SD = (i0 + 31) >> 5;
         uint32_t* seen = reinterpret_cast<uint32_t*>(stg);
-        for (int k = tid; k < 2 * SD; k += blockDim.x) seen[k] = 0u;
+        for (int k = tid; k < 2 * SD; k += kThreads) seen[k] = 0u;
         const double slack = cover ? pair_cover_slack(N) : 0.0;
         // One screened entry as both passes need it: the two values, the radius -- radq[q] = pair_radius(ceil(N / q), q)
         // from the host table next to geomf, the bound the proof in ph_pair.h states -- 1 / q in gamma mode and the skip
-        // bits.  At most blockDim.x entries (683 of 1024 threads at N = 4096) means one entry per thread: it is read
+        // bits.  At most kThreads entries (683 of 1024 threads at N = 4096) means one entry per thread: it is read
         // once and stays in registers across the barrier.
         struct Entry {
           f2 v;
@@ -484,7 +586,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
         if (idx_own < P) own = entry(idx_own);
         const double ninf = const_at_use(-1.0 / 0.0);  // (as a vector-register invariant it was spilled around the screen)
         double lo0 = ninf, lo1 = ninf;
-        for (int idx = idx_own; idx < P; idx += blockDim.x) {
+        for (int idx = idx_own; idx < P; idx += kThreads) {
           const Entry e = idx == idx_own ? own : entry(idx);
           double a = (double)e.v.x - e.rad * unit0, b = (double)e.v.y - e.rad * unit1;
           if (gamma) {
@@ -501,6 +603,9 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
           red[kMaxWaves + wv] = lo1;
         }
         __syncthreads();
+        // (every wavefront combines the two maxima itself.  Combined by wavefront 0 alone and read back behind one more
+        // barrier, the counter of a launch fell by 0.7e6 of the 4.8e6 its 2 x 31 v_max_f64 predict: with that form in the
+        // kernel the plan pointer of the screen is parked in lanes and read back in front of every pass.  Not kept.)
         lo0 = uniform_f64(red_combine<true, NW>(red, nw));
         lo1 = uniform_f64(red_combine<true, NW>(red + kMaxWaves, nw));
         // every screened period skipped: nothing bounds the winner from below, every period goes through the exact phase
@@ -509,7 +614,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
         if (tid == 0 && none1) ctl[MP_LISTED + 1] = kPairListCap + 1;
         // periods that tie with the winner in the ROUNDED norm survive too
         const double thr0 = lo0 - fabs(lo0) * 1e-9, thr1 = lo1 - fabs(lo1) * 1e-9;
-        for (int idx = idx_own; idx < P; idx += blockDim.x) {
+        for (int idx = idx_own; idx < P; idx += kThreads) {
           const Entry e = idx == idx_own ? own : entry(idx);
           const int q = p_lo + idx;
           const double rad = e.rad + slack;
@@ -551,6 +656,21 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
     // ---- 3. exact phase, one window at a time through the staging buffer
     for (int w = 0; w < 2; ++w) {
       if (!(w ? act1 : act0)) continue;
+      // (as in the scan: the arguments and the LDS layout of this window-sweep, fetched and derived behind the screen)
+      const step1_pair_args_ptr A = pair_args_at_use();
+      const int N = A->N, p_lo = A->p_lo, P = A->p_hi - p_lo + 1, SK = (P + 31) / 32;
+      const int num = A->num, p_scr = A->p_scr, gamma = A->gamma, max_iters = A->max_iters, row_stride = A->row_stride;
+      const Step1PairLds L = pair_lds_at_use(A, smem);
+      double *stg = L.stg, *red = L.red, *wbest = L.wbest, *norms = L.norms, *dst2 = L.dst2, *msm = L.msm, *prt = L.prt;
+      int *wbestp = L.wbestp, *list = L.list, *ctl = L.ctl;
+      uint32_t *periods = L.periods, *skip = L.skip;
+      float* pwf = reinterpret_cast<float*>(L.pw);
+      const size_t gstride = win_stride((size_t)N);
+      const bool fold_once = __double2hiint(A->thin_band) >= 0;  // (the sign bit, on the scalar unit)
+      const double* __restrict__ x = pair_arg_global(A->x);
+      double* __restrict__ gres = pair_arg_global(A->gres);
+      double* __restrict__ rows_out = pair_arg_global(A->rows_out);
+      const ConstTable<PGeom> geom = pair_arg_table(A->geom);
       const int64_t gw = 2 * (int64_t)blockIdx.x + w;
       int filled = __builtin_amdgcn_readfirstlane(ctl[MP_FILLED + w]), repeats = __builtin_amdgcn_readfirstlane(ctl[MP_REPEATS + w]), status = 0,
           iters = __builtin_amdgcn_readfirstlane(ctl[MP_SWEEPS + w]);
@@ -594,20 +714,20 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
           const PGeom gm = geom[fold_m];
           double part = 0.0;
           if (tid == 0) wbestp[0] = 0;  // the tie flag of the thinning below
-          for (int j = tid; j < fold_m; j += blockDim.x) {
+          for (int j = tid; j < fold_m; j += kThreads) {
             const bool full = j < gm.nfull;
             const double s = pair_column_sum_global(src, j, fold_m, full ? gm.rows : gm.rows - 1);
             part = fma(s * s, full ? gm.w_full : gm.w_short, part);
             stg[j] = s;
           }
-          fold_ss = block_sum<NW>(part, red);
+          fold_ss = block_sum_lead<NW>(part, red, wv, lane);
           clk.mark(2);
           if (ncand > 1) {
             // a wavefront per listed divisor: its value from S_m (pair_thin_part) against the threshold; one that reaches it
             // raises the flag (wbestp is idle on this path; cleared in front of the barriers of the block sum above)
             // the band in the units of the values: MP_UNIT without its scale, a power of two
             const int se = __builtin_amdgcn_frexp_exp(dst2[MP_SCALE + w]) - 1;
-            const double band = thin_band * ldexp(dst2[MP_UNIT + w], -2 * se);
+            const double band = A->thin_band * ldexp(dst2[MP_UNIT + w], -2 * se);
             // (1e-9 through a scalar register pair at its use: as a loop invariant in vector registers it is spilled around
             // the screen)
             double tie = 1e-9;
@@ -626,7 +746,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
           clk.mark(3);
         }
         if (fold_m == 0) {
-        load_window(src, stg, N);
+        load_window<NW>(src, stg, N);
         __syncthreads();
         clk.mark(2);
         if (p_scr > p_lo && !exact_all && ncand > 1) {
@@ -682,11 +802,14 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
             bestp = p;
           }
         };
-        double best = 0.0;
+        double best = 0.0;  // NOT identical in every thread on the fold-once path: the norm in wavefront 0, 0.0 elsewhere (thread 0 books it)
         if (fold_m != 0) {
           consider(fold_ss, fold_m);
-          best = bestp != 0 ? periodic_norm_from_sq_n(best_ss, sqrtN, gamma ? bestp : 0) : 0.0;
-          if (!(best > 0.0)) bestp = 0;
+          // The rounded norm of the winner is booked by thread 0 alone (mbest_book): wavefront 0 takes the square root and
+          // the divisions, the others do not.  Nobody needs the test `best > 0` here: consider() took m only with
+          // fold_ss > 0, and the root of a positive double is at least 2^-537, which divided by sqrt(N) sqrt(m) < 2^32
+          // stays positive -- so the norm is positive exactly when bestp is set.
+          if (wv == 0) best = bestp != 0 ? periodic_norm_from_sq_n(best_ss, sqrtN, gamma ? bestp : 0) : 0.0;
         } else if (ncand <= kPairCoop) {
           // few survivors (the normal case): the whole workgroup folds one candidate at a time, a wavefront per
           // 64 residues; partial sums are combined in wave order, so every thread holds the same value
@@ -698,7 +821,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
             if (p < 64) {
               if (wv == 0) part = wave_partial_small(stg, N, p, g, lane);
             } else {
-              part = pair_exact_part(stg, p, g, tid, blockDim.x);
+              part = pair_exact_part(stg, p, g, tid, kThreads);
             }
             consider(block_sum<NW>(part, red), p);
           }
@@ -748,7 +871,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
             // the means from the column sums in the staging buffer (S / cnt: residue_mean's expression); every thread
             // subtracts them from its own columns, read again from the source and written to the workspace -- in place
             // after the first sweep, a thread touches only its own columns
-            for (int j = tid; j < bestp; j += blockDim.x) {
+            for (int j = tid; j < bestp; j += kThreads) {
               const int cnt = f.count(j);
               const double m = stg[j] / (double)cnt;
               if (action == 1)
@@ -790,8 +913,8 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
             }
             if (more) {
               int idx = tid % bestp;
-              const int step = blockDim.x % bestp;
-              for (int n = tid; n < N; n += blockDim.x) {
+              const int step = kThreads % bestp;
+              for (int n = tid; n < N; n += kThreads) {
                 const double v = stg[n] - msm[idx];
                 dst[n] = v;
                 pwf[2 * n + w] = (float)(v * sc);
@@ -801,7 +924,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
               }
             }
           } else {
-            for (int j = tid; j < bestp; j += blockDim.x) {
+            for (int j = tid; j < bestp; j += kThreads) {
               const double m = residue_mean(stg, f, j, false);
               const int cnt = f.count(j);
               if (action == 1)
@@ -820,7 +943,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
             }
           }
           if (more) {
-            const double rsq = block_sum<NW>(acc, red);
+            const double rsq = block_sum_lead<NW>(acc, red, wv, lane);
             const double unit = rsq * sc * sc;
             // (pair_usable and pair_image_stale written out, their constants through scalar registers at this use: as
             // loop invariants in vector registers 1.79e308 and 9e-13 N were spilled around the round loop, and both
@@ -829,7 +952,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
             if (ok && unit < const_at_use(kPairStaleMeanSq) * (double)const_at_use(N)) {
               const double sc2 = uniform_f64(pair_pick_scale(rsq, N));
               __syncthreads();
-              pair_rescale(pwf, w, N, (float)(sc2 / sc), tid);
+              pair_rescale<NW>(pwf, w, N, (float)(sc2 / sc), tid);
               if (tid == 0) {
                 dst2[MP_UNIT + w] = rsq * sc2 * sc2 * (1.0 + 1e-9);
                 dst2[MP_SCALE + w] = sc2;
@@ -860,21 +983,33 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(PH_STEP1_W
   }
   if (kPairTimers && blockIdx.x < PH_PAIR_TIMERS_WGS && tid == 0)
     printf("pair timers (100 MHz ticks) screen %lld scan %lld load %lld thin %lld exact %lld update %lld  candidates %d exact_all %d folded %d sweeps %d %d\n",
-           clk.ticks(0), clk.ticks(1), clk.ticks(2), clk.ticks(3), clk.ticks(4), clk.ticks(5), clk.counted(0), clk.counted(1), clk.counted(2), ctl[MP_SWEEPS],
-           ctl[MP_SWEEPS + 1]);
+           clk.ticks(0), clk.ticks(1), clk.ticks(2), clk.ticks(3), clk.ticks(4), clk.ticks(5), clk.counted(0), clk.counted(1), clk.counted(2), scr_ctl[MP_SWEEPS],
+           scr_ctl[MP_SWEEPS + 1]);
   __syncthreads();
-  // rows the algorithm never filled keep period 0: step 2 writes them as zeros (np.zeros((num, N)), Periods.py:490)
-  for (int w = 0; w < 2; ++w) {
-    const int64_t gw = 2 * (int64_t)blockIdx.x + w;
-    if (gw >= W) continue;
-    for (int k = tid; k < num; k += blockDim.x) {
-      periods_out[gw * num + k] = periods[w * num + k];
-      norms_out[gw * num + k] = norms[w * num + k];
-    }
-    if (tid == 0) {
-      status_out[gw] = ctl[MP_STATUS + w] & 255;
-      // fold_report (PH_PAIR_FOLD_REPORT=1, tests): the fold-once count of the window above bit 16 of its sweep count
-      if (sweeps_out) sweeps_out[gw] = ctl[MP_SWEEPS + w] | (fold_report ? (ctl[MP_STATUS + w] >> 8) << 16 : 0);
+  {  // the outputs
+    const step1_pair_args_ptr A = pair_args_at_use();
+    const int num = A->num, fold_report = A->fold_report;
+    const Step1PairLds L = pair_lds_at_use(A, smem);
+    const double* norms = L.norms;
+    const uint32_t* periods = L.periods;
+    const int* ctl = L.ctl;
+    uint32_t* __restrict__ periods_out = pair_arg_global(A->periods_out);
+    double* __restrict__ norms_out = pair_arg_global(A->norms_out);
+    int* __restrict__ status_out = pair_arg_global(A->status_out);
+    int* __restrict__ sweeps_out = pair_arg_global(A->sweeps_out);
+    // rows the algorithm never filled keep period 0: step 2 writes them as zeros (np.zeros((num, N)), Periods.py:490)
+    for (int w = 0; w < 2; ++w) {
+      const int64_t gw = 2 * (int64_t)blockIdx.x + w;
+      if (gw >= A->W) continue;
+      for (int k = tid; k < num; k += kThreads) {
+        periods_out[gw * num + k] = periods[w * num + k];
+        norms_out[gw * num + k] = norms[w * num + k];
+      }
+      if (tid == 0) {
+        status_out[gw] = ctl[MP_STATUS + w] & 255;
+        // fold_report (PH_PAIR_FOLD_REPORT=1, tests): the fold-once count of the window above bit 16 of its sweep count
+        if (sweeps_out) sweeps_out[gw] = ctl[MP_SWEEPS + w] | (fold_report ? (ctl[MP_STATUS + w] >> 8) << 16 : 0);
+      }
     }
   }
 }

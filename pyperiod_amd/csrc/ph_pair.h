@@ -41,6 +41,13 @@ __device__ __forceinline__ f2 f2_make(float a, float b) {
   return r;
 }
 __device__ __forceinline__ f2 f2_zero() { return f2_make(0.0f, 0.0f); }
+// zero written into its registers at this point (the compiler's own zero may be one pair made in front of the kernel's
+// main loop and -- at the register cap -- brought back from a spill at every use)
+__device__ __forceinline__ f2 f2_zero_at_use() {
+  f2 r;
+  asm volatile("v_mov_b64 %0, 0" : "=v"(r));
+  return r;
+}
 __device__ __forceinline__ f2 f2_fma(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
 __device__ __forceinline__ f2 f2_max(f2 a, f2 b) { return __builtin_elementwise_max(a, b); }
 // accumulate one residue sum t: sum of squares (norm screens) or largest square (MX: the max |S| screen of
@@ -512,7 +519,8 @@ __device__ __forceinline__ void pair_duo_rows(const f2* __restrict__ xs, int N, 
     }
     for (; c + UA <= whole; c += UA) pair_duo_group<R, R, UA, 0>(at + 64 * c, q, pend, sa, pa, sb, pb);
   }
-  sb = pb = f2_zero();  // (not live in front of the cut)
+  sb = f2_zero_at_use();  // (not live in front of the cut)
+  pb = f2_zero_at_use();
   // From here on every column lies at R - 1 or behind it: the partner has R rows as well, (R - 1) (q + 64) < N, so
   // cut = N - (R - 1) q > 64 (R - 1) -- `whole` >= R - 1, and q has more than R chunk columns.
   const unsigned long inq = pair_lanes_below(q - 64 * last);  // lanes of the last column that are residues of q
@@ -571,8 +579,8 @@ __device__ __forceinline__ void pair_pass_duo(const f2* __restrict__ xs, int N, 
 // ---------------------------------------------------------------- multi-class pass, straight-line segments
 // Period p, 2p (and 4p) from the class sums of one fold: the weights of a part are compile-time indexed and chosen on
 // the scalar unit, the tail of a part is picked by two compares, and no flag survives a branch.
-template <int M, bool MX = false>
-__device__ __forceinline__ void pair_pass_multi(const f2* __restrict__ xs, int p, const PGeomF* __restrict__ geom,
+template <int M, bool MX = false, typename GT>
+__device__ __forceinline__ void pair_pass_multi(const f2* __restrict__ xs, int p, GT geom,
                                                 f2 (&total)[3]) {
   static_assert(M == 2 || M == 4, "two or four classes");
   const PGeomF g1 = geom[p], g2 = geom[2 * p], g4 = geom[(M == 4 ? 4 : 2) * p];
@@ -726,9 +734,9 @@ __device__ __forceinline__ f2 pair_chain_term(f2 tot, int lane, int q, const PGe
   return (lane < q) ? tot * tot * w : f2_zero();
 }
 
-template <bool MX, typename F, typename F2>
+template <bool MX, typename GT, typename F, typename F2>
 __device__ __forceinline__ void pair_chain_small(const f2* __restrict__ xs, int N, int L, int nlev,
-                                                 const PGeomF* __restrict__ geom, F&& consume, F2&& consume2) {
+                                                 GT geom, F&& consume, F2&& consume2) {
   const int lane = pair_lane();
   PGeomF g = geom[L];
   const int full = g.nfull == L ? g.rows : g.rows - 1;  // floor(N / L)
@@ -778,9 +786,9 @@ __device__ __forceinline__ void pair_chain_small(const f2* __restrict__ xs, int 
 // put them into an array.  Every period is reduced on its own: nothing is live across the folds (the online 8-period
 // butterfly of the fp64 sweeps kept pending partials that were spilled in every pass: 3.03 -> 2.82 ms in round 3).
 // DUO: the plan may hold shared-load entries (m = 3, pair_pass_duo); the other kernels never get such a plan.
-template <bool MX = false, bool DUO = false, typename F, typename F2>
-__device__ __forceinline__ void pair_sweep_plan(const f2* __restrict__ xs, int N, const PGeomF* __restrict__ geom,
-                                                const PassPlan* __restrict__ plan, int i_first, int i_end, int stride,
+template <bool MX = false, bool DUO = false, typename GT, typename PT, typename F, typename F2>
+__device__ __forceinline__ void pair_sweep_plan(const f2* __restrict__ xs, int N, GT geom,
+                                                PT plan, int i_first, int i_end, int stride,
                                                 F&& consume, F2&& consume2, int* __restrict__ queue = nullptr) {
   auto red = [](f2 v) { return pair_reduce1<MX>(v); };
   // `queue` (an LDS counter the caller has set to `stride`, the number of wavefronts): the passes are taken in plan
@@ -951,8 +959,9 @@ __device__ __forceinline__ bool pair_image_stale(double rsq, double sc, int N) {
 
 // float image of window w of a pair times a power of two: the rescaled image is the image at the new scale
 // (tid: for a kernel that recomputes its thread index to keep it out of long-lived registers)
+template <int NW = 0>
 __device__ __forceinline__ void pair_rescale(float* __restrict__ pwf, int w, int N, float up, int tid = threadIdx.x) {
-  for (int n = tid; n < N; n += blockDim.x) pwf[2 * n + w] *= up;
+  for (int n = tid; n < N; n += block_threads<NW>()) pwf[2 * n + w] *= up;
 }
 
 // upper bound of ceil(N / q) without an integer division (the radius only has to be an upper bound)

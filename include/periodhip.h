@@ -635,6 +635,31 @@ int ph_overlap_add_finish(ph_ctx* ctx, const double* acc, int64_t T, int N, int 
                           const double* win_a, const double* win_s, unsigned flags /* PH_FLAG_DEVICE | PH_FLAG_OLA_NORM */,
                           double* out /* (T, L) */);
 
+/* ph_period_path: the best path through a time-period map -- R cost tables cost (R, W, ld) float64, of
+ * which the first P columns of every row are used, -> the state of every frame.  With band B and pen[o] = jump * o:
+ *   c'[f][j]   = cost[f][j] if finite, else -inf                  (NaN, +inf and -inf all mean "forbidden")
+ *   D[0][j]    = c'[0][j];   D[f][j] = c'[f][j] + max_o (D[f-1][j+o] - pen[|o|])   over |o| <= B, 0 <= j + o < P
+ *                offsets tried in the order 0, -1, +1, -2, +2, ..., a later one kept only if strictly greater
+ *   score      = max_j D[W-1][j]; path[W-1] = the lowest such j; path[f-1] = path[f] + the offset kept at (f, path[f])
+ *   value[f]   = cost[f][path[f]]
+ * Every product, difference and sum is one float64 operation rounded once and max is exact, so path, value and score are
+ * bit for bit those of a plain loop over these lines.  status[r] = PH_ST_OK, or PH_ST_NO_PERIOD when score is -inf (some
+ * frame has no reachable state): then path[r] is all -1 and value[r] all 0.  path (R, W) int32, value (R, W) float64 or
+ * NULL, score (R) float64, status (R) int32.  The columns P .. ld - 1 of cost are never read by the kernel.
+ * One launch (k_period_path), one workgroup per map; the int8 back-pointers live in an (R, W, P rounded up to 16) workspace
+ * of the context (PH_E_NOMEM when it cannot be allocated) and the backtrace walks them in LDS, a tile of whole rows at a
+ * time.  R * W * P and R * W * ld may exceed 2^31.  The host-pointer form uploads the table as it lies, gaps included.
+ * Every array follows PH_FLAG_DEVICE.  PH_E_ARG, before any HIP call, for a NULL ctx / cost / path / score / status, P not in
+ * [1, 8192], band not in [0, 64], jump negative or not finite, W < 1, R < 0 or >= 2^31, ld < P, or R * W * ld * 16 beyond 64
+ * bits.  R == 0 is PH_OK and launches nothing.
+ * ph_period_path_plan_info: the launch shape for P columns -- threads per workgroup, LDS bytes, and the rows of one
+ * backtrace tile (what fits the LDS the forward pass leaves behind; PH_PATH_TILE_ROWS=n in the environment of ph_create
+ * caps it, for measurements).  Nothing runs on the device. */
+int ph_period_path(ph_ctx* ctx, const double* cost /* (R, W, ld) */, int64_t R, int64_t W, int P, int64_t ld, int band,
+                   double jump, unsigned flags /* PH_FLAG_DEVICE */, int32_t* path /* (R, W) */,
+                   double* value /* (R, W) or NULL */, double* score /* (R) */, int32_t* status /* (R) */);
+int ph_period_path_plan_info(ph_ctx* ctx, int P, int* block, int* lds_bytes, int* tile_rows);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,6 +36,14 @@ routed overlap-add.
 
     dr = st.decompose_ramanujan(recording, thresh=0.2, reference="recording", max_periods=16)
     dr.norms, dr.over, dr.frame_status, dr.track_periods, dr.tracks, dr.periodic
+
+``period_map`` is the time-period map of a recording for any of the periodic norms -- frames x periods, the periodicity
+analogue of a spectrogram -- and ``contour`` the period of the recording at every frame: the best path through that map
+(``PeriodEngine.period_path``), which a jump to a multiple of the true period costs more than it gains.
+
+    m = st.period_map(recording, kind="gamma")          # m.periods (P,), m.values (W, P)
+    c = st.contour(recording, kind="gamma", band=8, jump=0.002)
+    c.periods, c.salience, c.score
 """
 
 from __future__ import annotations
@@ -105,7 +113,31 @@ class ShortTimeRamanujan(NamedTuple):
     frame_status: Optional[np.ndarray] = None
 
 
+class ShortTimeMap(NamedTuple):
+    """What ``ShortTime.period_map`` returns: ``values[f, j]`` (W, P) float64 is the `kind` norm of frame f at period
+    ``periods[j]`` (P,) int32 -- numpy arrays for a numpy signal, tensors on the engine's device for a tensor signal."""
+
+    periods: object
+    values: object
+    kind: str
+
+
+class ShortTimeContour(NamedTuple):
+    """What ``ShortTime.contour`` returns: ``periods[f]`` (W,) int32 is the period of frame f on the best path through the
+    time-period map, ``salience[f]`` (W,) float64 the map's value there, ``score`` the path's summed salience minus its
+    jump penalties, ``map`` the ShortTimeMap when it was asked for."""
+
+    periods: np.ndarray
+    salience: np.ndarray
+    score: float
+    map: Optional[ShortTimeMap] = None
+
+
 _MAX_ROWS = 64  # rows per frame a 64-bit routing mask can name
+# period_map's kinds; the sweep mode of the two that ph_sweep computes
+_MAP_KINDS = {"norm": _ffi.PH_SWEEP_NORM, "gamma": _ffi.PH_SWEEP_NORM_GAMMA, "orth": None, "ramanujan": None}
+_RAM_MAX_PERIOD = 30030  # ph_ramanujan_norms' record format
+_PATH_MAX_BAND, _PATH_MAX_PERIODS = 64, 8192  # ph_period_path's limits
 
 
 class _Recording:
@@ -448,6 +480,135 @@ class ShortTime:
         if isinstance(block_frames, bool) or not isinstance(block_frames, (int, np.integer)) or block_frames < 1:
             raise ValueError(f"block_frames={block_frames!r} must be an int >= 1")
         return int(block_frames)
+
+    # ------------------------------------------------------------------ the time-period map and a track through it
+    def _map_args(self, kind, min_length, max_length):
+        """The refusals of ``period_map`` that need no engine, in the order the docstring lists them: -> (lo, hi)."""
+        if kind not in _MAP_KINDS:
+            raise ValueError(f"kind must be one of {tuple(_MAP_KINDS)}")
+        lo = int(min_length)
+        if lo < 1:
+            raise ValueError("min_length must be >= 1")
+        hi = self.frame_length // 3 if max_length is None else int(max_length)
+        if hi < lo:
+            raise ValueError(f"max_length={hi} must be >= min_length={lo}")
+        if kind == "ramanujan" and hi >= _RAM_MAX_PERIOD:
+            raise ValueError(f"max_length={hi}: the Ramanujan norms take periods below {_RAM_MAX_PERIOD}")
+        if kind in ("orth", "ramanujan") and (self._trunc_to_integer_multiple or self._orthogonalize):
+            raise ValueError(f"kind={kind!r} has no projection that trunc_to_integer_multiple / orthogonalize could apply to")
+        return lo, hi
+
+    def _map_plan(self, eng, kind, lo, hi):
+        """The kind's kernel asked whether it takes frames of this length and this range (the plan query of its entry
+        point: its own refusals, raised as ValueError, and nothing launched)."""
+        trunc, orth = self._trunc_to_integer_multiple, self._orthogonalize
+        if kind in ("norm", "gamma"):
+            eng.plan_info("sweep", self.frame_length, (lo, hi, _MAP_KINDS[kind]), self.dtype, trunc, orth)
+        elif kind == "orth":
+            eng.plan_info("orth_powers", self.frame_length, (hi + 1,), self.dtype)
+        else:
+            eng.plan_info("ramanujan", self.frame_length, (lo, hi), self.dtype)
+
+    def _map(self, signal, kind, lo, hi, B):
+        """The (W, P) map of `signal` on the device and whether the signal came as a device tensor.  The signal goes up
+        once (a tensor on the engine's device is used where it lies); the frames are cut on the device, all at once or
+        `B` at a time, and every block's rows of the kind's table are written into one (W, P) tensor."""
+        import torch
+
+        x = self._signal(signal)
+        eng = default_engine()
+        self._map_plan(eng, kind, lo, hi)
+        dev = torch.device("cuda", eng.device)
+        on_device = _is_torch(x)
+        if on_device:
+            if not x.is_cuda or x.device.index != eng.device:
+                raise ValueError(f"a tensor signal must live on cuda:{eng.device} (or pass a numpy array)")
+            xd = x.detach()
+            if xd.dtype not in (torch.float64, torch.float32):
+                xd = xd.to(torch.float64)
+            xd = xd.contiguous()
+        else:
+            xd = torch.as_tensor(x, device=dev)  # the one upload: L samples
+        W = self.frame_count(xd.shape[0])
+        win = None if self.window is None else torch.as_tensor(self.window, device=dev)
+        rec = _Recording(xd, W, eng, xd, win, torch.float64 if self.dtype == np.float64 else torch.float32)
+        trunc, orth = self._trunc_to_integer_multiple, self._orthogonalize
+
+        def rows(fr):  # (Wb, P): the columns lo .. hi of the kind's table, a view where the table is wider
+            if kind in ("norm", "gamma"):
+                return eng.sweep(fr, lo, hi, _MAP_KINDS[kind], trunc, orth)
+            if kind == "orth":
+                return eng.orth_powers(fr, hi + 1, normalize=True)[:, lo : hi + 1]
+            return eng.ramanujan_norms(fr, lo, hi)[:, lo : hi + 1]
+
+        if B is None or B >= W:
+            return rows(self._frames(rec, 0, W)), on_device
+        values = torch.empty((W, hi - lo + 1), dtype=torch.float64, device=dev)
+        for f0 in range(0, W, B):
+            values[f0 : f0 + B] = rows(self._frames(rec, f0, min(B, W - f0)))
+        return values, on_device
+
+    def period_map(self, signal, kind="gamma", min_length=2, max_length=None, block_frames=None):
+        """The time-period map of a recording: the frames x periods table of a periodic norm, the periodicity analogue
+        of a spectrogram.  -> ShortTimeMap(periods (P,), values (W, P) float64, kind); column j is period
+        ``min_length + j``, `max_length` defaults to ``frame_length // 3``.
+
+        `kind`: "norm" -- ``periodic_norm(project(frame, p))``, "gamma" -- the same divided by p (both ``PeriodEngine.sweep``,
+        with the constructor's trunc / orthogonalize flags), "orth" -- the normalised orthogonal period powers
+        (``orth_powers``), "ramanujan" -- the Ramanujan norms (``ramanujan_norms``).
+
+        The signal goes up once; the frames are cut on the device (window applied) all at once or `block_frames` at a
+        time, and each block's rows are written into one (W, P) device tensor: every partition gives the same map, bit
+        for bit.  A numpy signal returns numpy arrays; a tensor on the engine's device returns tensors and downloads
+        nothing.  ValueError before any launch: an unknown `kind`, ``min_length < 1``, ``max_length < min_length``, a
+        range the kind's kernel does not take, or either flag together with "orth" / "ramanujan"."""
+        B = self._block_frames(block_frames)
+        lo, hi = self._map_args(kind, min_length, max_length)
+        values, on_device = self._map(signal, kind, lo, hi, B)
+        return self._map_result(values, kind, lo, hi, on_device)
+
+    @staticmethod
+    def _map_result(values, kind, lo, hi, on_device):
+        if on_device:
+            import torch
+
+            return ShortTimeMap(torch.arange(lo, hi + 1, dtype=torch.int32, device=values.device), values, kind)
+        return ShortTimeMap(np.arange(lo, hi + 1, dtype=np.int32), values.cpu().numpy(), kind)
+
+    def contour(self, signal, kind="gamma", band=8, jump=0.0, min_length=2, max_length=None, block_frames=None,
+                return_map=False):
+        """The period track of a recording: the path through its time-period map (``period_map``, same arguments) that
+        maximises the summed map value minus ``jump * |step|`` over the paths that move at most `band` periods per frame
+        (``PeriodEngine.period_path``: one launch on the map where it lies on the device).  Frame-wise maxima jump to
+        multiples and near-multiples of the true period; the path does not, because a jump costs more than it gains.
+        -> ShortTimeContour(periods (W,) int32 = min_length + path, salience (W,) float64 = the map along the path,
+        score, map).  Only W integers, W doubles and the score come down; with ``return_map=True`` `map` is the
+        ShortTimeMap (numpy for a numpy signal, tensors for a tensor signal), otherwise None.
+
+        ValueError before any launch for what ``period_map`` refuses, `band` outside 0 .. 64, a negative or non-finite
+        `jump`, or more than 8192 periods; after the launch when no path exists, naming the first frame whose map row
+        has no finite value (a NaN sample in a frame makes its whole row NaN)."""
+        B = self._block_frames(block_frames)
+        lo, hi = self._map_args(kind, min_length, max_length)
+        if isinstance(band, bool) or not isinstance(band, (int, np.integer)) or not 0 <= int(band) <= _PATH_MAX_BAND:
+            raise ValueError(f"band={band!r} must be an int in 0 .. {_PATH_MAX_BAND}")
+        if isinstance(jump, bool) or not isinstance(jump, (int, float, np.integer, np.floating)) or not (
+                jump >= 0 and math.isfinite(jump)):
+            raise ValueError(f"jump={jump!r} must be finite and >= 0")
+        if hi - lo + 1 > _PATH_MAX_PERIODS:
+            raise ValueError(f"{hi - lo + 1} periods: the path kernel takes at most {_PATH_MAX_PERIODS}")
+        values, on_device = self._map(signal, kind, lo, hi, B)
+        path, sal, score, status = default_engine().period_path(values, int(band), float(jump))
+        if int(status.item()) != _ffi.PH_ST_OK:
+            import torch
+
+            dead = (~torch.isfinite(values)).all(dim=1).cpu().numpy()
+            if dead.any():
+                raise ValueError(f"contour: no path exists, the map row of frame {_first(dead)} has no finite value")
+            raise ValueError(f"contour: no path of band {int(band)} connects the finite values of the map")
+        periods = (path + lo).cpu().numpy().astype(np.int32, copy=False)
+        return ShortTimeContour(periods, sal.cpu().numpy(), float(score.item()),
+                                self._map_result(values, kind, lo, hi, on_device) if return_map else None)
 
     def decompose_qo(self, signal, num, thresh, min_length=2, max_length=None, update_weights=True, tracks=None,
                      max_tracks=8, max_rows=2048):

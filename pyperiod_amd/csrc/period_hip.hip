@@ -96,6 +96,7 @@ struct ph_ctx {
   int s2l_block = 1024;              // k_small_to_large_pair threads per workgroup (PH_S2L_BLOCK overrides, >= 512)
   bool qo_hbm_window = false;        // PH_QO_HBM_WINDOW=1: keep the residual of k_qo_find in HBM even when it fits LDS
   bool hbm_window = false;           // PH_HBM_WINDOW=1: every window and second window-sized buffer in HBM
+  int path_tile_cap = 0;             // PH_PATH_TILE_ROWS=n: k_period_path's backtrace tile holds at most n rows (0: what fits)
   // Moebius tables of the orthogonal powers for the last max_p (prepare_mobius)
   int mob_max_p = -1;
   std::vector<int32_t> mob_off, mob_d, mob_mu;
@@ -1060,6 +1061,33 @@ int resolve_orth_powers(const ph_ctx* c, int dtype, int N, int* max_p_io, Plan* 
   return PH_OK;
 }
 
+// ph_period_path: the limits of k_period_path (ph_path.h) and its launch shape -- threads, states per thread, the carve's
+// LDS bytes and backtrace tile height, the bytes of one back-pointer row.  R, W and ld are a launch's own; the plan query
+// asks with R = W = 1, ld = P.
+struct PathPlan {
+  int block, states, tile, row_bytes;
+  size_t lds;
+};
+
+int resolve_period_path(const ph_ctx* c, int64_t R, int64_t W, int P, int64_t ld, int band, double jump, PathPlan* pp) {
+  if (P < 1 || P > ph::kPathMaxP) return fail(PH_E_ARG, "ph_period_path: P=%d must be in [1, %d]", P, ph::kPathMaxP);
+  if (band < 0 || band > ph::kPathHalo)
+    return fail(PH_E_ARG, "ph_period_path: band=%d must be in [0, %d]", band, ph::kPathHalo);
+  if (!(jump >= 0.0) || !(jump <= 1.7976931348623157e308))
+    return fail(PH_E_ARG, "ph_period_path: jump=%g must be finite and >= 0", jump);
+  if (W < 1) return fail(PH_E_ARG, "ph_period_path: W=%lld must be >= 1", (long long)W);
+  if (R < 0 || R > 0x7fffffffLL) return fail(PH_E_ARG, "ph_period_path: R=%lld must be in [0, 2^31)", (long long)R);
+  if (ld < P) return fail(PH_E_ARG, "ph_period_path: ld=%lld must be >= P=%d", (long long)ld, P);
+  // R * W * ld doubles of cost, R * W * row_bytes of back-pointers (row_bytes <= 16 ld): both inside int64
+  if (W > (INT64_MAX / 16) / ld || (R > 0 && W * ld > (INT64_MAX / 16) / R))
+    return fail(PH_E_ARG, "ph_period_path: R * W * ld does not fit 64 bits");
+  const auto L = ph::path_carve(CarveCount(), P, c->path_tile_cap);
+  *pp = PathPlan{ph::path_block(P), ph::path_states(P), L.tile, ph::path_row_bytes(P), L.bytes};
+  if (pp->lds > (size_t)c->lds_limit)
+    return fail(PH_E_ARG, "ph_period_path: P=%d needs %zu B of LDS, device limit is %d B", P, pp->lds, c->lds_limit);
+  return PH_OK;
+}
+
 // (ph_qo_orth_select has no default or refusal beside plan_qo_orth_select's own max_p >= 2: that function is its resolver)
 
 // What the window-pair kernels take beside the one-window arguments: one fp64 row of win_stride(N) per window in the
@@ -1169,6 +1197,7 @@ int ph_create(int device, ph_ctx** out) {
     const int v = std::atoi(e);
     if (v >= 64 && v <= 512 && v % 64 == 0) c->sweep_block = v;
   }
+  if (const char* e = std::getenv("PH_PATH_TILE_ROWS")) c->path_tile_cap = std::max(0, std::atoi(e));
   *out = c;
   return PH_OK;
 }
@@ -2763,6 +2792,56 @@ int ph_overlap_add_finish(ph_ctx* c, const double* acc, int64_t T, int N, int ho
   PH_TRY(st.out(B_OUT0, out, (size_t)T * L * sizeof(double), &dout));
   PH_TRY(launch(c, "k_overlap_add_finish", ph::k_overlap_add_finish, dim3(flat_grid(c, T * L)), ph::kFramesBlock, 0,
                 (const double*)dacc, T, N, hop, L, W, sd.wa, sd.ws, sd.norm, (double*)dout));
+  return st.finish();
+}
+
+// ----------------------------------------------------------------------------- best path through a time-period map
+int ph_period_path_plan_info(ph_ctx* c, int P, int* block, int* lds_bytes, int* tile_rows) {
+  if (!c || !block || !lds_bytes || !tile_rows) return fail(PH_E_ARG, "NULL argument");
+  PathPlan pp;
+  PH_TRY(resolve_period_path(c, 1, 1, P, P, 0, 0.0, &pp));
+  *block = pp.block;
+  *lds_bytes = (int)pp.lds;
+  *tile_rows = pp.tile;
+  return PH_OK;
+}
+
+int ph_period_path(ph_ctx* c, const double* cost, int64_t R, int64_t W, int P, int64_t ld, int band, double jump,
+                   unsigned flags, int32_t* path, double* value, double* score, int32_t* status) {
+  if (!c) return fail(PH_E_ARG, "ctx is NULL");
+  if (!cost || !path || !score || !status) return fail(PH_E_ARG, "ph_period_path: cost / path / score / status is NULL");
+  PathPlan pp;
+  PH_TRY(resolve_period_path(c, R, W, P, ld, band, jump, &pp));
+  if (R == 0) return PH_OK;
+  PH_HIP(hipSetDevice(c->device));
+  const size_t rows = (size_t)R * (size_t)W;
+  PH_TRY(ensure(c, c->buf[B_WS0], rows * (size_t)pp.row_bytes));  // the back-pointers, (R, W, row_bytes) int8
+  Stage st(c, flags);
+  const void* dcost;
+  void *dpath, *dval, *dscore, *dstat;
+  // a strided host table goes up as it lies, gaps included, and the kernel walks it with the same ld
+  PH_TRY(st.in(cost, ((rows - 1) * (size_t)ld + (size_t)P) * sizeof(double), &dcost));
+  PH_TRY(st.out(B_OUT0, path, rows * sizeof(int32_t), &dpath));
+  PH_TRY(st.out(B_OUT1, value, rows * sizeof(double), &dval));
+  PH_TRY(st.out(B_OUT2, score, (size_t)R * sizeof(double), &dscore));
+  PH_TRY(st.out(B_GEN0, status, (size_t)R * sizeof(int32_t), &dstat));
+  const auto go = [&](auto ns) {
+    return launch(c, "k_period_path", ph::k_period_path<decltype(ns)::value>, dim3((unsigned)R), pp.block, pp.lds,
+                  (const double*)dcost, W, P, ld, band, jump, c->path_tile_cap, (signed char*)c->buf[B_WS0].p, (int*)dpath,
+                  (double*)dval, (double*)dscore, (int*)dstat);
+  };
+  int rc = PH_E_ARG;
+  switch (pp.states) {  // 1 .. kPathMaxStates, by the limit on P
+    case 1: rc = go(std::integral_constant<int, 1>{}); break;
+    case 2: rc = go(std::integral_constant<int, 2>{}); break;
+    case 3: rc = go(std::integral_constant<int, 3>{}); break;
+    case 4: rc = go(std::integral_constant<int, 4>{}); break;
+    case 5: rc = go(std::integral_constant<int, 5>{}); break;
+    case 6: rc = go(std::integral_constant<int, 6>{}); break;
+    case 7: rc = go(std::integral_constant<int, 7>{}); break;
+    case 8: rc = go(std::integral_constant<int, 8>{}); break;
+  }
+  PH_TRY(rc);
   return st.finish();
 }
 

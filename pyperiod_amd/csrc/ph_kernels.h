@@ -12,3 +12,4 @@
 #include "ph_ram.h"
 #include "ph_qo.h"
 #include "ph_project.h"
+#include "ph_path.h"

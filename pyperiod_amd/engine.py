@@ -845,6 +845,61 @@ class PeriodEngine:
         return self._ola_call(mk, tuple(acc.shape), W, L, self._lib.ph_overlap_add_finish, mk.addr(acc), T, N, hop, L, W,
                               mk.addr(wa), mk.addr(ws), fl=fl, normalize=normalize, out=out)
 
+    # ------------------------------------------------------------------ best path through a time-period map
+    def period_path_plan(self, P):
+        """-> (threads per workgroup, LDS bytes, rows of one backtrace tile) of the k_period_path launch for a map of P
+        columns (ph_period_path_plan_info).  Nothing runs on the device."""
+        block, lds, tile = C.c_int(0), C.c_int(0), C.c_int(0)
+        _ffi.check(self._lib.ph_period_path_plan_info(self._ctx, int(P), C.byref(block), C.byref(lds), C.byref(tile)))
+        return block.value, lds.value, tile.value
+
+    def period_path(self, cost, band=8, jump=0.0, want_values=True):
+        """The best path through a time-period map (ph_period_path, one launch): cost (W, P) or (R, W, P) float64 ->
+        (path, values, score, status).  The path maximises the sum of cost[f, path[f]] minus jump * |path[f] - path[f-1]|
+        over the paths that move at most `band` columns per frame; entries that are not finite are forbidden.  path
+        (W,) int32, values (W,) float64 = cost[f, path[f]] (None without `want_values`), score a float64 and status an
+        int32 scalar array; with a batch every result has the leading dimension R.  status PH_ST_NO_PERIOD: some frame has
+        no reachable state, the path is all -1 and the values 0.
+        A numpy array gives numpy results; a float64 tensor on the engine's device gives tensors, on torch's current
+        stream.  The last dimension must be contiguous; a strided last-but-one dimension (a column slice of a wider
+        map) is passed on as the row stride and not copied, anything else is."""
+        if getattr(cost, "ndim", None) not in (2, 3):
+            raise ValueError("expected cost of shape (W, P) or (R, W, P)")
+        batched = cost.ndim == 3
+        R, W, P = (int(v) for v in (cost.shape if batched else (1,) + tuple(cost.shape)))
+        band = int(band)
+        jump = float(jump)
+        if _is_torch(cost):
+            import torch
+
+            if not cost.is_cuda or cost.device.index != self.device:
+                raise ValueError(f"torch input must live on cuda:{self.device} (or pass a numpy array)")
+            if cost.dtype != torch.float64:
+                raise TypeError("cost must be float64")
+            strides, fl = tuple(cost.stride()), _ffi.PH_FLAG_DEVICE
+            mk = _Out(cost)
+            mk.stream = torch.cuda.current_stream(cost.device).cuda_stream or _ffi.PH_STREAM_DEFAULT
+        else:
+            cost = np.asarray(cost)
+            if cost.dtype != np.float64:
+                raise TypeError("cost must be float64")
+            strides, fl = tuple(s // 8 if s % 8 == 0 else -1 for s in cost.strides), 0
+            mk = _Out(cost)
+        ld = strides[-2] if W > 1 else max(P, 1)
+        ok = P >= 1 and W >= 1 and (strides[-1] == 1 or P == 1) and ld >= P and (not batched or R <= 1 or strides[0] == W * ld)
+        if not ok and P >= 1 and W >= 1:
+            cost, ld = (cost.contiguous() if mk.torch else np.ascontiguousarray(cost)), P
+        lead = (R,) if batched else ()
+        path = mk.empty((R, W), np.int32)
+        values = mk.empty((R, W), np.float64) if want_values else None
+        score = mk.empty((R,), np.float64)
+        status = mk.empty((R,), np.int32)
+        if R > 0:
+            self._call(mk, R, self._lib.ph_period_path, mk.addr(cost), R, W, P, int(ld), band, jump, fl, mk.addr(path),
+                       mk.addr(values), mk.addr(score), mk.addr(status))
+        return (path.reshape(lead + (W,)), None if values is None else values.reshape(lead + (W,)), score.reshape(lead),
+                status.reshape(lead))
+
     def fold_sums(self, x, p_list, keep):
         """W = A x for natural-basis rows (QOPeriods.py:782): (W, sum(keep)) float64."""
         x, code, W, N, fl, mk = self._prep(x)

@@ -660,6 +660,40 @@ int ph_period_path(ph_ctx* ctx, const double* cost /* (R, W, ld) */, int64_t R, 
                    double* value /* (R, W) or NULL */, double* score /* (R) */, int32_t* status /* (R) */);
 int ph_period_path_plan_info(ph_ctx* ctx, int P, int* block, int* lds_bytes, int* tile_rows);
 
+/* ph_follow: extraction along a period track -- the periodic component of every frame of a recording at
+ * the periods the caller names for that frame, peeled one after the other.  The kernel cuts its frames from the signal
+ * itself (L samples of in_dtype); no (W, N) array exists.  Frame f is what ph_frames would write, widened to double:
+ *   x_f[i] = (double)(frame_dtype)((double)signal[f * hop + i] * window[i]) for f * hop + i < L, else 0
+ * (window == NULL: no product; frame_dtype PH_F32 rounds each sample to float once, PH_F64 does not round).
+ *   C_f = counts[f] clipped to [0, pcap];  r_0 = x_f, off = 0
+ *   for a = 0 .. C_f - 1, p = periods[f, a]; the walk of the frame stops at the first block with p < 1, p > N or
+ *   off + p > ccap, otherwise
+ *     s = project(r_a, p, trunc, False, return_single_period=True)   residues added in row order, one division
+ *     seg[f, off + j] = s[j] for j < p
+ *     r_{a+1}[i] = r_a[i] - s[i mod p]                                one rounded subtraction per sample
+ *     powers[f, a] = (pn(r_a) - pn(r_{a+1})) / pn(x_f)                pn = periodic_norm; exactly 0.0 when pn(x_f) == 0
+ *     off += p
+ * done[f] = the blocks written, powers[f, a >= done[f]] = 0.0, and the elements of seg behind the last block are never
+ * written (the host-pointer form moves seg up and down again, so they come back as they were).  seg and done are those
+ * of a plain loop over these lines bit for bit; the sum of squares inside pn is a workgroup reduction, so powers is
+ * within 1e-10 * pn(r_a) / pn(x_f) of that loop.  Non-finite samples propagate; there is no status word.
+ * seg (W, ccap) float64, periods (W, pcap) int32 and counts (W) int32 are the layout ph_qo_get_periods writes and
+ * ph_overlap_add_periodic reads.  The first two stop rules are that kernel's; a frame that stops only on p > N does not
+ * stop in its walk, so such a frame must not be handed on as it stands.
+ * One launch (k_follow): a workgroup handles one frame at a time and the workgroups walk the frames grid-stride; the
+ * residual frame and one period of means (N doubles each) live in LDS while both fit the workgroup's limit, otherwise --
+ * always under PH_HBM_WINDOW=1 -- in a per-workgroup slice of a workspace of the context.  W * ccap may exceed 2^31.
+ * flags: PH_FLAG_DEVICE | PH_FLAG_TRUNC.  Every array follows PH_FLAG_DEVICE.  PH_E_ARG, before any HIP call, for a
+ * NULL ctx / signal / periods / counts / seg / powers / done, an unknown dtype, a size < 1, (W - 1) * hop >= L,
+ * pcap > 64, ccap > 2^24, or L * 8 / W * ccap * 8 / W * pcap * 8 beyond 64 bits.
+ * ph_follow_plan_info: the launch shape for frames of N samples -- threads per workgroup, LDS bytes and the placement
+ * of the two states (PH_PLAN_LDS or PH_PLAN_HBM).  Nothing runs on the device. */
+int ph_follow(ph_ctx* ctx, const void* signal, int in_dtype, int64_t L, int N, int hop, int64_t W,
+              const double* window /* N or NULL */, int frame_dtype, const int32_t* periods /* (W, pcap) */,
+              const int32_t* counts /* W */, int pcap, int ccap, unsigned flags /* PH_FLAG_DEVICE | PH_FLAG_TRUNC */,
+              double* seg /* (W, ccap) */, double* powers /* (W, pcap) */, int32_t* done /* W */);
+int ph_follow_plan_info(ph_ctx* ctx, int N, int* block, int* lds_bytes, int* placement);
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,6 +44,13 @@ analogue of a spectrogram -- and ``contour`` the period of the recording at ever
     m = st.period_map(recording, kind="gamma")          # m.periods (P,), m.values (W, P)
     c = st.contour(recording, kind="gamma", band=8, jump=0.002)
     c.periods, c.salience, c.score
+
+``follow`` is the sound along such a track: one kernel cuts the frames from the recording itself and takes, frame by
+frame, the projection onto the period the track names there (``PeriodEngine.follow``), and the routed overlap-add of
+``decompose_qo`` tiles those single periods back onto the time axis -- no frames x samples array exists.
+
+    f = st.follow(recording, c)                         # or an edited c.periods, or a list of tracks
+    f.tracks, f.periodic, f.residual, f.powers
 """
 
 from __future__ import annotations
@@ -131,6 +138,20 @@ class ShortTimeContour(NamedTuple):
     salience: np.ndarray
     score: float
     map: Optional[ShortTimeMap] = None
+
+
+class ShortTimeFollow(NamedTuple):
+    """What ``ShortTime.follow`` returns: ``periods`` (W, T) int32 as given (column t is track t, an entry below 1 a
+    silent frame); ``powers`` (W, T) float64, the drop of the frame's residual norm when column t's period was peeled,
+    over the frame's norm, 0.0 where silent; ``tracks`` (T, L) the overlap-added, window-normalised waveform of every
+    track; ``periodic`` (L,) the same sum over all blocks, a routed row of its own and not a sum of tracks;
+    ``residual = float64(signal) - periodic``.  numpy arrays for a numpy signal, tensors for a tensor signal."""
+
+    periods: object
+    powers: object
+    tracks: object
+    periodic: object
+    residual: object
 
 
 _MAX_ROWS = 64  # rows per frame a 64-bit routing mask can name
@@ -609,6 +630,141 @@ class ShortTime:
         periods = (path + lo).cpu().numpy().astype(np.int32, copy=False)
         return ShortTimeContour(periods, sal.cpu().numpy(), float(score.item()),
                                 self._map_result(values, kind, lo, hi, on_device) if return_map else None)
+
+    def follow(self, signal, periods):
+        """The sound of a recording along a period track: from every frame the projection onto the period the track
+        names for that frame is taken (``Periods.project``, whole, sub-periods included) and the per-frame waveforms are
+        overlap-added -> ShortTimeFollow(periods, powers, tracks, periodic, residual).
+
+        `periods`: a ShortTimeContour, a (W,) or (W, T) integer array, an integer tensor on the engine's device, or a
+        list of any of these, whose columns are stacked in list order.  Column t is track t; in a frame the columns are
+        peeled left to right, each from what the ones before it left.  An entry below 1 means the track is silent in
+        that frame, e.g. ``np.where(c.salience > s, c.periods, 0)``.
+
+        The signal goes up once.  Each frame's live periods are packed to the front (``pack_tracks``), one ``ph_follow``
+        launch cuts the frames inside the kernel and leaves one period per block, and one routed overlap-add
+        (``PeriodEngine.overlap_add_periodic``, the window as analysis and synthesis window, normalised) tiles them onto
+        T + 1 rows: the tracks and ``periodic``.  Nothing of W x frame_length samples exists, so there is nothing to
+        block.  `trunc_to_integer_multiple` and `dtype` are honoured.  numpy in gives numpy out; a tensor signal gives
+        tensors, and only the two scalars of the checks below come down.
+
+        ValueError before anything is launched: a row count other than ``frame_count(L)``, T outside 1 .. 64, a period
+        above ``frame_length``, a non-integer dtype, or a ``ShortTime`` built with ``orthogonalize=True``."""
+        if self._orthogonalize:
+            raise ValueError("follow takes the whole projection, sub-periods included: build the ShortTime with "
+                             "orthogonalize=False")
+        x = self._signal(signal)
+        L, N = int(x.shape[0]), self.frame_length
+        W = self.frame_count(L)
+        per = self._follow_periods(periods, W)
+        T = int(per.shape[1])
+        packed, counts, masks, slot, live = self.pack_tracks(per)
+        ccap = max(1, int(packed.sum(1).max()))
+
+        import torch
+
+        eng = default_engine()
+        dev = torch.device("cuda", eng.device)
+        on_device = _is_torch(x)
+        if on_device:
+            if not x.is_cuda or x.device.index != eng.device:
+                raise ValueError(f"a tensor signal must live on cuda:{eng.device} (or pass a numpy array)")
+            xd = x.detach()
+            if xd.dtype not in (torch.float64, torch.float32):
+                xd = xd.to(torch.float64)
+            xd = xd.contiguous()
+        else:
+            xd = torch.as_tensor(x, device=dev)  # the one upload: L samples
+        if _is_torch(per):
+            if per.device != dev:
+                raise ValueError(f"tensor periods must live on cuda:{eng.device} (or pass a numpy array)")
+        else:
+            per, packed, counts, slot, live = (torch.as_tensor(a, device=dev) for a in (per, packed, counts, slot, live))
+            masks = torch.as_tensor(masks.view(np.int64), device=dev)
+        win = None if self.window is None else torch.as_tensor(self.window, device=dev)
+        tdt = torch.float64 if self.dtype == np.float64 else torch.float32
+        seg, pw, _ = eng.follow(xd, N, self.hop, W, packed, counts, ccap, win, tdt, self._trunc_to_integer_multiple)
+        rows = eng.overlap_add_periodic(seg, packed, counts, masks, N, self.hop, L, win, win, True)
+        powers = torch.where(live, torch.gather(pw, 1, slot.clamp(min=0)), torch.zeros((), dtype=torch.float64, device=dev))
+        if on_device:
+            return ShortTimeFollow(per, powers, rows[:T], rows[T], xd.to(torch.float64) - rows[T])
+        rows = rows.cpu().numpy()
+        return ShortTimeFollow(per.cpu().numpy(), powers.cpu().numpy(), rows[:T], rows[T], x.astype(np.float64) - rows[T])
+
+    def _follow_periods(self, periods, W):
+        """`periods` of ``follow`` as one (W, T) int32 array -- a tensor if any part is one -- or ValueError."""
+        cols = []
+        for it in (periods if isinstance(periods, list) else [periods]):
+            if isinstance(it, ShortTimeContour):
+                it = it.periods
+            if _is_torch(it):
+                if it.dtype.is_floating_point or it.dtype.is_complex or str(it.dtype) == "torch.bool":
+                    raise ValueError(f"periods must be integers, not {it.dtype}")
+                a = it.detach()
+            else:
+                a = np.asarray(it)
+                if a.dtype.kind not in "iu":
+                    raise ValueError(f"periods must be integers, not {a.dtype}")
+            if a.ndim == 1:
+                a = a.reshape(-1, 1)
+            if a.ndim != 2 or a.shape[0] != W:
+                raise ValueError(f"periods must be (W,) or (W, T) with W = frame_count(L) = {W} rows, "
+                                 f"not {tuple(a.shape)}")
+            cols.append(a)
+        T = sum(int(a.shape[1]) for a in cols)
+        if not 1 <= T <= _MAX_ROWS:
+            raise ValueError(f"T={T} tracks: follow takes 1 .. {_MAX_ROWS}")
+        tensors = [a for a in cols if _is_torch(a)]
+        if tensors:
+            import torch
+
+            dev = tensors[0].device
+            per = torch.cat([(a if _is_torch(a) else torch.as_tensor(np.ascontiguousarray(a).astype(np.int64), device=dev))
+                             .to(device=dev, dtype=torch.int64) for a in cols], 1)
+        else:
+            per = np.concatenate([a.astype(np.int64) if a.dtype != np.uint64 else np.minimum(a, 2**31 - 1).astype(np.int64)
+                                  for a in cols], 1)
+        hi = int(per.max())
+        if hi > self.frame_length:
+            raise ValueError(f"period {hi} is longer than a frame of {self.frame_length} samples")
+        if tensors:
+            return per.clamp(min=-(2**31)).to(torch.int32)
+        return np.maximum(per, -(2**31)).astype(np.int32)
+
+    @staticmethod
+    def pack_tracks(periods):
+        """The block layout of ``follow`` for a (W, T) integer array or tensor of per-frame periods, T <= 64: each
+        frame's live entries (>= 1) packed to the front in column order.  -> (packed (W, T) int32, zeros behind the
+        live ones; counts (W,) int32; masks (T + 1, W) -- np.uint64, or torch.int64 with the same bits -- bit a of
+        masks[t, f] set for the block a that column t became in frame f, row T naming every block; slot (W, T) int64,
+        the block of column t where it is live; live (W, T) bool).  numpy ops for an array, torch ops on the tensor's
+        device for a tensor."""
+        W, T = (int(v) for v in periods.shape)
+        live = periods >= 1
+        if _is_torch(periods):
+            import torch
+
+            slot = torch.cumsum(live.to(torch.int64), 1) - 1
+            counts = live.sum(1).to(torch.int32)
+            f, t = torch.nonzero(live, as_tuple=True)
+            packed = torch.zeros((W, T), dtype=torch.int32, device=periods.device)
+            packed[f, slot[f, t]] = periods[f, t].to(torch.int32)
+            bits = torch.where(live, torch.bitwise_left_shift(torch.ones_like(slot), slot.clamp(min=0)),
+                               torch.zeros_like(slot))
+            masks = torch.empty((T + 1, W), dtype=torch.int64, device=periods.device)
+            masks[:T] = bits.T
+            masks[T] = bits.sum(1)  # (distinct bits: the sum is their union, bit 63 included -- int64 wraps)
+            return packed, counts, masks, slot, live
+        slot = np.cumsum(live, 1, dtype=np.int64) - 1
+        counts = live.sum(1).astype(np.int32)
+        f, t = np.nonzero(live)
+        packed = np.zeros((W, T), dtype=np.int32)
+        packed[f, slot[f, t]] = periods[f, t]
+        bits = np.where(live, np.uint64(1) << np.maximum(slot, 0).astype(np.uint64), np.uint64(0))
+        masks = np.empty((T + 1, W), dtype=np.uint64)
+        masks[:T] = bits.T
+        masks[T] = bits.sum(1, dtype=np.uint64)
+        return packed, counts, masks, slot, live
 
     def decompose_qo(self, signal, num, thresh, min_length=2, max_length=None, update_weights=True, tracks=None,
                      max_tracks=8, max_rows=2048):

@@ -15,6 +15,7 @@
 #include "ph_kernels.h"
 #include "ph_fit.h"
 #include "ph_frames.h"
+#include "ph_follow.h"
 
 namespace {
 
@@ -1085,6 +1086,20 @@ int resolve_period_path(const ph_ctx* c, int64_t R, int64_t W, int P, int64_t ld
   *pp = PathPlan{ph::path_block(P), ph::path_states(P), L.tile, ph::path_row_bytes(P), L.bytes};
   if (pp->lds > (size_t)c->lds_limit)
     return fail(PH_E_ARG, "ph_period_path: P=%d needs %zu B of LDS, device limit is %d B", P, pp->lds, c->lds_limit);
+  return PH_OK;
+}
+
+// ph_follow: the sizes k_follow (ph_follow.h) takes and its launch shape -- threads, the carve's LDS bytes, and where the
+// two per-workgroup states (the residual frame, one period of means) live: in LDS while both fit the workgroup's limit
+// and PH_HBM_WINDOW is not set, otherwise in one slice per workgroup of an HBM workspace.  Both move together.
+struct FollowPlan {
+  int block, placement;
+  size_t lds;
+};
+int resolve_follow(const ph_ctx* c, int N, FollowPlan* fp) {
+  if (N < 1) return fail(PH_E_ARG, "ph_follow: N=%d must be >= 1", N);
+  const bool in_lds = !c->hbm_window && ph::follow_carve(ph::CarveCount(), N, true).bytes <= (size_t)c->lds_limit;
+  *fp = FollowPlan{ph::follow_block(N), in_lds ? PH_PLAN_LDS : PH_PLAN_HBM, ph::follow_carve(ph::CarveCount(), N, in_lds).bytes};
   return PH_OK;
 }
 
@@ -2842,6 +2857,65 @@ int ph_period_path(ph_ctx* c, const double* cost, int64_t R, int64_t W, int P, i
     case 8: rc = go(std::integral_constant<int, 8>{}); break;
   }
   PH_TRY(rc);
+  return st.finish();
+}
+
+// ----------------------------------------------------------------------------- extraction along a period track
+int ph_follow_plan_info(ph_ctx* c, int N, int* block, int* lds_bytes, int* placement) {
+  if (!c || !block || !lds_bytes || !placement) return fail(PH_E_ARG, "NULL argument");
+  FollowPlan fp;
+  PH_TRY(resolve_follow(c, N, &fp));
+  *block = fp.block;
+  *lds_bytes = (int)fp.lds;
+  *placement = fp.placement;
+  return PH_OK;
+}
+
+int ph_follow(ph_ctx* c, const void* signal, int in_dtype, int64_t L, int N, int hop, int64_t W, const double* window,
+              int frame_dtype, const int32_t* periods, const int32_t* counts, int pcap, int ccap, unsigned flags,
+              double* seg, double* powers, int32_t* done) {
+  if (!c) return fail(PH_E_ARG, "ctx is NULL");
+  if (!signal || !periods || !counts || !seg || !powers || !done)
+    return fail(PH_E_ARG, "ph_follow: signal / periods / counts / seg / powers / done is NULL");
+  if ((in_dtype != PH_F64 && in_dtype != PH_F32) || (frame_dtype != PH_F64 && frame_dtype != PH_F32))
+    return fail(PH_E_ARG, "ph_follow: in_dtype and frame_dtype must be PH_F64 or PH_F32");
+  PH_TRY(check_frame_walk("ph_follow", W, nullptr, N, hop, L));
+  if (pcap < 1 || pcap > ph::kFollowMaxBlocks)
+    return fail(PH_E_ARG, "ph_follow: pcap=%d must be in [1, %d] (blocks per frame a 64-bit mask can name)", pcap,
+                ph::kFollowMaxBlocks);
+  if (ccap < 1 || ccap > ph::kFollowMaxSeg) return fail(PH_E_ARG, "ph_follow: ccap=%d must be in [1, 2^24]", ccap);
+  // (W * pcap * 8 follows from W * 2^9 <= INT64_MAX / 8 < W * ccap's bound only for ccap >= 64: both are checked)
+  if (L > INT64_MAX / 8 || W > (INT64_MAX / 8) / ccap || W > (INT64_MAX / 8) / pcap)
+    return fail(PH_E_ARG, "ph_follow: L, W * ccap or W * pcap does not fit 64 bits");
+  FollowPlan fp;
+  PH_TRY(resolve_follow(c, N, &fp));
+  PH_HIP(hipSetDevice(c->device));
+  // workgroups walk the frames grid-stride: at most eight per CU (four when each brings a workspace slice of 16 N
+  // bytes), and the workspace is theirs, not the frames'
+  const unsigned grid =
+      (unsigned)std::min<int64_t>(W, (int64_t)std::max(1, c->num_cu) * (fp.placement == PH_PLAN_LDS ? 8 : 4));
+  void* gws;
+  PH_TRY(place(c, fp.placement, B_WS0, (size_t)grid * ph::follow_work_doubles(N) * sizeof(double), &gws));
+  Stage st(c, flags);
+  const void *ds, *dwin = nullptr, *dper, *dcnt, *dold;
+  void *dseg, *dpow, *ddone;
+  PH_TRY(st.in(signal, (size_t)L * elem_size(in_dtype), &ds));  // the signal once: L elements, no frames
+  if (window) PH_TRY(st.in(window, (size_t)N * sizeof(double), &dwin, B_GWIN));
+  PH_TRY(st.in(periods, (size_t)W * pcap * sizeof(int32_t), &dper, B_GEN0));
+  PH_TRY(st.in(counts, (size_t)W * sizeof(int32_t), &dcnt, B_GBUF));
+  // seg travels both ways, whole: the elements the kernel never writes come back as they went up
+  PH_TRY(st.in(seg, (size_t)W * ccap * sizeof(double), &dold, B_OUT0));
+  PH_TRY(st.out(B_OUT0, seg, (size_t)W * ccap * sizeof(double), &dseg));
+  PH_TRY(st.out(B_OUT1, powers, (size_t)W * pcap * sizeof(double), &dpow));
+  PH_TRY(st.out(B_OUT2, done, (size_t)W * sizeof(int32_t), &ddone));
+  const unsigned kflags = flags & PH_FLAG_TRUNC;
+  PH_TRY(dispatch(in_dtype, [&](auto ti) {
+    return dispatch(frame_dtype, fp.placement == PH_PLAN_LDS, [&](auto tf, auto lw) {
+      return launch(c, "k_follow", ph::k_follow<decltype(ti), decltype(tf), decltype(lw)::value>, dim3(grid), fp.block,
+                    fp.lds, (const decltype(ti)*)ds, L, N, hop, W, (const double*)dwin, (const int*)dper, (const int*)dcnt,
+                    pcap, ccap, kflags, (double*)gws, (double*)dseg, (double*)dpow, (int*)ddone);
+    });
+  }));
   return st.finish();
 }
 

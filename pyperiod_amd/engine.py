@@ -900,6 +900,61 @@ class PeriodEngine:
         return (path.reshape(lead + (W,)), None if values is None else values.reshape(lead + (W,)), score.reshape(lead),
                 status.reshape(lead))
 
+    # ------------------------------------------------------------------ extraction along a period track
+    def follow_plan(self, n):
+        """-> (threads per workgroup, LDS bytes, placement) of the k_follow launch for frames of n samples
+        (ph_follow_plan_info); placement is PH_PLAN_LDS or PH_PLAN_HBM: where the residual frame and the period of means
+        live.  Nothing runs on the device."""
+        block, lds, placement = C.c_int(0), C.c_int(0), C.c_int(0)
+        _ffi.check(self._lib.ph_follow_plan_info(self._ctx, int(n), C.byref(block), C.byref(lds), C.byref(placement)))
+        return block.value, lds.value, placement.value
+
+    def follow(self, signal, frame_length, hop, count, periods, counts, ccap, window=None, frame_dtype=None, trunc=False,
+               seg=None):
+        """The periodic components of a recording along per-frame periods (ph_follow, one launch): the frames of
+        ``frames(signal, frame_length, hop, count, window, frame_dtype)`` are cut inside the kernel -- no (W, N) array
+        exists -- and from frame f the projections onto periods[f, 0], periods[f, 1], ... are peeled one after the
+        other (``Periods.project(residual, p, trunc, False, return_single_period=True)``, then the subtraction).
+        -> (seg, powers, done): seg (W, ccap) float64 holds one period of every block, block a of frame f at
+        sum(periods[f, :a]) -- the layout qo_get_periods returns and overlap_add_periodic takes; powers (W, pcap) float64
+        the drop of the residual's periodic norm per block over the frame's norm, 0.0 behind done; done (W,) int32 the
+        blocks written.  A frame's walk ends at counts[f] blocks (clipped to 0 .. pcap) or at the first period < 1,
+        > frame_length or running past ccap; the elements of seg behind a frame's last block are never written (`seg`:
+        an existing (W, ccap) float64 array of the signal's kind to write into, None for a new one).
+        `periods` (W, pcap <= 64) and `counts` (W) int32, `window` None or frame_length float64 samples: numpy arrays,
+        or with a tensor signal tensors on its device (on torch's current stream; the results are then tensors).
+        `frame_dtype`: None (the signal's), float64 or float32 -- the dtype the frame is rounded to."""
+        if getattr(signal, "ndim", None) != 1:
+            raise ValueError("expected a 1-D signal")
+        x, code, _, L, fl, mk = self._prep(signal.reshape(1, -1))
+        N, hop, W, ccap = int(frame_length), int(hop), int(count), int(ccap)
+        if W < 0:
+            raise ValueError("count must be >= 0")
+        fcode = self._dtype_code(mk, frame_dtype, code)
+        per = _side(mk, x, periods, np.int32, "periods", "signal")
+        if per.ndim != 2 or per.shape[0] != W or per.shape[1] < 1:
+            raise ValueError("periods must be (W, pcap) with pcap >= 1")
+        pcap = int(per.shape[1])
+        cnt = _side(mk, x, counts, np.int32, "counts", "signal")
+        if tuple(cnt.shape) != (W,):
+            raise ValueError("counts must hold one entry per frame")
+        win = None if window is None else self._window(mk, x, window, N)
+        if seg is None:
+            seg = mk.empty((W, max(ccap, 0)), np.float64)
+        else:
+            if _is_torch(seg) != mk.torch or (mk.torch and (seg.dtype != mk._t.float64 or seg.device != x.device)) or (
+                    not mk.torch and (not isinstance(seg, np.ndarray) or seg.dtype != np.float64)):
+                raise TypeError("seg must be a float64 array of the signal's kind, on its device")
+            ok = seg.is_contiguous() if mk.torch else (seg.flags.c_contiguous and seg.flags.writeable)
+            if tuple(seg.shape) != (W, ccap) or not ok:
+                raise ValueError("seg must be contiguous (and writable), of shape (W, ccap)")
+        powers = mk.empty((W, pcap), np.float64)
+        done = mk.empty((W,), np.int32)
+        self._call(mk, W, self._lib.ph_follow, mk.addr(x), code, L, N, hop, W, mk.addr(win), fcode, mk.addr(per),
+                   mk.addr(cnt), pcap, ccap, fl | (_ffi.PH_FLAG_TRUNC if trunc else 0), mk.addr(seg), mk.addr(powers),
+                   mk.addr(done))
+        return seg, powers, done
+
     def fold_sums(self, x, p_list, keep):
         """W = A x for natural-basis rows (QOPeriods.py:782): (W, sum(keep)) float64."""
         x, code, W, N, fl, mk = self._prep(x)

@@ -221,6 +221,7 @@ def best_correlation(data, num=5, max_length=None, ratio=0.01, trunc=False, orth
         second = 0.0  # test tooling (trace) only
         for p in range(2, max_length):  # EXCLUSIVE upper bound, :324
             col = np.abs(fold_sums(work, p))
+            col = np.where(col == col, col, -1.0)  # `cor > max_cor` is False for a NaN sum: the scan passes over it
             s = int(np.argmax(col))  # first maximum == strict '>' scan over s, :327-331
             if col[s] > best_cor:
                 best_cor, best_p, second = col[s], p, best_cor

@@ -37,8 +37,9 @@ def _raise_status(status, what):
     status = np.asarray(status)
     if np.any(status == _ffi.PH_ST_NO_PERIOD):
         # reference: max_base stays None -> TypeError at Periods.py:520/537 (project(data, None)
-        # at Periods.py:334 for best_correlation)
-        raise TypeError(f"{what}: no candidate period has a positive norm (all-zero or NaN window)")
+        # at Periods.py:334 for best_correlation).  A window with a single NaN or Inf is no such case for
+        # best_correlation: its strict '>' passes over the NaN sums, a finite one wins and the rows stay zero.
+        raise TypeError(f"{what}: no candidate period has a positive norm (an all-zero window, or every sum NaN)")
     if np.any(status == _ffi.PH_ST_ITER_CAP):
         raise RuntimeError(f"{what}: iteration bound reached before `num` periods were found")
 

@@ -1262,7 +1262,7 @@ class ShortTime:
             # the spectral peak was bin 0: the reference evaluates 2 * win_size / 0 and int(round(inf))
             raise OverflowError(f"cannot convert float infinity to integer (frame {_first(status != _ffi.PH_ST_OK)})")
         if np.any(status == _ffi.PH_ST_NO_PERIOD):
-            raise TypeError(f"{method}: no candidate period has a positive norm (all-zero or NaN window) in frame "
+            raise TypeError(f"{method}: no candidate period has a positive norm (an all-zero window, or every sum NaN) in frame "
                             f"{_first(status == _ffi.PH_ST_NO_PERIOD)}")
         if np.any(status == _ffi.PH_ST_ITER_CAP):
             raise RuntimeError(f"{method}: iteration bound reached before `num` periods were found in frame "

@@ -97,7 +97,10 @@ __global__ __launch_bounds__(kBlockWide) __attribute__((amdgpu_waves_per_eu(PH_S
         ctl->nsurv = 0;
       }
       __syncthreads();
-      {
+      // A NaN or Inf sample leaves no bound to screen with: every period exactly, as after a list overflow.  The
+      // reference's strict '>' passes over a NaN sum and takes the first infinite one (:329).
+      const bool screen = asum <= 1.7976931348623157e308;
+      if (screen) {
         const double radius = 4.0 * 1.1102230246251565e-16 * asum;  // 4 * 2^-53 * sum|x| per row
         double lrun = 0.0;
         wave_sweep_plan<T, LW, true>(work, N, geom, plan, wv, n_pass, nw, lane, [&](double v, int q) {
@@ -118,7 +121,7 @@ __global__ __launch_bounds__(kBlockWide) __attribute__((amdgpu_waves_per_eu(PH_S
         });
       }
       __syncthreads();
-      const int ncand = ctl->ncand;
+      const int ncand = screen ? ctl->ncand : kCandCap + 1;
       double best = 0.0;
       int bestp = 0;
       auto exact = [&](int q) {  // row-order sums, bit-identical to the reference's sum(x[s::q])
@@ -146,7 +149,7 @@ __global__ __launch_bounds__(kBlockWide) __attribute__((amdgpu_waves_per_eu(PH_S
         __syncthreads();
         const int ns = ctl->nsurv;
         for (int k = wv; k < ns; k += nw) exact(cand_q[k]);
-      } else {  // list overflow (many near-ties): every period exactly
+      } else {  // list overflow (many near-ties) or no screen: every period exactly
         for (int q = 2 + wv; q <= max_length - 1; q += nw) exact(q);
       }
       if (!(best > 0.0)) bestp = 0;

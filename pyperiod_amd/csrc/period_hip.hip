@@ -84,6 +84,7 @@ struct ph_ctx {
   bool pair_duo = true;    // PH_PAIR_DUO=0: the window-pair m_best screen folds every period in a pass of its own
   bool pair_fold_once = true;  // PH_PAIR_FOLD_ONCE=0: k_mbest_step1_pair stages, thins and evaluates every window-sweep as before the fold-once path
   bool pair_fold_report = false;  // PH_PAIR_FOLD_REPORT=1 (tests): n_sweeps carries the window's fold-once count above bit 16
+  bool step2_geom = true;  // PH_STEP2_GEOM=0: k_mbest_step2 rebuilds each factor's fold geometry instead of reading the table's
   DevBuf twid;  // cos/sin(2 pi k / L), k < L, of the last best_frequency win_size
   int twid_len = -1;
   DevBuf bs_tab;  // Bluestein tables of the last (win_size, min(N, win_size)): M twiddles, chirp, FFT of the wrapped chirp
@@ -1193,6 +1194,7 @@ int ph_create(int device, ph_ctx** out) {
   if (const char* e = std::getenv("PH_PAIR_DUO")) c->pair_duo = std::atoi(e) != 0;
   if (const char* e = std::getenv("PH_PAIR_FOLD_ONCE")) c->pair_fold_once = std::atoi(e) != 0;
   if (const char* e = std::getenv("PH_PAIR_FOLD_REPORT")) c->pair_fold_report = std::atoi(e) != 0;
+  if (const char* e = std::getenv("PH_STEP2_GEOM")) c->step2_geom = std::atoi(e) != 0;
   if (const char* e = std::getenv("PH_STEP1_BLOCK")) {
     const int v = std::atoi(e);
     if (v >= 64 && v <= 1024 && v % 64 == 0) c->step1_block = v;
@@ -1664,7 +1666,7 @@ int ph_m_best(ph_ctx* c, const void* x, int dtype, int64_t W, int N, int num, in
   PH_TRY(dispatch(dtype, !gwin2, [&](auto t, auto lw) {
     using T = decltype(t);
     return launch(c, "k_mbest_step2", ph::k_mbest_step2<T, decltype(lw)::value>, grid, s2.block, s2.lds, N, num, gamma,
-                  max_length, kflags, tb, geom, max_fac, (T*)gbuf2, (T*)gwin2, (uint32_t*)dper, (double*)dpow, (T*)dbases,
+                  max_length, kflags | (c->step2_geom ? ph::kStep2Geom : 0u), tb, geom, max_fac, (T*)gbuf2, (T*)gwin2, (uint32_t*)dper, (double*)dpow, (T*)dbases,
                   dnorm, (const int*)dstat, (T*)drows, row_stride);
   }));
   return st.finish();

@@ -1207,6 +1207,9 @@ constexpr bool kS2LTimers = PH_SWITCH(PH_S2L_TIMERS);
 constexpr bool kQoTimers = PH_SWITCH(PH_QO_TIMERS);
 constexpr bool kFitTimers = PH_SWITCH(PH_FIT_TIMERS);
 constexpr bool kClocks = PH_SWITCH(PH_CLOCKS);
+#ifndef PH_STEP2_TIMERS_EVERY
+#define PH_STEP2_TIMERS_EVERY 128  // every how many workgroups of k_mbest_step2 one prints its timers
+#endif
 #ifndef PH_PAIR_TIMERS_WGS
 #define PH_PAIR_TIMERS_WGS 6  // workgroups of k_mbest_step1_pair that print their timers
 #endif

@@ -1044,6 +1044,9 @@ __device__ __forceinline__ PGeom make_geom(int N, int p) {
 }
 
 constexpr int kStep2Pre = 3;  // a staged row has at most 3 elements per thread (p <= 3 * blockDim)
+// bit of k_mbest_step2's `flags` beside kTrunc / kOrth: a factor's fold geometry is read from the host's table
+// (PH_STEP2_GEOM=0 clears it: lane 0 rebuilds it per factor and hands it over through LDS)
+constexpr unsigned kStep2Geom = 0x100u;
 typedef __attribute__((address_space(3))) void* lds_void_ptr;
 typedef const __attribute__((address_space(1))) void* global_void_ptr;
 
@@ -1132,21 +1135,22 @@ __global__ __launch_bounds__(kBlockWide) __attribute__((amdgpu_waves_per_eu(PH_S
   zero_pad(rowbuf, N);
   __syncthreads();
 
-  StageClock<kStep2Timers, 6, 2> clk;  // stages: as printed below; counters: rows, splits
+  StageClock<kStep2Timers, 7, 2> clk;  // stages: as printed below; counters: rows, splits
   const int gdiv = gamma ? stale_p : 0;
   int i = (status[w] == 0) ? 0 : num;  // a window whose step 1 failed is passed through
   // a row whose period has no proper divisor (a prime) has nothing to test and is not even read
-  auto next_row = [&](int r) {
+  auto next_row = [&](int r) {  // (the same in every lane: scalar, and the row loop's branches with it)
     while (r < num && fa[r] == fb[r]) ++r;
-    return r;
+    return __builtin_amdgcn_readfirstlane(r);
   };
   // The rows are short and known one row ahead: the next row's elements and divisor list are copied
   // HBM -> LDS by LDS-DMA (global_load_lds: no registers, the 64-VGPR fold code has none to spare) into the
   // unused upper part of rowbuf while the current row is folded -- the loop is otherwise a chain of dependent
-  // HBM round trips (row, divisor list, geometry) per row.  The barrier behind the folds drains the DMA
-  // (hipcc waits vmcnt(0) before __syncthreads).
-  const T* stage = nullptr;
-  int stage_row = -1;
+  // HBM round trips (row, divisor list, geometry) per row.  The explicit s_waitcnt vmcnt(0) in front of the barrier
+  // behind the folds drains the DMA: hipcc puts only lgkmcnt(0) in front of a __syncthreads of this kernel (its
+  // other barriers do not wait for the tile-out stores).  On gfx950 vmcnt counts loads and stores alike, and the
+  // compiler's wait for a load behind stores is vmcnt(0): it waits for the stores in flight as well.
+  int stage_row = -1, stage_at = 0;  // the staged row and its offset in rowbuf
   // The (num, N) matrix is written exactly once, in final order: logical rows below the loop position can
   // no longer change (a split inserts at i and moves rows >= i only), so they are tiled out as the loop
   // passes them -- the stores drain while the next rows are folded.  Rows step 1 never filled (period 0)
@@ -1167,7 +1171,13 @@ __global__ __launch_bounds__(kBlockWide) __attribute__((amdgpu_waves_per_eu(PH_S
   i = next_row(i);
   clk.mark(0);
   while (i < num) {
-    const int per = (int)periods[i];
+    // The thread's LDS and table addresses below are loop invariants, which the compiler computes once in front of
+    // the loop and -- at the 64-VGPR cap of the fold code -- spills: every use then waits for a reload from scratch,
+    // a memory round trip behind vmcnt(0) (the tile-out stores in flight included), a dozen per row.  Through an
+    // opaque copy of the thread index per iteration each address is one or two vector instructions instead.
+    int t = tid, ln = lane;
+    asm volatile("" : "+v"(t), "+v"(ln));
+    const int per = __builtin_amdgcn_readfirstlane((int)periods[i]);  // (uniform: what follows from it stays scalar)
     const int a = fa[i], b = fb[i];
     const T* src = rows + (int64_t)slot[i] * row_stride;
     // v[k] = cnt_p[k] m[k] for k < per, then zeros for the extra row and the tail reads of the last group
@@ -1177,46 +1187,46 @@ __global__ __launch_bounds__(kBlockWide) __attribute__((amdgpu_waves_per_eu(PH_S
       const PGeom gp = make_geom(N, per);
       const double cf = (double)gp.rows, cs = (double)(gp.rows - 1);
       if (stage_row == i) {  // the staging area may overlap [0, zend): read, barrier, write
-        double t[kStep2Pre];
+        double el[kStep2Pre];
 #pragma unroll
         for (int u = 0; u < kStep2Pre; ++u) {
-          const int k = tid + u * blockDim.x;
-          t[u] = k < per ? (double)stage[k] : 0.0;
+          const int k = t + u * blockDim.x;
+          el[u] = k < per ? (double)rowbuf[stage_at + k] : 0.0;
         }
         __syncthreads();
 #pragma unroll
         for (int u = 0; u < kStep2Pre; ++u) {
-          const int k = tid + u * blockDim.x;
-          if (k < zend) rowbuf[k] = (T)(t[u] * (k < gp.nfull ? cf : cs));
+          const int k = t + u * blockDim.x;
+          if (k < zend) rowbuf[k] = (T)(el[u] * (k < gp.nfull ? cf : cs));
         }
-        for (int k = tid + kStep2Pre * blockDim.x; k < zend; k += blockDim.x) rowbuf[k] = T(0);
-        if (tid < b - a) ffac[tid] = ffac_next[tid];
+        for (int k = t + kStep2Pre * blockDim.x; k < zend; k += blockDim.x) rowbuf[k] = T(0);
+        if (t < b - a) ffac[t] = ffac_next[t];
       } else {
-        for (int k = tid; k < zend; k += blockDim.x)
+        for (int k = t; k < zend; k += blockDim.x)
           rowbuf[k] = (T)(k < per ? (double)src[k] * (k < gp.nfull ? cf : cs) : 0.0);
-        if (tid < b - a) ffac[tid] = tb.fac_q[a + tid];
+        if (t < b - a) ffac[t] = tb.fac_q[a + t];
       }
     } else {  // fp32 rows, trunc / orth modes, periods beyond 2N/3: the tiled row itself
       expand_row(src, per, rowbuf, N);
-      if (!general && tid < b - a) ffac[tid] = tb.fac_q[a + tid];
+      if (!general && t < b - a) ffac[t] = tb.fac_q[a + t];
     }
     __syncthreads();
     clk.mark(1);
     const int inext = next_row(i + 1);
     stage_row = -1;
     if (LW && short_row && inext < num) {  // LW == false: rowbuf is an HBM workspace, nothing to stage into
-      const int pn = (int)periods[inext];
+      const int pn = __builtin_amdgcn_readfirstlane((int)periods[inext]);
       const int so = (zend + 1) & ~1;          // 16-byte aligned, behind everything the folds of row i read
       const int npieces = (pn + 127) >> 7;     // 64 lanes x 16 B = 128 doubles per wave instruction
       if (pn <= kStep2Pre * (int)blockDim.x && pn + (pn >> 1) + 256 <= N + kPad && so + 128 * npieces <= N &&
           128 * npieces <= row_stride && fb[inext] - fa[inext] <= 64) {
         const T* srcn = rows + (int64_t)slot[inext] * row_stride;  // 128 * npieces <= row_stride: stays inside the row
         for (int j = wv; j < npieces; j += nw)
-          __builtin_amdgcn_global_load_lds((global_void_ptr)(srcn + 128 * j + 2 * lane),
+          __builtin_amdgcn_global_load_lds((global_void_ptr)(srcn + 128 * j + 2 * ln),
                                            (lds_void_ptr)(rowbuf + so + 128 * j), 16, 0, 0);
         if (wv == nw - 1)  // reads up to 63 words behind the list: the device table has that slack
-          __builtin_amdgcn_global_load_lds((global_void_ptr)(tb.fac_q + fa[inext] + lane), (lds_void_ptr)ffac_next, 4, 0, 0);
-        stage = rowbuf + so;
+          __builtin_amdgcn_global_load_lds((global_void_ptr)(tb.fac_q + fa[inext] + ln), (lds_void_ptr)ffac_next, 4, 0, 0);
+        stage_at = __builtin_amdgcn_readfirstlane(so);
         stage_row = inext;
       }
     }
@@ -1225,23 +1235,37 @@ __global__ __launch_bounds__(kBlockWide) __attribute__((amdgpu_waves_per_eu(PH_S
     if (!general) {
       // one wavefront per factor: ||P_f row||^2 = sum_j S_f[j]^2 / cnt_f[j]
       for (int k = wv; k < b - a; k += nw) {
-        const int f = ffac[k];
-        // one call site for both row forms (a second inlined copy of the fold costs spills): the geometry sits
-        // in this wavefront's LDS slot.  Compact row: a "window" of length per with per / f rows per residue,
-        // weights by the real counts of f (rows + 1: see the header; the f < 64 path ignores `rows`).
-        if (lane == 0) {
-          PGeom g;
-          if (short_row) {
-            g = make_geom(N, f);
-            g.rows = per / f + 1;
-          } else {
-            g = geom[f];
+        // one call site for both row forms (a second inlined copy of the fold costs spills).  Compact row: a
+        // "window" of length per with per / f rows per residue, weights by the real counts of f (rows + 1: see
+        // the header; the f < 64 path ignores `rows`).
+        PGeom g;
+        int f;
+        if (flags & kStep2Geom) {  // geom[f] holds make_geom(N, f) bit for bit (prepare_geom: the same expressions): scalar loads
+          f = __builtin_amdgcn_readfirstlane(ffac[k]);
+          g = geom[f];
+          if (short_row) g.rows = per / f + 1;
+        } else {  // lane 0 builds the geometry and hands it over in this wavefront's LDS slot
+          f = ffac[k];
+          if (lane == 0) {
+            PGeom g0;
+            if (short_row) {
+              g0 = make_geom(N, f);
+              g0.rows = per / f + 1;
+            } else {
+              g0 = geom[f];
+            }
+            fgeom[wv] = g0;
           }
-          fgeom[wv] = g;
+          ram_wave_sync();
+          const PGeom gl = fgeom[wv];  // (into scalar registers, where the table's copy arrives too)
+          g.rows = __builtin_amdgcn_readfirstlane(gl.rows);
+          g.nfull = __builtin_amdgcn_readfirstlane(gl.nfull);
+          g.w_full = uniform_f64(gl.w_full);
+          g.w_short = uniform_f64(gl.w_short);
+          f = __builtin_amdgcn_readfirstlane(f);
+          ram_wave_sync();  // the slot is rewritten for this wavefront's next factor
         }
-        ram_wave_sync();
-        const double ss = wave_sum(wave_partial<T, false, LW>(rowbuf, short_row ? per : N, f, fgeom[wv], lane));
-        ram_wave_sync();  // the slot is rewritten for this wavefront's next factor
+        const double ss = wave_sum(wave_partial<T, false, LW>(rowbuf, short_row ? per : N, f, g, lane));
         if (lane == 0) fvals[k] = periodic_norm_from_sq(ss, N, gdiv);
       }
       clk.mark(2);
@@ -1304,9 +1328,9 @@ __global__ __launch_bounds__(kBlockWide) __attribute__((amdgpu_waves_per_eu(PH_S
       T* dst = rows + (int64_t)s_last * row_stride;  // i == num - 1: the split row itself falls off
       if (i + 1 < num) {
         T* rem = rows + (int64_t)s_here * row_stride;
-        for (int k = tid; k < per; k += blockDim.x) rem[k] = rowbuf[k] - buf[k];
+        for (int k = t; k < per; k += blockDim.x) rem[k] = rowbuf[k] - buf[k];
       }
-      for (int k = tid; k < topf; k += blockDim.x) dst[k] = buf[k];
+      for (int k = t; k < topf; k += blockDim.x) dst[k] = buf[k];
     }
     if (tid == 0) {
       for (int r = num - 1; r >= i + 2; --r) {
@@ -1332,13 +1356,14 @@ __global__ __launch_bounds__(kBlockWide) __attribute__((amdgpu_waves_per_eu(PH_S
     __threadfence_block();
     __syncthreads();
     i = next_row(i);  // the new row i is examined next: i is not advanced (:581-594)
+    clk.mark(5);
   }
   __syncthreads();
   flush_rows(num);
-  clk.mark(5);
-  if (kStep2Timers && (blockIdx.x % 128) == 5 && tid == 0)
-    printf("step2 wg %d (100 MHz ticks): init %lld stage %lld folds %lld dma+barrier %lld flush+scan %lld rest(split,final flush) %lld total %lld rows %d splits %d\n",
-           (int)blockIdx.x, clk.ticks(0), clk.ticks(1), clk.ticks(2), clk.ticks(3), clk.ticks(4), clk.ticks(5), clk.total(), clk.counted(0), clk.counted(1));
+  clk.mark(6);
+  if (kStep2Timers && (blockIdx.x % PH_STEP2_TIMERS_EVERY) == 5 % PH_STEP2_TIMERS_EVERY && tid == 0)
+    printf("step2 wg %d (100 MHz ticks): init %lld stage %lld folds %lld dma+barrier %lld flush+scan %lld split %lld final flush %lld total %lld rows %d splits %d\n",
+           (int)blockIdx.x, clk.ticks(0), clk.ticks(1), clk.ticks(2), clk.ticks(3), clk.ticks(4), clk.ticks(5), clk.ticks(6), clk.total(), clk.counted(0), clk.counted(1));
   const double dn = dnorm[w];
   for (int k = tid; k < num; k += blockDim.x) {
     periods_io[w * num + k] = periods[k];

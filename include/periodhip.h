@@ -694,6 +694,29 @@ int ph_follow(ph_ctx* ctx, const void* signal, int in_dtype, int64_t L, int N, i
               double* seg /* (W, ccap) */, double* powers /* (W, pcap) */, int32_t* done /* W */);
 int ph_follow_plan_info(ph_ctx* ctx, int N, int* block, int* lds_bytes, int* placement);
 
+/* ph_follow_residual: the frames of a recording less the tracks named for them -- what ph_follow
+ * leaves of each frame after its peels, which ph_follow itself throws away.  Row i of `out` belongs to frame f0 + i:
+ *   x[j] = (double)(frame_dtype)((double)signal[(f0 + i) * hop + j] * window[j]) for (f0 + i) * hop + j < L, else 0
+ *   C_i = counts[i] clipped to [0, pcap];  r_0 = x
+ *   for a = 0 .. C_i - 1, p = periods[i, a]; the walk of the frame stops at the first block with p < 1 or p > N
+ *   (there is no ccap), otherwise
+ *     s = project(r_a, p, trunc, False, return_single_period=True)   residues added in row order, one division
+ *     r_{a+1}[j] = r_a[j] - s[j mod p]                                one rounded subtraction per sample
+ *   out[i, j] = r_C[j] for every j < N, C the blocks peeled (none: x itself, the row ph_frames writes, as double).
+ * One launch (k_follow_residual): the body, launch shape and placement of k_follow (ph_follow_plan_info reports them),
+ * compiled without the segment, powers and done outputs and hence without their sums of squares and reductions; the
+ * cut, the means and the subtractions are the same statements, so `out` is ph_follow's residual bit for bit.
+ * periods (Wb, pcap) and counts (Wb) are local to the block; pcap == 0: both may be NULL and the call is a float64
+ * ph_frames of the block.  Wb * N and f0 * hop may exceed 2^31.  Non-finite samples propagate; no status word.
+ * flags: PH_FLAG_DEVICE | PH_FLAG_TRUNC.  Every array follows PH_FLAG_DEVICE; the host-pointer form uploads the whole
+ * signal.  PH_E_ARG, before any HIP call, for a NULL ctx / signal / out, NULL periods / counts with pcap > 0, an unknown
+ * dtype, N, hop, L or Wb < 1, f0 < 0, (f0 + Wb - 1) * hop >= L, pcap outside 0 .. 64, or Wb * N * 8 / L * 8 /
+ * Wb * pcap * 4 beyond 64 bits. */
+int ph_follow_residual(ph_ctx* ctx, const void* signal, int in_dtype, int64_t L, int N, int hop, int64_t f0, int64_t Wb,
+                       const double* window /* N or NULL */, int frame_dtype,
+                       const int32_t* periods /* (Wb, pcap), block-local */, const int32_t* counts /* Wb */, int pcap,
+                       unsigned flags /* PH_FLAG_DEVICE | PH_FLAG_TRUNC */, double* out /* (Wb, N) */);
+
 #ifdef __cplusplus
 }
 #endif

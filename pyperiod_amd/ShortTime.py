@@ -51,6 +51,14 @@ frame, the projection onto the period the track names there (``PeriodEngine.foll
 
     f = st.follow(recording, c)                         # or an edited c.periods, or a list of tracks
     f.tracks, f.periodic, f.residual, f.powers
+
+``contours`` finds the tracks of several sources by peeling: round k takes the best path through the map of what the
+tracks before it left of every frame (``PeriodEngine.follow_residual``: ``follow``'s kernel, keeping the residual frames
+it otherwise throws away), so the tracks are tracks of exactly what ``follow`` then extracts.
+
+    cs = st.contours(recording, 2, kind="gamma", band=8, jump=0.002)
+    cs.periods, cs.salience, cs.scores                  # (W, 2), (W, 2), (2,)
+    st.follow(recording, cs).tracks                     # (2, L)
 """
 
 from __future__ import annotations
@@ -138,6 +146,18 @@ class ShortTimeContour(NamedTuple):
     salience: np.ndarray
     score: float
     map: Optional[ShortTimeMap] = None
+
+
+class ShortTimeContours(NamedTuple):
+    """What ``ShortTime.contours`` returns: column k of ``periods`` (W, K) int32 is the period track of round k -- the
+    best path through the map of what the tracks before it left of every frame -- and 0 where `floor` silenced it;
+    ``salience`` (W, K) float64 is that round's map along its path (kept where the track is silent); ``scores`` (K,)
+    float64 the paths' scores; ``maps`` the K ShortTimeMap when they were asked for, map k as round k's path saw it."""
+
+    periods: np.ndarray
+    salience: np.ndarray
+    scores: np.ndarray
+    maps: Optional[tuple] = None
 
 
 class ShortTimeFollow(NamedTuple):
@@ -519,16 +539,40 @@ class ShortTime:
             raise ValueError(f"kind={kind!r} has no projection that trunc_to_integer_multiple / orthogonalize could apply to")
         return lo, hi
 
-    def _map_plan(self, eng, kind, lo, hi):
+    def _map_plan(self, eng, kind, lo, hi, dtype=None):
         """The kind's kernel asked whether it takes frames of this length and this range (the plan query of its entry
-        point: its own refusals, raised as ValueError, and nothing launched)."""
+        point: its own refusals, raised as ValueError, and nothing launched).  `dtype`: the frames' (None: ``dtype``)."""
         trunc, orth = self._trunc_to_integer_multiple, self._orthogonalize
+        dtype = self.dtype if dtype is None else dtype
         if kind in ("norm", "gamma"):
-            eng.plan_info("sweep", self.frame_length, (lo, hi, _MAP_KINDS[kind]), self.dtype, trunc, orth)
+            eng.plan_info("sweep", self.frame_length, (lo, hi, _MAP_KINDS[kind]), dtype, trunc, orth)
         elif kind == "orth":
-            eng.plan_info("orth_powers", self.frame_length, (hi + 1,), self.dtype)
+            eng.plan_info("orth_powers", self.frame_length, (hi + 1,), dtype)
         else:
-            eng.plan_info("ramanujan", self.frame_length, (lo, hi), self.dtype)
+            eng.plan_info("ramanujan", self.frame_length, (lo, hi), dtype)
+
+    def _map_rows(self, eng, fr, kind, lo, hi):
+        """(Wb, P): the columns lo .. hi of the kind's table for the frames `fr`, a view where the table is wider."""
+        if kind in ("norm", "gamma"):
+            return eng.sweep(fr, lo, hi, _MAP_KINDS[kind], self._trunc_to_integer_multiple, self._orthogonalize)
+        if kind == "orth":
+            return eng.orth_powers(fr, hi + 1, normalize=True)[:, lo : hi + 1]
+        return eng.ramanujan_norms(fr, lo, hi)[:, lo : hi + 1]
+
+    @staticmethod
+    def _device_signal(x, eng):
+        """The signal of ``_signal`` on the engine's device: -> (tensor, whether it came as one).  A numpy signal goes
+        up here, once; a tensor on the engine's device is used where it lies."""
+        import torch
+
+        if not _is_torch(x):
+            return torch.as_tensor(x, device=torch.device("cuda", eng.device)), False  # the one upload: L samples
+        if not x.is_cuda or x.device.index != eng.device:
+            raise ValueError(f"a tensor signal must live on cuda:{eng.device} (or pass a numpy array)")
+        xd = x.detach()
+        if xd.dtype not in (torch.float64, torch.float32):
+            xd = xd.to(torch.float64)
+        return xd.contiguous(), True
 
     def _map(self, signal, kind, lo, hi, B):
         """The (W, P) map of `signal` on the device and whether the signal came as a device tensor.  The signal goes up
@@ -540,33 +584,15 @@ class ShortTime:
         eng = default_engine()
         self._map_plan(eng, kind, lo, hi)
         dev = torch.device("cuda", eng.device)
-        on_device = _is_torch(x)
-        if on_device:
-            if not x.is_cuda or x.device.index != eng.device:
-                raise ValueError(f"a tensor signal must live on cuda:{eng.device} (or pass a numpy array)")
-            xd = x.detach()
-            if xd.dtype not in (torch.float64, torch.float32):
-                xd = xd.to(torch.float64)
-            xd = xd.contiguous()
-        else:
-            xd = torch.as_tensor(x, device=dev)  # the one upload: L samples
+        xd, on_device = self._device_signal(x, eng)
         W = self.frame_count(xd.shape[0])
         win = None if self.window is None else torch.as_tensor(self.window, device=dev)
         rec = _Recording(xd, W, eng, xd, win, torch.float64 if self.dtype == np.float64 else torch.float32)
-        trunc, orth = self._trunc_to_integer_multiple, self._orthogonalize
-
-        def rows(fr):  # (Wb, P): the columns lo .. hi of the kind's table, a view where the table is wider
-            if kind in ("norm", "gamma"):
-                return eng.sweep(fr, lo, hi, _MAP_KINDS[kind], trunc, orth)
-            if kind == "orth":
-                return eng.orth_powers(fr, hi + 1, normalize=True)[:, lo : hi + 1]
-            return eng.ramanujan_norms(fr, lo, hi)[:, lo : hi + 1]
-
         if B is None or B >= W:
-            return rows(self._frames(rec, 0, W)), on_device
+            return self._map_rows(eng, self._frames(rec, 0, W), kind, lo, hi), on_device
         values = torch.empty((W, hi - lo + 1), dtype=torch.float64, device=dev)
         for f0 in range(0, W, B):
-            values[f0 : f0 + B] = rows(self._frames(rec, f0, min(B, W - f0)))
+            values[f0 : f0 + B] = self._map_rows(eng, self._frames(rec, f0, min(B, W - f0)), kind, lo, hi)
         return values, on_device
 
     def period_map(self, signal, kind="gamma", min_length=2, max_length=None, block_frames=None):
@@ -611,6 +637,18 @@ class ShortTime:
         has no finite value (a NaN sample in a frame makes its whole row NaN)."""
         B = self._block_frames(block_frames)
         lo, hi = self._map_args(kind, min_length, max_length)
+        band, jump = self._path_args(band, jump, lo, hi)
+        values, on_device = self._map(signal, kind, lo, hi, B)
+        path, sal, score, status = default_engine().period_path(values, band, jump)
+        if int(status.item()) != _ffi.PH_ST_OK:
+            self._no_path("contour", values, band)
+        periods = (path + lo).cpu().numpy().astype(np.int32, copy=False)
+        return ShortTimeContour(periods, sal.cpu().numpy(), float(score.item()),
+                                self._map_result(values, kind, lo, hi, on_device) if return_map else None)
+
+    @staticmethod
+    def _path_args(band, jump, lo, hi):
+        """The refusals of the path through a map of the periods lo .. hi that need no engine: -> (band, jump)."""
         if isinstance(band, bool) or not isinstance(band, (int, np.integer)) or not 0 <= int(band) <= _PATH_MAX_BAND:
             raise ValueError(f"band={band!r} must be an int in 0 .. {_PATH_MAX_BAND}")
         if isinstance(jump, bool) or not isinstance(jump, (int, float, np.integer, np.floating)) or not (
@@ -618,25 +656,119 @@ class ShortTime:
             raise ValueError(f"jump={jump!r} must be finite and >= 0")
         if hi - lo + 1 > _PATH_MAX_PERIODS:
             raise ValueError(f"{hi - lo + 1} periods: the path kernel takes at most {_PATH_MAX_PERIODS}")
-        values, on_device = self._map(signal, kind, lo, hi, B)
-        path, sal, score, status = default_engine().period_path(values, int(band), float(jump))
-        if int(status.item()) != _ffi.PH_ST_OK:
-            import torch
+        return int(band), float(jump)
 
-            dead = (~torch.isfinite(values)).all(dim=1).cpu().numpy()
-            if dead.any():
-                raise ValueError(f"contour: no path exists, the map row of frame {_first(dead)} has no finite value")
-            raise ValueError(f"contour: no path of band {int(band)} connects the finite values of the map")
-        periods = (path + lo).cpu().numpy().astype(np.int32, copy=False)
-        return ShortTimeContour(periods, sal.cpu().numpy(), float(score.item()),
-                                self._map_result(values, kind, lo, hi, on_device) if return_map else None)
+    @staticmethod
+    def _no_path(what, values, band):
+        """The ValueError of a map without a path, naming the first frame whose row has no finite value."""
+        import torch
+
+        dead = (~torch.isfinite(values)).all(dim=1).cpu().numpy()
+        if dead.any():
+            raise ValueError(f"{what}: no path exists, the map row of frame {_first(dead)} has no finite value")
+        raise ValueError(f"{what}: no path of band {band} connects the finite values of the map")
+
+    def contours(self, signal, count, kind="gamma", band=8, jump=0.0, min_length=2, max_length=None, floor=None,
+                 guard=None, block_frames=None, return_maps=False):
+        """`count` period tracks of a recording with several sources, by peeling: track k is the best path
+        (``contour``'s, same `kind`, `band`, `jump`, `min_length`, `max_length`) through the time-period map of what the
+        tracks 0 .. k-1 left of every frame.  The second-best path through ONE map follows a multiple of the first
+        track, not the second source; the map of the residual does not hold the first source any more.
+        -> ShortTimeContours(periods (W, count) int32, salience (W, count) float64, scores (count,) float64, maps).
+
+        Every round k = 0 .. count-1, the first included, is four steps on device tensors:
+          1. residual frames: for every block of `block_frames` frames (None: all W), ``PeriodEngine.follow_residual``
+             of the recording with the live entries (>= 1) of the columns 0 .. k-1 of `periods`, packed to the front
+             (``pack_tracks``) and peeled in column order -- the subtraction ``follow`` performs, so the tracks found
+             are tracks of exactly what ``follow`` then extracts.  The constructor's `trunc_to_integer_multiple`,
+             `window` and `dtype` are honoured as in ``follow``;
+          2. map: the kind's kernel on those float64 frames, the columns `min_length` .. `max_length`, into one (W, P)
+             tensor.  With ``dtype=float32`` the frames are rounded to float32 once, as everywhere, but they come out
+             of step 1 widened to float64 and every round runs the kind's float64 kernel on them (``contour`` runs
+             the float32 one);
+          3. guard: with ``guard=g`` (an int >= 0) the cells within g columns of an earlier track's live period in that
+             frame are set to -inf, which the path kernel treats as forbidden; None forbids nothing;
+          4. path: one ``PeriodEngine.period_path`` launch.  Column k is ``min_length + path`` and ``salience[:, k]``
+             the map along it.  With `floor` set, the frames whose salience is not > floor get period 0: the track is
+             silent there and later rounds do not peel it there; ``salience`` keeps the map's value.
+        Per round only the status scalar comes down (and the row count inside ``pack_tracks``); at the end the (W, count)
+        integers and doubles and the scores.  ``return_maps=True`` returns the maps as a tuple of ShortTimeMap, map k as
+        the path of round k saw it, guard included: numpy for a numpy signal, tensors for a tensor signal.
+
+        For float64 frames ``contours(x, 1, ...)`` is ``contour(x, ...)`` bit for bit, and ``follow`` takes the result
+        wherever it takes a ShortTimeContour, its columns in order.
+
+        ValueError before any launch for what ``contour`` refuses, `count` not an int in 1 .. 64, `guard` neither None
+        nor an int >= 0, a `floor` that is not a finite number, or a ``ShortTime`` built with ``orthogonalize=True``
+        (as in ``follow``: the whole projection is peeled); after a round's launch when that round has no path, with
+        the round named."""
+        if self._orthogonalize:
+            raise ValueError("contours peels the whole projection, sub-periods included, as follow does: build the "
+                             "ShortTime with orthogonalize=False")
+        B = self._block_frames(block_frames)
+        lo, hi = self._map_args(kind, min_length, max_length)
+        band, jump = self._path_args(band, jump, lo, hi)
+        if isinstance(count, bool) or not isinstance(count, (int, np.integer)) or not 1 <= int(count) <= _MAX_ROWS:
+            raise ValueError(f"count={count!r} must be an int in 1 .. {_MAX_ROWS}")
+        if guard is not None and (isinstance(guard, bool) or not isinstance(guard, (int, np.integer)) or guard < 0):
+            raise ValueError(f"guard={guard!r} must be None or an int >= 0")
+        if floor is not None and (isinstance(floor, bool) or not isinstance(floor, (int, float, np.integer, np.floating))
+                                  or not math.isfinite(floor)):
+            raise ValueError(f"floor={floor!r} must be None or a finite number")
+        K = int(count)
+
+        import torch
+
+        x = self._signal(signal)
+        eng = default_engine()
+        self._map_plan(eng, kind, lo, hi, np.float64)
+        dev = torch.device("cuda", eng.device)
+        xd, on_device = self._device_signal(x, eng)
+        N, hop, W, P = self.frame_length, self.hop, self.frame_count(xd.shape[0]), hi - lo + 1
+        B = W if B is None or B >= W else B
+        win = None if self.window is None else torch.as_tensor(self.window, device=dev)
+        tdt = torch.float64 if self.dtype == np.float64 else torch.float32
+        periods = torch.zeros((W, K), dtype=torch.int32, device=dev)
+        salience = torch.empty((W, K), dtype=torch.float64, device=dev)
+        scores = torch.empty((K,), dtype=torch.float64, device=dev)
+        cols = torch.arange(lo, hi + 1, dtype=torch.int32, device=dev)
+        maps = []
+        for k in range(K):
+            packed, counts = self.pack_tracks(periods[:, :k])[:2] if k else (None, None)
+
+            def rows(f0, Wb):
+                fr = eng.follow_residual(xd, N, hop, f0, Wb, packed[f0 : f0 + Wb] if k else None,
+                                         counts[f0 : f0 + Wb] if k else None, win, tdt, self._trunc_to_integer_multiple)
+                return self._map_rows(eng, fr, kind, lo, hi)
+
+            if B == W:
+                values = rows(0, W)
+            else:
+                values = torch.empty((W, P), dtype=torch.float64, device=dev)
+                for f0 in range(0, W, B):
+                    values[f0 : f0 + B] = rows(f0, min(B, W - f0))
+            if guard is not None:
+                for t in range(k):
+                    pt = periods[:, t : t + 1]
+                    # (no two periods of the range lie more than hi apart: a wider guard is that one)
+                    values.masked_fill_((pt >= 1) & ((cols[None, :] - pt).abs() <= min(int(guard), hi)), -math.inf)
+            path, sal, score, status = eng.period_path(values, band, jump)
+            if int(status.item()) != _ffi.PH_ST_OK:
+                self._no_path(f"contours: round {k}", values, band)
+            col = path + lo
+            periods[:, k] = col if floor is None else torch.where(sal > float(floor), col, torch.zeros_like(col))
+            salience[:, k], scores[k] = sal, score
+            if return_maps:
+                maps.append(self._map_result(values, kind, lo, hi, on_device))
+        return ShortTimeContours(periods.cpu().numpy(), salience.cpu().numpy(), scores.cpu().numpy(),
+                                 tuple(maps) if return_maps else None)
 
     def follow(self, signal, periods):
         """The sound of a recording along a period track: from every frame the projection onto the period the track
         names for that frame is taken (``Periods.project``, whole, sub-periods included) and the per-frame waveforms are
         overlap-added -> ShortTimeFollow(periods, powers, tracks, periodic, residual).
 
-        `periods`: a ShortTimeContour, a (W,) or (W, T) integer array, an integer tensor on the engine's device, or a
+        `periods`: a ShortTimeContour, a ShortTimeContours (its columns in order), a (W,) or (W, T) integer array, an integer tensor on the engine's device, or a
         list of any of these, whose columns are stacked in list order.  Column t is track t; in a frame the columns are
         peeled left to right, each from what the ones before it left.  An entry below 1 means the track is silent in
         that frame, e.g. ``np.where(c.salience > s, c.periods, 0)``.
@@ -665,16 +797,7 @@ class ShortTime:
 
         eng = default_engine()
         dev = torch.device("cuda", eng.device)
-        on_device = _is_torch(x)
-        if on_device:
-            if not x.is_cuda or x.device.index != eng.device:
-                raise ValueError(f"a tensor signal must live on cuda:{eng.device} (or pass a numpy array)")
-            xd = x.detach()
-            if xd.dtype not in (torch.float64, torch.float32):
-                xd = xd.to(torch.float64)
-            xd = xd.contiguous()
-        else:
-            xd = torch.as_tensor(x, device=dev)  # the one upload: L samples
+        xd, on_device = self._device_signal(x, eng)
         if _is_torch(per):
             if per.device != dev:
                 raise ValueError(f"tensor periods must live on cuda:{eng.device} (or pass a numpy array)")
@@ -695,7 +818,7 @@ class ShortTime:
         """`periods` of ``follow`` as one (W, T) int32 array -- a tensor if any part is one -- or ValueError."""
         cols = []
         for it in (periods if isinstance(periods, list) else [periods]):
-            if isinstance(it, ShortTimeContour):
+            if isinstance(it, (ShortTimeContour, ShortTimeContours)):
                 it = it.periods
             if _is_torch(it):
                 if it.dtype.is_floating_point or it.dtype.is_complex or str(it.dtype) == "torch.bool":

@@ -11,9 +11,10 @@ cuda:LOCAL_RANK and fails loudly if libperiod_hip.so or a GPU is missing (no CPU
 from .Periods import Periods
 from .QOPeriods import QOPeriods
 from .RamanujanPeriods import RamanujanPeriods
-from .ShortTime import ShortTime, ShortTimeContour, ShortTimeFollow, ShortTimeMap, ShortTimeRamanujan, ShortTimeTracks
+from .ShortTime import (ShortTime, ShortTimeContour, ShortTimeContours, ShortTimeFollow, ShortTimeMap, ShortTimeRamanujan,
+                        ShortTimeTracks)
 from .engine import PeriodEngine, default_engine
 
 __all__ = ["Periods", "QOPeriods", "RamanujanPeriods", "ShortTime", "ShortTimeTracks", "ShortTimeRamanujan", "ShortTimeMap",
-           "ShortTimeContour", "ShortTimeFollow", "PeriodEngine", "default_engine"]
+           "ShortTimeContour", "ShortTimeContours", "ShortTimeFollow", "PeriodEngine", "default_engine"]
 __version__ = "0.1.0"

@@ -87,6 +87,7 @@ SIGNATURES = {
     "ph_period_path": [_vp, _vp, _i64, _i64, _i, _i64, _i, _d, _u, _vp, _vp, _vp, _vp],
     "ph_period_path_plan_info": [_vp, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)],
     "ph_follow": [_vp, _vp, _i, _i64, _i, _i, _i64, _vp, _i, _pi32, _pi32, _i, _i, _u, _vp, _vp, _vp],
+    "ph_follow_residual": [_vp, _vp, _i, _i64, _i, _i, _i64, _i64, _vp, _i, _pi32, _pi32, _i, _u, _vp],
     "ph_follow_plan_info": [_vp, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)],
 }
 

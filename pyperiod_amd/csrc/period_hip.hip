@@ -2921,4 +2921,52 @@ int ph_follow(ph_ctx* c, const void* signal, int in_dtype, int64_t L, int N, int
   return st.finish();
 }
 
+int ph_follow_residual(ph_ctx* c, const void* signal, int in_dtype, int64_t L, int N, int hop, int64_t f0, int64_t Wb,
+                       const double* window, int frame_dtype, const int32_t* periods, const int32_t* counts, int pcap,
+                       unsigned flags, double* out) {
+  if (!c) return fail(PH_E_ARG, "ctx is NULL");
+  if (!signal || !out) return fail(PH_E_ARG, "ph_follow_residual: signal / out is NULL");
+  if (pcap > 0 && (!periods || !counts))
+    return fail(PH_E_ARG, "ph_follow_residual: periods / counts is NULL with pcap=%d (no tracks: pcap = 0)", pcap);
+  if ((in_dtype != PH_F64 && in_dtype != PH_F32) || (frame_dtype != PH_F64 && frame_dtype != PH_F32))
+    return fail(PH_E_ARG, "ph_follow_residual: in_dtype and frame_dtype must be PH_F64 or PH_F32");
+  PH_TRY(check_frame_walk("ph_follow_residual", Wb, nullptr, N, hop, L));  // (the sizes, and the block as if f0 were 0)
+  if (f0 < 0) return fail(PH_E_ARG, "ph_follow_residual: f0=%lld must be >= 0", (long long)f0);
+  if (f0 > (L - 1) / hop - (Wb - 1))  // (no f0 + Wb, which may overflow)
+    return fail(PH_E_ARG, "ph_follow_residual: the block's last frame starts at or behind the end of the signal "
+                "((f0 + Wb - 1) * hop >= L = %lld with f0 = %lld, Wb = %lld)", (long long)L, (long long)f0, (long long)Wb);
+  if (pcap < 0 || pcap > ph::kFollowMaxBlocks)
+    return fail(PH_E_ARG, "ph_follow_residual: pcap=%d must be in [0, %d]", pcap, ph::kFollowMaxBlocks);
+  PH_TRY(check_framed_size("ph_follow_residual", Wb, 1, N));
+  if (L > INT64_MAX / 8 || (pcap > 0 && Wb > (INT64_MAX / 4) / pcap))
+    return fail(PH_E_ARG, "ph_follow_residual: L or Wb * pcap does not fit 64 bits");
+  FollowPlan fp;
+  PH_TRY(resolve_follow(c, N, &fp));
+  PH_HIP(hipSetDevice(c->device));
+  // (the grid and the workspace of ph_follow)
+  const unsigned grid =
+      (unsigned)std::min<int64_t>(Wb, (int64_t)std::max(1, c->num_cu) * (fp.placement == PH_PLAN_LDS ? 8 : 4));
+  void* gws;
+  PH_TRY(place(c, fp.placement, B_WS0, (size_t)grid * ph::follow_work_doubles(N) * sizeof(double), &gws));
+  Stage st(c, flags);
+  const void *ds, *dwin = nullptr, *dper = nullptr, *dcnt = nullptr;
+  void* dout;
+  PH_TRY(st.in(signal, (size_t)L * elem_size(in_dtype), &ds));  // the signal once, whole: f0 indexes into it
+  if (window) PH_TRY(st.in(window, (size_t)N * sizeof(double), &dwin, B_GWIN));
+  if (pcap > 0) {
+    PH_TRY(st.in(periods, (size_t)Wb * pcap * sizeof(int32_t), &dper, B_GEN0));
+    PH_TRY(st.in(counts, (size_t)Wb * sizeof(int32_t), &dcnt, B_GBUF));
+  }
+  PH_TRY(st.out(B_OUT0, out, (size_t)Wb * N * sizeof(double), &dout));
+  const unsigned kflags = flags & PH_FLAG_TRUNC;
+  PH_TRY(dispatch(in_dtype, [&](auto ti) {
+    return dispatch(frame_dtype, fp.placement == PH_PLAN_LDS, [&](auto tf, auto lw) {
+      return launch(c, "k_follow_residual", ph::k_follow_residual<decltype(ti), decltype(tf), decltype(lw)::value>,
+                    dim3(grid), fp.block, fp.lds, (const decltype(ti)*)ds, L, N, hop, f0, Wb, (const double*)dwin,
+                    (const int*)dper, (const int*)dcnt, pcap, kflags, (double*)gws, (double*)dout);
+    });
+  }));
+  return st.finish();
+}
+
 }  // extern "C"

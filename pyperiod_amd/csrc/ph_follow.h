@@ -13,6 +13,12 @@
 //     off += p
 //   done[f] = the blocks written; powers[f, a >= done[f]] = 0.0; seg behind the last block is never written.
 //
+// k_follow_residual is the same body on the frames f0 .. f0 + Wb of the recording, and keeps what k_follow throws away:
+//   x_f as above with f0 + f for f;  the walk stops at the first p < 1 or p > N (no ccap);  out[f, i] = r_{C}[i], the
+//   residual after the last block peeled, every sample of every row (no blocks: x_f itself, the frame k_frames writes
+//   as double).  It writes no seg, powers or done, so it sums no squares and reduces nothing.  The statements of both
+//   kernels are ph_follow_body.h, included into each: the residual has k_follow's bits by construction.
+//
 // The means are residue_mean's (follow_mean: column_sum, plus numpy's +0.0 identity): one thread per residue, rows added in order with one division, the bits of
 // the reference's np.sum(cp, 0) / divs (trunc: np.mean over the complete rows).  p <= N gives every residue a sample
 // and trunc a complete row.  (p = 1 alone is no row-order sum in the reference: see numpy_contiguous_sum below.)  The
@@ -157,77 +163,26 @@ __global__ __launch_bounds__(1024) void k_follow(const Tin* __restrict__ s, int6
                                                  const int* __restrict__ counts, int pcap, int ccap, unsigned flags,
                                                  double* gws, double* __restrict__ seg, double* __restrict__ powers,
                                                  int* __restrict__ done) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const FollowLds Ld = follow_carve(Carve(smem), N, LW);
-  double* r = LW ? Ld.r : gws + (size_t)blockIdx.x * follow_work_doubles(N);
-  double* m = LW ? Ld.m : r + win_stride((size_t)N);
-  double* red = Ld.red;
-  const int tid = threadIdx.x, nt = blockDim.x;
-  const bool trunc = flags & kTrunc;
+  constexpr bool RES = false;  // (one body for both kernels: ph_follow_body.h says what RES selects and why it is text)
+  constexpr int64_t f0 = 0;
+  double* const out = nullptr;
+#include "ph_follow_body.h"
+}
 
-  for (int64_t f = blockIdx.x; f < W; f += gridDim.x) {
-    // ---- the frame, as k_frames rounds it, and its sum of squares
-    const int64_t at = f * hop;
-    double acc = 0.0;
-    for (int i = tid; i < N; i += nt) {
-      double v = 0.0;
-      if (at + i < L) {
-        const double t = win ? (double)s[at + i] * win[i] : (double)s[at + i];
-        v = (double)(Tf)t;
-      }
-      r[i] = v;
-      acc += v * v;
-    }
-    // (the barriers of block_sum also make r whole for every thread; the ones of the last frame's final block_sum stand
-    // between that frame's reads of r and these writes)
-    const double pn0 = periodic_norm_from_sq(block_sum(acc, red), N, 0);
-    double pn_prev = pn0;
-
-    const int cf = counts[f] < 0 ? 0 : counts[f] > pcap ? pcap : counts[f];
-    const int* prow = periods + f * (int64_t)pcap;
-    double* srow = seg + f * (int64_t)ccap;
-    double* wrow = powers + f * (int64_t)pcap;
-    int64_t off = 0;
-    int a = 0;
-    for (; a < cf; ++a) {
-      const int p = prow[a];  // (the same value in every thread: the stop is uniform)
-      if (p < 1 || p > N || off + p > ccap) break;
-      // ---- one period of means, in row order: kept for the subtraction and written out as the block's segment
-      if (p == 1) {  // the mean: numpy's own order (above); trunc or not, the sum over all N samples by N
-        if (tid == 0) {
-          const double mj = numpy_contiguous_sum(r, N, red) / (double)N;
-          m[0] = mj;
-          srow[off] = mj;
-        }
-      } else {
-        const Fold fo(N, p);
-        for (int j = tid; j < p; j += nt) {
-          const double mj = follow_mean(r, fo, j, trunc);
-          m[j] = mj;
-          srow[off + j] = mj;
-        }
-      }
-      __syncthreads();
-      // ---- r <- r - tile(means), one rounded subtraction per sample; i mod p kept incrementally
-      acc = 0.0;
-      int j = tid % p;
-      const int step = nt % p;
-      for (int i = tid; i < N; i += nt) {
-        const double v = r[i] - m[j];
-        r[i] = v;
-        acc += v * v;
-        j += step;
-        if (j >= p) j -= p;
-      }
-      // (block_sum's barriers: r is whole before the next block's column sums, m is read before it is rewritten)
-      const double pn = periodic_norm_from_sq(block_sum(acc, red), N, 0);
-      if (tid == 0) wrow[a] = pn0 == 0.0 ? 0.0 : (pn_prev - pn) / pn0;
-      pn_prev = pn;
-      off += p;
-    }
-    if (tid == 0) done[f] = a;
-    for (int k = a + tid; k < pcap; k += nt) wrow[k] = 0.0;
-  }
+// The frames f0 .. f0 + W of the recording less the tracks named for them: periods (W, pcap) and counts (W) are
+// block-local, out is (W, N).  pcap == 0: no tracks, periods and counts are not read.
+template <typename Tin, typename Tf, bool LW>
+__global__ __launch_bounds__(1024) void k_follow_residual(const Tin* __restrict__ s, int64_t L, int N, int hop,
+                                                          int64_t f0, int64_t W, const double* __restrict__ win,
+                                                          const int* __restrict__ periods,
+                                                          const int* __restrict__ counts, int pcap, unsigned flags,
+                                                          double* gws, double* __restrict__ out) {
+  constexpr bool RES = true;
+  constexpr int ccap = 0;
+  double* const seg = nullptr;
+  double* const powers = nullptr;
+  int* const done = nullptr;
+#include "ph_follow_body.h"
 }
 
 }  // namespace ph

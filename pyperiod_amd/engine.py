@@ -955,6 +955,43 @@ class PeriodEngine:
                    mk.addr(done))
         return seg, powers, done
 
+    def follow_residual(self, signal, frame_length, hop, first, count, periods, counts, window=None, frame_dtype=None,
+                        trunc=False):
+        """The frames of a recording less the tracks named for them (ph_follow_residual, one launch of
+        k_follow_residual): -> (count, frame_length) float64, row i what `follow` leaves of frame ``first + i`` after
+        peeling periods[i, 0], periods[i, 1], ... -- the same cut, means and subtractions, bit for bit -- so
+        ``frames(...)[first + i]`` widened to double minus the tiled blocks `follow` writes to seg, in order.  A row's
+        walk ends at counts[i] blocks (clipped to 0 .. pcap) or at the first period < 1 or > frame_length; there is no
+        ccap.  `periods` (count, pcap <= 64) and `counts` (count) int32 are local to the block of frames; both None (or
+        pcap == 0): no tracks, the float64 frames themselves.  `window`, `frame_dtype`, `trunc` and the kinds of array
+        as in `follow`."""
+        if getattr(signal, "ndim", None) != 1:
+            raise ValueError("expected a 1-D signal")
+        x, code, _, L, fl, mk = self._prep(signal.reshape(1, -1))
+        N, hop, f0, W = int(frame_length), int(hop), int(first), int(count)
+        if W < 0:
+            raise ValueError("count must be >= 0")
+        fcode = self._dtype_code(mk, frame_dtype, code)
+        if (periods is None) != (counts is None):
+            raise ValueError("periods and counts come together (both None: no tracks)")
+        per = cnt = None
+        pcap = 0
+        if periods is not None:
+            per = _side(mk, x, periods, np.int32, "periods", "signal")
+            if per.ndim != 2 or per.shape[0] != W:
+                raise ValueError("periods must be (count, pcap)")
+            pcap = int(per.shape[1])
+            cnt = _side(mk, x, counts, np.int32, "counts", "signal")
+            if tuple(cnt.shape) != (W,):
+                raise ValueError("counts must hold one entry per frame")
+            if pcap == 0:
+                per = cnt = None
+        win = None if window is None else self._window(mk, x, window, N)
+        out = mk.empty((W, max(N, 0)), np.float64)
+        self._call(mk, W, self._lib.ph_follow_residual, mk.addr(x), code, L, N, hop, f0, W, mk.addr(win), fcode,
+                   mk.addr(per), mk.addr(cnt), pcap, fl | (_ffi.PH_FLAG_TRUNC if trunc else 0), mk.addr(out))
+        return out
+
     def fold_sums(self, x, p_list, keep):
         """W = A x for natural-basis rows (QOPeriods.py:782): (W, sum(keep)) float64."""
         x, code, W, N, fl, mk = self._prep(x)
